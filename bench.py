@@ -11,10 +11,15 @@ Workloads (BASELINE.json `configs`; synthetic stand-ins of SURVEY.md 8d [D] -- n
            clean-up + occupancy mapper for the dynamic part, invalid_depth_decay 0.8, TSDF / occupancy decay every 6th frame.
   lidar    configs[4]: 1024x64 spinning LiDAR, 0.10 m voxels, 200 m; step = one scan.  N > 1 GPUs: azimuth sectors.
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both sides (max over ranks);
-blocks are repeated until >= 1 s has been timed (`repeats`), `ms_per_step` / `value` come from the MEDIAN block (camera / multicam: the
-EXPLORING figure, mean over complete loops of the unique poses on a map emptied per loop -- see main_camera).
-`roofline` is quoted for the LONGEST kernel of the step (by time); the kernel with the most bytes is listed beside it.
+Timing, camera: one untimed pass over the poses and W warm-up steps, then EXACTLY K = --steps timed steps of the EXPLORING loop over the
+unique poses on a map emptied before the first and whenever the loop starts over (segments between two emptyings are bracketed by barrier +
+synchronize on both sides, max over ranks); `ms_per_step` = timed seconds / K, `value` from it -- see main_camera.  The other workloads:
+W warm-up steps, then blocks of EXACTLY K steps bracketed the same way, repeated until >= 1 s has been timed (`repeats`); `ms_per_step` /
+`value` come from the MEDIAN block (multicam, and the camera's `ms_per_step_blocks` under --full: the EXPLORING blocks' mean over complete
+loops -- the camera's `ms_per_step` before the exact headline).
+A plain camera run prints the headline only; --full adds everything else its line reports (block statistics, revisit and classic-order
+figures, per-component times, frame latency, per-kernel durations and `roofline` -- quoted for the LONGEST kernel of the step by time, the
+kernel with the most bytes beside it --, CPU baseline, parity with the checker).  --dump-outputs DIR writes the map the timed steps built.
 """
 import argparse
 import gc
@@ -191,6 +196,57 @@ class Timer:
                 gc.enable(); gc.unfreeze()
         return float(np.median(dts)), dts, first
 
+    def exact(self, run, barrier, steps, warmup, segment, before_segment=None, prime=0):
+        """EXACTLY `steps` timed steps after `prime` + `warmup` untimed ones, cut into segments of at most `segment` steps; each segment is one
+        block (before_segment() outside the timed region, barrier on both sides, max over ranks).  -> (timed seconds in all, per-segment seconds,
+        sizes).  The collector is parked as in run(), but BEFORE the untimed steps: its full pass idles the device for tens of ms, and a first
+        block right after it ran ~20 % slow."""
+        park = os.environ.get("NVBX_BENCH_KEEP_GC") != "1"
+        if park:
+            gc.collect(); gc.freeze(); gc.disable()
+        dts, sizes = [], []
+        try:
+            for i in range(prime):
+                run(i)
+            for i in range(warmup):
+                run(i)
+            done = 0
+            while done < steps:
+                n = min(segment, steps - done)
+                dts.append(self.block(run, barrier, n, warmup + done, before_segment)); sizes.append(n); done += n
+        finally:
+            if park:
+                gc.enable(); gc.unfreeze()
+        return float(np.sum(dts)), dts, sizes
+
+
+def dump_map(M, g, out_dir, budget_bytes=56 << 20, seed=0):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the TSDF, colour and ESDF layers (blocks in sorted Index3D
+    order, every voxel field as float32, block indices as float64) and the ESDF distance slice -- as out_dir/<name>.npy.  A layer with more blocks
+    than the budget allows is written as a fixed, seeded sample of its sorted blocks."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    fields = {M.LAYER_TSDF: ("tsdf", ("distance", "weight")), M.LAYER_COLOR: ("color", ("r", "g", "b", "weight")),
+              M.LAYER_ESDF: ("esdf", ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"))}
+    per_voxel = sum(len(f) for _, f in fields.values()) + 2          # (parent_direction holds three numbers)
+    cap = max(1, budget_bytes // (per_voxel * 4 * 512))                # blocks per layer within the budget
+    for layer, (name, fs) in fields.items():
+        idx = g.block_indices(layer)
+        idx = idx[np.lexsort((idx[:, 2], idx[:, 1], idx[:, 0]))] if len(idx) else idx.reshape(0, 3)
+        arrays[name + "_blocks_total"] = np.array([len(idx)], np.float64)
+        if len(idx) > cap:
+            idx = idx[np.sort(np.random.default_rng(seed).choice(len(idx), size=cap, replace=False))]
+        blocks, found = g.get_blocks(layer, idx)
+        assert found.all(), "a listed block was not found"
+        arrays[name + "_block_indices"] = idx.astype(np.float64)
+        for f in fs:
+            arrays["%s_%s" % (name, f)] = blocks[f].astype(np.float32)
+    sl, aabb = g.esdf_slice_image()
+    arrays["esdf_slice"] = sl.astype(np.float32); arrays["esdf_slice_aabb"] = np.asarray(aabb, np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
 
 def complete_loops(tags, dts, nu, steps):
     """Exploring bookkeeping: tags[i] = position in the loop over the nu unique poses at which timed block i started (0 = the map had just been
@@ -328,25 +384,28 @@ def map_parity(M, g, o, oracle):
     return out
 
 
-def exploring_parity(M, g, gpu_step, drain, n_frames, checker_step, steps, oracle, threads=8):
-    """The sequence the headline times, run once more OUTSIDE the timed region and compared with the checker at its end: clear(), every pose
-    of the loop once (depth, colour, updateEsdf per frame through `gpu_step(k)`), a drain (`drain()`: what ends a timed block -- synchronize,
-    which replays whatever the mapper holds back) after every `steps` frames; then the CPU checker is fed the same frames in plain call order."""
+def exploring_parity(M, g, gpu_step, drain, n_frames, checker_step, steps, oracle, threads=8, first=0):
+    """One exploring loop at a timing's drain cadence, run once more OUTSIDE the timed region and compared with the checker at its end: clear(),
+    every pose of the loop once starting at pose `first` (depth, colour, updateEsdf per frame through `gpu_step(k)`), a drain (`drain()`: what
+    ends a timed block or segment -- synchronize, which replays whatever the mapper holds back) after every `steps` frames; then the CPU checker
+    is fed the same frames in plain call order.  The camera headline's cadence: first = W mod nu, steps = nu (one drain per loop segment); the
+    block figure's: first = 0, steps = K."""
     g.clear()
-    for k in range(n_frames):
+    order = [(first + j) % n_frames for j in range(n_frames)]
+    for j, k in enumerate(order):
         gpu_step(k)
-        if (k + 1) % steps == 0:
+        if (j + 1) % steps == 0:
             drain()
     drain()
     oracle.set_num_threads(min(threads, os.cpu_count() or 1))
     o = oracle.OracleMap(copy_params(oracle, g.params))
     t = time.perf_counter()
-    for k in range(n_frames):
+    for k in order:
         checker_step(o, k)
     out = map_parity(M, g, o, oracle)
-    out["steps_compared"] = int(n_frames); out["drain_every"] = int(steps); out["checker_s"] = round(time.perf_counter() - t, 2)
-    out["what"] = ("one more exploring loop exactly as timed (map emptied, %d steps of depth + colour + updateEsdf, a drain every %d steps) against "
-                   "oracle/nvblox_oracle.c fed the same frames in plain call order; outside the timed region" % (n_frames, steps))
+    out["steps_compared"] = int(n_frames); out["drain_every"] = int(steps); out["first_pose"] = int(first); out["checker_s"] = round(time.perf_counter() - t, 2)
+    out["what"] = ("one more exploring loop at the drain cadence of the timing it stands for (map emptied, %d steps of depth + colour + updateEsdf from "
+                   "pose %d, a drain every %d steps) against oracle/nvblox_oracle.c fed the same frames in plain call order; outside the timed region" % (n_frames, first, steps))
     return out
 
 
@@ -1034,13 +1093,19 @@ def main_camera(args):
     staged = deferral and not args.zero_copy_deferral          # (frames / staged: the mapper's default setting, nvbx_mapper_set_color_deferral(m, 2))
     g.set_color_deferral(deferral, staged=staged)
 
-    # EXPLORING (the headline): the map is EMPTIED at the start of every loop over the nu unique poses and the timed blocks of K steps tile the
-    # loop (K = 200 = nu: one block per loop; the driver's K = 20: ten blocks per loop, the map emptied before every tenth), so every pose is
-    # integrated exactly once per map and block allocation, hash inserts and first-touch of the pools are inside the timed region, as they are
-    # when the reference fuses a sequence (the README's per-component timers run over a whole dataset).  The figure is the MEAN over complete
-    # loops (timed seconds / steps: the early, allocation-heavy blocks count in proportion); the blocks that start from the empty map are also
-    # quoted on their own (`first_block_of_loop`).  REVISIT (beside it): the same blocks of K steps on the fully allocated map after one
-    # untimed loop -- the steady state of a robot that stays in a mapped room.
+    # EXPLORING: the timed steps walk the loop over the nu unique poses on a map EMPTIED at its start (outside the timed region; the drain before it
+    # is inside), so every pose is integrated exactly once per map and block allocation, hash inserts and first-touch of the pools are inside the
+    # timed region, as they are when the reference fuses a sequence (the README's per-component timers run over a whole dataset).  Two timings:
+    #  * the camera headline (`ms_per_step`, `value`): EXACTLY K = --steps timed steps after one untimed pass over the poses and the W warm-up
+    #    steps, the map emptied before the first and whenever the loop starts over; timed seconds / K (over whole loops, K a multiple of nu, the
+    #    mean over complete loops);
+    #  * the BLOCK figure (`ms_per_step_blocks`; with --full, and multicam's headline -- an A/B configuration that keeps this timing): blocks of K
+    #    steps tile the loop (K = 200 = nu: one block per loop; K = 20: ten blocks per loop, the map emptied before every tenth), repeated until
+    #    MIN_TIMED_MS, the MEAN over complete loops (the early, allocation-heavy blocks count in proportion); the blocks that start from the empty
+    #    map are also quoted on their own (`first_block_of_loop`).
+    # With --full, beside them: REVISIT, blocks of K steps on the fully allocated map after one untimed loop -- the steady state of a robot that
+    # stays in a mapped room.
+    full = args.full or multicam or args.profile_run       # (multicam: an A/B configuration, always its whole line with the camera sweep)
     loop_pos, tags = [0], []
 
     def fresh_map():
@@ -1050,13 +1115,53 @@ def main_camera(args):
             loop_pos[0] = 0
         tags.append(loop_pos[0])
         loop_pos[0] += args.steps
+
+    def new_loop():
+        g.clear()
+        mf_prev[0] = None
     timed_step = (lambda i: step(i, mesh=True)) if args.with_mesh else step       # (--with-mesh: profiling passes that need k_mesh in the trace)
-    dt, dts, base = tm.run(timed_step, barrier, args.steps, args.warmup, before_block=fresh_map)
-    per_loop, starts, whole, kept = complete_loops(tags, dts, nu, args.steps)
-    dt = float(np.sum(kept)) / len(kept)                 # mean block of the complete loops
+    if multicam:
+        dt, dts, base = tm.run(timed_step, barrier, args.steps, args.warmup, before_block=fresh_map)
+        per_loop, starts, whole, kept = complete_loops(tags, dts, nu, args.steps)
+        sec_per_step = float(np.sum(kept)) / len(kept) / args.steps            # mean block of the complete loops
+        n_timed = len(dts)
+        value_is = ("exploring: the map is emptied at the start of every loop over the %d unique poses; timed blocks of %d steps tile the loop "
+                    "(%d per loop), every pose is integrated once per map (allocation inside the timed region); mean over the %d complete "
+                    "loops timed" % (nu, args.steps, per_loop, len(whole)))
+    else:
+        # prime = one untimed pass over the loop's poses before the W warm-up steps: the pools, the resident frames and the device clocks come
+        # up, so a short run's K steps meet the device a long run meets.  The map is emptied before the first timed step all the same.
+        dt_all, dts_head, _ = tm.exact(timed_step, barrier, args.steps, args.warmup, nu, before_segment=new_loop, prime=nu)
+        sec_per_step = dt_all / args.steps
+        n_timed = len(dts_head)
+        value_is = ("exploring: %d timed steps walk the loop over the %d unique poses on a map emptied before the first and whenever the "
+                    "loop starts over (allocation inside the timed region, every pose integrated once per map; one untimed pass over the poses and "
+                    "the warm-up steps before); timed seconds / steps, timed in %d segment%s between the emptyings"
+                    % (args.steps, nu, n_timed, "" if n_timed == 1 else "s"))
+    ms_per_step = sec_per_step * 1e3
+    fps = world * ncam / sec_per_step
+    dumped = dump_map(M, g, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
+    if not full:
+        if rank == 0:
+            out = {"metric": "frames/s, TSDF+Color+ESDF integrate per frame, synthetic Replica-like 640x480 @0.05m",
+                   "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "repeats": n_timed,
+                   "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                   "dtype": "f32", "data": "synthetic", "ms_per_frame": round(ms_per_step / ncam, 4), "timing": {"value_is": value_is},
+                   "config": {"workload": "configs[1]: " + ("synthetic Replica-like room (SURVEY 8d)" if args.scene == "room" else "NOT the metric's scene -- a 14 x 12 x 3 m hall"),
+                              "scene": args.scene, "cameras_per_gpu": ncam, "unique_frames": nu, "color_deferral": bool(deferral),
+                              "parallelism": "single GPU" if world == 1 else ("one camera per GPU, fusion by " + args.fusion)}}
+            if dumped is not None:
+                out["dump_outputs"] = dumped
+            print(json.dumps(out))
+        return finish_dist(dist, world)
+
+    # ---- --full: everything beyond the headline
+    if not multicam:
+        # the block figure, in a run of its own beside the headline
+        dt, dts, base = tm.run(timed_step, barrier, args.steps, 0, before_block=fresh_map, first=args.warmup + args.steps)
+        per_loop, starts, whole, kept = complete_loops(tags, dts, nu, args.steps)
+    ms_blocks = float(np.sum(kept)) / len(kept) / args.steps * 1e3
     dt_first = float(np.median([dts[i] for i in starts]))
-    ms_per_step = dt / args.steps * 1e3
-    fps = world * ncam * args.steps / dt
     for i in range(nu):                      # one untimed loop: the map is complete
         step(base + i)
     dt_rev, dts_rev, base = tm.run(step, barrier, args.steps, 0, min_ms=MIN_TIMED_MS / 4, first=base + nu)
@@ -1066,7 +1171,7 @@ def main_camera(args):
         g.set_color_deferral(False)
         dt_c, dts_c, base = tm.run(step, barrier, args.steps, 0, min_ms=MIN_TIMED_MS / 4, first=base)
         ms_classic = dt_c / args.steps * 1e3
-        # ... and the EXPLORING figure in classic order: what a host that only swaps the library gets for the headline sequence
+        # ... and the block figure in classic order: what a host that only swaps the library gets for the exploring sequence
         loop_pos[0] = 0; n_tags0 = len(tags)
         dt_ce, dts_ce, base = tm.run(step, barrier, args.steps, 0, min_ms=MIN_TIMED_MS / 2, before_block=fresh_map, first=0)
         _, _, whole_c, kept_c = complete_loops(tags[n_tags0:], dts_ce, nu, args.steps)
@@ -1105,8 +1210,8 @@ def main_camera(args):
         # under rocprofv3 (tools/gpu_round.sh): nothing but the timed step is launched, so the trace's per-kernel averages are the step's
         # (the classic-order comparison, the per-component calls and the per-frame latency loop launch the same kernels in other forms)
         out = {"metric": "frames/s, TSDF+Color+ESDF integrate per frame, synthetic Replica-like 640x480 @0.05m", "value": round(fps, 2), "unit": "frames/s",
-               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "repeats": len(dts), "ms_per_step": round(ms_per_step, 4),
-               "ms_per_step_revisit": round(ms_revisit, 4), "profile_run": True, "color_deferral": {"enabled": bool(deferral)},
+               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "repeats": n_timed, "ms_per_step": round(ms_per_step, 4),
+               "ms_per_step_blocks": round(ms_blocks, 4), "ms_per_step_revisit": round(ms_revisit, 4), "profile_run": True, "color_deferral": {"enabled": bool(deferral)},
                "config": {"workload": args.workload, "cameras_per_gpu": ncam, "unique_frames": nu}}
         print(json.dumps(out))
         return finish_dist(dist, world)
@@ -1259,12 +1364,15 @@ def main_camera(args):
 
         def drain_local():
             g.synchronize(); torch.cuda.synchronize(dev)
-        parity = exploring_parity(M, g, lambda k: step(k, exchange=False), drain_local, nu, checker_step, args.steps, oracle)
+        # (the headline's cadence: from pose W mod nu, a drain at the end of each loop segment; multicam's headline is the block figure:
+        #  from pose 0, a drain every K steps)
+        parity = exploring_parity(M, g, lambda k: step(k, exchange=False), drain_local, nu, checker_step, args.steps if multicam else nu, oracle,
+                                  first=0 if multicam else args.warmup % nu)
         parity["mode"] = "color_deferral" if deferral else "classic"
 
     out = {
         "metric": "frames/s, TSDF+Color+ESDF integrate per frame, synthetic Replica-like 640x480 @0.05m",
-        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "repeats": len(dts),
+        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "repeats": n_timed,
         "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": ("configs[3] on one GPU: %d cameras (45 deg yaw offsets) through one mapper, %s; " % (ncam, "one batched launch set per step" if (batch_ok and ncam in bd) else "sequential calls") if multicam else "configs[1]: ") +
@@ -1284,9 +1392,11 @@ def main_camera(args):
                            else "classic launch order (--no-color-deferral / NVBX_COLOR_DEFERRAL=0; a new mapper defaults to staged colour deferral)"},
         "ms_per_frame": round(ms_per_step / ncam, 4),
         "ms_per_step_classic_order": (round(ms_classic_exploring, 4) if ms_classic_exploring else (None if deferral else round(ms_per_step, 4))),
-        "timing": {"value_is": "exploring: the map is emptied at the start of every loop over the %d unique poses; timed blocks of %d steps tile the loop "
-                               "(%d per loop), every pose is integrated once per map (allocation inside the timed region); mean over the %d complete "
-                               "loops timed" % (nu, args.steps, per_loop, len(whole)),
+        "ms_per_step_blocks": round(ms_blocks, 4),
+        "timing": {"value_is": value_is,
+                   "blocks_note": "ms_per_step_blocks (%s): the map is emptied at the start of every loop over the %d unique poses; timed blocks of %d "
+                                  "steps tile the loop (%d per loop), repeated until %g ms are timed; mean over the %d complete loops timed"
+                                  % ("the headline itself" if multicam else "a run of its own beside the headline", nu, args.steps, per_loop, MIN_TIMED_MS, len(whole)),
                    "loops": len(whole), "blocks_per_loop": per_loop,
                    "first_block_of_loop_ms_per_step": round(dt_first / args.steps * 1e3, 4),
                    "exploring_ms_per_step": block_stats(kept, args.steps),
@@ -1321,6 +1431,8 @@ def main_camera(args):
     }
     if sweep is not None:
         out["camera_sweep_ms_per_step"] = sweep
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     print(json.dumps(out))
     finish_dist(dist, world)
 
@@ -1328,8 +1440,15 @@ def main_camera(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (camera: exactly this many)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="camera workload: besides the headline, everything else the line reports -- the block figure ms_per_step_blocks (>= 1 s of "
+                         "K-step blocks, what ms_per_step meant before) and its statistics, revisit and classic-order figures, "
+                         "per-component times, frame latency, per-kernel roofline, CPU baseline, parity with the checker (the other workloads always print "
+                         "their whole line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="camera / multicam: after the timed steps, write the map they built (TSDF, colour, ESDF layers and the ESDF slice) as DIR/<name>.npy")
     ap.add_argument("--unique-frames", type=int, default=200, help="distinct rendered frames cycled through (HBM-resident); independent of --steps")
     ap.add_argument("--cpu-frames", type=int, default=48, help="minimum number of frames of the same workload timed on the CPU oracle")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="the CPU baseline keeps integrating (cycling the same frames) until this much CPU wall time has passed")
@@ -1353,6 +1472,10 @@ def main():
                     help="camera = BASELINE.json configs[1] (the metric's configuration, default); multicam = configs[3] on one GPU; "
                          "decay = configs[2]; lidar = configs[4]")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload not in ("camera", "multicam"):
+        ap.error("--dump-outputs: camera / multicam workloads only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks (one process per GPU) -- the same command line the driver uses
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))

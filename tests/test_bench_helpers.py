@@ -116,3 +116,58 @@ def test_pair_launch_byte_formulas():
     second = bench.algorithmic_bytes("k_integrate_tsdf_color", cb, rows, cols) - (rows * cols * 3 + (rows // 4) * (cols // 4) * 4)      # (no colour image on an occupancy mapper)
     assert bench.algorithmic_bytes("k_integrate_tsdf_color_pair", c, rows, cols, fused=True) == bench.algorithmic_bytes("k_integrate_tsdf_color", c, rows, cols) + second
     assert bench.short("void k_integrate_tsdf_color_pair<nvbx::DepthF32, nvbx::PixRgb8>(FusedArgs<...>)") == "k_integrate_tsdf_color_pair"
+
+
+def test_exact_timer_runs_exactly_k_steps_in_segments():
+    """The camera headline's timer: W untimed steps, then EXACTLY K timed ones, cut where the loop starts over (before_segment between them)."""
+    calls, segs = [], []
+    tm = bench.Timer(None, None, None, 1)
+    total, dts, sizes = tm.exact(calls.append, lambda: None, 45, 3, 20, before_segment=lambda: segs.append(len(calls)))
+    assert calls == list(range(3 + 45)) and sizes == [20, 20, 5] and len(dts) == 3 and segs == [3, 23, 43]
+    assert abs(total - sum(dts)) < 1e-12
+    assert tm.exact(calls.append, lambda: None, 7, 0, 200)[2] == [7]
+    calls.clear()
+    assert tm.exact(calls.append, lambda: None, 4, 2, 200, prime=3)[2] == [4] and calls == [0, 1, 2, 0, 1, 2, 3, 4, 5]      # (prime, warm-up, timed)
+
+
+def test_dump_map_writes_sorted_float_arrays_within_the_budget(tmp_path):
+    from isaac_ros_nvblox_amd import mapper as M
+
+    rng = np.random.default_rng(3)
+    grid = np.stack(np.meshgrid(np.arange(6), np.arange(5), np.arange(4), indexing="ij"), -1).reshape(-1, 3)
+    shuffled = {L: rng.permutation(grid).astype(np.int32) for L in (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF)}     # (unsorted, as the hash lists them)
+
+    class FakeMap:
+        idx = shuffled
+
+        def block_indices(self, layer):
+            return self.idx[layer].copy()
+
+        def get_blocks(self, layer, indices):
+            out = np.zeros((len(indices), 512), M._DT[layer])
+            out[out.dtype.names[0]] = np.asarray(indices)[:, :1] * 100 + np.asarray(indices)[:, 1:2] * 10 + np.asarray(indices)[:, 2:3]
+            return out, np.ones(len(indices), bool)
+
+        def esdf_slice_image(self):
+            return np.ones((7, 9), np.float32), np.zeros(6, np.float32)
+
+    r = bench.dump_map(M, FakeMap(), str(tmp_path / "all"))
+    t = np.load(str(tmp_path / "all" / "tsdf_block_indices.npy"))
+    assert t.dtype == np.float64 and len(t) == 120 and np.array_equal(t, t[np.lexsort((t[:, 2], t[:, 1], t[:, 0]))])
+    d = np.load(str(tmp_path / "all" / "tsdf_distance.npy"))
+    assert d.dtype == np.float32 and d.shape == (120, 512) and np.array_equal(d[:, 0], t[:, 0] * 100 + t[:, 1] * 10 + t[:, 2])
+    assert np.load(str(tmp_path / "all" / "esdf_parent_direction.npy")).shape == (120, 512, 3) and r["arrays"] == len(list((tmp_path / "all").iterdir()))
+    # a budget for 10 blocks per layer: the same seeded sample of the sorted blocks, every time
+    small = 10 * 13 * 4 * 512
+    bench.dump_map(M, FakeMap(), str(tmp_path / "s1"), budget_bytes=small); bench.dump_map(M, FakeMap(), str(tmp_path / "s2"), budget_bytes=small)
+    s1 = np.load(str(tmp_path / "s1" / "color_block_indices.npy"))
+    assert len(s1) == 10 and np.array_equal(s1, np.load(str(tmp_path / "s2" / "color_block_indices.npy")))
+    assert np.load(str(tmp_path / "s1" / "color_blocks_total.npy"))[0] == 120
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) < small + 4096
+
+
+def test_argument_checks():
+    import subprocess
+    for extra in (["--steps", "0"], ["--workload", "lidar", "--dump-outputs", "x"]):
+        p = subprocess.run([sys.executable, bench.__file__] + extra, capture_output=True, text=True, timeout=120)
+        assert p.returncode == 2 and "error" in p.stderr, (extra, p.stderr[-500:])

@@ -3,8 +3,8 @@
 * the camera-BATCH path at 640x480 against the checker -- `nvblox_ros/include/nvblox_ros/nvblox_node.hpp:298-332` feeds up to four cameras through one
   mapper; BASELINE.md quotes 4- and 8-camera figures for a launch shape (2 688 tile workgroups beside 1 200 sphere-tracing riders, 2 / 4 lanes per
   ray, both frame sets in one 4 KiB argument block) that only ran at 160x120 in the tests;
-* the sequence bench.py's headline times -- 200 poses, map emptied per loop, colour deferral on, a drain per block of K steps -- compared with the
-  checker at its end, through the very function bench.py prints its `parity` block with;
+* the sequence bench.py times -- 200 poses, map emptied per loop, colour deferral on, at the headline's drain cadence (one per loop segment) and at
+  the block figure's (one per block of K steps) -- compared with the checker at its end, through the very function bench.py prints its `parity` block with;
 * the bench line itself (subprocess): `parity.ok`, the mode label, the classic-order figure;
 * a repeated-run stress of the fused launches with the replay / carry knobs toggled (the 65a453c race showed in 5 runs of 8).
 """
@@ -80,8 +80,9 @@ def test_camera_batch_at_640x480_against_the_checker(oracle_mod, hip_lib, n_cams
 
 
 def test_the_sequence_the_headline_times_ends_in_the_checkers_map(oracle_mod, hip_lib):
-    """bench.py's exploring loop as it is timed with the driver's flags (--steps 20): clear(), the 200 poses of SURVEY 8d at 640x480, depth + colour +
-    updateEsdf per frame with colour deferral on (two launches per frame), a drain after every 20 frames -- then the checker, plain call order."""
+    """bench.py's exploring loop at both of its timings' cadences with the driver's flags (--steps 20 --warmup 5): clear(), the 200 poses of SURVEY 8d
+    at 640x480, depth + colour + updateEsdf per frame with colour deferral on (two launches per frame) -- the headline's (from pose 5, one drain per
+    loop segment) and the block figure's (from pose 0, a drain after every 20 frames) -- each time then the checker, plain call order."""
     import bench
     from isaac_ros_nvblox_amd import mapper as M
     cam = S.REPLICA_LIKE_CAM
@@ -96,6 +97,9 @@ def test_the_sequence_the_headline_times_ends_in_the_checkers_map(oracle_mod, hi
     def checker_step(o, k):
         d, rgb, T = fr[k]
         o.integrate_depth(d, T, cam); o.integrate_color(rgb, T, cam); o.update_esdf()
+    r = bench.exploring_parity(M, g, gpu_step, g.synchronize, len(fr), checker_step, len(fr), oracle_mod, first=5)
+    assert r["ok"] and r["index_sets_equal"] and r["max_abs_tsdf"] <= 1e-4 and r["blocks"] > 1200 and r["first_pose"] == 5, r
+    g.set_profiling(True)                 # (clears the spans: the launch count below is the block cadence's 200 frames)
     r = bench.exploring_parity(M, g, gpu_step, g.synchronize, len(fr), checker_step, 20, oracle_mod)
     assert r["ok"] and r["index_sets_equal"] and r["max_abs_tsdf"] <= 1e-4 and r["blocks"] > 1200, r
     prof = g.profile()
@@ -105,16 +109,18 @@ def test_the_sequence_the_headline_times_ends_in_the_checkers_map(oracle_mod, hi
 
 
 def test_bench_line_carries_parity_and_mode():
-    """`python bench.py --steps 20 --warmup 5` (the driver's flags; CPU baseline shortened): rc 0, one JSON line, `parity.ok`, the mode label and
-    the classic-order exploring figure as first-class fields."""
+    """`python bench.py --steps 20 --warmup 5 --full` (the driver's flags, whole line; CPU baseline shortened): rc 0, one JSON line, `parity.ok`,
+    the mode label and the classic-order exploring figure as first-class fields."""
     env = dict(os.environ); env["NVBX_BENCH_MIN_MS"] = "150"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--cpu-seconds", "1", "--cpu-frames", "4"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "1", "--cpu-frames", "4"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
     assert out["parity"]["ok"] and out["parity"]["index_sets_equal"] and out["parity"]["steps_compared"] == 200, out["parity"]
-    assert "color_deferral" in out["config"]["mode"] and out["ms_per_step_classic_order"] > out["ms_per_step"] > 0
+    assert out["parity"]["first_pose"] == 5 and out["parity"]["drain_every"] == 200, out["parity"]          # (the headline's cadence)
+    assert "color_deferral" in out["config"]["mode"] and out["ms_per_step"] > 0
+    assert out["ms_per_step_classic_order"] > out["ms_per_step_blocks"] > 0     # (like for like: both block figures)
     assert out["roofline"]["frac"] > 0 and out["cpu_baseline"]["value"] > 0 and out["n_gpus"] == 1
 
 
@@ -144,7 +150,7 @@ def test_bench_gpus_2_starts_itself_and_prints_one_line():
     device 0 and rendezvous over gloo (NVBX_BENCH_SAME_DEVICE / NVBX_BENCH_BACKEND): a control-flow check of the N > 1 path, not a measurement."""
     env = dict(os.environ); env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     env.update(NVBX_BENCH_SAME_DEVICE="1", NVBX_BENCH_BACKEND="gloo", NVBX_BENCH_MIN_MS="60", OMP_NUM_THREADS="4")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--unique-frames", "8", "--cpu-seconds", "0.5", "--cpu-frames", "2"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--unique-frames", "8", "--full", "--cpu-seconds", "0.5", "--cpu-frames", "2"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

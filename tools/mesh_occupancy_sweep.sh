@@ -21,7 +21,7 @@ for w in 2 4 5 6; do
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('   full-layer mesh on the LiDAR map:', {k: v['avg_us'] for k, v in d['kernels'].items() if 'mesh' in k})"
-  NVBX_LIB=$PWD/isaac_ros_nvblox_amd/variants/libnvblox_hip_mesh$w.so NVBX_BENCH_MIN_MS=200 timeout 200 python bench.py --steps 100 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "
+  NVBX_LIB=$PWD/isaac_ros_nvblox_amd/variants/libnvblox_hip_mesh$w.so NVBX_BENCH_MIN_MS=200 timeout 200 python bench.py --steps 100 --warmup 20 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('   per-frame k_mesh us:', d['kernels']['k_mesh']['avg_us'], ' mesh component ms:', d['ms_components'].get('mesh'))"
 done

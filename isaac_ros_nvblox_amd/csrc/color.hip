@@ -8,7 +8,7 @@
 //                     fused, no block list round trip -- with the ESDF site marking riding in extra workgroups
 //                     (nvbx_color_worker.h; [U] ProjectiveColorIntegrator::integrateFrame restated).
 // Pipelined order (colour deferral): the frame is held back; its sphere tracing, candidate discovery and the marking
-// pass ride in the next depth frame's view-marking launch and its colour integration in that frame's TSDF-update launch (tsdf.hip) --
+// pass ride in the next depth frame's view-marking launch (nvbx_view.h) and its colour integration in that frame's TSDF-update launch (tsdf.hip) --
 // this file keeps the held-back state's set-up (pending_*) and the replay in classic order.
 // Call site served: nvblox_ros/src/lib/nvblox_node.cpp:1264.
 #include <algorithm>

@@ -1,5 +1,5 @@
 // nvbx_esdf_edt.h -- the 2-D Euclidean distance transform worker (second half of MultiMapper::updateEsdf), shared by k_esdf_edt
-// (esdf.hip) and by k_mark_view (tsdf.hip), which runs a pending EDT in extra workgroups of the next depth frame's first
+// (esdf.hip) and by k_mark_view (nvbx_view.h), which runs a pending EDT in extra workgroups of the next depth frame's first
 // launch: the EDT touches only the ESDF layer and the (insert-only) hash, so it overlaps the view marking of the next frame.
 #pragma once
 #include "nvbx_mapper.h"

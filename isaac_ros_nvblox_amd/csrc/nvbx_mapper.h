@@ -207,8 +207,8 @@ struct nvbx_mapper {
   void pending_marking_args(int32_t* mark_wg, nvbx::EsdfArgs* ea_out, bool single_frame);
   int pending_color_fused_args(void* fsc_out, int* kind, int32_t* srows, int32_t* scols);
   void* table_spare = nullptr; void* table_dirty = nullptr; uint32_t table_mask_extra = 0xFFFFFFFFu;       // decay's rotating hash tables: the all-empty one k_decay builds the next table in, and the one it empties for the call after (maintenance.hip, round 6)
-  uint8_t* view_class = nullptr; int64_t view_class_cap = 0;        // LiDAR: per view record, 1 = updated by the beam-centric launch (tsdf.hip k_lidar_sparse)
-  // LiDAR view calculation over a dense grid (tsdf.hip k_mark_view_grid): one byte per block of the box around the sensor (cell-major, 64 B per
+  uint8_t* view_class = nullptr; int64_t view_class_cap = 0;        // LiDAR: per view record, 1 = updated by the beam-centric launch (lidar.hip k_lidar_sparse)
+  // LiDAR view calculation over a dense grid (lidar.hip k_mark_view_grid): one byte per block of the box around the sensor (cell-major, 64 B per
   // 4 x 4 x 4 cell) + one byte per cell; all-zero between scans (k_scan_view_grid puts back what the scan set).  `view_grid_dirty`: a scan's
   // launches were not all enqueued (an error return in between) -- the next scan clears the arrays first.
   uint8_t* view_grid_fine = nullptr; int64_t view_grid_cells_cap = 0; bool view_grid_dirty = false;

@@ -1,5 +1,5 @@
 // nvbx_sphere_trace.h -- the sphere-tracing worker of MultiMapper::integrateColor (synthetic depth image for the occlusion test), shared by
-// k_sphere_trace (color.hip) and by k_mark_view (tsdf.hip), which runs it in extra workgroups of the NEXT depth frame's view-marking launch
+// k_sphere_trace (color.hip) and by k_mark_view (nvbx_view.h), which runs it in extra workgroups of the NEXT depth frame's view-marking launch
 // when the colour frame was held back (nvbx_mapper_set_color_deferral): the two are independent -- sphere tracing reads the
 // TSDF and the insert-only hash, view marking inserts hash entries whose pool slots are all-zero (= unobserved, exactly like a missing block).
 #pragma once

@@ -151,7 +151,7 @@ def test_lidar_parity_wide_fov_and_tilted_sensor(oracle_mod, hip_lib, lidar, til
 @pytest.mark.parametrize("thr", [(2.0, 0.5), (0.3, 1.5)])
 def test_lidar_parity_noisy_ranges_with_dropouts(oracle_mod, hip_lib, thr):
     """Range noise and 3 % missing returns: four-beam neighbourhoods that disagree or have holes fall from the bilinear blend to the
-    nearest-beam rule (LidarSensor::sample, tsdf.hip) for a large share of the voxels -- the branch the clean scenes of the other tests
+    nearest-beam rule (LidarSensor::sample, nvbx_view.h) for a large share of the voxels -- the branch the clean scenes of the other tests
     rarely take.  Bit for bit against the oracle, with the thresholds in two positions."""
     from isaac_ros_nvblox_amd import mapper as M
     kw = dict(voxel_size=0.1, lidar_max_integration_distance_m=30.0, raycast_subsampling_factor=2,

@@ -1,7 +1,7 @@
 """Independent float64 model of the view calculation (ViewCalculator::getBlocksInImageViewRaycast as DESIGN.md 3 restates it): which blocks does
 the segment sensor origin -> (depth + truncation distance, capped) of every sub-sampled pixel's ray pass through?  Pure geometry in numpy
 float64 -- the segment's parameter values at the block-grid planes, sorted; the block at the midpoint of every interval -- no stepping, no
-Amanatides-Woo, no float32: it shares no code and no arithmetic with oracle/nvblox_oracle.c raycast_blocks or csrc/tsdf.hip (whose closed-form
+Amanatides-Woo, no float32: it shares no code and no arithmetic with oracle/nvblox_oracle.c raycast_blocks or csrc/nvbx_view.h (whose closed-form
 crossing parameters T_a(k) = fmaf(k, tdelta_a, tmax0_a) are a definition of THIS round, so a third opinion is due).
 
 Float32 stepping and float64 geometry may disagree on blocks a ray only grazes (a corner within rounding error), so the comparison is two-sided

@@ -5,14 +5,9 @@ cd "$(dirname "$0")/.."
 V=${V:-"1,4,16 1,2,32 2,2,16"}
 PFX=${PFX:-LIDAR}; WL=${WL:-lidar}; ARGS=${ARGS:---steps 60 --warmup 10}
 if [ "$1" = build ]; then
-  mkdir -p isaac_ros_nvblox_amd/variants
+  # (the tile constants reach every translation unit that instantiates a view-marking kernel: each variant is a whole build_variant.sh library)
   for v in $V; do IFS=, read tr tc sg <<< "$v"
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -DNVBX_${PFX}_TR=$tr -DNVBX_${PFX}_TC=$tc -DNVBX_${PFX}_SEG=$sg \
-      -c isaac_ros_nvblox_amd/csrc/tsdf.hip -o /tmp/tsdf_$tr$tc$sg.o &
-  done; wait
-  for v in $V; do IFS=, read tr tc sg <<< "$v"
-    objs=$(ls isaac_ros_nvblox_amd/csrc/*.o | grep -v tsdf.o)
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o isaac_ros_nvblox_amd/variants/libnvblox_hip_$tr$tc$sg.so $objs /tmp/tsdf_$tr$tc$sg.o
+    tools/build_variant.sh $tr$tc$sg "-DNVBX_${PFX}_TR=$tr -DNVBX_${PFX}_TC=$tc -DNVBX_${PFX}_SEG=$sg" || exit 1
   done
   ls -la isaac_ros_nvblox_amd/variants
 else

@@ -414,6 +414,20 @@ int nvbx_pointcloud_from_slice(nvbx_mapper* m, const float* image_dev, int32_t r
  * out[x*(Ny*Nz) + y*Nz + z] = signed metres or default_value; AABB given in global voxel indices. */
 int nvbx_esdf_dense_grid(nvbx_mapper* m, const int32_t min_vox[3], const int32_t size_vox[3], float default_value,
                          float* grid_dev);
+/* [U] Interpolator::interpolateOnGPU(points_L, layer, &distances, &success_flags) (nvblox/interpolation/interpolation_3d.h) with
+ * gradients: distance, gradient and validity at n arbitrary points (SEMANTICS.md "Point queries").  layer = NVBX_LAYER_TSDF or
+ * NVBX_LAYER_ESDF (exactly one).  Per axis u = p / voxel_size - 0.5, b = floor(u), t = u - b; the corners are the voxels b + {0, 1}.
+ * Valid when every corner's block carries the layer and the voxel passes the layer's test (TSDF: weight >= min_weight; ESDF: observed,
+ * value +-sqrt(squared_distance_vox) * voxel_size as nvbx_esdf_dense_grid): distance = the trilinear interpolant, gradient = its
+ * analytic gradient per metre.  Otherwise distance = unknown_value, gradient = 0, valid = 0 -- also for a point whose corners leave
+ * the addressable range.  ESDF of a 2-D mapper (esdf_mode 0): bilinear over the plane z = floor(esdf_slice_height / voxel_size),
+ * p.z ignored, gradient z = 0.  min_weight is ignored by ESDF queries; a TSDF query on an occupancy mapper is NVBX_E_INVALID.
+ * points_xyz_dev[n][3], distance_dev[n], gradient_xyz_dev[n][3] (NULL: not written), valid_dev[n] (NULL: not written).
+ * Asynchronous on the mapper's stream; n == 0 launches nothing.  An ESDF query carries held-back work out first; a TSDF query
+ * leaves it held back (it reads nothing that work writes).  The same arithmetic for callers' kernels: nvbx_dev_interpolate_tsdf /
+ * nvbx_dev_interpolate_esdf in nvblox_hip_device.h, bit-identical. */
+int nvbx_query_points(nvbx_mapper* m, uint32_t layer, const float* points_xyz_dev, int64_t n, float min_weight, float unknown_value,
+                      float* distance_dev, float* gradient_xyz_dev, uint8_t* valid_dev);
 
 /* ---- map file (Mapper::saveLayerCake(path) -> bool, loadMap(path) -> bool: nvblox_node.cpp:1663-1668,1698-1703) -----------------
  * A path ending in .nvblx is written as an SQLITE database, like the reference's layer cake: table layers(layer_type, voxel_size,

@@ -161,6 +161,7 @@ SIGNATURES = {
     "nvbx_occupancy_grid_from_slice": (C.c_int, [_vp, _vp, _i32, _i32, _f, _vp]),
     "nvbx_pointcloud_from_slice": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _f, _f, _vp, _pi32]),
     "nvbx_esdf_dense_grid": (C.c_int, [_vp, _vp, _vp, _f, _vp]),
+    "nvbx_query_points": (C.c_int, [_vp, C.c_uint32, _vp, _i64, _f, _f, _vp, _vp, _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),
     "nvbx_block_indices": (_i64, [_vp, C.c_uint32, _vp, _i64]),
     "nvbx_get_block": (C.c_int, [_vp, C.c_uint32, Index3D, _vp]),

@@ -660,6 +660,55 @@ class Mapper:
         self.synchronize()
         return out.cpu().numpy()
 
+    # -- interpolated point queries (nvbx_query_points; SEMANTICS.md "Point queries")
+    def query_tsdf(self, points, min_weight=None, unknown_value=1000.0, out=None):
+        """Trilinear TSDF distance and its gradient per metre at `points` ((n, 3) float32 torch tensor or numpy array, metres):
+        -> (distance [n] f32, gradient [n, 3] f32, valid [n] bool) on the mapper's device.  A corner counts with weight >= min_weight
+        (default: the mapper's mesh_min_weight).  out=(distance, gradient, valid): preallocated tensors, nothing is allocated."""
+        mw = self.params.mesh_min_weight if min_weight is None else min_weight
+        return self._query(LAYER_TSDF, points, mw, unknown_value, out)
+
+    def query_esdf(self, points, unknown_value=1000.0, out=None):
+        """Interpolated ESDF distance and gradient (trilinear in 3-D mode; bilinear in the slice plane in 2-D mode, z ignored);
+        same shapes and rules as query_tsdf."""
+        return self._query(LAYER_ESDF, points, 0.0, unknown_value, out)
+
+    def _query(self, layer, points, min_weight, unknown_value, out):
+        """Runs on the mapper's stream, ordered behind torch's current stream (which produced the points) and ahead of it (which
+        reads the results): no host synchronisation either way."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(points, torch.Tensor):
+            p = points if points.device == dev else points.to(dev)
+            p = p.contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
+        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError("points must be an (n, 3) float32 array, got %s %s" % (tuple(p.shape), p.dtype))
+        n = p.shape[0]
+        if out is None:
+            d = torch.empty(n, dtype=torch.float32, device=dev)
+            g = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            v = torch.empty(n, dtype=torch.bool, device=dev)
+        else:
+            d, g, v = out
+            for t, shape, dts in ((d, (n,), (torch.float32,)), (g, (n, 3), (torch.float32,)), (v, (n,), (torch.bool, torch.uint8))):
+                if t is not None and (t.device != dev or tuple(t.shape) != shape or t.dtype not in dts or not t.is_contiguous()):
+                    raise ValueError("out tensor %s %s does not fit %d points" % (tuple(t.shape), t.dtype, n))
+            if d is None:
+                raise ValueError("out needs a distance tensor")
+        cur = torch.cuda.current_stream(self.device); ms = self.torch_stream()
+        other = ms.cuda_stream != cur.cuda_stream
+        if other and n:
+            ms.wait_stream(cur)
+        self._check(self.lib.nvbx_query_points(self._h, layer, C.c_void_p(p.data_ptr()), n, float(min_weight), float(unknown_value),
+                                               C.c_void_p(d.data_ptr()), C.c_void_p(g.data_ptr()) if g is not None else None,
+                                               C.c_void_p(v.data_ptr()) if v is not None else None))
+        if other and n:
+            cur.wait_stream(ms)
+        self._hold("_keep_q", [p])      # (the kernel reads the points: they, and an uploaded copy, live until the next query)
+        return d, g, v
+
     def mesh(self):
         """Mesh of the last update_color_mesh: dict block index tuple -> dict(vertices, normals, colors, triangles)."""
         nb, nv, nt = C.c_int64(), C.c_int64(), C.c_int64()

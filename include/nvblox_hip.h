@@ -347,7 +347,8 @@ int nvbx_integrate_color_batch(nvbx_mapper* m, int32_t n, const uint8_t* const* 
  * held-back calls each of them carries, "last view" queries: bit for bit -- but the two view-marking launches share one grid and so do the two
  * TSDF-update launches (k_mark_view_pair, k_integrate_tsdf_color_pair): two launches instead of four; the maps share nothing, so nothing else changes.
  * Needs both mappers on one device and one stream (what nvblox::MultiMapper hands out); whatever the pair cannot express -- different streams, depth
- * dilation, a held-back colour BATCH, the ESDF side stream -- falls back to the two calls.  NVBX_DEPTH_PAIR=0 in the environment: always the two calls. */
+ * dilation, a held-back colour BATCH, held-back colour frames of BOTH mappers in different encodings (one rgb8, the other bgra8), the ESDF side
+ * stream -- falls back to the two calls.  NVBX_DEPTH_PAIR=0 in the environment: always the two calls. */
 int nvbx_integrate_depth_pair(nvbx_mapper* ma, const float* depth_a_dev, nvbx_mapper* mb, const float* depth_b_dev, int32_t rows, int32_t cols,
                               const float T_L_C[16], const nvbx_camera* camera);
 /* MultiMapper::updateEsdf() (EsdfMode::k2D) -- nvblox_node.cpp:781.

@@ -486,7 +486,7 @@ static int integrate_depth_pair_impl(nvbx_mapper* ma, FrameSet<Img, 1> fa, nvbx_
   //  launch is residency-bound: every idle 8-wavefront workgroup holds a slot for ~1.5 us)
   static const int pair_b_edt = getenv("NVBX_PAIR_B_EDT_RIDERS") ? atoi(getenv("NVBX_PAIR_B_EDT_RIDERS")) : 64;
   if (sb.n_edt > pair_b_edt && pair_b_edt >= 8) sb.n_edt = pair_b_edt & ~7;
-  const int kind = sa.has_color ? sa.f_kind : (sb.has_color ? sb.f_kind : 0);
+  const int kind = sa.has_color ? sa.f_kind : (sb.has_color ? sb.f_kind : 0);      // (both, in different encodings: the two calls, nvbx_integrate_depth_pair)
   auto fused_args = [&](nvbx_mapper* m, const FrameSet<Img, 1>& f, const DepthSteps<1>& st, auto* out) {
     using FA = std::remove_pointer_t<decltype(out)>;
     FA x{}; x.m = m->d; x.fs = f; x.view_list = (const int4*)m->view_list; x.list_cap = (int32_t)m->capacity; x.mesh_list = m->mesh_list_live(); x.view_export = m->view_export;
@@ -633,12 +633,18 @@ static bool pair_can_fuse(const nvbx_mapper* m) {
   if (m->color_pending.on && (m->color_pending.n != 1 || !fused_colour_applies(m))) return false;      // (its colour frame would be carried in three launches)
   return true;
 }
+// (the pair launch decodes ONE pixel type -- that of whichever mapper holds a colour frame: two held-back frames in different encodings, rgb8 and bgra8,
+//  cannot share it.  Checked before either mapper's preparation, which consumes host state)
+static bool pair_colour_kinds_differ(const nvbx_mapper* ma, const nvbx_mapper* mb) {
+  return ma->color_pending.on && mb->color_pending.on && ma->color_pending.kind != mb->color_pending.kind;
+}
 extern "C" int nvbx_integrate_depth_pair(nvbx_mapper* ma, const float* depth_a_dev, nvbx_mapper* mb, const float* depth_b_dev, int32_t rows, int32_t cols,
                                          const float T_L_C[16], const nvbx_camera* camera) {
   if (!ma || !mb || ma == mb || !depth_a_dev || !depth_b_dev || !T_L_C || !camera || !image_dims_ok(rows, cols)) { set_error("nvbx_integrate_depth_pair: invalid argument (two different mappers, image sides 1 .. 32768)"); return NVBX_E_INVALID; }
   if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_depth_pair: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
   static const int pair_on = getenv("NVBX_DEPTH_PAIR") ? atoi(getenv("NVBX_DEPTH_PAIR")) : 1;       // (A/B: 0 = always the two separate calls)
-  if (!pair_on || ma->device != mb->device || ma->stream != mb->stream || !pair_can_fuse(ma) || !pair_can_fuse(mb)) {
+  if (!pair_on || ma->device != mb->device || ma->stream != mb->stream || !pair_can_fuse(ma) || !pair_can_fuse(mb) ||
+      pair_colour_kinds_differ(ma, mb)) {
     const int rc = nvbx_integrate_depth(ma, depth_a_dev, rows, cols, T_L_C, camera); if (rc) return rc;
     return nvbx_integrate_depth(mb, depth_b_dev, rows, cols, T_L_C, camera);
   }

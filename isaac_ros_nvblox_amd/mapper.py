@@ -385,6 +385,9 @@ class Mapper:
         return self._batch(self.lib.nvbx_integrate_depth_batch, depths, self._torch.float32, poses, cams)
 
     def prepare_color_batch(self, rgbs, poses, cams):
+        # (nvbx_integrate_color_batch takes rgb8 only: a bgra8 frame would be decoded as rgb8)
+        if any(isinstance(i, ColorFrame) and i.channels != 3 for i in rgbs):
+            raise ValueError("integrate_color_batch: rgb8 frames only (3 channels)")
         return self._batch(self.lib.nvbx_integrate_color_batch, rgbs, self._torch.uint8, poses, cams)
 
     def integrate_prepared_batch(self, a):

@@ -62,8 +62,8 @@ __global__ __launch_bounds__(512) void k_integrate_color(DMap m, FrameSetC<Pix, 
 
 // lanes per ray of the sphere-tracing launch for a batch of n cameras (1, 2, 4 or 8)
 static int sphere_trace_lanes(int n) {
-  static const int forced = getenv("NVBX_ST_LANES") ? atoi(getenv("NVBX_ST_LANES")) : 0;       // (sweeps)
-  if (forced == 1 || forced == 2 || forced == 4 || forced == 8) return forced;
+  static const int forced = nvbx_knob_st_lanes(getenv("NVBX_ST_LANES"));       // (sweeps)
+  if (forced) return forced;
   // measured (tools/st_lanes_sweep.sh, profiles/r03d_st_lanes.txt; us per launch at 8 / 4 / 2 / 1 lanes): 8 cameras 30.6 / 23.6 / 21.8 / 26.3,
   // 4 cameras 20.0 / 16.7 / 18.2 / 24.4, 2 cameras 13.1 / 13.5 / 16.1 / 21.4
   return n >= 6 ? 2 : (n >= 3 ? 4 : 8);
@@ -237,8 +237,8 @@ static int trace_rider_of(nvbx_mapper* m, TraceRiderT<NB>* tr) {
   if (rc) return rc;
   tr->synth = m->synth; tr->srows = srows; tr->scols = scols; tr->max_steps = m->p.sphere_tracing_max_steps;
   tr->max_len = m->p.sphere_tracing_max_ray_length_m; tr->eps_m = m->p.sphere_tracing_surface_eps_vox * m->p.voxel_size;
-  static const int fused_lanes = getenv("NVBX_FUSED_TRACE_LANES") ? atoi(getenv("NVBX_FUSED_TRACE_LANES")) : 8;       // (A/B, one frame: 4 or 8 lanes per ray)
-  tr->lanes = NB == 1 ? (fused_lanes == 4 ? 4 : 8) : std::max(2, sphere_trace_lanes(c.n));
+  static const int fused_lanes = nvbx_knob_fused_trace_lanes(getenv("NVBX_FUSED_TRACE_LANES"));       // (A/B, one frame: 4 or 8 lanes per ray)
+  tr->lanes = NB == 1 ? fused_lanes : std::max(2, sphere_trace_lanes(c.n));
   tr->n_wg = sphere_trace_workgroups(tr->lanes, srows, scols, c.n);
   return NVBX_OK;
 }
@@ -260,9 +260,9 @@ void nvbx_mapper::pending_marking_args(int32_t* mark_wg, EsdfArgs* ea_out, bool 
     // longest part of the view-marking launch (18.6 us against the tiles' 16.1; tools/wg_timeline.py --scene hall: k_mark_view 17.7 -> 16.6 us, tools/mark_riders_ab.sh).
     // A BATCH keeps 256: its view-marking launch is residency-bound and more riders in front keep the tiles waiting (8 cameras: 27.0 -> 27.9 us).
     // NVBX_MARK_RIDERS=n: fixed (A/B).
-    static const int fixed = getenv("NVBX_MARK_RIDERS") ? atoi(getenv("NVBX_MARK_RIDERS")) : 0;
+    static const int fixed = nvbx_knob_mark_riders(getenv("NVBX_MARK_RIDERS"));
     const int64_t n_hint = std::max<int64_t>(0, __atomic_load_n(&h_mirror[2], __ATOMIC_RELAXED));
-    *mark_wg = fixed > 0 ? (fixed + 7) / 8 * 8 : (!single_frame ? 256 : (int32_t)std::min<int64_t>(1024, std::max<int64_t>(256, ((n_hint + n_hint / 4 + 3) / 4 + 7) / 8 * 8)));
+    *mark_wg = fixed > 0 ? fixed : (!single_frame ? 256 : (int32_t)std::min<int64_t>(1024, std::max<int64_t>(256, ((n_hint + n_hint / 4 + 3) / 4 + 7) / 8 * 8)));
   }
   *ea_out = ea;
 }

@@ -543,7 +543,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NVBX_SPARSE
 // the beam-centric far-field launch; view_class = nullptr: everything goes to the dense launch
 int launch_lidar_sparse(nvbx_mapper* m, const FrameSet<DepthF32, 1>& fs, const LidarSensor& sensor, bool plain, uint8_t** view_class, int32_t** dense_list) {
   *view_class = nullptr; *dense_list = nullptr;
-  static const int enabled = getenv("NVBX_LIDAR_SPARSE") ? atoi(getenv("NVBX_LIDAR_SPARSE")) : 1;       // (A/B: 0 = dense launch only)
+  static const int enabled = nvbx_knob_switch(getenv("NVBX_LIDAR_SPARSE"));       // (A/B: 0 = dense launch only)
   if (!enabled || !plain || !(m->p.lidar_nearest_interpolation_max_allowable_dist_to_ray_vox <= 0.55f)) return NVBX_OK;
   if (m->view_class_cap < m->capacity) {
     NVBX_HIP(hipStreamSynchronize(m->stream));
@@ -553,9 +553,9 @@ int launch_lidar_sparse(nvbx_mapper* m, const FrameSet<DepthF32, 1>& fs, const L
     NVBX_HIP(hipMalloc(&m->view_class, (((size_t)m->capacity + 15) & ~(size_t)15) + (size_t)NSH * (size_t)m->capacity * 4));
     m->view_class_cap = m->capacity;
   }
-  static const int sparse_grid = getenv("NVBX_LIDAR_SPARSE_GRID") ? atoi(getenv("NVBX_LIDAR_SPARSE_GRID")) : 2048;    // (six resident wavefronts per SIMD = 1536 workgroups; 1536 / 2048 / 2560 / 3072 / 3584 / 4096 / 8192 workgroups: 111.1 / 109.5 / 110.5 / 111.0 / 114.8 / 115.3 / 114.3 us with strided passes and the work list)
+  static const int sparse_grid = nvbx_knob_lidar_sparse_grid(getenv("NVBX_LIDAR_SPARSE_GRID"));    // (six resident wavefronts per SIMD = 1536 workgroups; 1536 / 2048 / 2560 / 3072 / 3584 / 4096 / 8192 workgroups: 111.1 / 109.5 / 110.5 / 111.0 / 114.8 / 115.3 / 114.3 us with strided passes and the work list)
   // (with an exchange buffer registered -- nvbx_set_view_export -- the dense launch walks the whole view list, as it writes every record's index there)
-  static const int use_list = getenv("NVBX_LIDAR_DENSE_LIST") ? atoi(getenv("NVBX_LIDAR_DENSE_LIST")) : 1;       // (A/B: 0 = the dense launch skips the taken records of the whole list)
+  static const int use_list = nvbx_knob_switch(getenv("NVBX_LIDAR_DENSE_LIST"));       // (A/B: 0 = the dense launch skips the taken records of the whole list)
   int32_t* dense = (use_list && !m->view_export) ? reinterpret_cast<int32_t*>(m->view_class + (((size_t)m->capacity + 15) & ~(size_t)15)) : nullptr;
   NVBX_LAUNCH(m, (k_lidar_sparse<DepthF32>), dim3(sparse_grid), dim3(256), m->d, fs, sensor, (const int4*)m->view_list, (int32_t)m->capacity, m->mesh_list_live(), m->view_class, dense);
   *dense_list = dense;

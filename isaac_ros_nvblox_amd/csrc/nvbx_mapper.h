@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/nvblox_hip.h"
 #include "nvbx_internal.h"
+#include "nvbx_knobs.h"       // the NVBX_* environment knobs, validated
 
 namespace nvbx {
 

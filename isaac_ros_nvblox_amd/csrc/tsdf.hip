@@ -282,7 +282,7 @@ int nvbx_mapper::ensure_fuse_buffers() {
 // steps of TWO mappers around two shared launches (k_mark_view_pair, k_integrate_tsdf_color_pair).  The steps are the former body of integrate_depth_impl, cut
 // where it launches; what each step does to the mapper's host state, and in which order, is unchanged.
 static bool fused_colour_applies(const nvbx_mapper* m) {
-  static const int fuse_on = getenv("NVBX_FUSE_COLC") ? atoi(getenv("NVBX_FUSE_COLC")) : 1;      // (A/B: 0 = three launches per frame)
+  static const int fuse_on = nvbx_knob_switch(getenv("NVBX_FUSE_COLC"));      // (A/B: 0 = three launches per frame)
   return fuse_on && m->p.projective_layer_type != 1 && m->p.esdf_mode == 0 && m->p.esdf_propagation == 0 && !m->lidar_integrated && m->capacity <= (1ll << 24);
 }
 template <int NB> struct DepthSteps {
@@ -332,7 +332,7 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
     // riders before or after the tiles (A/B: NVBX_MARK_TILES_FIRST = 0 / 1).  One frame: tiles first (15.2 vs 15.8 us).  A batch of 8: riders first
     // (32.4 vs 42.0 us) -- its 2 688 single-wavefront tile workgroups, each holding its LDS key set, take most of the workgroup slots, and
     // sphere-tracing workgroups dispatched behind them start when the tiles are done: the launch took the SUM of its parts.
-    static const int tiles_first_env = getenv("NVBX_MARK_TILES_FIRST") ? atoi(getenv("NVBX_MARK_TILES_FIRST")) : -1;
+    static const int tiles_first_env = nvbx_knob_mark_tiles_first(getenv("NVBX_MARK_TILES_FIRST"));
     const bool tiles_first = tiles_first_env >= 0 ? tiles_first_env != 0 : NB == 1;
     if (tiles_first) st.tr.n_tile_wg = st.tiles;
     if (st.fused && !st.has_color) m->pending_marking_args(&st.tr.n_mark_wg, &st.ea, NB == 1);
@@ -352,10 +352,9 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
 // a launch grid sized from the count the GPU last reported keeps a margin over it: 25 % + 64 is what a view that grows while exploring needs
 // (NVBX_GRID_MARGIN="percent,blocks": A/B only -- tools/env_ab.sh)
 static int64_t with_grid_margin(int64_t n) {
-  static const char* env = getenv("NVBX_GRID_MARGIN");
-  static const int pct = env ? atoi(env) : 25;
-  static const int blocks = (env && strchr(env, ',')) ? atoi(strchr(env, ',') + 1) : 64;
-  return n + n * pct / 100 + blocks;
+  struct Margin { int pct, blocks; Margin() { nvbx_knob_grid_margin(getenv("NVBX_GRID_MARGIN"), &pct, &blocks); } };
+  static const Margin mg;
+  return n + n * mg.pct / 100 + mg.blocks;
 }
 // step 2: between the two launches -- the host-side steps of the held-back calls, then the sizes of the TSDF-update part
 template <typename Sensor, int NB>
@@ -375,7 +374,7 @@ static int depth_step_between(nvbx_mapper* m, DepthSteps<NB>& st) {
   // grid-stride over the view list: exactly the 1024 workgroups that are resident together (4 per CU)
   // (a camera BATCH: 512 -- its fused launch is residency-bound, 1 024 eight-wavefront workgroups resident, and 1 024 TSDF workgroups in front kept the colour
   //  part waiting: 4 / 8 cameras 0.0382 / 0.0560 -> 0.0365 / 0.0547 ms per step, tools/fused_grid_sweep.sh)
-  static const int grid_cap_env = getenv("NVBX_INTEG_GRID") ? atoi(getenv("NVBX_INTEG_GRID")) : 0;    // (env: tools/integ_grid_sweep.sh, tools/fused_grid_sweep.sh)
+  static const int grid_cap_env = nvbx_knob_integ_grid(getenv("NVBX_INTEG_GRID"));    // (env: tools/integ_grid_sweep.sh, tools/fused_grid_sweep.sh)
   const int grid_cap = grid_cap_env > 0 ? grid_cap_env : (NB > 1 ? 512 : 1024);
   // ... or fewer when the view is smaller: sized from the view count of the last launch the GPU has finished (pinned host memory, not
   // waited for) + 25 % + 64; a hint only -- the kernel grid-strides over whatever the count turns out to be
@@ -393,13 +392,13 @@ static int depth_step_between(nvbx_mapper* m, DepthSteps<NB>& st) {
 template <int NB>
 static void depth_step_fused_riders(nvbx_mapper* m, DepthSteps<NB>& st) {
   st.n_edt = 0; st.ea_edt = m->edt_args;
-  static const int edt_riders = getenv("NVBX_EDT_RIDERS") ? atoi(getenv("NVBX_EDT_RIDERS")) : 256;      // (A/B; a multiple of 8)
+  static const int edt_riders = nvbx_knob_edt_riders(getenv("NVBX_EDT_RIDERS"));      // (A/B; a multiple of 8, at least 8)
   if (m->edt_pending) { st.n_edt = edt_riders; m->edt_pending = false; }
   st.cand = st.tr.cand;
   st.cand_idx = st.tr.cand_cnt_idx;
   const int64_t c_hint = std::max<int64_t>(0, __atomic_load_n(&m->h_mirror[3], __ATOMIC_RELAXED));         // candidates of the last colour frame the GPU has finished
   // (no colour frame: update + distance transform only; no colour launch finished yet -- a new or just cleared map: as many as the TSDF part)
-  static const int color_cap = getenv("NVBX_COLOR_GRID") ? atoi(getenv("NVBX_COLOR_GRID")) : 1024;      // (A/B: workgroups of the colour part, tools/fused_grid_sweep.sh)
+  static const int color_cap = nvbx_knob_color_grid(getenv("NVBX_COLOR_GRID"));      // (A/B: workgroups of the colour part, tools/fused_grid_sweep.sh)
   st.cgrid = !st.has_color ? 0 : (int)std::max<int64_t>(8, std::min<int64_t>(std::min<int64_t>(m->capacity, color_cap), c_hint == 0 ? (int64_t)st.grid : ((with_grid_margin(c_hint) + 7) / 8) * 8));
   // a held-back union step of the multi-GPU exchange (nvbx_mark_esdf_dirty_gathered_deferred) rides here in eight workgroups: the peers'
   // blocks become ESDF-dirty for the NEXT marking pass (its own marking launch, or a ride in the colour launch, would be a third launch;
@@ -484,8 +483,8 @@ static int integrate_depth_pair_impl(nvbx_mapper* ma, FrameSet<Img, 1> fa, nvbx_
   if (sb.fused) depth_step_fused_riders<1>(mb, sb);
   // (the second mapper of a pair is the foreground mapper: a few blocks.  Its distance transform gets 64 workers instead of 256 -- they grid-stride, and the
   //  launch is residency-bound: every idle 8-wavefront workgroup holds a slot for ~1.5 us)
-  static const int pair_b_edt = getenv("NVBX_PAIR_B_EDT_RIDERS") ? atoi(getenv("NVBX_PAIR_B_EDT_RIDERS")) : 64;
-  if (sb.n_edt > pair_b_edt && pair_b_edt >= 8) sb.n_edt = pair_b_edt & ~7;
+  static const int pair_b_edt = nvbx_knob_pair_b_edt_riders(getenv("NVBX_PAIR_B_EDT_RIDERS"));
+  if (sb.n_edt > pair_b_edt) sb.n_edt = pair_b_edt;
   const int kind = sa.has_color ? sa.f_kind : (sb.has_color ? sb.f_kind : 0);      // (both, in different encodings: the two calls, nvbx_integrate_depth_pair)
   auto fused_args = [&](nvbx_mapper* m, const FrameSet<Img, 1>& f, const DepthSteps<1>& st, auto* out) {
     using FA = std::remove_pointer_t<decltype(out)>;
@@ -642,7 +641,7 @@ extern "C" int nvbx_integrate_depth_pair(nvbx_mapper* ma, const float* depth_a_d
                                          const float T_L_C[16], const nvbx_camera* camera) {
   if (!ma || !mb || ma == mb || !depth_a_dev || !depth_b_dev || !T_L_C || !camera || !image_dims_ok(rows, cols)) { set_error("nvbx_integrate_depth_pair: invalid argument (two different mappers, image sides 1 .. 32768)"); return NVBX_E_INVALID; }
   if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_depth_pair: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
-  static const int pair_on = getenv("NVBX_DEPTH_PAIR") ? atoi(getenv("NVBX_DEPTH_PAIR")) : 1;       // (A/B: 0 = always the two separate calls)
+  static const int pair_on = nvbx_knob_switch(getenv("NVBX_DEPTH_PAIR"));       // (A/B: 0 = always the two separate calls)
   if (!pair_on || ma->device != mb->device || ma->stream != mb->stream || !pair_can_fuse(ma) || !pair_can_fuse(mb) ||
       pair_colour_kinds_differ(ma, mb)) {
     const int rc = nvbx_integrate_depth(ma, depth_a_dev, rows, cols, T_L_C, camera); if (rc) return rc;

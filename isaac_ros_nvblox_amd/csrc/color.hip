@@ -94,13 +94,7 @@ static int color_setup(nvbx_mapper* m, int32_t n, const Pix* imgs, int32_t rows,
     fs->chunk = ch; }
   const int32_t srows = rows / f.subsample, scols = cols / f.subsample;
   if (srows < 2 || scols < 2) { set_error("colour image too small for the sphere-tracing subsampling"); return NVBX_E_INVALID; }
-  if ((int64_t)srows * scols * n > m->synth_cap) {
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    if (m->synth) NVBX_HIP(hipFree(m->synth));
-    m->synth = nullptr; m->synth_cap = 0;
-    NVBX_HIP(hipMalloc(&m->synth, (size_t)srows * scols * n * 4));
-    m->synth_cap = (int64_t)srows * scols * n;
-  }
+  if (m->synth.ensure(m->stream, (size_t)srows * scols * n * 4)) return NVBX_E_DEVICE;
   m->synth_rows = srows; m->synth_cols = scols; m->synth_last = n - 1;
   *srows_out = srows; *scols_out = scols;
   return NVBX_OK;
@@ -117,7 +111,7 @@ static int color_launch_trace(nvbx_mapper* m, const PoseSet<NB>& ps, int32_t n, 
   const int rl = sphere_trace_lanes(n);
   const int32_t n_trace = sphere_trace_workgroups(rl, srows, scols, n);
   const dim3 st_grid((unsigned)(n_trace + mark_wg));
-#define NVBX_ST_LAUNCH(RL) NVBX_LAUNCH(m, (k_sphere_trace<NB, RL>), st_grid, dim3(256), m->d, ps, m->synth, srows, scols, m->p.sphere_tracing_max_steps, \
+#define NVBX_ST_LAUNCH(RL) NVBX_LAUNCH(m, (k_sphere_trace<NB, RL>), st_grid, dim3(256), m->d, ps, m->synth.as<float>(), srows, scols, m->p.sphere_tracing_max_steps, \
                                        m->p.sphere_tracing_max_ray_length_m, m->p.sphere_tracing_surface_eps_vox * m->p.voxel_size, n_trace, mark_wg, ea)
   if (rl == 8) NVBX_ST_LAUNCH(8); else if (rl == 4) NVBX_ST_LAUNCH(4); else if (rl == 2) NVBX_ST_LAUNCH(2); else NVBX_ST_LAUNCH(1);
 #undef NVBX_ST_LAUNCH
@@ -145,7 +139,7 @@ static int color_launch_integrate(nvbx_mapper* m, const FrameSetC<Pix, NB>& fs, 
   // (replay_pair: the distance transform the held-back updateEsdf has just armed rides here -- its marking pass rode in the sphere-tracing launch)
   int32_t n_edt = 0;
   if (take_edt && mark_wg == 0 && m->edt_pending) { n_edt = 256; ea = m->edt_args; m->edt_pending = false; }
-  NVBX_LAUNCH(m, (k_integrate_color<Pix, NB>), dim3(grid + mark_wg + n_edt), dim3(512), m->d, fs, m->synth, srows, scols, m->mesh_list_live(), (int32_t)mark_wg, ea, imp, n_edt);
+  NVBX_LAUNCH(m, (k_integrate_color<Pix, NB>), dim3(grid + mark_wg + n_edt), dim3(512), m->d, fs, m->synth.as<float>(), srows, scols, m->mesh_list_live(), (int32_t)mark_wg, ea, imp, n_edt);
   NVBX_HIP(hipGetLastError());
   // this launch looks at every allocated slot and votes + repairs the band bits of each block a LiDAR scan left F_BAND_STALE: from here on (stream
   // order) no block is stale, and the next camera frames may take the fused launches again (the switch was sticky until clear())
@@ -235,7 +229,7 @@ static int trace_rider_of(nvbx_mapper* m, TraceRiderT<NB>* tr) {
   if (c.kind == 0) { FrameSetC<PixRgb8, NB> fs; rc = pending_setup<PixRgb8, NB>(m, c, &fs, &tr->ps, &srows, &scols); }
   else { FrameSetC<PixBgra8, NB> fs; rc = pending_setup<PixBgra8, NB>(m, c, &fs, &tr->ps, &srows, &scols); }
   if (rc) return rc;
-  tr->synth = m->synth; tr->srows = srows; tr->scols = scols; tr->max_steps = m->p.sphere_tracing_max_steps;
+  tr->synth = m->synth.as<float>(); tr->srows = srows; tr->scols = scols; tr->max_steps = m->p.sphere_tracing_max_steps;
   tr->max_len = m->p.sphere_tracing_max_ray_length_m; tr->eps_m = m->p.sphere_tracing_surface_eps_vox * m->p.voxel_size;
   static const int fused_lanes = nvbx_knob_fused_trace_lanes(getenv("NVBX_FUSED_TRACE_LANES"));       // (A/B, one frame: 4 or 8 lanes per ray)
   tr->lanes = NB == 1 ? fused_lanes : std::max(2, sphere_trace_lanes(c.n));
@@ -365,7 +359,7 @@ extern "C" int nvbx_get_synthetic_depth(nvbx_mapper* m, float* out_host, int64_t
   const int64_t n = (int64_t)m->synth_rows * m->synth_cols;
   if (!out_host || n == 0) return NVBX_OK;
   if (n > capacity) return NVBX_E_CAPACITY;
-  NVBX_HIP(hipMemcpyAsync(out_host, m->synth + (size_t)m->synth_last * n, n * 4, hipMemcpyDeviceToHost, m->stream));    // (a batch: its last camera's image)
+  NVBX_HIP(hipMemcpyAsync(out_host, m->synth.as<float>() + (size_t)m->synth_last * n, n * 4, hipMemcpyDeviceToHost, m->stream));    // (a batch: its last camera's image)
   NVBX_HIP(hipStreamSynchronize(m->stream));
   return NVBX_OK;
 }

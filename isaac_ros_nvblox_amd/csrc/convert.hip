@@ -207,18 +207,13 @@ extern "C" int nvbx_split_depth_by_mask(nvbx_mapper* m, const float* depth_dev, 
     set_error("nvbx_split_depth_by_mask: invalid argument"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
   const int64_t mn = (int64_t)mask_rows * mask_cols;
-  if (mn > m->mask_zmin_cap) {
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    if (m->mask_zmin) NVBX_HIP(hipFree(m->mask_zmin));
-    m->mask_zmin = nullptr; m->mask_zmin_cap = 0;
-    NVBX_HIP(hipMalloc(&m->mask_zmin, (size_t)mn * 4));
-    m->mask_zmin_cap = mn;
-  }
+  if (m->mask_zmin.ensure(m->stream, (size_t)mn * 4)) return NVBX_E_DEVICE;
+  uint32_t* zmin = m->mask_zmin.as<uint32_t>();
   const MaskGeom g = make_mask_geom(T_CM_CD, dc, mc, rows, cols, mask_rows, mask_cols);
-  NVBX_HIP(hipMemsetAsync(m->mask_zmin, 0x7F, (size_t)mn * 4, m->stream));        // 0x7F7F7F7F = 3.4e38
+  NVBX_HIP(hipMemsetAsync(zmin, 0x7F, (size_t)mn * 4, m->stream));        // 0x7F7F7F7F = 3.4e38
   const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)rows * cols + 255) / 256, 2048);
-  NVBX_LAUNCH(m, k_mask_zmin, dim3(grid), dim3(256), g, depth_dev, m->mask_zmin);
-  NVBX_LAUNCH(m, k_split_depth, dim3(grid), dim3(256), g, depth_dev, mask_dev, (const uint32_t*)m->mask_zmin, occlusion_threshold_m, unmasked_dev, masked_dev, overlay_dev);
+  NVBX_LAUNCH(m, k_mask_zmin, dim3(grid), dim3(256), g, depth_dev, zmin);
+  NVBX_LAUNCH(m, k_split_depth, dim3(grid), dim3(256), g, depth_dev, mask_dev, (const uint32_t*)zmin, occlusion_threshold_m, unmasked_dev, masked_dev, overlay_dev);
   NVBX_HIP(hipGetLastError());
   return NVBX_OK;
 }

@@ -223,14 +223,10 @@ extern "C" int nvbx_remove_small_components(nvbx_mapper* m, uint8_t* mask_dev, i
   if (!m || !mask_dev || rows <= 0 || cols <= 0) { set_error("nvbx_remove_small_components: invalid argument"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
   const int64_t n = (int64_t)rows * cols;
-  if (3 * n + 16 > m->cc_scratch_elems) {
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    if (m->cc_scratch) NVBX_HIP(hipFree(m->cc_scratch));
-    m->cc_scratch = nullptr; m->cc_scratch_elems = 0; m->cc_ready_n = 0;
-    NVBX_HIP(hipMalloc(&m->cc_scratch, (size_t)(3 * n + 16) * 4));
-    m->cc_scratch_elems = 3 * n + 16;
-  }
-  int32_t* label = m->cc_scratch;
+  bool grew = false;
+  if (m->cc_scratch.ensure(m->stream, (size_t)(3 * n + 16) * 4, &grew)) return NVBX_E_DEVICE;
+  if (grew) m->cc_ready_n = 0;
+  int32_t* label = m->cc_scratch.as<int32_t>();
   const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
   if (m->cc_ready_n != n) {            // first call / another image size: establish the resting state
     NVBX_LAUNCH(m, k_cc_init, dim3(grid), dim3(256), n, label, label + n, label + 2 * n);
@@ -365,14 +361,10 @@ extern "C" int nvbx_dynamic_depth_split(nvbx_mapper* m, const float* depth_dev, 
   NVBX_HIP(hipSetDevice(m->device));
   if (m->join_side_keeping_held()) return NVBX_E_DEVICE;      // (reads TSDF voxels and the freespace layer only: held-back work stays held back, as for nvbx_detect_dynamics)
   const int64_t n = (int64_t)rows * cols;
-  if (6 * n + 16 > m->dyn_scratch_elems) {
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    if (m->dyn_scratch) NVBX_HIP(hipFree(m->dyn_scratch));
-    m->dyn_scratch = nullptr; m->dyn_scratch_elems = 0; m->dyn_ready_n = 0;
-    NVBX_HIP(hipMalloc(&m->dyn_scratch, (size_t)(6 * n + 16) * 4));
-    m->dyn_scratch_elems = 6 * n + 16;
-  }
-  int32_t* label2 = m->dyn_scratch; int32_t* size2 = label2 + 2 * n; uint32_t* zmin2 = reinterpret_cast<uint32_t*>(size2 + 2 * n);
+  bool grew = false;
+  if (m->dyn_scratch.ensure(m->stream, (size_t)(6 * n + 16) * 4, &grew)) return NVBX_E_DEVICE;
+  if (grew) m->dyn_ready_n = 0;
+  int32_t* label2 = m->dyn_scratch.as<int32_t>(); int32_t* size2 = label2 + 2 * n; uint32_t* zmin2 = reinterpret_cast<uint32_t*>(size2 + 2 * n);
   const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
   if (m->dyn_ready_n != n) {            // first call / another image size: resting state of both parities
     NVBX_LAUNCH(m, k_dyn_init, dim3(grid), dim3(256), n, label2, size2, zmin2);

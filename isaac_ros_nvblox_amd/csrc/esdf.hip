@@ -283,16 +283,6 @@ extern "C" int nvbx_esdf_slice_to_image(nvbx_mapper* m, float unknown_value, flo
   return NVBX_OK;
 }
 
-static int ensure_staging(nvbx_mapper* m, int64_t bytes) {
-  if (bytes <= m->staging_bytes) return NVBX_OK;
-  NVBX_HIP(hipStreamSynchronize(m->stream));
-  if (m->staging) NVBX_HIP(hipFree(m->staging));
-  m->staging = nullptr; m->staging_bytes = 0;
-  NVBX_HIP(hipMalloc(&m->staging, bytes));
-  m->staging_bytes = bytes;
-  return NVBX_OK;
-}
-
 // The slice for a HOST caller in ONE wait (processEsdf slices right after updateEsdf and publishes from the host, nvblox_node.cpp:774-889: ten
 // times a second the node drains its pipeline here).  Size, then image, then download used to be three round trips to the device -- the layer's AABB
 // had to reach the host before the slicing launch could be sized.  k_esdf_slice_rows reads the AABB itself (device counters), writes

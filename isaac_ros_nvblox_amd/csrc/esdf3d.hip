@@ -175,15 +175,10 @@ int nvbx_mapper::update_esdf_3d() {
   const int64_t nblk = (int64_t)w.nbx * w.nby * w.nbz, nvox = nblk * 512;
   if (nvox > (1ll << 31)) { set_error("3-D ESDF update: the changed region (+ 2 R) exceeds 2^31 voxels; update more often or lower esdf_max_distance_m"); return NVBX_E_CAPACITY; }
   const int64_t need = nvox / 8 + nvox + nvox * 4 + 1024;
-  if (need > esdf3_scratch_bytes) {
-    if (esdf3_scratch) NVBX_HIP(hipFree(esdf3_scratch));
-    esdf3_scratch = nullptr; esdf3_scratch_bytes = 0;
-    NVBX_HIP(hipMalloc(&esdf3_scratch, (size_t)need));
-    esdf3_scratch_bytes = need;
-  }
-  uint32_t* B = (uint32_t*)esdf3_scratch;                         // 4 B / voxel first (alignment), then 1 B / voxel, then the bits
-  int8_t* A = (int8_t*)esdf3_scratch + nvox * 4;
-  uint8_t* bits = (uint8_t*)esdf3_scratch + nvox * 5;
+  if (esdf3_scratch.ensure(stream, (size_t)need)) return NVBX_E_DEVICE;
+  uint32_t* B = esdf3_scratch.as<uint32_t>();                        // 4 B / voxel first (alignment), then 1 B / voxel, then the bits
+  int8_t* A = esdf3_scratch.as<int8_t>() + nvox * 4;
+  uint8_t* bits = esdf3_scratch.as<uint8_t>() + nvox * 5;
   const unsigned gblk = (unsigned)std::min<int64_t>(nblk, 1 << 16);
   NVBX_LAUNCH(this, k_esdf3_bits, dim3(gblk), dim3(64), d, w, bits);
   NVBX_LAUNCH(this, k_esdf3_x, dim3((unsigned)std::min<int64_t>((nvox / 8 + 255) / 256, 1 << 16)), dim3(256), w, (const uint8_t*)bits, A, a.ri);

@@ -59,16 +59,10 @@ extern "C" int64_t nvbx_tsdf_zero_crossings(nvbx_mapper* m, float min_z_m, float
     m->zc_valid = false; m->zc_points.clear();
     int64_t cap = std::min<int64_t>(m->capacity * 64, (int64_t)1 << 24);       // one crossing per column and block in practice; a column can hold up to four
     for (int attempt = 0; attempt < 2; attempt++) {
-      if (m->staging_bytes < cap * 16) {
-        NVBX_HIP(hipStreamSynchronize(m->stream));
-        if (m->staging) NVBX_HIP(hipFree(m->staging));
-        m->staging = nullptr; m->staging_bytes = 0;
-        NVBX_HIP(hipMalloc(&m->staging, (size_t)cap * 16));
-        m->staging_bytes = cap * 16;
-      }
+      if (m->staging.ensure(m->stream, (size_t)cap * 16)) return NVBX_E_DEVICE;
       NVBX_LAUNCH(m, k_zero_tmp3, dim3(1), dim3(1), m->d);
       NVBX_LAUNCH(m, k_tsdf_zero_crossings, dim3((unsigned)std::min<int64_t>(m->capacity, 4096)), dim3(64), m->d, m->p.voxel_size, min_z_m, max_z_m,
-                  m->p.esdf_min_weight > 0.0f ? m->p.esdf_min_weight : 1e-4f, (float4*)m->staging, (int32_t)cap);
+                  m->p.esdf_min_weight > 0.0f ? m->p.esdf_min_weight : 1e-4f, m->staging.as<float4>(), (int32_t)cap);
       if (m->fetch_counters()) return NVBX_E_DEVICE;
       const int64_t found = m->h_counters[C_TMP];
       if (found <= cap) break;
@@ -78,7 +72,7 @@ extern "C" int64_t nvbx_tsdf_zero_crossings(nvbx_mapper* m, float min_z_m, float
     }
     const int64_t n = m->h_counters[C_TMP];
     std::vector<float> tmp((size_t)n * 4);
-    if (n) NVBX_HIP(hipMemcpy(tmp.data(), m->staging, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (n) NVBX_HIP(hipMemcpy(tmp.data(), m->staging.p, (size_t)n * 16, hipMemcpyDeviceToHost));
     std::vector<int64_t> order((size_t)n);
     for (int64_t i = 0; i < n; i++) order[(size_t)i] = i;
     std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {      // deterministic order: x, then y, then z

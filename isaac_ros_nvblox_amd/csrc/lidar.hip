@@ -545,21 +545,17 @@ int launch_lidar_sparse(nvbx_mapper* m, const FrameSet<DepthF32, 1>& fs, const L
   *view_class = nullptr; *dense_list = nullptr;
   static const int enabled = nvbx_knob_switch(getenv("NVBX_LIDAR_SPARSE"));       // (A/B: 0 = dense launch only)
   if (!enabled || !plain || !(m->p.lidar_nearest_interpolation_max_allowable_dist_to_ray_vox <= 0.55f)) return NVBX_OK;
-  if (m->view_class_cap < m->capacity) {
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    if (m->view_class) NVBX_HIP(hipFree(m->view_class));
-    m->view_class = nullptr; m->view_class_cap = 0;
-    // [capacity class bytes][NSH x capacity view-list indices: the dense launch's work list, one region per shard]
-    NVBX_HIP(hipMalloc(&m->view_class, (((size_t)m->capacity + 15) & ~(size_t)15) + (size_t)NSH * (size_t)m->capacity * 4));
-    m->view_class_cap = m->capacity;
-  }
+  // [capacity class bytes][NSH x capacity view-list indices: the dense launch's work list, one region per shard]
+  const size_t class_bytes = ((size_t)m->capacity + 15) & ~(size_t)15;
+  if (m->view_class.ensure(m->stream, class_bytes + (size_t)NSH * (size_t)m->capacity * 4)) return NVBX_E_DEVICE;
+  uint8_t* vc = m->view_class.as<uint8_t>();
   static const int sparse_grid = nvbx_knob_lidar_sparse_grid(getenv("NVBX_LIDAR_SPARSE_GRID"));    // (six resident wavefronts per SIMD = 1536 workgroups; 1536 / 2048 / 2560 / 3072 / 3584 / 4096 / 8192 workgroups: 111.1 / 109.5 / 110.5 / 111.0 / 114.8 / 115.3 / 114.3 us with strided passes and the work list)
   // (with an exchange buffer registered -- nvbx_set_view_export -- the dense launch walks the whole view list, as it writes every record's index there)
   static const int use_list = nvbx_knob_switch(getenv("NVBX_LIDAR_DENSE_LIST"));       // (A/B: 0 = the dense launch skips the taken records of the whole list)
-  int32_t* dense = (use_list && !m->view_export) ? reinterpret_cast<int32_t*>(m->view_class + (((size_t)m->capacity + 15) & ~(size_t)15)) : nullptr;
-  NVBX_LAUNCH(m, (k_lidar_sparse<DepthF32>), dim3(sparse_grid), dim3(256), m->d, fs, sensor, (const int4*)m->view_list, (int32_t)m->capacity, m->mesh_list_live(), m->view_class, dense);
+  int32_t* dense = (use_list && !m->view_export) ? reinterpret_cast<int32_t*>(vc + class_bytes) : nullptr;
+  NVBX_LAUNCH(m, (k_lidar_sparse<DepthF32>), dim3(sparse_grid), dim3(256), m->d, fs, sensor, (const int4*)m->view_list, (int32_t)m->capacity, m->mesh_list_live(), vc, dense);
   *dense_list = dense;
-  *view_class = m->view_class;
+  *view_class = vc;
   return NVBX_OK;
 }
 
@@ -585,17 +581,13 @@ int launch_view_grid(nvbx_mapper* m, const FrameSet<DepthF32, 1>& fs, const Lida
   static const int64_t cap_mb = getenv("NVBX_VIEW_GRID_MAX_MB") ? atoll(getenv("NVBX_VIEW_GRID_MAX_MB")) : 128;
   if (ncx > 256 || ncz > 256 || cells * 64 > (cap_mb << 20)) return NVBX_OK;
   const size_t coarse_bytes = ((size_t)cells + 3) & ~(size_t)3;
-  if (m->view_grid_cells_cap < cells) {
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    if (m->view_grid_fine) NVBX_HIP(hipFree(m->view_grid_fine));
-    m->view_grid_fine = nullptr; m->view_grid_cells_cap = 0;
-    NVBX_HIP(hipMalloc(&m->view_grid_fine, (size_t)cells * 64 + coarse_bytes));      // [fine: 64 B per cell][coarse: 1 B per cell]
-    m->view_grid_cells_cap = cells; m->view_grid_dirty = true;
-  }
-  if (m->view_grid_dirty) NVBX_HIP(hipMemsetAsync(m->view_grid_fine, 0, (size_t)m->view_grid_cells_cap * 64 + (((size_t)m->view_grid_cells_cap + 3) & ~(size_t)3), m->stream));
+  bool grew = false;
+  if (m->view_grid_fine.ensure(m->stream, (size_t)cells * 64 + coarse_bytes, &grew)) return NVBX_E_DEVICE;      // [fine: 64 B per cell][coarse: 1 B per cell]
+  if (grew) { m->view_grid_cells = cells; m->view_grid_dirty = true; }
+  if (m->view_grid_dirty) NVBX_HIP(hipMemsetAsync(m->view_grid_fine.p, 0, m->view_grid_fine.bytes, m->stream));
   m->view_grid_dirty = true;                 // until all three launches are enqueued
   ViewGrid vg{};
-  vg.fine = m->view_grid_fine; vg.coarse = m->view_grid_fine + (size_t)m->view_grid_cells_cap * 64;
+  vg.fine = m->view_grid_fine.as<uint8_t>(); vg.coarse = vg.fine + (size_t)m->view_grid_cells * 64;
   vg.cx = (int32_t)std::floor(f.t_LC[0] / f.block_size); vg.cy = (int32_t)std::floor(f.t_LC[1] / f.block_size); vg.cz = (int32_t)std::floor(f.t_LC[2] / f.block_size);
   vg.ox = vg.cx - (int32_t)H; vg.oy = vg.cy - (int32_t)H; vg.oz = vg.cz - (int32_t)Hz;
   vg.ncx = (int32_t)ncx; vg.ncy = (int32_t)ncx; vg.ncz = (int32_t)ncz;
@@ -621,15 +613,9 @@ static bool same_lidar(const nvbx_lidar& a, const nvbx_lidar& b) { return memcmp
 // beam direction tables: sin / cos evaluated in double on the host from the float model parameters, rounded to float
 // (the oracle builds the same tables the same way, so view rays are bit-identical)
 static int ensure_lidar_tables(nvbx_mapper* m, const nvbx_lidar* ld, const nvbx_lidar_model& l) {
-  if (m->lidar_tab && same_lidar(m->lidar_cached, *ld)) return NVBX_OK;
+  if (m->lidar_tab.p && same_lidar(m->lidar_cached, *ld)) return NVBX_OK;
   const size_t n = (size_t)l.rows + (size_t)l.cols;
-  if (n > m->lidar_tab_cap) {
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    if (m->lidar_tab) NVBX_HIP(hipFree(m->lidar_tab));
-    m->lidar_tab = nullptr; m->lidar_tab_cap = 0;
-    NVBX_HIP(hipMalloc(&m->lidar_tab, n * sizeof(float2)));
-    m->lidar_tab_cap = n;
-  }
+  if (m->lidar_tab.ensure(m->stream, n * sizeof(float2))) return NVBX_E_DEVICE;
   m->lidar_host.resize(n * 2);
   for (int k = 0; k < l.rows; k++) {
     const double el = (double)l.max_el - (double)k * (double)l.rpp_el;
@@ -639,7 +625,7 @@ static int ensure_lidar_tables(nvbx_mapper* m, const nvbx_lidar* ld, const nvbx_
     const double az = -(double)NVBX_PI_F + (double)j * (double)l.rpp_az;
     m->lidar_host[2 * ((size_t)l.rows + j)] = (float)sin(az); m->lidar_host[2 * ((size_t)l.rows + j) + 1] = (float)cos(az);
   }
-  NVBX_HIP(hipMemcpyAsync(m->lidar_tab, m->lidar_host.data(), n * sizeof(float2), hipMemcpyHostToDevice, m->stream));
+  NVBX_HIP(hipMemcpyAsync(m->lidar_tab.p, m->lidar_host.data(), n * sizeof(float2), hipMemcpyHostToDevice, m->stream));
   NVBX_HIP(hipStreamSynchronize(m->stream));    // once per sensor model
   m->lidar_cached = *ld;
   return NVBX_OK;
@@ -667,7 +653,7 @@ extern "C" int nvbx_integrate_lidar_depth(nvbx_mapper* m, const float* range_dev
   FrameSet<DepthF32, 1> fs{}; fs.n = 1; fs.img[0] = DepthF32{range_dev};
   fs.f[0] = m->make_frame(T_L_C, &none, rows, cols, m->p.raycast_subsampling_factor);
   fs.f[0].max_dist = m->p.lidar_max_integration_distance_m;
-  LidarSensor s{l, (const float2*)m->lidar_tab, (const float2*)m->lidar_tab + rows,
+  LidarSensor s{l, m->lidar_tab.as<const float2>(), m->lidar_tab.as<const float2>() + rows,
                 m->p.lidar_linear_interpolation_max_allowable_difference_vox * m->p.voxel_size,
                 m->p.lidar_nearest_interpolation_max_allowable_dist_to_ray_vox * m->p.voxel_size};
   return integrate_lidar_frame(m, fs, s);

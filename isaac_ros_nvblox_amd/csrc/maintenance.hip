@@ -476,11 +476,6 @@ __global__ void k_remap_mesh_records(MeshRecord* rec, int32_t n, int64_t old_vre
   }
 }
 
-namespace {
-struct PoolArr { void** p; size_t bytes_per_block; int fill; };
-template <typename T> PoolArr arr(T** p, size_t bpb, int fill) { return PoolArr{reinterpret_cast<void**>(p), bpb, fill}; }
-}  // namespace
-
 int nvbx_mapper::grow_map(int64_t new_cap) {
   if (new_cap <= capacity) return NVBX_OK;
   if (new_cap > (1ll << 24)) new_cap = 1ll << 24;
@@ -493,15 +488,11 @@ int nvbx_mapper::grow_map(int64_t new_cap) {
     if (free_b < need) { set_error("pool growth: not enough free HBM, the block pools stay at their size"); max_capacity = capacity; return NVBX_OK; } }
   // Failure-atomic: EVERY new array is allocated first; if one allocation fails they are all released and the map is untouched
   // (the pools stay at their size).  Only then are the contents copied and the pointers / capacity swapped in one commit step.
-  std::vector<PoolArr> arrs = {
-      arr(&d.free_stack, 4, -1), arr(&d.slot_flags, 4, 0), arr(&d.slot_index, 12, 0), arr(&d.slot_entry, 4, 0), arr(&d.slot_stamp, 4, 0xFF),
-      arr(&d.slot_consumed, 4, 0xFF), arr(&d.slot_cam, 4, 0xFF), arr(&d.tsdf, 4096, 0), arr(&d.color, 4096, 0), arr(&d.esdf, 4096, 0), arr(&view_list, 16, -1),
-      arr(&export_idx, 12, -1), arr(&cleared_idx, 12, -1), arr(&d.site_bits, 8, 0), arr(&d.obs_bits, 8, 0), arr(&d.inside_bits, 8, 0),
-      arr(&mesh_rec, sizeof(MeshRecord), -1)};
-  if (d.freespace) arrs.push_back(arr(&d.freespace, 512 * 16, 0));
-  const int64_t new_vcap = std::min<int64_t>(new_cap * 192, 48ll << 20), new_tcap = new_vcap * 2;
+  std::vector<PoolArr> arrs;                                   // the per-block arrays that exist (pool_arrays, mapper.hip)
+  for (const PoolArr& a : pool_arrays(new_cap)) if (a.bytes_per_block && *a.p) arrs.push_back(a);
+  const int64_t new_vcap = mesh_verts(new_cap), new_tcap = new_vcap * 2;
   const bool grow_mesh = new_vcap > mesh_vert_cap;
-  uint64_t tsz = 1; while (tsz < (uint64_t)new_cap * 2) tsz <<= 1;
+  const uint64_t tsz = hash_slots(new_cap);
   std::vector<void*> fresh;                                    // everything allocated so far (released on failure)
   auto take = [&](size_t bytes) -> void* {
     void* q = nullptr;

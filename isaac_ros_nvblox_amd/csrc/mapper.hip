@@ -180,45 +180,39 @@ __global__ __launch_bounds__(512) void k_recompute_band(DMap m, float trunc) {
 }
 
 // ------------------------------------------------------------------------------------------------ host helpers
+std::vector<PoolArr> nvbx_mapper::pool_arrays(int64_t cap) {
+  const size_t n = (size_t)cap, mv = (size_t)mesh_verts(cap);
+  auto per_block = [n](auto** p, size_t bpb, int fill) { return PoolArr{reinterpret_cast<void**>(p), bpb, fill, bpb * n}; };
+  auto other = [](auto** p, size_t bytes) { return PoolArr{reinterpret_cast<void**>(p), 0, -1, bytes}; };
+  return {
+      // (grow_map copies the per-block arrays in this order)
+      per_block(&d.free_stack, 4, -1), per_block(&d.slot_flags, 4, 0), per_block(&d.slot_index, 12, 0), per_block(&d.slot_entry, 4, 0), per_block(&d.slot_stamp, 4, 0xFF),
+      per_block(&d.slot_consumed, 4, 0xFF), per_block(&d.slot_cam, 4, 0xFF), per_block(&d.tsdf, 4096, 0), per_block(&d.color, 4096, 0), per_block(&d.esdf, 4096, 0),
+      per_block(&view_list, 16, -1),       // int4 {slot, x, y, z} per block in view
+      per_block(&export_idx, 12, -1), per_block(&cleared_idx, 12, -1), per_block(&d.site_bits, 8, 0), per_block(&d.obs_bits, 8, 0), per_block(&d.inside_bits, 8, 0),
+      per_block(&mesh_rec, sizeof(MeshRecord), -1),
+      PoolArr{reinterpret_cast<void**>(&d.freespace), 512 * 16, 0, 0},       // on first use: ensure_freespace_pool (dynamics.hip)
+      // grow_map has code of its own for these: the hash table is rebuilt, the work lists and mesh arenas move segment by segment
+      other(&d.table, hash_slots(cap) * sizeof(Entry)), other(&d.lists, (size_t)N_LISTS * NSH * n * 4),
+      other(&mesh_vert, mv * 12), other(&mesh_nrm, mv * 12), other(&mesh_col, mv * 4), other(&mesh_tri, mv * 2 * 12),
+      // one size at every capacity
+      other(&d.counters, C_NUM * 4), other(&d.shc, S_NUM * NSH * SH_STRIDE * 4), other(&export_count, 64),
+      // decay's spare hash tables, on first use: prepare_tables (maintenance.hip)
+      other(&table_spare, 0), other(&table_dirty, 0)};
+}
+
 static int alloc_all(nvbx_mapper* m) {
   const int64_t cap = m->capacity;
-  uint64_t tsz = 1; while (tsz < (uint64_t)cap * 2) tsz <<= 1;
+  const uint64_t tsz = nvbx_mapper::hash_slots(cap);
   DMap& d = m->d;
   d.capacity = (uint32_t)cap; d.mask = (uint32_t)(tsz - 1);
   { uint32_t lg = 0; while ((1ull << lg) < tsz) lg++; d.shift = 32u - lg; }
-  NVBX_HIP(hipMalloc(&d.table, tsz * sizeof(Entry)));
-  NVBX_HIP(hipMalloc(&d.free_stack, cap * 4));
-  NVBX_HIP(hipMalloc(&d.counters, C_NUM * 4));
+  for (const PoolArr& a : m->pool_arrays(cap)) if (a.bytes) NVBX_HIP(hipMalloc(a.p, a.bytes));
+  m->mesh_vert_cap = nvbx_mapper::mesh_verts(cap); m->mesh_tri_cap = m->mesh_vert_cap * 2;
   // (k_init_map of the -DNVBX_CHECK_INVARIANTS variant keeps some of them across clear().  ON THE MAPPER'S STREAM: a memset on the null stream is
   //  not ordered with a non-blocking stream and landed after k_init_map once in a while -- a map with no free slot, tests/cpp rccl_fusion)
   NVBX_HIP(hipMemsetAsync(d.counters, 0, C_NUM * 4, m->stream));
-  NVBX_HIP(hipMalloc(&d.slot_flags, cap * 4));
-  NVBX_HIP(hipMalloc(&d.slot_index, cap * 12));
-  NVBX_HIP(hipMalloc(&d.slot_entry, cap * 4));
-  NVBX_HIP(hipMalloc(&d.slot_stamp, cap * 4));
-  NVBX_HIP(hipMalloc(&d.slot_consumed, cap * 4));
-  NVBX_HIP(hipMalloc(&d.slot_cam, cap * 4));
-  NVBX_HIP(hipMalloc(&d.tsdf, cap * 4096));
-  NVBX_HIP(hipMalloc(&d.color, cap * 4096));
-  NVBX_HIP(hipMalloc(&d.esdf, cap * 4096));
-  NVBX_HIP(hipMalloc(&m->view_list, cap * 16));    // int4 {slot, x, y, z} per block in view
-  NVBX_HIP(hipMalloc(&d.lists, (size_t)N_LISTS * NSH * cap * 4));
-  NVBX_HIP(hipMalloc(&d.shc, S_NUM * NSH * SH_STRIDE * 4));
-  NVBX_HIP(hipMalloc(&m->export_idx, cap * 12));
-  NVBX_HIP(hipMalloc(&m->export_count, 64));
-  NVBX_HIP(hipMalloc(&m->cleared_idx, cap * 12));
-  NVBX_HIP(hipMalloc(&d.site_bits, cap * 8));
-  NVBX_HIP(hipMalloc(&d.obs_bits, cap * 8));
-  NVBX_HIP(hipMalloc(&d.inside_bits, cap * 8));
-  // mesh arena
-  m->mesh_vert_cap = std::min<int64_t>(cap * 192, 48ll << 20); m->mesh_tri_cap = m->mesh_vert_cap * 2;
-  NVBX_HIP(hipMalloc(&m->mesh_vert, m->mesh_vert_cap * 12));
-  NVBX_HIP(hipMalloc(&m->mesh_nrm, m->mesh_vert_cap * 12));
-  NVBX_HIP(hipMalloc(&m->mesh_col, m->mesh_vert_cap * 4));
-  NVBX_HIP(hipMalloc(&m->mesh_tri, m->mesh_tri_cap * 12));
-  NVBX_HIP(hipMalloc(&m->mesh_rec, cap * sizeof(MeshRecord)));
-  m->staging_bytes = 8 << 20;
-  NVBX_HIP(hipMalloc(&m->staging, m->staging_bytes));
+  if (m->staging.ensure(m->stream, 8 << 20)) return NVBX_E_DEVICE;
   NVBX_HIP(hipHostMalloc(&m->h_counters, C_NUM * 4));
   NVBX_HIP(hipHostMalloc(&m->h_shc, S_NUM * NSH * SH_STRIDE * 4));
   NVBX_HIP(hipHostMalloc(&m->h_mirror, 64, hipHostMallocMapped));
@@ -393,11 +387,7 @@ extern "C" int nvbx_mapper_destroy(nvbx_mapper* m) {
   if (m->ev_main) (void)hipEventDestroy(m->ev_main);
   if (m->ev_side) (void)hipEventDestroy(m->ev_side);
   if (m->side) (void)hipStreamDestroy(m->side);
-  DMap& d = m->d;
-  void* ptrs[] = {d.table, d.free_stack, d.counters, d.slot_flags, d.slot_index, d.slot_entry, d.slot_stamp, d.slot_consumed, d.slot_cam, d.tsdf, d.color, d.esdf,
-                  m->view_list, d.lists, d.shc, m->export_idx, m->export_count, m->cleared_idx, d.site_bits, d.obs_bits, d.inside_bits,
-                  m->table_spare, m->table_dirty, m->synth, m->view_class, m->view_grid_fine, m->color_cand, m->depth_pre, m->mask_zmin, m->apply_postab, m->esdf3_scratch, m->cc_scratch, m->dyn_scratch, d.freespace, m->lidar_tab, m->mesh_vert, m->mesh_nrm, m->mesh_col, m->mesh_tri, m->mesh_rec, m->staging};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
+  for (const PoolArr& a : m->pool_arrays(m->capacity)) if (*a.p) (void)hipFree(*a.p);      // (a half-built mapper: what was not allocated is null)
   // (both streams are idle: whatever read a held-back colour frame has finished)
   (void)m->take_pending(); m->release_consumed_frames();
   if (m->stream_registered) nvbx::frames_forget_owner(m, m->device, m->stream);
@@ -408,7 +398,7 @@ extern "C" int nvbx_mapper_destroy(nvbx_mapper* m) {
   if (m->h_mirror) (void)hipHostFree(m->h_mirror);
   if (m->slice_pinned) (void)hipHostFree(m->slice_pinned);
   if (m->own_stream && m->stream) (void)hipStreamDestroy(m->stream);
-  delete m;
+  delete m;      // (the scratch buffers: ~DevBuf)
   return NVBX_OK;
 }
 
@@ -611,11 +601,11 @@ extern "C" int nvbx_get_blocks(nvbx_mapper* m, uint32_t layer, const nvbx_index3
   const size_t bb = 512 * ref_voxel_bytes(layer);
   const uint32_t ilayer = internal_layer(m, layer);
   if (!ilayer) { if (found_out) memset(found_out, 0, (size_t)n * 4); return NVBX_OK; }
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)((m->staging_bytes - 65536) / (bb + 16)));
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)((m->staging.bytes - 65536) / (bb + 16)));
   for (int64_t o = 0; o < n; o += chunk) {
     const int64_t c = std::min(chunk, n - o);
-    int32_t* d_idx = (int32_t*)m->staging; int32_t* d_found = d_idx + 3 * c;
-    uint8_t* d_out = (uint8_t*)m->staging + (((size_t)c * 16 + 255) & ~(size_t)255);
+    int32_t* d_idx = m->staging.as<int32_t>(); int32_t* d_found = d_idx + 3 * c;
+    uint8_t* d_out = m->staging.as<uint8_t>() + (((size_t)c * 16 + 255) & ~(size_t)255);
     NVBX_HIP(hipMemcpyAsync(d_idx, idx + o, (size_t)c * 12, hipMemcpyHostToDevice, m->stream));
     NVBX_LAUNCH(m, k_gather_blocks, dim3((unsigned)c), dim3(512), m->d, ilayer, (int32_t)(layer == NVBX_LAYER_OCCUPANCY), d_idx, (int32_t)c, d_out, d_found);
     NVBX_HIP(hipMemcpyAsync((uint8_t*)voxels_out + (size_t)o * bb, d_out, (size_t)c * bb, hipMemcpyDeviceToHost, m->stream));
@@ -644,11 +634,11 @@ extern "C" int nvbx_set_blocks(nvbx_mapper* m, uint32_t layer, const nvbx_index3
   if (m->begin_dirtying()) return NVBX_E_DEVICE;
   const size_t bb = 512 * ref_voxel_bytes(layer);
   const EsdfArgs ea = m->make_esdf_args();
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)((m->staging_bytes - 65536) / (bb + 16)));
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)((m->staging.bytes - 65536) / (bb + 16)));
   for (int64_t o = 0; o < n; o += chunk) {
     const int64_t c = std::min(chunk, n - o);
-    int32_t* d_idx = (int32_t*)m->staging;
-    uint8_t* d_in = (uint8_t*)m->staging + (((size_t)c * 16 + 255) & ~(size_t)255);
+    int32_t* d_idx = m->staging.as<int32_t>();
+    uint8_t* d_in = m->staging.as<uint8_t>() + (((size_t)c * 16 + 255) & ~(size_t)255);
     NVBX_HIP(hipMemcpyAsync(d_idx, idx + o, (size_t)c * 12, hipMemcpyHostToDevice, m->stream));
     NVBX_HIP(hipMemcpyAsync(d_in, (const uint8_t*)voxels_in + (size_t)o * bb, (size_t)c * bb, hipMemcpyHostToDevice, m->stream));
     NVBX_LAUNCH(m, k_scatter_blocks, dim3((unsigned)c), dim3(512), m->d, ilayer, (int32_t)(layer == NVBX_LAYER_OCCUPANCY), (const int32_t*)d_idx, (const uint8_t*)d_in, bb,

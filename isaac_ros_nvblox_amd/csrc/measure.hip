@@ -136,23 +136,18 @@ extern "C" int nvbx_apply_measurements(nvbx_mapper* m, const nvbx_measurement_bl
   NVBX_HIP(hipSetDevice(m->device));
   if (m->join_side()) return NVBX_E_DEVICE;
   { const int rc = m->maybe_grow(); if (rc) return rc; }
-  if (!m->apply_postab || m->apply_postab_cap < m->capacity) {
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    if (m->apply_postab) NVBX_HIP(hipFree(m->apply_postab));
-    m->apply_postab = nullptr; m->apply_postab_cap = 0;
-    NVBX_HIP(hipMalloc(&m->apply_postab, (size_t)m->capacity * MAX_BATCH * 4));
-    NVBX_HIP(hipMemsetAsync(m->apply_postab, 0, (size_t)m->capacity * MAX_BATCH * 4, m->stream));
-    m->apply_postab_cap = m->capacity;
-  }
+  bool grew = false;
+  if (m->apply_postab.ensure(m->stream, (size_t)m->capacity * MAX_BATCH * 4, &grew)) return NVBX_E_DEVICE;
+  if (grew) NVBX_HIP(hipMemsetAsync(m->apply_postab.p, 0, m->apply_postab.bytes, m->stream));
   if (m->begin_dirtying()) return NVBX_E_DEVICE;
   { const int rc = next_frame_id(m); if (rc) return rc; }
   nvbx_camera none{1.f, 1.f, 0.f, 0.f, 1, 1};
   float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   const Frame f = m->make_frame(I, &none, 1, 1, 1);          // (the integrator parameters; no camera is involved in applying measurements)
   const MeasRec* all = reinterpret_cast<const MeasRec*>(gathered_dev);
-  NVBX_LAUNCH(m, k_apply_index, dim3(64, (unsigned)world), dim3(256), m->d, all, counts_dev, world, stride_blocks, owner_mod, owner_rank, m->frame_id, m->apply_postab,
+  NVBX_LAUNCH(m, k_apply_index, dim3(64, (unsigned)world), dim3(256), m->d, all, counts_dev, world, stride_blocks, owner_mod, owner_rank, m->frame_id, m->apply_postab.as<int32_t>(),
               (int4*)m->view_list, (int32_t)m->capacity);
-  NVBX_LAUNCH(m, k_apply_fuse, dim3((unsigned)std::min<int64_t>(m->capacity, 1024)), dim3(512), m->d, f, all, stride_blocks, world, m->apply_postab,
+  NVBX_LAUNCH(m, k_apply_fuse, dim3((unsigned)std::min<int64_t>(m->capacity, 1024)), dim3(512), m->d, f, all, stride_blocks, world, m->apply_postab.as<int32_t>(),
               (const int4*)m->view_list, (int32_t)m->capacity, m->mesh_list_live());
   NVBX_HIP(hipGetLastError());
   m->last_view_frame = m->frame_id; m->last_camera_view_frame = m->frame_id; m->last_camera_view_mask = 1u << (world - 1); m->last_view_batch = world;

@@ -4,10 +4,12 @@
 #include <stdint.h>
 #include <string>
 #include <cmath>
+#include <algorithm>
 #include <vector>
 #include "../../include/nvblox_hip.h"
 #include "nvbx_internal.h"
 #include "nvbx_knobs.h"       // the NVBX_* environment knobs, validated
+#include "nvbx_devbuf.h"      // DevBuf (scratch memory that grows on demand), PoolArr (the table of capacity-sized arrays)
 
 namespace nvbx {
 
@@ -88,6 +90,10 @@ struct nvbx_mapper {
   int32_t* h_mirror = nullptr;       // host view of DMap::host_mirror
   int maybe_grow(int64_t extra_blocks_wanted = 0);
   int grow_map(int64_t new_capacity);
+  // THE list of the map's device arrays, with their sizes at `cap` blocks (mapper.hip): creation, pool growth and destruction all walk it
+  std::vector<nvbx::PoolArr> pool_arrays(int64_t cap);
+  static uint64_t hash_slots(int64_t cap) { uint64_t tsz = 1; while (tsz < (uint64_t)cap * 2) tsz <<= 1; return tsz; }      // hash table entries: a power of two, load <= 1/2
+  static int64_t mesh_verts(int64_t cap) { return std::min<int64_t>(cap * 192, 48ll << 20); }                              // mesh arena: vertices (triangles: twice as many)
   int64_t growths = 0;
   nvbx::DMap d{};
   // lists (device)
@@ -97,19 +103,19 @@ struct nvbx_mapper {
   int32_t* export_count = nullptr;
   int32_t* cleared_idx = nullptr;    // int32[capacity][3]: Index3D of projective-layer blocks deallocated since nvbx_take_cleared_blocks
   // LiDAR beam direction tables (float2 {sin, cos}: rows elevations then cols azimuths), rebuilt when the model changes
-  void* lidar_tab = nullptr; size_t lidar_tab_cap = 0; nvbx_lidar lidar_cached{}; std::vector<float> lidar_host;
+  nvbx::DevBuf lidar_tab; nvbx_lidar lidar_cached{}; std::vector<float> lidar_host;
   // mask splitting scratch: nearest depth (in the mask camera) that landed on each mask pixel
-  uint32_t* mask_zmin = nullptr; int64_t mask_zmin_cap = 0;
+  nvbx::DevBuf mask_zmin;
   // depth preprocessing scratch (dilated depth image)
-  float* depth_pre = nullptr; int64_t depth_pre_cap = 0;
+  nvbx::DevBuf depth_pre;
   // colour scratch
-  float* synth = nullptr; int64_t synth_cap = 0; int32_t synth_rows = 0, synth_cols = 0, synth_last = 0;
+  nvbx::DevBuf synth; int32_t synth_rows = 0, synth_cols = 0, synth_last = 0;
   // mesh arena
   float* mesh_vert = nullptr; float* mesh_nrm = nullptr; uint8_t* mesh_col = nullptr; int32_t* mesh_tri = nullptr;
   nvbx::MeshRecord* mesh_rec = nullptr;
   int64_t mesh_vert_cap = 0, mesh_tri_cap = 0;
   // staging
-  void* staging = nullptr; int64_t staging_bytes = 0;
+  nvbx::DevBuf staging;
   // nvbx_esdf_slice_to_host: pinned, device-mapped [16-int header][image] that k_esdf_slice_rows writes directly (one wait per host slice)
   float* slice_pinned = nullptr; float* slice_pinned_dev = nullptr; int64_t slice_pinned_elems = 0;
   // every kernel launch bumps enqueue_seq (NVBX_LAUNCH*); nvbx_esdf_slice_size remembers it: a slice_to_image right behind it re-uses the counters
@@ -134,14 +140,14 @@ struct nvbx_mapper {
   int64_t time_ms = 0;               // update_time_ms of the next integrateDepth
   int ensure_freespace_pool();
   int update_freespace();            // after the TSDF update of a depth frame (projective_layer_type 2)
-  int32_t* apply_postab = nullptr; int64_t apply_postab_cap = 0;      // nvbx_apply_measurements: per slot, the record position of each rank (+1)
-  int32_t* cc_scratch = nullptr; int64_t cc_scratch_elems = 0;      // connected components: label[n], size[2][n]
+  nvbx::DevBuf apply_postab;         // nvbx_apply_measurements: per slot, the record position of each rank (+1)
+  nvbx::DevBuf cc_scratch;           // connected components: label[n], size[2][n]
   int64_t cc_ready_n = 0; int cc_parity = 0;                         // image size the arrays are initialised for; which size array the next call uses
-  int32_t* dyn_scratch = nullptr; int64_t dyn_scratch_elems = 0;    // nvbx_dynamic_depth_split: label[2][n], size[2][n], nearest depth[2][n] (by call parity)
+  nvbx::DevBuf dyn_scratch;          // nvbx_dynamic_depth_split: label[2][n], size[2][n], nearest depth[2][n] (by call parity)
   int64_t dyn_ready_n = 0; int dyn_parity = 0;
   // EsdfMode::k3D (esdf3d.hip)
   int update_esdf_3d();
-  void* esdf3_scratch = nullptr; int64_t esdf3_scratch_bytes = 0; int64_t esdf3_blocks_marked = 0, esdf3_window_voxels = 0;
+  nvbx::DevBuf esdf3_scratch; int64_t esdf3_blocks_marked = 0, esdf3_window_voxels = 0;
   // held-back EDT of the last updateEsdf (NVBX_DEFER_EDT=0 disables): see nvbx_update_esdf
   bool defer_edt = true, edt_pending = false; nvbx::EsdfArgs edt_args{};
   int flush_edt();
@@ -198,21 +204,19 @@ struct nvbx_mapper {
   bool replay_pair_applies() const;  // color.hip: a held-back colour frame + updateEsdf can be replayed in two launches (replay_pair)
   int replay_pair();
 // -- fused colour + TSDF launch of the pipelined order (two launches per frame)
-  int4* color_cand = nullptr;        // [2][fuse_cap] candidate records {slot, block index} of the held-back colour frame (parity cand_parity)
-  int64_t fuse_cap = 0;
+  nvbx::DevBuf color_cand;           // int4 [2][capacity] candidate records {slot, block index} of the held-back colour frame (parity cand_parity)
   int cand_parity = 0;
   bool lidar_integrated = false;     // a LiDAR scan has been integrated since the last clear: blocks may be F_BAND_STALE -> no fused launches
-  int ensure_fuse_buffers();         // tsdf.hip
   // color.hip: the marking pass that rides in the view-marking launch (0 workgroups: none), and the held-back colour frame's set-up for the
   // fused launch (FrameSetC<Pix, 1>: rgb8 / bgra8 share one layout; FrameSetC<PixRgb8, MAX_BATCH> for a held-back batch)
   void pending_marking_args(int32_t* mark_wg, nvbx::EsdfArgs* ea_out, bool single_frame);
   int pending_color_fused_args(void* fsc_out, int* kind, int32_t* srows, int32_t* scols);
   void* table_spare = nullptr; void* table_dirty = nullptr; uint32_t table_mask_extra = 0xFFFFFFFFu;       // decay's rotating hash tables: the all-empty one k_decay builds the next table in, and the one it empties for the call after (maintenance.hip, round 6)
-  uint8_t* view_class = nullptr; int64_t view_class_cap = 0;        // LiDAR: per view record, 1 = updated by the beam-centric launch (lidar.hip k_lidar_sparse)
+  nvbx::DevBuf view_class;           // LiDAR: per view record, 1 = updated by the beam-centric launch (lidar.hip k_lidar_sparse)
   // LiDAR view calculation over a dense grid (lidar.hip k_mark_view_grid): one byte per block of the box around the sensor (cell-major, 64 B per
   // 4 x 4 x 4 cell) + one byte per cell; all-zero between scans (k_scan_view_grid puts back what the scan set).  `view_grid_dirty`: a scan's
   // launches were not all enqueued (an error return in between) -- the next scan clears the arrays first.
-  uint8_t* view_grid_fine = nullptr; int64_t view_grid_cells_cap = 0; bool view_grid_dirty = false;
+  nvbx::DevBuf view_grid_fine; int64_t view_grid_cells = 0; bool view_grid_dirty = false;      // (view_grid_cells: the cell count the arrays are laid out for)
   int32_t* view_export = nullptr; int64_t view_export_cap = 0;      // nvbx_set_view_export
   int reset_consumed_list();         // empty a consumed dirty list (tiny launch; rare paths only)
   int begin_dirtying() { const int rc = reset_consumed_list(); dirty_since_mark = true; return rc; }

@@ -268,16 +268,6 @@ static_assert(2 * sizeof(FusedArgs<DepthF32, PixRgb8>) <= 4096, "k_integrate_tsd
 // (a depth batch AND a colour batch in one argument block: the 4 KiB kernel-argument limit is why the colour path's frames are FrameCore)
 static_assert(sizeof(DMap) + sizeof(FrameSet<DepthF32, MAX_BATCH>) + sizeof(FrameSetC<PixRgb8, MAX_BATCH>) + sizeof(EsdfArgs) + sizeof(ImportArgs) + 160 <= 4096, "k_integrate_tsdf_color<.., MAX_BATCH>: kernel arguments");
 
-int nvbx_mapper::ensure_fuse_buffers() {
-  if (fuse_cap == capacity && color_cand) return NVBX_OK;
-  NVBX_HIP(hipStreamSynchronize(stream));
-  if (color_cand) NVBX_HIP(hipFree(color_cand));
-  color_cand = nullptr; fuse_cap = 0;
-  NVBX_HIP(hipMalloc(&color_cand, (size_t)capacity * 2 * sizeof(int4)));
-  fuse_cap = capacity;
-  return NVBX_OK;
-}
-
 // ---- One depth frame's two launches, in STEPS (round 6): integrate_depth_impl runs them in order for one mapper; nvbx_integrate_depth_pair interleaves the
 // steps of TWO mappers around two shared launches (k_mark_view_pair, k_integrate_tsdf_color_pair).  The steps are the former body of integrate_depth_impl, cut
 // where it launches; what each step does to the mapper's host state, and in which order, is unchanged.
@@ -337,10 +327,10 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
     if (tiles_first) st.tr.n_tile_wg = st.tiles;
     if (st.fused && !st.has_color) m->pending_marking_args(&st.tr.n_mark_wg, &st.ea, NB == 1);
     if (st.fused && st.has_color) {
-      if (m->ensure_fuse_buffers()) { m->pipelined_order = false; return NVBX_E_DEVICE; }
+      if (m->color_cand.ensure(m->stream, (size_t)m->capacity * 2 * sizeof(int4))) { m->pipelined_order = false; return NVBX_E_DEVICE; }      // (the capacity only grows: the buffer is [2][capacity])
       const int64_t hw_seen = std::max<int64_t>(1, __atomic_load_n(&m->h_mirror[1], __ATOMIC_RELAXED));
       st.tr.n_scan_wg = (int32_t)std::min<int64_t>(256, 8 * ((hw_seen + hw_seen / 4 + 64 + 2047) / 2048));      // 256 slots per workgroup and pass; a hint only (the riders grid-stride)
-      st.tr.cand = m->color_cand + (size_t)m->cand_parity * m->fuse_cap;
+      st.tr.cand = m->color_cand.as<int4>() + (size_t)m->cand_parity * (size_t)m->capacity;
       st.tr.cand_cnt_idx = C_CAND_COUNT + m->cand_parity; st.tr.cand_reset_idx = C_CAND_COUNT + (1 - m->cand_parity);
       m->cand_parity ^= 1;      // (the next fused launch resets THIS count, whether or not the colour launch below is reached: an error return in between leaves no stale candidates behind)
       m->pending_marking_args(&st.tr.n_mark_wg, &st.ea, NB == 1);        // (the held-back integrateColor's marking pass, in call order: before its colour integration below)
@@ -441,7 +431,7 @@ static int integrate_depth_impl(nvbx_mapper* m, FrameSet<Img, NB> fs, const Sens
       depth_step_fused_riders<NB>(m, st);
       const dim3 g((unsigned)(st.n_edt + grid + st.cgrid + st.imp.n_wg));
 #define NVBX_FUSED_LAUNCH(PIX, PLAIN, FC) NVBX_LAUNCH(m, (k_integrate_tsdf_color<Img, PIX, NB, PLAIN>), g, dim3(512), m->d, fs, sensor, (const int4*)m->view_list, (int32_t)m->capacity, \
-        m->mesh_list_live(), m->view_export, (int32_t)m->view_export_cap, spec_lanes, (int32_t)grid, FC, (const float*)m->synth, st.f_srows, st.f_scols, st.cand, st.cand_idx, st.n_edt, st.ea_edt, st.imp)
+        m->mesh_list_live(), m->view_export, (int32_t)m->view_export_cap, spec_lanes, (int32_t)grid, FC, m->synth.as<const float>(), st.f_srows, st.f_scols, st.cand, st.cand_idx, st.n_edt, st.ea_edt, st.imp)
       if (NB > 1 || st.f_kind == 0) {
         if (plain) NVBX_FUSED_LAUNCH(PixRgb8, true, st.fsc); else NVBX_FUSED_LAUNCH(PixRgb8, false, st.fsc);
       } else if constexpr (NB == 1) {
@@ -490,7 +480,7 @@ static int integrate_depth_pair_impl(nvbx_mapper* ma, FrameSet<Img, 1> fa, nvbx_
     using FA = std::remove_pointer_t<decltype(out)>;
     FA x{}; x.m = m->d; x.fs = f; x.view_list = (const int4*)m->view_list; x.list_cap = (int32_t)m->capacity; x.mesh_list = m->mesh_list_live(); x.view_export = m->view_export;
     x.view_export_cap = (int32_t)m->view_export_cap; x.spec_lanes = st.spec_lanes; x.n_tsdf_wg = (int32_t)st.grid; memcpy(&x.fsc, &st.fsc, sizeof(x.fsc));
-    x.synth = (const float*)m->synth; x.srows = st.f_srows; x.scols = st.f_scols; x.cand = st.cand; x.cand_cnt_idx = st.cand_idx; x.n_edt_wg = st.n_edt; x.ea = st.ea_edt; x.imp = st.imp;
+    x.synth = m->synth.as<const float>(); x.srows = st.f_srows; x.scols = st.f_scols; x.cand = st.cand; x.cand_cnt_idx = st.cand_idx; x.n_edt_wg = st.n_edt; x.ea = st.ea_edt; x.imp = st.imp;
     x.n_wg = st.n_edt + st.grid + st.cgrid + st.imp.n_wg;
     *out = x;
   };
@@ -578,16 +568,10 @@ static int integrate_cameras(nvbx_mapper* m, int32_t n, const Img* imgs, int32_t
   for (int c = 0; c < n; c++) { fs.f[c] = m->make_frame(T_L_C + 16 * c, cameras + c, rows, cols, m->p.raycast_subsampling_factor); fs.img[c] = imgs[c]; }
   if (dilate) {             // (single frames only: nvbx_integrate_depth_batch falls back to separate calls)
     const int64_t npx = (int64_t)rows * cols;
-    if (npx > m->depth_pre_cap) {
-      NVBX_HIP(hipStreamSynchronize(m->stream));
-      if (m->depth_pre) NVBX_HIP(hipFree(m->depth_pre));
-      m->depth_pre = nullptr; m->depth_pre_cap = 0;
-      NVBX_HIP(hipMalloc(&m->depth_pre, (size_t)npx * 4));
-      m->depth_pre_cap = npx;
-    }
+    if (m->depth_pre.ensure(m->stream, (size_t)npx * 4)) return NVBX_E_DEVICE;
     NVBX_LAUNCH(m, (k_dilate_invalid<Img>), dim3((unsigned)std::min<int64_t>((npx + 255) / 256, 4096)), dim3(256), imgs[0], rows, cols,
-                m->p.depth_preprocessing_num_dilations, m->depth_pre);
-    FrameSet<DepthF32, 1> fd{}; fd.n = 1; fd.f[0] = fs.f[0]; fd.img[0] = DepthF32{m->depth_pre};
+                m->p.depth_preprocessing_num_dilations, m->depth_pre.as<float>());
+    FrameSet<DepthF32, 1> fd{}; fd.n = 1; fd.f[0] = fs.f[0]; fd.img[0] = DepthF32{m->depth_pre.as<float>()};
     return integrate_depth_impl<DepthF32, CameraSensor, 1>(m, fd, CameraSensor{});
   }
   return integrate_depth_impl<Img, CameraSensor, NB>(m, fs, CameraSensor{});

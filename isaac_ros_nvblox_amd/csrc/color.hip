@@ -126,19 +126,19 @@ static int color_launch_integrate(nvbx_mapper* m, const FrameSetC<Pix, NB>& fs, 
   EsdfArgs ea = m->make_esdf_args();
   ImportArgs imp{};
   const bool own = m->p.esdf_mode == 0 && m->p.esdf_propagation == 0 && m->dirty_since_mark && !m->premark_consumed && ea.bz_hi >= ea.bz_lo && ea.bz_hi - ea.bz_lo + 1 <= 63;
-  if (own || m->import_pending) {
+  if (own || m->held.import_pending) {
     m->mark_pass++; ea.mark_pass = m->mark_pass; m->unresolved_marks = true;
     if (own) { mark_wg = 256; m->dirty_since_mark = false; m->premark_consumed = !ea.self_reset; }     // (pipelined order: the pass empties the list itself)
-    if (m->import_pending) {             // (only ever set in 2-D mode with a valid band: nvbx_mark_esdf_dirty_gathered_deferred)
-      imp.g = m->import_ptr; imp.world = m->import_world; imp.self_rank = m->import_rank; imp.max_count = m->import_max;
-      { const int n_peers = std::max(1, (m->import_rank >= 0 && m->import_rank < m->import_world) ? m->import_world - 1 : m->import_world);
+    if (m->held.import_pending) {             // (only ever set in 2-D mode with a valid band: nvbx_mark_esdf_dirty_gathered_deferred)
+      imp.g = m->held.import_ptr; imp.world = m->held.import_world; imp.self_rank = m->held.import_rank; imp.max_count = m->held.import_max;
+      { const int n_peers = std::max(1, (m->held.import_rank >= 0 && m->held.import_rank < m->held.import_world) ? m->held.import_world - 1 : m->held.import_world);
         imp.n_wg = n_peers * std::max(32, std::min(256, 1024 / n_peers)); }       // ~one list entry per worker at a few hundred blocks per peer
-      mark_wg += imp.n_wg; m->import_pending = false;
+      mark_wg += imp.n_wg; m->held.import_pending = false;
     }
   }
   // (replay_pair: the distance transform the held-back updateEsdf has just armed rides here -- its marking pass rode in the sphere-tracing launch)
   int32_t n_edt = 0;
-  if (take_edt && mark_wg == 0 && m->edt_pending) { n_edt = 256; ea = m->edt_args; m->edt_pending = false; }
+  if (take_edt && mark_wg == 0 && m->held.edt_pending) { n_edt = 256; ea = m->held.edt_args; m->held.edt_pending = false; }
   NVBX_LAUNCH(m, (k_integrate_color<Pix, NB>), dim3(grid + mark_wg + n_edt), dim3(512), m->d, fs, m->synth.as<float>(), srows, scols, m->mesh_list_live(), (int32_t)mark_wg, ea, imp, n_edt);
   NVBX_HIP(hipGetLastError());
   // this launch looks at every allocated slot and votes + repairs the band bits of each block a LiDAR scan left F_BAND_STALE: from here on (stream
@@ -179,7 +179,7 @@ static bool defer_color(nvbx_mapper* m, int kind, int32_t n, const void* const* 
   if (*rc_out) return true;
   if (hipSetDevice(m->device) != hipSuccess || m->replay_deferred()) { *rc_out = NVBX_E_DEVICE; return true; }     // an older held-back frame goes first
   m->release_consumed_frames();
-  nvbx_mapper::ColorPending& c = m->color_pending;
+  nvbx_mapper::ColorPending& c = m->held.color_pending;
   const size_t bytes = (size_t)rows * (size_t)cols * (kind == 0 ? 3u : 4u);
   // Where each held-back image lives until it is carried out:
   //   a frame of nvbx_frame_acquire (nvblox::Image<T> device memory, nvbx_color_image_acquire): RETAINED -- no copy, in either mode (frames.hip);
@@ -223,7 +223,7 @@ static int pending_setup(nvbx_mapper* m, const nvbx_mapper::ColorPending& c, Fra
 }
 template <int NB>
 static int trace_rider_of(nvbx_mapper* m, TraceRiderT<NB>* tr) {
-  const nvbx_mapper::ColorPending& c = m->color_pending;
+  const nvbx_mapper::ColorPending& c = m->held.color_pending;
   int32_t srows = 0, scols = 0;
   int rc;
   if (c.kind == 0) { FrameSetC<PixRgb8, NB> fs; rc = pending_setup<PixRgb8, NB>(m, c, &fs, &tr->ps, &srows, &scols); }
@@ -238,7 +238,7 @@ static int trace_rider_of(nvbx_mapper* m, TraceRiderT<NB>* tr) {
 }
 // ... its sphere tracing as a rider of the caller's launch
 int nvbx_mapper::pending_color_trace_rider(void* out) {
-  return color_pending.n == 1 ? trace_rider_of<1>(this, static_cast<TraceRiderT<1>*>(out)) : trace_rider_of<MAX_BATCH>(this, static_cast<TraceRiderT<MAX_BATCH>*>(out));
+  return held.color_pending.n == 1 ? trace_rider_of<1>(this, static_cast<TraceRiderT<1>*>(out)) : trace_rider_of<MAX_BATCH>(this, static_cast<TraceRiderT<MAX_BATCH>*>(out));
 }
 // Fused colour + TSDF launch (tsdf.hip): the held-back frame's ESDF marking pass rides in the view-marking launch of the next depth frame
 // (color_launch_integrate's own part, decided before that launch) ...
@@ -292,10 +292,10 @@ static int replay_pair_t(nvbx_mapper* m, const nvbx_mapper::ColorPending& c) {
 }
 bool nvbx_mapper::replay_pair_applies() const {
   static const int on = getenv("NVBX_REPLAY_PAIR") ? atoi(getenv("NVBX_REPLAY_PAIR")) : 1;      // (A/B: 0 = three classic launches)
-  return on && color_pending.on && esdf_update_pending && p.projective_layer_type != 1 && p.esdf_mode == 0 && p.esdf_propagation == 0 && !use_side && defer_edt && !import_pending;
+  return on && held.color_pending.on && held.esdf_update_pending && p.projective_layer_type != 1 && p.esdf_mode == 0 && p.esdf_propagation == 0 && !use_side && defer_edt && !held.import_pending;
 }
 int nvbx_mapper::replay_pair() {
-  const ColorPending c = take_pending(); esdf_update_pending = false;
+  const ColorPending c = take_pending(); held.esdf_update_pending = false;
   const int rc = c.n > 1 ? replay_pair_t<PixRgb8, MAX_BATCH>(this, c) : (c.kind == 0 ? replay_pair_t<PixRgb8, 1>(this, c) : replay_pair_t<PixBgra8, 1>(this, c));
   release_consumed_frames();
   return rc;
@@ -335,7 +335,7 @@ extern "C" int nvbx_integrate_color_owned(nvbx_mapper* m, void* frame, int32_t b
   // a frame that was NOT held back (deferral off, an occupancy mapper) has just been read by launches enqueued on the mapper's stream: it is let go of
   // behind them, with a fence, like a held-back one -- and so is the frame of a call that failed on the device (NVBX_E_DEVICE): reader launches may
   // already be enqueued
-  if (rc == NVBX_OK && m->color_pending.on && m->color_pending.frames[0] == frame) (void)nvbx_frame_release(frame);     // (held back: the mapper keeps the reference defer_color took)
+  if (rc == NVBX_OK && m->held.color_pending.on && m->held.color_pending.frames[0] == frame) (void)nvbx_frame_release(frame);     // (held back: the mapper keeps the reference defer_color took)
   else { m->consumed_frames.push_back(frame); m->release_consumed_frames(); }
   return rc;
 }

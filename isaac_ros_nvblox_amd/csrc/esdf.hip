@@ -172,11 +172,11 @@ extern "C" int nvbx_update_esdf(nvbx_mapper* m) {
   // (... or, with the switch on and no colour frame around, behind nothing: the next camera depth frame carries it alone -- depth-only hosts,
   //  occupancy mappers; nvbx_mapper::esdf_only_carry)
   static const int esdf_only = getenv("NVBX_ESDF_ONLY_CARRY") ? atoi(getenv("NVBX_ESDF_ONLY_CARRY")) : 1;      // (A/B: 0 = an updateEsdf is held back behind a colour frame only)
-  if ((m->color_pending.on || (esdf_only && m->color_deferral && !m->pipelined_order && !m->import_pending)) && !m->replaying && m->p.esdf_propagation == 0 && !m->use_side && m->defer_edt) {
+  if ((m->held.color_pending.on || (esdf_only && m->color_deferral && !m->pipelined_order && !m->held.import_pending)) && !m->replaying && m->p.esdf_propagation == 0 && !m->use_side && m->defer_edt) {
     // (an update already held back is carried out first: two updates in a row stay two updates -- epochs and the "last update" counters as in
     //  the undeferred sequence)
-    if (m->esdf_update_pending && m->replay_deferred()) return NVBX_E_DEVICE;
-    if (m->color_pending.on || (esdf_only && m->color_deferral && !m->import_pending)) { m->esdf_update_pending = true; return NVBX_OK; }
+    if (m->held.esdf_update_pending && m->replay_deferred()) return NVBX_E_DEVICE;
+    if (m->held.color_pending.on || (esdf_only && m->color_deferral && !m->held.import_pending)) { m->held.esdf_update_pending = true; return NVBX_OK; }
   }
   if (!m->replaying && !m->pipelined_order && m->replay_deferred()) return NVBX_E_DEVICE;
   // a distance transform still held back by the PREVIOUS update goes first: this update's marking pass overwrites the masks
@@ -209,7 +209,7 @@ extern "C" int nvbx_update_esdf(nvbx_mapper* m) {
   if (m->defer_edt && !m->use_side) {
     // The EDT is held back until the next entry point: the next camera depth frame runs it inside its first launch (beside
     // the view marking, which it does not interact with); every other entry point launches it first (flush_edt).
-    m->edt_pending = true; m->edt_args = a;
+    m->held.edt_pending = true; m->held.edt_args = a;
   } else {
     NVBX_LAUNCH_ON(m, s, k_esdf_edt, dim3(1024), dim3(256), m->d, a);
   }
@@ -259,7 +259,7 @@ extern "C" int nvbx_esdf_slice_to_image(nvbx_mapper* m, float unknown_value, flo
   // (called right behind nvbx_esdf_slice_size -- the facade's EsdfSlicer sizes its image first -- nothing has been enqueued since: the counters
   //  on the host are still the device's, no second round trip)
   int rc = NVBX_OK;
-  if (m->slice_size_seq != 0 && m->slice_size_seq == m->enqueue_seq && !m->color_pending.on && !m->esdf_update_pending && !m->edt_pending && !m->import_pending && !m->side_pending) {
+  if (m->slice_size_seq != 0 && m->slice_size_seq == m->enqueue_seq && !m->held.any() && !m->side_pending) {
     // (the parts of join_side() that still apply: this mapper's device is the current one -- the call may come from another thread, or behind a call
     //  into a mapper on another GPU -- and the launch below counts as work on the main stream; nothing is held back and the side stream is joined)
     { int cur = -1; if (hipGetDevice(&cur) != hipSuccess || cur != m->device) NVBX_HIP(hipSetDevice(m->device)); }
@@ -589,26 +589,26 @@ extern "C" int nvbx_mark_esdf_dirty_gathered_deferred(nvbx_mapper* m, const int3
   const EsdfArgs probe = m->make_esdf_args();
   if (!(m->p.esdf_mode == 0 && probe.bz_hi >= probe.bz_lo && probe.bz_hi - probe.bz_lo + 1 <= 63))
     return nvbx_mark_esdf_dirty_gathered(m, gathered_dev, world, self_rank, max_count);
-  m->import_pending = true; m->import_ptr = gathered_dev; m->import_world = world; m->import_rank = self_rank; m->import_max = max_count;
+  m->held.import_pending = true; m->held.import_ptr = gathered_dev; m->held.import_world = world; m->held.import_rank = self_rank; m->held.import_max = max_count;
   return NVBX_OK;
 }
 int nvbx_mapper::flush_import() {
-  if (!import_pending) return NVBX_OK;
-  import_pending = false;
+  if (!held.import_pending) return NVBX_OK;
+  held.import_pending = false;
   if (flush_edt()) return NVBX_E_DEVICE;                         // the EDT of the previous update reads the masks this marking overwrites
   mark_pass++;
   const EsdfArgs a = make_esdf_args();
   unresolved_marks = true;
-  NVBX_LAUNCH(this, k_import_mark_gathered, dim3(256, (unsigned)import_world), dim3(64), d, a, import_ptr, import_rank, import_max);
+  NVBX_LAUNCH(this, k_import_mark_gathered, dim3(256, (unsigned)held.import_world), dim3(64), d, a, held.import_ptr, held.import_rank, held.import_max);
   NVBX_HIP(hipGetLastError());
   return NVBX_OK;
 }
 
 // launch a held-back EDT now (every entry point except the camera integrateDepth, which lets it ride in k_mark_view)
 int nvbx_mapper::flush_edt() {
-  if (edt_pending) {
-    edt_pending = false;
-    NVBX_LAUNCH(this, k_esdf_edt, dim3(1024), dim3(256), d, edt_args);
+  if (held.edt_pending) {
+    held.edt_pending = false;
+    NVBX_LAUNCH(this, k_esdf_edt, dim3(1024), dim3(256), d, held.edt_args);
     NVBX_HIP(hipGetLastError());
   }
   return NVBX_OK;

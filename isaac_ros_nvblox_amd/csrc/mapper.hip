@@ -1,13 +1,8 @@
-// mapper.hip -- lifetime, parameters, layer accessors of libnvblox_hip.so (host code + small utility kernels).
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
+// mapper.hip -- a mapper's lifetime, memory, parameters and counters (host code + small utility kernels).  Its held-back work: held.hip; layer
+// access: layers.hip; map files: map_io.hip; per-kernel timing: profile.hip.
 #include <cstdlib>
-#include <chrono>
 #include <cstring>
-#include <mutex>
 #include "nvbx_mapper.h"
-
 using namespace nvbx;
 
 namespace nvbx {
@@ -19,7 +14,6 @@ void set_error(const char* what) { g_err = what; }
 }  // namespace nvbx
 
 extern "C" const char* nvbx_last_error(void) { return nvbx::g_err.c_str(); }
-
 // ------------------------------------------------------------------------------------------------ utility kernels
 __global__ void k_init_map(DMap m) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -41,132 +35,6 @@ __global__ void k_init_map(DMap m) {
     if (i >= C_INV_I1 && i <= C_INV_I3) v = m.counters[i];      // (violations survive clear(): a mapper answers for all its launches when it is closed)
 #endif
     m.counters[i] = v;
-  }
-}
-
-// collect Index3D of every live slot carrying `layer` (order arbitrary; host sorts)
-__global__ void k_collect_indices(DMap m, uint32_t layer, int32_t* out, int32_t cap) {
-  const int32_t hw = m.counters[C_HIGH_WATER];
-  for (int32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < hw; s += gridDim.x * blockDim.x) {
-    if (m.slot_flags[s] & layer) {
-      const int32_t p = atomicAdd(&m.counters[C_TMP], 1);
-      if (p < cap) { out[3 * p] = m.slot_index[3 * s]; out[3 * p + 1] = m.slot_index[3 * s + 1]; out[3 * p + 2] = m.slot_index[3 * s + 2]; }
-    }
-  }
-}
-__global__ void k_zero_tmp(DMap m) { m.counters[C_TMP] = 0; }
-
-// view list ({slot, x, y, z} records of one frame) -> Index3D.  cam_mask != 0 (the frame was a batch): only the blocks the
-// cameras of the mask had in view -- "the last depth view" of a batch is its last camera's, as separate calls would leave it.
-__global__ void k_viewlist_to_indices(DMap m, const int4* list, int32_t count_idx, uint32_t cam_mask, int32_t* out, int32_t cap) {
-  int32_t n = m.counters[count_idx]; if (n > cap) n = cap;
-  for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const int4 r = list[i];
-    bool ok = slot_ok((uint32_t)r.x) && m.slot_flags[(uint32_t)r.x];
-    if (ok && cam_mask && !(m.table[m.slot_entry[(uint32_t)r.x]].stamp & cam_mask)) ok = false;
-    out[3 * i] = ok ? r.y : INT32_MIN; out[3 * i + 1] = ok ? r.z : INT32_MIN; out[3 * i + 2] = ok ? r.w : INT32_MIN;
-  }
-}
-
-// sharded work list (slot ids) -> Index3D, written to out[0..n) in list order; *n_out = entries
-__global__ void k_shardlist_to_indices(DMap m, int list, int32_t* out, int32_t cap, int32_t* n_out) {
-  ListView v; int32_t n = list_open(m, list, &v); if (n > cap) n = cap;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *n_out = n;
-  for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const uint32_t s = (uint32_t)list_at(m, list, v, i);
-    if (slot_ok(s) && m.slot_flags[s]) { out[3 * i] = m.slot_index[3 * s]; out[3 * i + 1] = m.slot_index[3 * s + 1]; out[3 * i + 2] = m.slot_index[3 * s + 2]; }
-    else { out[3 * i] = INT32_MIN; out[3 * i + 1] = INT32_MIN; out[3 * i + 2] = INT32_MIN; }
-  }
-}
-
-// gather n blocks of `layer` into a dense buffer in the REFERENCE voxel struct layout (z + 8y + 64x order).
-// found[i] = 1 if the block exists.  One 512-thread workgroup per block.
-// `layer` is the INTERNAL flag; occupancy = 1: the projective pool holds log-odds and leaves as nvbx_occupancy_voxel {f32}
-__global__ __launch_bounds__(512) void k_gather_blocks(DMap m, uint32_t layer, int32_t occupancy, const int32_t* idx, int32_t n, uint8_t* out, int32_t* found) {
-  const int i = blockIdx.x; if (i >= n) return;
-  const uint32_t s = find_slot(m, idx[3 * i], idx[3 * i + 1], idx[3 * i + 2], layer);
-  const int t = threadIdx.x;
-  if (t == 0) found[i] = slot_ok(s) ? 1 : 0;
-  if (!slot_ok(s)) {            // absent block: zeros, never stale staging bytes
-    const size_t vb = layer == F_ESDF ? sizeof(nvbx_esdf_voxel) : (layer == F_FREESPACE ? sizeof(nvbx_freespace_voxel) : ((layer == F_TSDF && occupancy) ? 4 : 8));
-    for (size_t q = t; q < 512 * vb / 4; q += 512) reinterpret_cast<uint32_t*>(out + (size_t)i * 512 * vb)[q] = 0u;
-    return;
-  }
-  if (layer == F_TSDF && occupancy) { reinterpret_cast<float*>(out)[(size_t)i * 512 + t] = m.tsdf[(size_t)s * 512 + t].x; }
-  else if (layer == F_TSDF) { reinterpret_cast<float2*>(out)[(size_t)i * 512 + t] = m.tsdf[(size_t)s * 512 + t]; }
-  else if (layer == F_COLOR) { reinterpret_cast<uint2*>(out)[(size_t)i * 512 + t] = m.color[(size_t)s * 512 + t]; }
-  else if (layer == F_FREESPACE) {
-    const int4 v = m.freespace[(size_t)s * 512 + t];
-    nvbx_freespace_voxel o;
-    o.last_occupied_timestamp_ms = (int64_t)(((u64)(uint32_t)v.y << 32) | (u64)(uint32_t)v.x);
-    o.consecutive_occupancy_duration_ms = (int64_t)v.z;
-    o.is_high_confidence_freespace = (uint8_t)(v.w & 1); o.initialized = (uint8_t)((v.w >> 1) & 1);
-    for (int q = 0; q < 6; q++) o.pad[q] = 0;
-    reinterpret_cast<nvbx_freespace_voxel*>(out)[(size_t)i * 512 + t] = o;
-  }
-  else if (layer == F_ESDF) {
-    const int x = t >> 6, y = (t >> 3) & 7, z = t & 7;             // reference order
-    const uint2 v = m.esdf[(size_t)s * 512 + x + 8 * y + 64 * z];  // device order
-    nvbx_esdf_voxel o;
-    o.squared_distance_vox = __uint_as_float(v.x);
-    o.parent_direction[0] = (int8_t)(v.y & 0xFF); o.parent_direction[1] = (int8_t)((v.y >> 8) & 0xFF); o.parent_direction[2] = (int8_t)((v.y >> 16) & 0xFF);
-    o.observed = (v.y & ESDF_OBSERVED) ? 1 : 0; o.is_inside = (v.y & ESDF_INSIDE) ? 1 : 0; o.is_site = (v.y & ESDF_SITE) ? 1 : 0; o.pad = 0;
-    reinterpret_cast<nvbx_esdf_voxel*>(out)[(size_t)i * 512 + t] = o;
-  }
-}
-
-// allocateBlockAtIndex + whole-block write from reference structs: workgroup i writes block idx[i] from in[i][512]
-__global__ __launch_bounds__(512) void k_scatter_blocks(DMap m, uint32_t layer, int32_t occupancy, const int32_t* idx, const uint8_t* in_all, size_t block_bytes,
-                                                        int32_t mesh_list, int32_t bz_out, int32_t vz_out, float trunc) {
-  __shared__ uint32_t s_slot;
-  __shared__ u64 s_sites, s_obs, s_ins;
-  const int t = threadIdx.x;
-  const int32_t x = idx[3 * blockIdx.x], y = idx[3 * blockIdx.x + 1], z = idx[3 * blockIdx.x + 2];
-  const uint8_t* in = in_all + (size_t)blockIdx.x * block_bytes;
-  if (t == 0) {
-    bool is_new; const int32_t h = hash_insert(m, x, y, z, layer, &is_new);
-    uint32_t s = SLOT_NONE;
-    // (a duplicate index in one batch: the workgroup that lost the insert waits for the winner to publish the slot, as mark_block does)
-    if (h >= 0) { do { s = ld_slot_acquire(&m.table[h]); } while (s == SLOT_INVALID); }
-    if (slot_ok(s)) {
-      uint32_t add = layer;
-      if (layer == F_TSDF) add |= F_DIRTY_ESDF | F_DIRTY_MESH;
-      const uint32_t old = atomicOr(&m.slot_flags[s], add);
-      if (layer == F_TSDF) {
-        if (!(old & F_DIRTY_ESDF)) list_append(m, S_LIST_ESDF_DIRTY, (int32_t)s);
-        if (!(old & F_DIRTY_MESH)) list_append(m, mesh_list, (int32_t)s);
-      }
-      if (layer == F_ESDF && z == bz_out) {     // (3-D ESDF: only the slice plane's blocks span the slicer's image)
-        atomicMin(&m.counters[C_ESDF_AABB + 0], x); atomicMin(&m.counters[C_ESDF_AABB + 1], y);
-        atomicMax(&m.counters[C_ESDF_AABB + 2], x); atomicMax(&m.counters[C_ESDF_AABB + 3], y);
-      }
-    }
-    s_slot = s; s_sites = 0ull; s_obs = 0ull; s_ins = 0ull;
-  }
-  __syncthreads();
-  const uint32_t s = s_slot;
-  if (!slot_ok(s)) return;
-  if (layer == F_TSDF && occupancy) m.tsdf[(size_t)s * 512 + t] = make_float2(reinterpret_cast<const float*>(in)[t], 0.0f);
-  else if (layer == F_TSDF) {
-    const float2 v = reinterpret_cast<const float2*>(in)[t];
-    m.tsdf[(size_t)s * 512 + t] = v;
-    publish_band(m.slot_flags, s, t, in_band(v.x, v.y, trunc));        // (uniform branch: every wavefront is here)
-  }
-  else if (layer == F_COLOR) m.color[(size_t)s * 512 + t] = reinterpret_cast<const uint2*>(in)[t];
-  else if (layer == F_ESDF) {
-    const int vx = t >> 6, vy = (t >> 3) & 7, vz = t & 7;
-    const nvbx_esdf_voxel v = reinterpret_cast<const nvbx_esdf_voxel*>(in)[t];
-    m.esdf[(size_t)s * 512 + vx + 8 * vy + 64 * vz] =
-        make_uint2(__float_as_uint(v.squared_distance_vox),
-                   esdf_meta(v.parent_direction[0], v.parent_direction[1], v.parent_direction[2], v.observed, v.is_inside, v.is_site));
-    // keep the slice plane's site mask (what k_esdf_edt reads) consistent with the written voxels
-    if (z == bz_out && vz == vz_out) {
-      if (v.is_site) atomicOr(&s_sites, 1ull << (vx + 8 * vy));
-      if (v.observed) atomicOr(&s_obs, 1ull << (vx + 8 * vy));
-      if (v.is_inside) atomicOr(&s_ins, 1ull << (vx + 8 * vy));
-    }
-    __syncthreads();
-    if (t == 0) { m.site_bits[s] = (z == bz_out) ? s_sites : 0ull; m.obs_bits[s] = (z == bz_out) ? s_obs : 0ull; m.inside_bits[s] = (z == bz_out) ? s_ins : 0ull; }
   }
 }
 
@@ -236,8 +104,7 @@ static int reset_map(nvbx_mapper* m) {
   const int64_t n = std::max<int64_t>(cap, std::max<int64_t>(C_NUM, S_NUM * NSH * SH_STRIDE));
   NVBX_LAUNCH(m, k_init_map, dim3((unsigned)((n + 255) / 256)), dim3(256), d);
   NVBX_HIP(hipGetLastError());
-  m->dirty_since_mark = false; m->premark_consumed = false; m->mark_pass = 0; m->edt_pending = false; m->import_pending = false;
-  m->unresolved_marks = false; m->pass_at_last_edt = 0; (void)m->take_pending(); m->release_consumed_frames(); m->esdf_update_pending = false; m->lidar_integrated = false;
+  m->reset_marking(); m->held.drop(*m); m->lidar_integrated = false;
   if (m->h_mirror) { m->h_mirror[0] = (int32_t)m->capacity; m->h_mirror[1] = 0; m->h_mirror[2] = 0; m->h_mirror[3] = 0; }
   m->frame_id = 0; m->esdf_epoch = 0; m->mesh_epoch = 0; m->last_view_frame = 0; m->last_camera_view_frame = 0; m->synth_rows = m->synth_cols = 0;
   return NVBX_OK;
@@ -509,392 +376,11 @@ extern "C" int nvbx_mapper_wait_for(nvbx_mapper* waiter, nvbx_mapper* producer) 
   NVBX_HIP(hipStreamWaitEvent(waiter->stream, producer->ev_order, 0));
   return NVBX_OK;
 }
-extern "C" int nvbx_flush(nvbx_mapper* m) {
-  if (!m) return NVBX_E_INVALID;
-  NVBX_HIP(hipSetDevice(m->device));
-  return m->join_side();
-}
 extern "C" int nvbx_mapper_clear(nvbx_mapper* m) {
   if (!m) return NVBX_E_INVALID;
   NVBX_HIP(hipSetDevice(m->device));
   if (m->join_side()) return NVBX_E_DEVICE;
   return reset_map(m);
-}
-
-// ------------------------------------------------------------------------------------------------ C-ABI: layer access
-static bool single_layer(uint32_t layer) { return layer == F_TSDF || layer == F_COLOR || layer == F_ESDF || layer == F_MESH || layer == NVBX_LAYER_OCCUPANCY || layer == F_FREESPACE; }
-// API layer id -> internal slot flag; 0 = this mapper cannot hold that layer (it reads as empty).  The projective layer of a
-// mapper (TSDF or occupancy, Mapper's ProjectiveLayerType) lives in the same pool under the same internal flag.
-static uint32_t internal_layer(const nvbx_mapper* m, uint32_t layer) {
-  const bool occ = m->p.projective_layer_type == 1;
-  if (layer == NVBX_LAYER_OCCUPANCY) return occ ? F_TSDF : 0u;
-  if (layer == F_TSDF) return occ ? 0u : F_TSDF;
-  if (layer == F_FREESPACE) return m->d.freespace ? F_FREESPACE : 0u;
-  return layer;
-}
-
-static void sort_indices(nvbx_index3d* v, int64_t n) {
-  std::sort(v, v + n, [](const nvbx_index3d& a, const nvbx_index3d& b) {
-    if (a.x != b.x) return a.x < b.x; if (a.y != b.y) return a.y < b.y; return a.z < b.z; });
-}
-
-extern "C" int64_t nvbx_block_indices(nvbx_mapper* m, uint32_t layer, nvbx_index3d* out, int64_t capacity) {
-  if (!m || !single_layer(layer)) return NVBX_E_INVALID;
-  layer = internal_layer(m, layer);
-  if (!layer) return 0;
-  if (m->join_side()) return NVBX_E_DEVICE;
-  NVBX_LAUNCH(m, k_zero_tmp, dim3(1), dim3(1), m->d);
-  NVBX_LAUNCH(m, k_collect_indices, dim3(256), dim3(256), m->d, layer, m->export_idx, (int32_t)m->capacity);
-  if (m->fetch_counters()) return NVBX_E_DEVICE;
-  int64_t n = m->h_counters[C_TMP];
-  if (n > m->capacity) n = m->capacity;
-  const int64_t k = std::min<int64_t>(n, capacity);
-  if (out && k > 0) {
-    std::vector<nvbx_index3d> tmp((size_t)n);
-    NVBX_HIP(hipMemcpy(tmp.data(), m->export_idx, (size_t)n * 12, hipMemcpyDeviceToHost));
-    sort_indices(tmp.data(), n);
-    memcpy(out, tmp.data(), (size_t)k * 12);
-  }
-  return n;
-}
-extern "C" int64_t nvbx_num_blocks(nvbx_mapper* m, uint32_t layer) { return nvbx_block_indices(m, layer, nullptr, 0); }
-
-extern "C" int64_t nvbx_last_depth_view(nvbx_mapper* m, nvbx_index3d* out, int64_t capacity) {
-  if (!m) return NVBX_E_INVALID;
-  if (m->last_view_frame == 0) return 0;
-  if (m->join_side()) return NVBX_E_DEVICE;
-  const uint32_t cam_mask = m->last_view_batch > 1 ? (1u << (m->last_view_batch - 1)) : 0u;
-  NVBX_LAUNCH(m, k_viewlist_to_indices, dim3(64), dim3(256), m->d, (const int4*)m->view_list, C_VIEW_COUNT + (int)(m->last_view_frame & 3), cam_mask, m->export_idx, (int32_t)m->capacity);
-  if (m->fetch_counters()) return NVBX_E_DEVICE;
-  int64_t n = m->h_counters[C_VIEW_COUNT + (m->last_view_frame & 3)]; if (n > m->capacity) n = m->capacity;
-  std::vector<nvbx_index3d> tmp((size_t)std::max<int64_t>(n, 1));
-  if (n > 0) NVBX_HIP(hipMemcpy(tmp.data(), m->export_idx, (size_t)n * 12, hipMemcpyDeviceToHost));
-  tmp.resize((size_t)n);
-  tmp.erase(std::remove_if(tmp.begin(), tmp.end(), [](const nvbx_index3d& i) { return i.x == INT32_MIN; }), tmp.end());   // deallocated since / not in the mask
-  n = (int64_t)tmp.size();
-  const int64_t k = std::min<int64_t>(n, capacity);
-  if (out && k > 0) { sort_indices(tmp.data(), n); memcpy(out, tmp.data(), (size_t)k * 12); }
-  return n;
-}
-extern "C" int64_t nvbx_last_color_view(nvbx_mapper* m, nvbx_index3d* out, int64_t capacity) {
-  if (!m) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
-  NVBX_LAUNCH(m, k_shardlist_to_indices, dim3(64), dim3(256), m->d, (int)S_LIST_COLOR, m->export_idx, (int32_t)m->capacity, m->export_count);
-  int32_t n32 = 0;
-  NVBX_HIP(hipMemcpyAsync(&n32, m->export_count, 4, hipMemcpyDeviceToHost, m->stream));
-  NVBX_HIP(hipStreamSynchronize(m->stream));
-  const int64_t n = n32, k = std::min<int64_t>(n, capacity);
-  if (out && k > 0) {
-    std::vector<nvbx_index3d> tmp((size_t)n);
-    NVBX_HIP(hipMemcpy(tmp.data(), m->export_idx, (size_t)n * 12, hipMemcpyDeviceToHost));
-    sort_indices(tmp.data(), n);
-    memcpy(out, tmp.data(), (size_t)k * 12);
-  }
-  return n;
-}
-
-static size_t ref_voxel_bytes(uint32_t layer) { return layer == F_ESDF ? sizeof(nvbx_esdf_voxel) : (layer == NVBX_LAYER_OCCUPANCY ? sizeof(nvbx_occupancy_voxel) : (layer == F_FREESPACE ? sizeof(nvbx_freespace_voxel) : 8)); }
-
-extern "C" int nvbx_get_blocks(nvbx_mapper* m, uint32_t layer, const nvbx_index3d* idx, int64_t n, void* voxels_out, int32_t* found_out) {
-  if (!m || !idx || !voxels_out || n < 0 || !(layer == F_TSDF || layer == F_COLOR || layer == F_ESDF || layer == NVBX_LAYER_OCCUPANCY || layer == F_FREESPACE)) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
-  const size_t bb = 512 * ref_voxel_bytes(layer);
-  const uint32_t ilayer = internal_layer(m, layer);
-  if (!ilayer) { if (found_out) memset(found_out, 0, (size_t)n * 4); return NVBX_OK; }
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)((m->staging.bytes - 65536) / (bb + 16)));
-  for (int64_t o = 0; o < n; o += chunk) {
-    const int64_t c = std::min(chunk, n - o);
-    int32_t* d_idx = m->staging.as<int32_t>(); int32_t* d_found = d_idx + 3 * c;
-    uint8_t* d_out = m->staging.as<uint8_t>() + (((size_t)c * 16 + 255) & ~(size_t)255);
-    NVBX_HIP(hipMemcpyAsync(d_idx, idx + o, (size_t)c * 12, hipMemcpyHostToDevice, m->stream));
-    NVBX_LAUNCH(m, k_gather_blocks, dim3((unsigned)c), dim3(512), m->d, ilayer, (int32_t)(layer == NVBX_LAYER_OCCUPANCY), d_idx, (int32_t)c, d_out, d_found);
-    NVBX_HIP(hipMemcpyAsync((uint8_t*)voxels_out + (size_t)o * bb, d_out, (size_t)c * bb, hipMemcpyDeviceToHost, m->stream));
-    if (found_out) NVBX_HIP(hipMemcpyAsync(found_out + o, d_found, (size_t)c * 4, hipMemcpyDeviceToHost, m->stream));
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-  }
-  return NVBX_OK;
-}
-extern "C" int nvbx_get_block(nvbx_mapper* m, uint32_t layer, nvbx_index3d idx, void* voxels_out) {
-  int32_t found = 0;
-  const int rc = nvbx_get_blocks(m, layer, &idx, 1, voxels_out, &found);
-  if (rc) return rc;
-  return found ? NVBX_OK : NVBX_E_NOTFOUND;
-}
-extern "C" int nvbx_set_blocks(nvbx_mapper* m, uint32_t layer, const nvbx_index3d* idx, int64_t n, const void* voxels_in) {
-  if (!m || (n > 0 && (!voxels_in || !idx)) || n < 0 || !(layer == F_TSDF || layer == F_COLOR || layer == F_ESDF || layer == NVBX_LAYER_OCCUPANCY)) return NVBX_E_INVALID;
-  const uint32_t ilayer = internal_layer(m, layer);
-  if (!ilayer) { set_error("nvbx_set_blocks: this mapper's projective layer type does not hold that layer"); return NVBX_E_INVALID; }
-  for (int64_t i = 0; i < n; i++) if (!nvbx_index_in_range(idx[i].x, idx[i].y, idx[i].z)) { set_error("nvbx_set_blocks: block index outside +-2^20"); return NVBX_E_INVALID; }
-  if (m->join_side()) return NVBX_E_DEVICE;
-  if (m->capacity < m->max_capacity) {          // explicit allocation (allocateBlockAtIndex, loadMap): room for all of it, plus the usual head-room
-    if (m->fetch_counters()) return NVBX_E_DEVICE;
-    m->h_mirror[0] = m->h_counters[C_FREE_TOP];
-    const int rcg = m->maybe_grow(n); if (rcg) return rcg;
-  }
-  if (m->begin_dirtying()) return NVBX_E_DEVICE;
-  const size_t bb = 512 * ref_voxel_bytes(layer);
-  const EsdfArgs ea = m->make_esdf_args();
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)((m->staging.bytes - 65536) / (bb + 16)));
-  for (int64_t o = 0; o < n; o += chunk) {
-    const int64_t c = std::min(chunk, n - o);
-    int32_t* d_idx = m->staging.as<int32_t>();
-    uint8_t* d_in = m->staging.as<uint8_t>() + (((size_t)c * 16 + 255) & ~(size_t)255);
-    NVBX_HIP(hipMemcpyAsync(d_idx, idx + o, (size_t)c * 12, hipMemcpyHostToDevice, m->stream));
-    NVBX_HIP(hipMemcpyAsync(d_in, (const uint8_t*)voxels_in + (size_t)o * bb, (size_t)c * bb, hipMemcpyHostToDevice, m->stream));
-    NVBX_LAUNCH(m, k_scatter_blocks, dim3((unsigned)c), dim3(512), m->d, ilayer, (int32_t)(layer == NVBX_LAYER_OCCUPANCY), (const int32_t*)d_idx, (const uint8_t*)d_in, bb,
-                (int32_t)m->mesh_list_live(), ea.bz_out, ea.vz_out, m->p.truncation_distance_vox * m->p.voxel_size);
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-  }
-  return NVBX_OK;
-}
-extern "C" int nvbx_set_block(nvbx_mapper* m, uint32_t layer, nvbx_index3d idx, const void* voxels_in) {
-  return nvbx_set_blocks(m, layer, &idx, 1, voxels_in);
-}
-
-// ------------------------------------------------------------------------------------------------ map file
-// Mapper::saveLayerCake / loadMap (nvblox_node.cpp:1668,1703).  The reference's .nvblx container is defined in the absent
-// nvblox core; this is our own little-endian container of the same content: the TSDF, colour and ESDF layers as
-// {Index3D, 512 reference voxel structs} per block.  Layout: MapFileHeader, then per layer MapLayerHeader,
-// int32[n][3] indices (sorted), voxel structs.
-namespace {
-struct MapFileHeader { char magic[8]; uint32_t version; float voxel_size; uint32_t n_layers; uint32_t reserved; };
-struct MapLayerHeader { uint32_t layer; uint32_t voxel_bytes; uint64_t n_blocks; };
-const char kMapMagic[8] = {'N', 'V', 'B', 'X', 'M', 'A', 'P', '1'};
-struct FileCloser { FILE* f; ~FileCloser() { if (f) fclose(f); } };
-}  // namespace
-
-// ---- .nvblx: the layer cake as an SQLite database ([U]: the reference's serializer (nvblox/serialization, absent) stores the layers in
-// an SQLite file, saveLayerCake / loadMap of nvblox_node.cpp:1663-1703 take a *.nvblx path; the schema below is a guess at that layout,
-// so files are readable with any sqlite3 tool but NOT verified against upstream's):
-//   layers(layer_type TEXT PRIMARY KEY, voxel_size REAL, block_size REAL, voxel_bytes INTEGER, num_blocks INTEGER)
-//   <layer_type>_blocks(index_x INTEGER, index_y INTEGER, index_z INTEGER, data BLOB, PRIMARY KEY(index_x, index_y, index_z))
-// with layer_type in {tsdf_layer, color_layer, esdf_layer, occupancy_layer}; data = the block's 512 voxels as the reference's
-// structs in z + 8y + 64x order.  libsqlite3 is loaded at run time (dlopen): no header / link dependency; without it (or for a path
-// that does not end in .nvblx) the compact container of our own is written / read.
-#include <dlfcn.h>
-namespace {
-struct Sqlite {
-  void* lib = nullptr;
-  int (*open)(const char*, void**) = nullptr; int (*close)(void*) = nullptr;
-  int (*exec)(void*, const char*, int (*)(void*, int, char**, char**), void*, char**) = nullptr;
-  int (*prepare)(void*, const char*, int, void**, const char**) = nullptr;
-  int (*bind_int)(void*, int, int) = nullptr; int (*bind_double)(void*, int, double) = nullptr;
-  int (*bind_text)(void*, int, const char*, int, void (*)(void*)) = nullptr; int (*bind_blob)(void*, int, const void*, int, void (*)(void*)) = nullptr;
-  int (*step)(void*) = nullptr; int (*reset)(void*) = nullptr; int (*finalize)(void*) = nullptr;
-  int (*column_int)(void*, int) = nullptr; double (*column_double)(void*, int) = nullptr; const void* (*column_blob)(void*, int) = nullptr;
-  int (*column_bytes)(void*, int) = nullptr; const unsigned char* (*column_text)(void*, int) = nullptr;
-  bool ok() const { return lib != nullptr; }
-};
-const Sqlite& sqlite() {
-  static Sqlite s = [] {
-    Sqlite q;
-    for (const char* name : {"libsqlite3.so.0", "libsqlite3.so"}) { q.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL); if (q.lib) break; }
-    if (!q.lib) return q;
-    auto sym = [&](const char* n) { void* p = dlsym(q.lib, n); if (!p) q.lib = nullptr; return p; };
-    void* lib = q.lib;
-#define NVBX_SQL(field, name) *(void**)(&q.field) = sym(name)
-    NVBX_SQL(open, "sqlite3_open"); NVBX_SQL(close, "sqlite3_close"); NVBX_SQL(exec, "sqlite3_exec"); NVBX_SQL(prepare, "sqlite3_prepare_v2");
-    NVBX_SQL(bind_int, "sqlite3_bind_int"); NVBX_SQL(bind_double, "sqlite3_bind_double"); NVBX_SQL(bind_text, "sqlite3_bind_text"); NVBX_SQL(bind_blob, "sqlite3_bind_blob");
-    NVBX_SQL(step, "sqlite3_step"); NVBX_SQL(reset, "sqlite3_reset"); NVBX_SQL(finalize, "sqlite3_finalize"); NVBX_SQL(column_int, "sqlite3_column_int");
-    NVBX_SQL(column_double, "sqlite3_column_double"); NVBX_SQL(column_blob, "sqlite3_column_blob"); NVBX_SQL(column_bytes, "sqlite3_column_bytes");
-    NVBX_SQL(column_text, "sqlite3_column_text");
-#undef NVBX_SQL
-    if (!q.lib) { dlclose(lib); }
-    return q;
-  }();
-  return s;
-}
-constexpr int kSqlOk = 0, kSqlRow = 100, kSqlDone = 101;
-struct LayerName { uint32_t layer; const char* name; };
-const LayerName kLayerNames[] = {{F_TSDF, "tsdf_layer"}, {F_COLOR, "color_layer"}, {F_ESDF, "esdf_layer"}, {NVBX_LAYER_OCCUPANCY, "occupancy_layer"}};
-bool ends_with(const char* s, const char* suffix) { const size_t a = strlen(s), b = strlen(suffix); return a >= b && strcmp(s + a - b, suffix) == 0; }
-struct DbCloser { void* db; ~DbCloser() { if (db) sqlite().close(db); } };
-struct StmtCloser { void* st; ~StmtCloser() { if (st) sqlite().finalize(st); } };
-}  // namespace
-
-static int save_map_nvblx(nvbx_mapper* m, const char* path) {
-  const Sqlite& q = sqlite();
-  remove(path);
-  DbCloser db{nullptr};
-  if (q.open(path, &db.db) != kSqlOk) { set_error("nvbx_save_map: cannot create the .nvblx (SQLite) file"); return NVBX_E_IO; }
-  if (q.exec(db.db, "PRAGMA journal_mode=OFF; PRAGMA synchronous=OFF; BEGIN;"
-                    "CREATE TABLE layers(layer_type TEXT PRIMARY KEY, voxel_size REAL, block_size REAL, voxel_bytes INTEGER, num_blocks INTEGER);", nullptr, nullptr, nullptr) != kSqlOk) {
-    set_error("nvbx_save_map: SQLite schema"); return NVBX_E_IO; }
-  const uint32_t layers[3] = {m->p.projective_layer_type == 1 ? NVBX_LAYER_OCCUPANCY : F_TSDF, F_COLOR, F_ESDF};
-  for (uint32_t layer : layers) {
-    const char* name = nullptr; for (const LayerName& ln : kLayerNames) if (ln.layer == layer) name = ln.name;
-    const int64_t n = nvbx_num_blocks(m, layer);
-    if (n < 0) return (int)n;
-    std::vector<nvbx_index3d> idx((size_t)std::max<int64_t>(n, 1));
-    if (n > 0 && nvbx_block_indices(m, layer, idx.data(), n) < 0) return NVBX_E_DEVICE;
-    const size_t bb = 512 * ref_voxel_bytes(layer);
-    char sql[256];
-    snprintf(sql, sizeof(sql), "CREATE TABLE %s_blocks(index_x INTEGER, index_y INTEGER, index_z INTEGER, data BLOB, PRIMARY KEY(index_x, index_y, index_z));", name);
-    if (q.exec(db.db, sql, nullptr, nullptr, nullptr) != kSqlOk) { set_error("nvbx_save_map: SQLite create table"); return NVBX_E_IO; }
-    {
-      StmtCloser st{nullptr};
-      if (q.prepare(db.db, "INSERT INTO layers VALUES(?, ?, ?, ?, ?);", -1, &st.st, nullptr) != kSqlOk) { set_error("nvbx_save_map: SQLite prepare"); return NVBX_E_IO; }
-      q.bind_text(st.st, 1, name, -1, nullptr); q.bind_double(st.st, 2, (double)m->p.voxel_size); q.bind_double(st.st, 3, (double)(m->p.voxel_size * 8.0f));
-      q.bind_int(st.st, 4, (int)ref_voxel_bytes(layer)); q.bind_int(st.st, 5, (int)n);
-      if (q.step(st.st) != kSqlDone) { set_error("nvbx_save_map: SQLite insert"); return NVBX_E_IO; }
-    }
-    snprintf(sql, sizeof(sql), "INSERT INTO %s_blocks VALUES(?, ?, ?, ?);", name);
-    StmtCloser st{nullptr};
-    if (q.prepare(db.db, sql, -1, &st.st, nullptr) != kSqlOk) { set_error("nvbx_save_map: SQLite prepare"); return NVBX_E_IO; }
-    const int64_t chunk = 4096;
-    std::vector<uint8_t> buf((size_t)std::min<int64_t>(std::max<int64_t>(n, 1), chunk) * bb);
-    for (int64_t o = 0; o < n; o += chunk) {
-      const int64_t c = std::min(chunk, n - o);
-      const int rc = nvbx_get_blocks(m, layer, idx.data() + o, c, buf.data(), nullptr);
-      if (rc) return rc;
-      for (int64_t i = 0; i < c; i++) {
-        q.reset(st.st);
-        q.bind_int(st.st, 1, idx[(size_t)(o + i)].x); q.bind_int(st.st, 2, idx[(size_t)(o + i)].y); q.bind_int(st.st, 3, idx[(size_t)(o + i)].z);
-        q.bind_blob(st.st, 4, buf.data() + (size_t)i * bb, (int)bb, nullptr);          // (static: the buffer outlives the step)
-        if (q.step(st.st) != kSqlDone) { set_error("nvbx_save_map: SQLite insert block"); return NVBX_E_IO; }
-      }
-    }
-  }
-  if (q.exec(db.db, "COMMIT;", nullptr, nullptr, nullptr) != kSqlOk) { set_error("nvbx_save_map: SQLite commit"); return NVBX_E_IO; }
-  return NVBX_OK;
-}
-
-static int load_map_nvblx(nvbx_mapper* m, const char* path) {
-  const Sqlite& q = sqlite();
-  DbCloser db{nullptr};
-  if (q.open(path, &db.db) != kSqlOk) { set_error("nvbx_load_map: cannot open the .nvblx (SQLite) file"); return NVBX_E_IO; }
-  // validate before the current map is touched: the layer table, voxel size, voxel struct sizes, block counts, blob sizes
-  struct L { uint32_t layer; std::string name; int64_t n; size_t bb; };
-  std::vector<L> found;
-  {
-    StmtCloser st{nullptr};
-    if (q.prepare(db.db, "SELECT layer_type, voxel_size, voxel_bytes, num_blocks FROM layers;", -1, &st.st, nullptr) != kSqlOk) { set_error("nvbx_load_map: not an .nvblx layer cake"); return NVBX_E_IO; }
-    int rc;
-    while ((rc = q.step(st.st)) == kSqlRow) {
-      const char* nm = (const char*)q.column_text(st.st, 0);
-      uint32_t layer = 0; for (const LayerName& ln : kLayerNames) if (nm && !strcmp(nm, ln.name)) layer = ln.layer;
-      const double vs = q.column_double(st.st, 1); const int vb = q.column_int(st.st, 2); const int64_t n = q.column_int(st.st, 3);
-      if (!layer || vb != (int)ref_voxel_bytes(layer) || n < 0) { set_error("nvbx_load_map: unknown layer record"); return NVBX_E_IO; }
-      if (fabs(vs - (double)m->p.voxel_size) > 1e-6 * m->p.voxel_size) { set_error("nvbx_load_map: voxel size of the file differs from the mapper's"); return NVBX_E_INVALID; }
-      if (n > 0 && !internal_layer(m, layer)) { set_error("nvbx_load_map: the file holds a layer this mapper's projective layer type cannot"); return NVBX_E_IO; }
-      if (n > (1ll << 24)) { set_error("nvbx_load_map: implausible block count"); return NVBX_E_CAPACITY; }
-      found.push_back({layer, nm, n, 512 * ref_voxel_bytes(layer)});
-    }
-    if (rc != kSqlDone || found.empty()) { set_error("nvbx_load_map: not an .nvblx layer cake"); return NVBX_E_IO; }
-  }
-  for (const L& l : found) {
-    char sql[256]; snprintf(sql, sizeof(sql), "SELECT COUNT(*), MIN(LENGTH(data)), MAX(LENGTH(data)) FROM %s_blocks;", l.name.c_str());
-    StmtCloser st{nullptr};
-    if (q.prepare(db.db, sql, -1, &st.st, nullptr) != kSqlOk || q.step(st.st) != kSqlRow) { set_error("nvbx_load_map: block table missing"); return NVBX_E_IO; }
-    const int64_t cnt = q.column_int(st.st, 0);
-    if (cnt != l.n || (cnt > 0 && (q.column_int(st.st, 1) != (int)l.bb || q.column_int(st.st, 2) != (int)l.bb))) { set_error("nvbx_load_map: block table does not match its layer record"); return NVBX_E_IO; }
-  }
-  int rc = nvbx_mapper_clear(m);
-  if (rc) return rc;
-  for (const L& l : found) {
-    char sql[256]; snprintf(sql, sizeof(sql), "SELECT index_x, index_y, index_z, data FROM %s_blocks;", l.name.c_str());
-    StmtCloser st{nullptr};
-    if (q.prepare(db.db, sql, -1, &st.st, nullptr) != kSqlOk) { set_error("nvbx_load_map: SQLite prepare"); return NVBX_E_IO; }
-    const int64_t chunk = 2048;
-    std::vector<nvbx_index3d> idx; std::vector<uint8_t> buf;
-    idx.reserve((size_t)chunk); buf.reserve((size_t)chunk * l.bb);
-    int s;
-    for (;;) {
-      s = q.step(st.st);
-      if (s == kSqlRow) {
-        idx.push_back({q.column_int(st.st, 0), q.column_int(st.st, 1), q.column_int(st.st, 2)});
-        const uint8_t* blob = (const uint8_t*)q.column_blob(st.st, 3);
-        buf.insert(buf.end(), blob, blob + l.bb);
-      }
-      if ((s != kSqlRow || (int64_t)idx.size() == chunk) && !idx.empty()) {
-        rc = nvbx_set_blocks(m, l.layer, idx.data(), (int64_t)idx.size(), buf.data());
-        if (rc) return rc;
-        idx.clear(); buf.clear();
-      }
-      if (s != kSqlRow) break;
-    }
-    if (s != kSqlDone) { set_error("nvbx_load_map: SQLite read"); return NVBX_E_IO; }
-  }
-  return NVBX_OK;
-}
-
-extern "C" int nvbx_save_map(nvbx_mapper* m, const char* path) {
-  if (!m || !path) { set_error("nvbx_save_map: invalid argument"); return NVBX_E_INVALID; }
-  if (ends_with(path, ".nvblx") && sqlite().ok()) return save_map_nvblx(m, path);
-  FileCloser fc{fopen(path, "wb")};
-  if (!fc.f) { set_error("nvbx_save_map: cannot open file for writing"); return NVBX_E_IO; }
-  const uint32_t layers[3] = {m->p.projective_layer_type == 1 ? NVBX_LAYER_OCCUPANCY : F_TSDF, F_COLOR, F_ESDF};
-  MapFileHeader h{}; memcpy(h.magic, kMapMagic, 8); h.version = 1; h.voxel_size = m->p.voxel_size; h.n_layers = 3;
-  if (fwrite(&h, sizeof(h), 1, fc.f) != 1) { set_error("nvbx_save_map: write failed"); return NVBX_E_IO; }
-  for (uint32_t layer : layers) {
-    const int64_t n = nvbx_num_blocks(m, layer);
-    if (n < 0) return (int)n;
-    std::vector<nvbx_index3d> idx((size_t)std::max<int64_t>(n, 1));
-    if (n > 0 && nvbx_block_indices(m, layer, idx.data(), n) < 0) return NVBX_E_DEVICE;
-    const size_t bb = 512 * ref_voxel_bytes(layer);
-    MapLayerHeader lh{layer, (uint32_t)ref_voxel_bytes(layer), (uint64_t)n};
-    if (fwrite(&lh, sizeof(lh), 1, fc.f) != 1) { set_error("nvbx_save_map: write failed"); return NVBX_E_IO; }
-    if (n > 0 && fwrite(idx.data(), 12, (size_t)n, fc.f) != (size_t)n) { set_error("nvbx_save_map: write failed"); return NVBX_E_IO; }
-    const int64_t chunk = 4096;                      // blocks per round trip (16-40 MiB of host memory)
-    std::vector<uint8_t> buf((size_t)std::min<int64_t>(std::max<int64_t>(n, 1), chunk) * bb);
-    for (int64_t o = 0; o < n; o += chunk) {
-      const int64_t c = std::min(chunk, n - o);
-      const int rc = nvbx_get_blocks(m, layer, idx.data() + o, c, buf.data(), nullptr);
-      if (rc) return rc;
-      if (fwrite(buf.data(), bb, (size_t)c, fc.f) != (size_t)c) { set_error("nvbx_save_map: write failed"); return NVBX_E_IO; }
-    }
-  }
-  return NVBX_OK;
-}
-
-extern "C" int nvbx_load_map(nvbx_mapper* m, const char* path) {
-  if (!m || !path) { set_error("nvbx_load_map: invalid argument"); return NVBX_E_INVALID; }
-  FileCloser fc{fopen(path, "rb")};
-  if (!fc.f) { set_error("nvbx_load_map: cannot open file"); return NVBX_E_IO; }
-  { char magic[16] = {0};                             // an SQLite database = an .nvblx layer cake
-    if (fread(magic, 1, 16, fc.f) == 16 && !memcmp(magic, "SQLite format 3", 16)) {
-      if (!sqlite().ok()) { set_error("nvbx_load_map: the file is an SQLite .nvblx but libsqlite3 cannot be loaded"); return NVBX_E_IO; }
-      fclose(fc.f); fc.f = nullptr;
-      return load_map_nvblx(m, path);
-    }
-    fseek(fc.f, 0, SEEK_SET); }
-  MapFileHeader h{};
-  if (fread(&h, sizeof(h), 1, fc.f) != 1 || memcmp(h.magic, kMapMagic, 8) != 0 || h.version != 1) { set_error("nvbx_load_map: not a libnvblox_hip map file"); return NVBX_E_IO; }
-  if (fabsf(h.voxel_size - m->p.voxel_size) > 1e-6f * m->p.voxel_size) { set_error("nvbx_load_map: voxel size of the file differs from the mapper's"); return NVBX_E_INVALID; }
-  if (h.n_layers > 16) { set_error("nvbx_load_map: implausible layer count"); return NVBX_E_IO; }
-  // validate the whole file before the current map is touched
-  struct Section { MapLayerHeader lh; long idx_off, vox_off; };
-  std::vector<Section> sections;
-  for (uint32_t l = 0; l < h.n_layers; l++) {
-    Section sc{};
-    if (fread(&sc.lh, sizeof(sc.lh), 1, fc.f) != 1) { set_error("nvbx_load_map: truncated file"); return NVBX_E_IO; }
-    if (!(sc.lh.layer == F_TSDF || sc.lh.layer == F_COLOR || sc.lh.layer == F_ESDF || sc.lh.layer == NVBX_LAYER_OCCUPANCY) ||
-        sc.lh.voxel_bytes != ref_voxel_bytes(sc.lh.layer) || (sc.lh.n_blocks > 0 && !internal_layer(m, sc.lh.layer))) {
-      set_error("nvbx_load_map: unknown layer record"); return NVBX_E_IO; }
-    if (sc.lh.n_blocks > (uint64_t)m->capacity) { set_error("nvbx_load_map: map has more blocks than the mapper's block capacity"); return NVBX_E_CAPACITY; }
-    sc.idx_off = ftell(fc.f); sc.vox_off = sc.idx_off + (long)(sc.lh.n_blocks * 12);
-    if (fseek(fc.f, sc.vox_off + (long)(sc.lh.n_blocks * 512 * sc.lh.voxel_bytes), SEEK_SET) != 0) { set_error("nvbx_load_map: truncated file"); return NVBX_E_IO; }
-    sections.push_back(sc);
-  }
-  { const long end = ftell(fc.f); fseek(fc.f, 0, SEEK_END); if (ftell(fc.f) < end) { set_error("nvbx_load_map: truncated file"); return NVBX_E_IO; } }
-  int rc = nvbx_mapper_clear(m);
-  if (rc) return rc;
-  for (const Section& sc : sections) {
-    const int64_t n = (int64_t)sc.lh.n_blocks;
-    const size_t bb = 512 * (size_t)sc.lh.voxel_bytes;
-    std::vector<nvbx_index3d> idx((size_t)std::max<int64_t>(n, 1));
-    fseek(fc.f, sc.idx_off, SEEK_SET);
-    if (n > 0 && fread(idx.data(), 12, (size_t)n, fc.f) != (size_t)n) { set_error("nvbx_load_map: read failed"); return NVBX_E_IO; }
-    const int64_t chunk = 4096;
-    std::vector<uint8_t> buf((size_t)std::min<int64_t>(std::max<int64_t>(n, 1), chunk) * bb);
-    for (int64_t o = 0; o < n; o += chunk) {
-      const int64_t c = std::min(chunk, n - o);
-      if (fread(buf.data(), bb, (size_t)c, fc.f) != (size_t)c) { set_error("nvbx_load_map: read failed"); return NVBX_E_IO; }
-      rc = nvbx_set_blocks(m, sc.lh.layer, idx.data() + o, c, buf.data());
-      if (rc) return rc;
-    }
-  }
-  return NVBX_OK;
 }
 
 extern "C" int nvbx_get_counters(nvbx_mapper* m, nvbx_counters* out) {
@@ -916,120 +402,5 @@ extern "C" int nvbx_get_counters(nvbx_mapper* m, nvbx_counters* out) {
   out->mesh_triangles = m->mesh_epoch ? m->shc_sum(S_MESH_REC + mpar, 3) : 0;
   out->capacity_overflow = c[C_OVERFLOW];
   out->lidar_blocks_beam_centric = m->shc_sum(S_LIDAR_SPARSE, 0);
-  return NVBX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ per-kernel timing
-hipEvent_t nvbx_mapper::get_event() {
-  if (!event_pool.empty()) { hipEvent_t e = event_pool.back(); event_pool.pop_back(); return e; }
-  hipEvent_t e = nullptr; (void)hipEventCreate(&e); return e;
-}
-void nvbx_mapper::span_begin(const char* name, hipStream_t st) {
-  Span s{name, get_event(), get_event()};
-  (void)hipEventRecord(s.a, st);
-  spans.push_back(s);
-}
-void nvbx_mapper::span_end(hipStream_t st) { (void)hipEventRecord(spans.back().b, st); }
-
-__global__ void k_reset_esdf_dirty_list(DMap m) { if (threadIdx.x < NSH) *shc_at(m, S_LIST_ESDF_DIRTY, threadIdx.x, 0) = 0; }
-int nvbx_mapper::reset_consumed_list() {
-  if (premark_consumed) { NVBX_LAUNCH(this, k_reset_esdf_dirty_list, dim3(1), dim3(64), d); premark_consumed = false; }
-  return NVBX_OK;
-}
-int nvbx_mapper::join_side() {
-  enqueue_seq++;                     // (an entry point runs: host copies of device counters are stale from here on, esdf.hip nvbx_esdf_slice_to_image)
-  zc_valid = false;                  // (whatever follows may change the TSDF: the kept zero-crossing list is dropped)
-  // every entry point passes here before its first HIP call: make this mapper's device current (hosts with one mapper per GPU in
-  // one process); a thread-local read when it already is
-  { int cur = -1; if (hipGetDevice(&cur) != hipSuccess || cur != device) NVBX_HIP(hipSetDevice(device)); }
-  if (!replaying && !pipelined_order && replay_deferred()) return NVBX_E_DEVICE;      // held-back integrateColor / updateEsdf: carried out first, in call order
-  if (flush_edt()) return NVBX_E_DEVICE;
-  if (flush_import()) return NVBX_E_DEVICE;
-  main_dirty = true;
-  if (side_pending) { NVBX_HIP(hipStreamWaitEvent(stream, ev_side, 0)); side_pending = false; }
-  return NVBX_OK;
-}
-int nvbx_mapper::join_side_keeping_held() {
-  const bool e = edt_pending, i = import_pending, u = esdf_update_pending, c = color_pending.on;
-  edt_pending = false; import_pending = false; esdf_update_pending = false; color_pending.on = false;
-  const int rc = join_side();
-  edt_pending = e; import_pending = i; esdf_update_pending = u; color_pending.on = c;
-  return rc;
-}
-// the held-back calls of colour deferral, carried out as they would have been at call time
-int nvbx_mapper::replay_deferred() {
-  if (!color_pending.on && !esdf_update_pending) return NVBX_OK;
-  replaying = true;
-  int rc = NVBX_OK;
-  if (replay_pair_applies()) { rc = replay_pair(); replaying = false; return rc == NVBX_OK ? NVBX_OK : NVBX_E_DEVICE; }
-  if (color_pending.on) {
-    const ColorPending c = take_pending();
-    if (c.n > 1) rc = nvbx_integrate_color_batch(this, c.n, reinterpret_cast<const uint8_t* const*>(c.imgs), c.rows, c.cols, c.T, c.cams);
-    else rc = c.kind == 0 ? nvbx_integrate_color(this, (const uint8_t*)c.imgs[0], c.rows, c.cols, c.T, &c.cams[0])
-                          : nvbx_integrate_color_bgra8(this, (const uint8_t*)c.imgs[0], c.rows, c.cols, c.T, &c.cams[0]);
-  }
-  if (rc == NVBX_OK && esdf_update_pending) { esdf_update_pending = false; rc = nvbx_update_esdf(this); }
-  esdf_update_pending = false;
-  replaying = false;
-  release_consumed_frames();
-  return rc == NVBX_OK ? NVBX_OK : NVBX_E_DEVICE;
-}
-extern "C" int nvbx_mapper_set_color_deferral(nvbx_mapper* m, int32_t enable) {
-  if (!m) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;          // (anything held back under the old setting is carried out)
-  if (enable < 0 || enable > 2) { set_error("nvbx_mapper_set_color_deferral: 0 = off, 1 = on (the caller keeps the image valid), 2 = on with a staged copy"); return NVBX_E_INVALID; }
-  m->color_deferral = enable != 0; m->color_staging = enable == 2;
-  return NVBX_OK;
-}
-int nvbx_mapper::mark_main() {
-  if (use_side) { NVBX_HIP(hipEventRecord(ev_main, stream)); main_dirty = false; }
-  return NVBX_OK;
-}
-
-extern "C" int nvbx_set_profiling(nvbx_mapper* m, int32_t enable) {
-  if (!m) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
-  NVBX_HIP(hipStreamSynchronize(m->stream));
-  for (auto& s : m->spans) { m->event_pool.push_back(s.a); m->event_pool.push_back(s.b); }
-  m->spans.clear();
-  m->profiling = enable != 0;
-  return NVBX_OK;
-}
-
-// JSON object {"kernel": {"count": n, "total_ms": t}, ...} of every launch since nvbx_set_profiling(m, 1).
-extern "C" int nvbx_get_profile(nvbx_mapper* m, char* json_out, int64_t capacity) {
-  if (!m || !json_out || capacity < 4) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
-  NVBX_HIP(hipStreamSynchronize(m->stream));
-  struct Acc { const char* name; int64_t n; double ms; double max_ms; };
-  std::vector<Acc> acc;
-  for (auto& s : m->spans) {
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, s.a, s.b) != hipSuccess) continue;
-    bool hit = false;
-    for (auto& a : acc) if (!strcmp(a.name, s.name)) { a.n++; a.ms += ms; if (ms > a.max_ms) a.max_ms = ms; hit = true; break; }
-    if (!hit) acc.push_back({s.name, 1, ms, ms});
-  }
-  // what a hipEvent pair adds to the span of ONE launch: pairs with nothing between them, on the same (now idle) stream
-  {
-    const int kPairs = 32; double ms_sum = 0.0; int n_ok = 0;
-    std::vector<hipEvent_t> ev;
-    for (int i = 0; i < 2 * kPairs; i++) { ev.push_back(m->get_event()); (void)hipEventRecord(ev.back(), m->stream); }
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    for (int i = 0; i < kPairs; i++) { float ms = 0.0f; if (hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) { ms_sum += ms; n_ok++; } }
-    for (hipEvent_t e : ev) m->event_pool.push_back(e);
-    if (n_ok) acc.push_back({"_empty_event_pair", n_ok, ms_sum, 0.0});
-  }
-  std::string out = "{";
-  for (size_t i = 0; i < acc.size(); i++) {
-    char buf[256];
-    std::string nm = acc[i].name;
-    for (char& c : nm) if (c == '(' || c == ')' ) c = ' ';
-    snprintf(buf, sizeof(buf), "%s\"%s\": {\"count\": %lld, \"total_ms\": %.6f, \"max_ms\": %.6f}", i ? ", " : "", nm.c_str(), (long long)acc[i].n, acc[i].ms, acc[i].max_ms);
-    out += buf;
-  }
-  out += "}";
-  if ((int64_t)out.size() + 1 > capacity) return NVBX_E_CAPACITY;
-  memcpy(json_out, out.c_str(), out.size() + 1);
   return NVBX_OK;
 }

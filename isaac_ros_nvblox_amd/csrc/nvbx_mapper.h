@@ -24,11 +24,10 @@ struct EsdfArgs {
   uint32_t mark_pass;               // stamp of this marking pass (column de-duplication within one pass)
   int32_t rec;                      // C_ESDF_UPD + 8 * (epoch & 1)
   int32_t rec_next;                 // record of the next epoch (reset by this update)
-  // Who empties the ESDF-dirty list a marking pass has consumed.  Classic order (marking -> view marking of the next frame / EDT -> TSDF
-  // update): the next k_mark_view or the EDT does (the consumed list still names "the blocks dirtied since the last updateEsdf" for
-  // nvbx_esdf_dirty_list until then).  Pipelined order (colour deferral, DESIGN.md 2.8: view marking(i+1) || sphere tracing(i) -> colour(i) +
-  // marking -> TSDF update(i+1)): nothing runs between the marking pass and the next appends, so the pass empties the list itself --
-  // its last worker, counted in C_MARK_DONE (self_reset) -- and the EDT of that update, which then runs AFTER those appends, must not (keep_list).
+  // Who empties the ESDF-dirty list a marking pass has consumed.  Classic order: the next k_mark_view or the EDT does (the consumed list still names
+  // "the blocks dirtied since the last updateEsdf" for nvbx_esdf_dirty_list until then).  Pipelined order (held.hip): nothing runs between the marking
+  // pass and the next appends, so the pass empties the list itself -- its last worker, counted in C_MARK_DONE (self_reset) -- and the EDT of that
+  // update, which then runs AFTER those appends, must not (keep_list).
   int32_t self_reset, keep_list;
   // [U] ground-plane-relative slice (nvbx_mapper_params::esdf_use_ground_plane): the z band of column (x, y) is [h + above, h + above + thick],
   // h = height of the plane {n, d} at the column's centre (esdf_plane_height); 0 = the fixed band kz_min .. kz_max above
@@ -45,6 +44,13 @@ void frames_register_stream(int device, hipStream_t stream);
 void frames_forget_owner(const void* owner, int device, hipStream_t stream);
 void set_error(const char* what, hipError_t e);
 void set_error(const char* what);
+// layers.hip.  API layer id -> internal slot flag (0 = this mapper cannot hold that layer); bytes of one voxel in the reference's struct layout
+uint32_t internal_layer(const nvbx_mapper* m, uint32_t layer);
+size_t ref_voxel_bytes(uint32_t layer);
+// API layer ids by what can be done with them: written block by block (nvbx_set_blocks, map files) / read block by block / listed
+static inline bool layer_writable(uint32_t l) { return l == F_TSDF || l == F_COLOR || l == F_ESDF || l == NVBX_LAYER_OCCUPANCY; }
+static inline bool layer_readable(uint32_t l) { return layer_writable(l) || l == F_FREESPACE; }
+static inline bool layer_listable(uint32_t l) { return layer_readable(l) || l == F_MESH; }
 
 }  // namespace nvbx
 
@@ -79,7 +85,7 @@ struct nvbx_mapper {
   bool use_side = false;        // NVBX_SIDE_STREAM=0 disables
   bool side_pending = false;    // ESDF work enqueued on `side` that `stream` has not waited for yet
   bool main_dirty = true;       // non-colour work enqueued on `stream` since ev_main was recorded
-  int join_side();              // make `stream` wait for the side stream (no host sync)
+  int join_side(bool carry_out_held = true);      // first call of every entry point (held.hip): held-back work is carried out, `stream` waits for the side stream (no host sync)
   int mark_main();              // record ev_main on `stream` (call right after a non-colour operation)
   nvbx_mapper_params p{};
   int64_t capacity = 0;
@@ -127,6 +133,7 @@ struct nvbx_mapper {
   // ESDF marking state: `dirty_since_mark` = TSDF changed since the last marking pass; `premark_consumed` = the dirty list
   // was processed by a pass that no EDT followed yet, so it must be emptied before anything is appended to it
   bool dirty_since_mark = false, premark_consumed = false;
+  void reset_marking() { dirty_since_mark = false; premark_consumed = false; mark_pass = 0; unresolved_marks = false; pass_at_last_edt = 0; }      // (a cleared map)
   // `unresolved_marks` = a marking pass ran that no distance transform has followed yet (its columns are only PENDING):
   // an operation that deallocates blocks takes such passes back first (undo_marks, esdf.hip), so that the ESDF update that
   // eventually runs sees exactly the dirty set the reference semantics define at that moment.  `pass_at_last_edt` =
@@ -148,37 +155,31 @@ struct nvbx_mapper {
   // EsdfMode::k3D (esdf3d.hip)
   int update_esdf_3d();
   nvbx::DevBuf esdf3_scratch; int64_t esdf3_blocks_marked = 0, esdf3_window_voxels = 0;
-  // held-back EDT of the last updateEsdf (NVBX_DEFER_EDT=0 disables): see nvbx_update_esdf
-  bool defer_edt = true, edt_pending = false; nvbx::EsdfArgs edt_args{};
-  int flush_edt();
-  // held-back union step of the multi-GPU exchange (nvbx_mark_esdf_dirty_gathered_deferred): rides in the next integrateColor
-  // launch beside the marking of the mapper's own dirty blocks; every other entry point launches it first (flush_import)
-  bool import_pending = false; const int32_t* import_ptr = nullptr; int32_t import_world = 0, import_rank = 0; int64_t import_max = 0;
-  int flush_import();
-  // Colour deferral (nvbx_mapper_set_color_deferral): integrateColor of a single frame is HELD BACK -- arguments remembered,
-  // nothing launched -- and so is an updateEsdf that follows it.  The next single-camera integrateDepth carries them out in pipelined
-  // order: view marking of the new depth frame || sphere tracing of the held-back colour frame (one launch), colour integration + ESDF
-  // marking, TSDF update of the new frame -- three launches per frame instead of four.  Every other entry point first replays the held-back
-  // calls as they are (join_side -> replay_deferred), so the API observes call order.  Contract: the colour image must stay valid and
-  // unchanged until the next call into the mapper has returned.
-  // (n = 1: integrateColor, kind 0 = rgb8 / 1 = bgra8; n > 1: nvbx_integrate_color_batch, rgb8 -- carried out by a depth BATCH in pipelined order)
-  // (frames[i] != nullptr: imgs[i] lives in a library-owned frame this mapper has RETAINED -- the caller's own frame of nvbx_frame_acquire, or the
-  //  frame the staged form copied a raw pointer's image into; let go of, with a fence, once the launches that read it are enqueued: frames.hip)
+  bool defer_edt = true;             // the EDT of an updateEsdf is held back (NVBX_DEFER_EDT=0 disables): see nvbx_update_esdf
+  int flush_edt(); int flush_import();      // esdf.hip: launch the held-back EDT / union step now
+  // (n = 1: integrateColor, kind 0 = rgb8 / 1 = bgra8; n > 1: nvbx_integrate_color_batch, rgb8.  frames[i] != nullptr: imgs[i] lives in a library-owned
+  //  frame this mapper has RETAINED, let go of with a fence once the launches that read it are enqueued: frames.hip)
   struct ColorPending { bool on = false; int kind = 0; int32_t n = 1; const void* imgs[nvbx::MAX_BATCH] = {}; void* frames[nvbx::MAX_BATCH] = {}; int32_t rows = 0, cols = 0; float T[16 * nvbx::MAX_BATCH]; nvbx_camera cams[nvbx::MAX_BATCH]; };
+  struct Held {      // work an entry point has accepted but not launched yet: what, who carries it out and in which order -- the top of held.hip
+    bool edt_pending = false; nvbx::EsdfArgs edt_args{};       // the distance transform of the last updateEsdf
+    bool import_pending = false; const int32_t* import_ptr = nullptr; int32_t import_world = 0, import_rank = 0; int64_t import_max = 0;      // the union step of the multi-GPU exchange
+    ColorPending color_pending;                                // an integrateColor (colour deferral) ...
+    bool esdf_update_pending = false;                          // ... and an updateEsdf called behind it, or with colour deferral on and no colour at all
+    bool any() const { return edt_pending || import_pending || color_pending.on || esdf_update_pending; }
+    // (a cleared map) nothing is carried out, the frames of a held-back colour call are let go of with their fence
+    void drop(nvbx_mapper& m) { edt_pending = false; import_pending = false; esdf_update_pending = false; (void)m.take_pending(); m.release_consumed_frames(); }
+  } held;
   bool color_deferral = true;        // the switch (default: on, staged -- nvbx_mapper_create; NVBX_COLOR_DEFERRAL=0 in the environment: off)
-  // nvbx_mapper_set_color_deferral(m, 2): a held-back frame is COPIED into mapper-owned staging memory when it is held back (one asynchronous
-  // device-to-device copy on the mapper's stream per frame) -- the caller may recycle or overwrite its image as soon as integrateColor has
-  // returned, as without deferral.  One buffer per camera of a batch suffices: the copy of the next frame is stream-ordered behind the launches
-  // that read the previous one.
+  // nvbx_mapper_set_color_deferral(m, 2): a held-back frame is COPIED into mapper-owned staging memory when it is held back (one asynchronous copy on the
+  // mapper's stream, ordered behind the launches that read the previous one), so the caller may overwrite its image as soon as integrateColor has returned
   bool color_staging = true;
-  ColorPending color_pending;        // the held-back integrateColor
   // frames of held-back colour images (frames.hip).  take_pending: the held-back call is being carried out -- its frames move to `consumed_frames`;
   // release_consumed_frames (after the launches that read them are enqueued, or abandoned): refs dropped with the fence {h_mirror[4] >= seq}.
   // h_mirror[4] is written by the next view-marking launch as its first action (TraceRiderT::fence_report = color_reads_enqueued at that time).
   std::vector<void*> consumed_frames;
   int32_t color_reads_enqueued = 0;      // fence sequence: bumped once per release_consumed_frames
   int32_t fence_reports_enqueued = 0;    // the largest fence_report any ENQUEUED launch carries
-  ColorPending take_pending() { ColorPending c = color_pending; color_pending.on = false; for (int i = 0; i < nvbx::MAX_BATCH; i++) { if (c.frames[i]) consumed_frames.push_back(c.frames[i]); color_pending.frames[i] = nullptr; } return c; }
+  ColorPending take_pending() { ColorPending c = held.color_pending; held.color_pending.on = false; for (int i = 0; i < nvbx::MAX_BATCH; i++) { if (c.frames[i]) consumed_frames.push_back(c.frames[i]); held.color_pending.frames[i] = nullptr; } return c; }
   void release_consumed_frames() {
     if (consumed_frames.empty()) return;
     const int32_t seq = ++color_reads_enqueued;
@@ -187,18 +188,18 @@ struct nvbx_mapper {
   }
   int32_t next_fence_report() { __atomic_store_n(&fence_reports_enqueued, color_reads_enqueued, __ATOMIC_RELEASE); return color_reads_enqueued; }
   int64_t inv_i8 = 0;                // (-DNVBX_CHECK_INVARIANTS) colour-reading launches enqueued on a library frame that nobody holds
-  bool esdf_update_pending = false;  // an updateEsdf called while a colour frame was held back
+  // The two modes of held.hip, each true for a stretch of code and false outside it, whichever way that stretch is left: set by a ModeScope only.
   bool replaying = false;            // inside replay_deferred: the calls run as usual
   bool pipelined_order = false;      // inside the pipelined integrateDepth: marking passes empty their list, EDTs keep it (EsdfArgs)
+  struct ModeScope {
+    bool* flag = nullptr; ModeScope() = default; explicit ModeScope(bool& f) { enter(f); } ModeScope(const ModeScope&) = delete; ~ModeScope() { leave(); }
+    void enter(bool& f) { flag = &f; f = true; }
+    void leave() { if (flag) *flag = false; flag = nullptr; }
+  };
   int replay_deferred();
-  // join_side for an entry point that neither reads nor writes what the held-back work touches (colour layer, ESDF layer, site masks, the
-  // ESDF-dirty list): the held-back distance transform, union step, colour frame and ESDF update stay held back (nvbx_detect_dynamics: TSDF +
-  // freespace reads only -- the dynamic-mapping frame starts with it, and flushing there would cost the pipeline every frame)
-  int join_side_keeping_held();
-  // a held-back updateEsdf with NO colour frame in front of it (colour deferral on, the caller integrates no colour: depth-only hosts, occupancy
-  // mappers) that the next camera launch can carry in two-launch order: marking pass in the view-marking launch, distance transform in the
-  // TSDF-update launch
-  bool esdf_only_carry() const { return esdf_update_pending && !color_pending.on && p.esdf_mode == 0 && p.esdf_propagation == 0 && !import_pending && !use_side && defer_edt; }
+  int join_side_keeping_held() { return join_side(false); }      // for an entry point that touches nothing the held-back work does: it all stays held back
+  // a held-back updateEsdf with NO colour frame in front of it (depth-only hosts, occupancy mappers) that the next camera launch can carry in two-launch order
+  bool esdf_only_carry() const { return held.esdf_update_pending && !held.color_pending.on && p.esdf_mode == 0 && p.esdf_propagation == 0 && !held.import_pending && !use_side && defer_edt; }
   int pending_color_trace_rider(void* trace_rider_out);   // color.hip: set the held-back frame(s) up; the sphere tracing as a nvbx::TraceRiderT<1> (one frame) / <MAX_BATCH> (a batch)
   int launch_pending_color_after_trace();
   bool replay_pair_applies() const;  // color.hip: a held-back colour frame + updateEsdf can be replayed in two launches (replay_pair)

@@ -281,6 +281,7 @@ template <int NB> struct DepthSteps {
   FrameSetC<PixRgb8, NB> fsc{}; int f_kind = 0; int32_t f_srows = 0, f_scols = 0;      // launch 2 (fused form)
   int grid = 8; int32_t spec_lanes = 1;
   int32_t n_edt = 0; EsdfArgs ea_edt{}; const int4* cand = nullptr; int32_t cand_idx = 0; int cgrid = 0; ImportArgs imp{};
+  nvbx_mapper::ModeScope pipelined_order;      // the mapper's flag: on in step 1, off in step 2 -- or wherever the frame is given up in between
 };
 // step 1: everything in front of the view-marking launch (ray grid, riders of the held-back calls, the fence report)
 template <typename Img, typename Sensor, int NB>
@@ -289,9 +290,9 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
   const Frame& f = fs.f[0];
   st.tiles = mark_view_tile_wgs<Sensor>(f) * fs.n;       // tile workgroups (padded: the groups of one XCD are a contiguous band, k_mark_view); camera after camera
   // a held-back EDT rides in this launch (camera: 256-thread workgroups); the LiDAR launch is 64 threads wide, so flush first
-  st.edt_wg = 0; st.ea = m->edt_args;
-  if (m->edt_pending) {
-    if (Sensor::kRiders) { st.edt_wg = 256; m->edt_pending = false; }        // (256 .. 1024 riders measured: no difference, profiles/r02x_kernel_isolation.txt)
+  st.edt_wg = 0; st.ea = m->held.edt_args;
+  if (m->held.edt_pending) {
+    if (Sensor::kRiders) { st.edt_wg = 256; m->held.edt_pending = false; }        // (256 .. 1024 riders measured: no difference, profiles/r02x_kernel_isolation.txt)
     else if (m->flush_edt()) return NVBX_E_DEVICE;
   }
   // Colour deferral: a held-back integrateColor (and an updateEsdf behind it) is carried out in PIPELINED order -- its sphere tracing rides
@@ -304,10 +305,10 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
   st.tr = TraceRiderT<NB>{};
   st.plain = true;
   for (int c = 0; c < fs.n; c++) st.plain = st.plain && frame_is_plain(fs.f[c]);
-  st.has_color = m->color_pending.on;
+  st.has_color = m->held.color_pending.on;
   // (one frame carries a frame, a batch a batch; a held-back updateEsdf WITHOUT a colour frame -- depth-only and occupancy mappers -- is carried by
   //  any camera launch: integrate_cameras has checked that the two-launch order applies, nvbx_mapper::esdf_only_carry)
-  st.pipelined = Sensor::kRiders && (st.has_color ? ((NB == 1) == (m->color_pending.n == 1)) : m->esdf_update_pending);
+  st.pipelined = Sensor::kRiders && (st.has_color ? ((NB == 1) == (m->held.color_pending.n == 1)) : m->held.esdf_update_pending);
   st.fused = false;
   if (st.pipelined) {
     // TSDF mapper (with or without a freespace layer), 2-D ESDF by the exact transform (the marking pass / distance transform that ride are the
@@ -316,9 +317,9 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
     st.fused = st.has_color ? fused_colour_applies(m)
                             : true;      // (no colour: no candidates, no band flags -- esdf_only_carry has checked the rest)
     // (a distance transform armed outside the pipeline must precede the marking pass that rides in this launch: its own launch, rare)
-    if (st.fused && st.edt_wg) { m->edt_pending = true; st.edt_wg = 0; if (m->flush_edt()) return NVBX_E_DEVICE; }
-    m->pipelined_order = true;
-    if (st.has_color) { const int rc = m->pending_color_trace_rider(&st.tr); if (rc) { m->pipelined_order = false; return rc; } }
+    if (st.fused && st.edt_wg) { m->held.edt_pending = true; st.edt_wg = 0; if (m->flush_edt()) return NVBX_E_DEVICE; }
+    st.pipelined_order.enter(m->pipelined_order);
+    if (st.has_color) { const int rc = m->pending_color_trace_rider(&st.tr); if (rc) return rc; }
     // riders before or after the tiles (A/B: NVBX_MARK_TILES_FIRST = 0 / 1).  One frame: tiles first (15.2 vs 15.8 us).  A batch of 8: riders first
     // (32.4 vs 42.0 us) -- its 2 688 single-wavefront tile workgroups, each holding its LDS key set, take most of the workgroup slots, and
     // sphere-tracing workgroups dispatched behind them start when the tiles are done: the launch took the SUM of its parts.
@@ -327,7 +328,7 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
     if (tiles_first) st.tr.n_tile_wg = st.tiles;
     if (st.fused && !st.has_color) m->pending_marking_args(&st.tr.n_mark_wg, &st.ea, NB == 1);
     if (st.fused && st.has_color) {
-      if (m->color_cand.ensure(m->stream, (size_t)m->capacity * 2 * sizeof(int4))) { m->pipelined_order = false; return NVBX_E_DEVICE; }      // (the capacity only grows: the buffer is [2][capacity])
+      if (m->color_cand.ensure(m->stream, (size_t)m->capacity * 2 * sizeof(int4))) return NVBX_E_DEVICE;      // (the capacity only grows: the buffer is [2][capacity])
       const int64_t hw_seen = std::max<int64_t>(1, __atomic_load_n(&m->h_mirror[1], __ATOMIC_RELAXED));
       st.tr.n_scan_wg = (int32_t)std::min<int64_t>(256, 8 * ((hw_seen + hw_seen / 4 + 64 + 2047) / 2048));      // 256 slots per workgroup and pass; a hint only (the riders grid-stride)
       st.tr.cand = m->color_cand.as<int4>() + (size_t)m->cand_parity * (size_t)m->capacity;
@@ -356,8 +357,8 @@ static int depth_step_between(nvbx_mapper* m, DepthSteps<NB>& st) {
     int rc = NVBX_OK;
     if (st.fused) { if (st.has_color) rc = m->pending_color_fused_args(&st.fsc, &st.f_kind, &st.f_srows, &st.f_scols); }
     else rc = m->launch_pending_color_after_trace();
-    if (rc == NVBX_OK && m->esdf_update_pending) { m->esdf_update_pending = false; rc = nvbx_update_esdf(m); }
-    m->pipelined_order = false;
+    if (rc == NVBX_OK && m->held.esdf_update_pending) { m->held.esdf_update_pending = false; rc = nvbx_update_esdf(m); }
+    st.pipelined_order.leave();
     if (rc) return rc;
   }
   m->premark_consumed = false; m->dirty_since_mark = true;
@@ -381,9 +382,9 @@ static int depth_step_between(nvbx_mapper* m, DepthSteps<NB>& st) {
 // [distance transform the held-back updateEsdf has just armed][TSDF update of this frame][colour integration of the held-back frame]
 template <int NB>
 static void depth_step_fused_riders(nvbx_mapper* m, DepthSteps<NB>& st) {
-  st.n_edt = 0; st.ea_edt = m->edt_args;
+  st.n_edt = 0; st.ea_edt = m->held.edt_args;
   static const int edt_riders = nvbx_knob_edt_riders(getenv("NVBX_EDT_RIDERS"));      // (A/B; a multiple of 8, at least 8)
-  if (m->edt_pending) { st.n_edt = edt_riders; m->edt_pending = false; }
+  if (m->held.edt_pending) { st.n_edt = edt_riders; m->held.edt_pending = false; }
   st.cand = st.tr.cand;
   st.cand_idx = st.tr.cand_cnt_idx;
   const int64_t c_hint = std::max<int64_t>(0, __atomic_load_n(&m->h_mirror[3], __ATOMIC_RELAXED));         // candidates of the last colour frame the GPU has finished
@@ -394,9 +395,9 @@ static void depth_step_fused_riders(nvbx_mapper* m, DepthSteps<NB>& st) {
   // blocks become ESDF-dirty for the NEXT marking pass (its own marking launch, or a ride in the colour launch, would be a third launch;
   // beside this frame's view marking it would meet blocks that launch is just allocating -- DESIGN.md 6.1)
   st.imp = ImportArgs{};
-  if (m->import_pending) {
-    st.imp.g = m->import_ptr; st.imp.world = m->import_world; st.imp.self_rank = m->import_rank; st.imp.max_count = m->import_max; st.imp.n_wg = 8;
-    m->import_pending = false;
+  if (m->held.import_pending) {
+    st.imp.g = m->held.import_ptr; st.imp.world = m->held.import_world; st.imp.self_rank = m->held.import_rank; st.imp.max_count = m->held.import_max; st.imp.n_wg = 8;
+    m->held.import_pending = false;
   }
 }
 // step 4: behind the TSDF-update launch
@@ -456,17 +457,17 @@ static int integrate_depth_pair_impl(nvbx_mapper* ma, FrameSet<Img, 1> fa, nvbx_
   struct ReleaseFrames { nvbx_mapper* m; ~ReleaseFrames() { m->release_consumed_frames(); } } release_a{ma}, release_b{mb};
   DepthSteps<1> sa, sb;
   { const int rc = depth_step_before_mark_view<Img, CameraSensor, 1>(ma, fa, sa); if (rc) return rc; }
-  { const int rc = depth_step_before_mark_view<Img, CameraSensor, 1>(mb, fb, sb); if (rc) { ma->pipelined_order = false; return rc; } }
+  { const int rc = depth_step_before_mark_view<Img, CameraSensor, 1>(mb, fb, sb); if (rc) return rc; }
   // (a distance transform armed in classic order would ride with the LDS of an EdtShared: launched on its own first -- rare, a mapper that has just left the classic order)
-  if (sa.edt_wg) { ma->edt_pending = true; sa.edt_wg = 0; if (ma->flush_edt()) return NVBX_E_DEVICE; }
-  if (sb.edt_wg) { mb->edt_pending = true; sb.edt_wg = 0; if (mb->flush_edt()) return NVBX_E_DEVICE; }
+  if (sa.edt_wg) { ma->held.edt_pending = true; sa.edt_wg = 0; if (ma->flush_edt()) return NVBX_E_DEVICE; }
+  if (sb.edt_wg) { mb->held.edt_pending = true; sb.edt_wg = 0; if (mb->flush_edt()) return NVBX_E_DEVICE; }
   // (tiles-first layout inside each mapper's numbering, whether or not it has riders: the pair kernel deals the tiles of both out first)
   sa.tr.n_tile_wg = sa.tiles; sb.tr.n_tile_wg = sb.tiles;
   MarkViewArgs<Img> A{ma->d, fa, (int4*)ma->view_list, (int32_t)ma->capacity, (int32_t)(ma->premark_consumed ? 1 : 0), 0, sa.ea, sa.tr, sa.tiles, sa.tiles + sa.tr.n_wg + sa.tr.n_scan_wg + sa.tr.n_mark_wg};
   MarkViewArgs<Img> B{mb->d, fb, (int4*)mb->view_list, (int32_t)mb->capacity, (int32_t)(mb->premark_consumed ? 1 : 0), 0, sb.ea, sb.tr, sb.tiles, sb.tiles + sb.tr.n_wg + sb.tr.n_scan_wg + sb.tr.n_mark_wg};
   mb->enqueue_seq++;
   NVBX_LAUNCH_SMEM(ma, (k_mark_view_pair<Img>), dim3((unsigned)(A.n_wg + B.n_wg)), dim3(CameraSensor::kThreads), mark_view_smem<CameraSensor>(false), A, B);
-  { const int rc = depth_step_between<CameraSensor, 1>(ma, sa); if (rc) { mb->pipelined_order = false; return rc; } }
+  { const int rc = depth_step_between<CameraSensor, 1>(ma, sa); if (rc) return rc; }
   { const int rc = depth_step_between<CameraSensor, 1>(mb, sb); if (rc) return rc; }
   // the TSDF-update launch in its fused form for both (a mapper with nothing held back: no riders -- the same worker as k_integrate_tsdf)
   if (sa.fused) depth_step_fused_riders<1>(ma, sa);      // (else: zero riders, DepthSteps' defaults)
@@ -539,21 +540,12 @@ static int cameras_prepare(nvbx_mapper* m, int32_t n, const float* T_L_C /* n x 
       set_error("integrate depth: T_L_C is not finite or lies outside the addressable block range (+-2^20 blocks)"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
   const bool dilate_first = m->p.do_depth_preprocessing && m->p.depth_preprocessing_num_dilations > 0;
-  // held-back integrateColor / updateEsdf that this call cannot carry out in pipelined order are replayed NOW, with the whole held-back
-  // state in view (the replayed calls launch / re-arm the held-back EDT themselves) -- before the EDT is hidden from join_side below
-  const bool carry = !dilate_first && (m->color_pending.on ? ((NB == 1) == (m->color_pending.n == 1)) : m->esdf_only_carry());      // this call can carry the held-back calls out in pipelined order
+  // held-back integrateColor / updateEsdf that this call cannot carry out in pipelined order are replayed NOW (the replayed calls launch / re-arm the EDT)
+  const bool carry = !dilate_first && (m->held.color_pending.on ? ((NB == 1) == (m->held.color_pending.n == 1)) : m->esdf_only_carry());      // this call can carry the held-back calls out in pipelined order
   if (!carry && m->replay_deferred()) return NVBX_E_DEVICE;
-  { const bool pend = m->edt_pending, ipend = m->import_pending; m->edt_pending = false; m->import_pending = false;
-    // (join_side would launch a held-back EDT / union step; the EDT rides in k_mark_view instead, the union step stays held back
-    //  for the next integrateColor -- it belongs to the NEXT ESDF update and touches nothing this launch reads)
-    // A held-back colour frame (+ ESDF update) stays held back too when this call can carry it out in pipelined order (a single frame,
-    // no dilation launch in front); otherwise join_side replays it now.
-    const bool keep = carry;
-    const nvbx_mapper::ColorPending cp = m->color_pending; const bool up = m->esdf_update_pending;
-    if (keep) { m->color_pending.on = false; m->esdf_update_pending = false; }
-    const int rc = m->join_side(); m->edt_pending = pend; m->import_pending = ipend;
-    if (keep) { m->color_pending = cp; m->esdf_update_pending = up; }
-    if (rc) return NVBX_E_DEVICE; }
+  // (join_side would launch a held-back EDT / union step; the EDT rides in k_mark_view instead, the union step stays held back for the next
+  //  integrateColor -- it belongs to the NEXT ESDF update and touches nothing this launch reads.  What else is still held back, this call carries out)
+  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
   { const int rc = m->maybe_grow(); if (rc) return rc; }          // (before anything of this frame is enqueued)
   return NVBX_OK;
 }
@@ -613,13 +605,13 @@ extern "C" int nvbx_integrate_depth_batch(nvbx_mapper* m, int32_t n, const float
 static bool pair_can_fuse(const nvbx_mapper* m) {
   if (m->use_side || m->capacity > (1ll << 24)) return false;
   if (m->p.do_depth_preprocessing && m->p.depth_preprocessing_num_dilations > 0) return false;          // (a dilation launch in front)
-  if (m->color_pending.on && (m->color_pending.n != 1 || !fused_colour_applies(m))) return false;      // (its colour frame would be carried in three launches)
+  if (m->held.color_pending.on && (m->held.color_pending.n != 1 || !fused_colour_applies(m))) return false;      // (its colour frame would be carried in three launches)
   return true;
 }
 // (the pair launch decodes ONE pixel type -- that of whichever mapper holds a colour frame: two held-back frames in different encodings, rgb8 and bgra8,
 //  cannot share it.  Checked before either mapper's preparation, which consumes host state)
 static bool pair_colour_kinds_differ(const nvbx_mapper* ma, const nvbx_mapper* mb) {
-  return ma->color_pending.on && mb->color_pending.on && ma->color_pending.kind != mb->color_pending.kind;
+  return ma->held.color_pending.on && mb->held.color_pending.on && ma->held.color_pending.kind != mb->held.color_pending.kind;
 }
 extern "C" int nvbx_integrate_depth_pair(nvbx_mapper* ma, const float* depth_a_dev, nvbx_mapper* mb, const float* depth_b_dev, int32_t rows, int32_t cols,
                                          const float T_L_C[16], const nvbx_camera* camera) {
@@ -648,7 +640,7 @@ extern "C" int nvbx_integrate_depth_pair(nvbx_mapper* ma, const float* depth_a_d
 void launch_mark_view_camera(nvbx_mapper* m, const FrameSet<DepthF32, 1>& fs) {
   TraceRider no_riders{}; no_riders.fence_report = m->next_fence_report();
   NVBX_LAUNCH_SMEM(m, (k_mark_view<DepthF32, CameraSensor, 1>), dim3(mark_view_tile_wgs<CameraSensor>(fs.f[0])), dim3(CameraSensor::kThreads), mark_view_smem<CameraSensor>(false), m->d, fs, CameraSensor{},
-              (int4*)m->view_list, (int32_t)m->capacity, (int32_t)(m->premark_consumed ? 1 : 0), (int32_t)0, m->edt_args, no_riders);
+              (int4*)m->view_list, (int32_t)m->capacity, (int32_t)(m->premark_consumed ? 1 : 0), (int32_t)0, m->held.edt_args, no_riders);
   m->premark_consumed = false;
 }
 int integrate_lidar_frame(nvbx_mapper* m, FrameSet<DepthF32, 1> fs, const LidarSensor& sensor) {

@@ -165,7 +165,8 @@ def test_dynamic_front_end_in_three_launches_equals_the_three_calls_and_the_chec
     """nvbx_dynamic_depth_split (detect dynamics -> remove small components -> split, three launches, no memset) against the three separate entry
     points on a second mapper fed the same frames, and against the checker's detect / remove_small_components / split_depth_by_mask: the cleaned
     mask and both depth images bit for bit, every frame -- from the first (no freespace layer yet) to frames with a moving box in view; also
-    with the component filter off and with the overlay image."""
+    with the component filter off and with the overlay image.  (A box is one roughly convex blob: for mask SHAPES that need the cross-patch
+    rules of k_dyn_detect_union see tests/test_gpu_dynamic_masks.py.)"""
     import torch
     from isaac_ros_nvblox_amd import mapper as M
     rows, cols = cam[5], cam[4]

@@ -173,14 +173,14 @@ __global__ __launch_bounds__(256) void k_stage_color(StagePtrs p, int64_t bytes,
     for (int64_t i = (int64_t)wg * 256 + threadIdx.x; i < bytes; i += (int64_t)wg_per_image * 256) d[i] = s[i];
   }
 }
-static bool defer_color(nvbx_mapper* m, int kind, int32_t n, const void* const* imgs, int32_t rows, int32_t cols, const float* T_L_C, const nvbx_camera* cameras, int* rc_out) {
+static bool defer_color(nvbx_mapper* m, ColorEnc enc, int32_t n, const void* const* imgs, int32_t rows, int32_t cols, const float* T_L_C, const nvbx_camera* cameras, int* rc_out) {
   if (!m->color_deferral || m->replaying || m->p.projective_layer_type == 1) return false;
   *rc_out = color_precheck(m, n, rows, cols, T_L_C);            // argument errors are reported by the call that made them
   if (*rc_out) return true;
   if (hipSetDevice(m->device) != hipSuccess || m->replay_deferred()) { *rc_out = NVBX_E_DEVICE; return true; }     // an older held-back frame goes first
   m->release_consumed_frames();
   nvbx_mapper::ColorPending& c = m->held.color_pending;
-  const size_t bytes = (size_t)rows * (size_t)cols * (kind == 0 ? 3u : 4u);
+  const size_t bytes = (size_t)rows * (size_t)cols * with_color_types(enc, n, [](auto pix, auto) { return decltype(pix)::kBytes; });
   // Where each held-back image lives until it is carried out:
   //   a frame of nvbx_frame_acquire (nvblox::Image<T> device memory, nvbx_color_image_acquire): RETAINED -- no copy, in either mode (frames.hip);
   //   a raw device pointer, staged form (the default): copied into a frame of the mapper's own, one launch for the whole call (the caller may
@@ -204,14 +204,13 @@ static bool defer_color(nvbx_mapper* m, int kind, int32_t n, const void* const* 
     NVBX_LAUNCH(m, k_stage_color, dim3((unsigned)(wgi * n_copy)), dim3(256), sp, (int64_t)bytes, wgi);
     if (hipGetLastError() != hipSuccess) { undo(); set_error("colour staging copy"); *rc_out = NVBX_E_DEVICE; return true; }
   }
-  c.on = true; c.kind = kind; c.n = n; c.rows = rows; c.cols = cols;
+  c.on = true; c.enc = enc; c.n = n; c.rows = rows; c.cols = cols;
   for (int i = 0; i < MAX_BATCH; i++) { c.imgs[i] = i < n ? use[i] : nullptr; c.frames[i] = i < n ? frames[i] : nullptr; if (i < n) c.cams[i] = cameras[i]; }
   memcpy(c.T, T_L_C, sizeof(float) * 16 * (size_t)n);
   *rc_out = NVBX_OK;
   return true;
 }
 // the held-back frames' set-up (NB = 1: one frame, NB = MAX_BATCH: a batch)
-static_assert(sizeof(FrameSetC<PixRgb8, 1>) == sizeof(FrameSetC<PixBgra8, 1>), "colour frame sets share one layout");
 template <typename Pix, int NB>
 static int pending_setup(nvbx_mapper* m, const nvbx_mapper::ColorPending& c, FrameSetC<Pix, NB>* fs, PoseSet<NB>* ps, int32_t* srows, int32_t* scols) {
   Pix imgs[NB];
@@ -221,25 +220,27 @@ static int pending_setup(nvbx_mapper* m, const nvbx_mapper::ColorPending& c, Fra
 #endif
   return color_setup<Pix, NB>(m, c.n, imgs, c.rows, c.cols, c.T, c.cams, fs, ps, srows, scols);
 }
-template <int NB>
-static int trace_rider_of(nvbx_mapper* m, TraceRiderT<NB>* tr) {
-  const nvbx_mapper::ColorPending& c = m->held.color_pending;
+// ... handed to a depth call of NB frames: f(Pix{}).  THE check that the counts agree (the depth call has asked ColorPending::carried_by before it comes here)
+template <int NB, typename F> static int with_held_pix(const nvbx_mapper::ColorPending& c, F&& f) {
+  return with_color_types(c.enc, c.n, [&](auto pix, auto nb) -> int {
+    if constexpr (decltype(nb)::value == NB) return f(pix);
+    else { set_error("held-back colour: one frame is carried by one depth frame, a batch by a depth batch"); return NVBX_E_INVALID; }
+  });
+}
+// ... its sphere tracing as a rider of the caller's launch
+template <int NB> int nvbx_mapper::pending_color_trace_rider(TraceRiderT<NB>* tr) {
+  const ColorPending& c = held.color_pending;
   int32_t srows = 0, scols = 0;
-  int rc;
-  if (c.kind == 0) { FrameSetC<PixRgb8, NB> fs; rc = pending_setup<PixRgb8, NB>(m, c, &fs, &tr->ps, &srows, &scols); }
-  else { FrameSetC<PixBgra8, NB> fs; rc = pending_setup<PixBgra8, NB>(m, c, &fs, &tr->ps, &srows, &scols); }
+  const int rc = with_held_pix<NB>(c, [&](auto pix) { FrameSetC<decltype(pix), NB> fs; return pending_setup<decltype(pix), NB>(this, c, &fs, &tr->ps, &srows, &scols); });
   if (rc) return rc;
-  tr->synth = m->synth.as<float>(); tr->srows = srows; tr->scols = scols; tr->max_steps = m->p.sphere_tracing_max_steps;
-  tr->max_len = m->p.sphere_tracing_max_ray_length_m; tr->eps_m = m->p.sphere_tracing_surface_eps_vox * m->p.voxel_size;
+  tr->synth = synth.as<float>(); tr->srows = srows; tr->scols = scols; tr->max_steps = p.sphere_tracing_max_steps;
+  tr->max_len = p.sphere_tracing_max_ray_length_m; tr->eps_m = p.sphere_tracing_surface_eps_vox * p.voxel_size;
   static const int fused_lanes = nvbx_knob_fused_trace_lanes(getenv("NVBX_FUSED_TRACE_LANES"));       // (A/B, one frame: 4 or 8 lanes per ray)
   tr->lanes = NB == 1 ? fused_lanes : std::max(2, sphere_trace_lanes(c.n));
   tr->n_wg = sphere_trace_workgroups(tr->lanes, srows, scols, c.n);
   return NVBX_OK;
 }
-// ... its sphere tracing as a rider of the caller's launch
-int nvbx_mapper::pending_color_trace_rider(void* out) {
-  return held.color_pending.n == 1 ? trace_rider_of<1>(this, static_cast<TraceRiderT<1>*>(out)) : trace_rider_of<MAX_BATCH>(this, static_cast<TraceRiderT<MAX_BATCH>*>(out));
-}
+template int nvbx_mapper::pending_color_trace_rider<1>(TraceRiderT<1>*);  template int nvbx_mapper::pending_color_trace_rider<MAX_BATCH>(TraceRiderT<MAX_BATCH>*);
 // Fused colour + TSDF launch (tsdf.hip): the held-back frame's ESDF marking pass rides in the view-marking launch of the next depth frame
 // (color_launch_integrate's own part, decided before that launch) ...
 void nvbx_mapper::pending_marking_args(int32_t* mark_wg, EsdfArgs* ea_out, bool single_frame) {
@@ -261,14 +262,13 @@ void nvbx_mapper::pending_marking_args(int32_t* mark_wg, EsdfArgs* ea_out, bool 
   *ea_out = ea;
 }
 // ... and its colour integration shares a launch with that frame's TSDF update: frames and scratch as for the separate launch
-int nvbx_mapper::pending_color_fused_args(void* fsc_out, int* kind, int32_t* srows, int32_t* scols) {
-  const ColorPending c = take_pending();      // (its frames are let go of by the caller, once the launch that reads them is enqueued: release_consumed_frames)
-  *kind = c.kind;
-  if (c.n > 1) { PoseSet<MAX_BATCH> ps; return pending_setup<PixRgb8, MAX_BATCH>(this, c, static_cast<FrameSetC<PixRgb8, MAX_BATCH>*>(fsc_out), &ps, srows, scols); }
-  PoseSet<1> ps;
-  if (c.kind == 0) return pending_setup<PixRgb8, 1>(this, c, static_cast<FrameSetC<PixRgb8, 1>*>(fsc_out), &ps, srows, scols);
-  return pending_setup<PixBgra8, 1>(this, c, static_cast<FrameSetC<PixBgra8, 1>*>(fsc_out), &ps, srows, scols);
+template <int NB> int nvbx_mapper::pending_color_fused_args(HeldColorFrames<NB>* out) {
+  return with_held_pix<NB>(held.color_pending, [&](auto pix) {
+    PoseSet<NB> ps; const ColorPending c = take_pending();      // (its frames are let go of by the caller, once the launch that reads them is enqueued: release_consumed_frames)
+    return pending_setup<decltype(pix), NB>(this, c, &out->fs.template emplace<FrameSetC<decltype(pix), NB>>(), &ps, &out->srows, &out->scols);
+  });
 }
+template int nvbx_mapper::pending_color_fused_args<1>(HeldColorFrames<1>*);  template int nvbx_mapper::pending_color_fused_args<MAX_BATCH>(HeldColorFrames<MAX_BATCH>*);
 template <typename Pix, int NB>
 static int launch_pending_integrate(nvbx_mapper* m, const nvbx_mapper::ColorPending& c) {
   FrameSetC<Pix, NB> fs; PoseSet<NB> ps; int32_t srows = 0, scols = 0;
@@ -296,13 +296,13 @@ bool nvbx_mapper::replay_pair_applies() const {
 }
 int nvbx_mapper::replay_pair() {
   const ColorPending c = take_pending(); held.esdf_update_pending = false;
-  const int rc = c.n > 1 ? replay_pair_t<PixRgb8, MAX_BATCH>(this, c) : (c.kind == 0 ? replay_pair_t<PixRgb8, 1>(this, c) : replay_pair_t<PixBgra8, 1>(this, c));
+  const int rc = with_color_types(c.enc, c.n, [&](auto pix, auto nb) { return replay_pair_t<decltype(pix), decltype(nb)::value>(this, c); });
   release_consumed_frames();
   return rc;
 }
 int nvbx_mapper::launch_pending_color_after_trace() {
   const ColorPending c = take_pending();
-  const int rc = c.n > 1 ? launch_pending_integrate<PixRgb8, MAX_BATCH>(this, c) : (c.kind == 0 ? launch_pending_integrate<PixRgb8, 1>(this, c) : launch_pending_integrate<PixBgra8, 1>(this, c));
+  const int rc = with_color_types(c.enc, c.n, [&](auto pix, auto nb) { return launch_pending_integrate<decltype(pix), decltype(nb)::value>(this, c); });
   release_consumed_frames();
   return rc;
 }
@@ -311,7 +311,7 @@ extern "C" int nvbx_integrate_color(nvbx_mapper* m, const uint8_t* rgb_dev, int3
                                     const nvbx_camera* camera) {
   if (!m || !rgb_dev || !T_L_C || !camera || !image_dims_ok(rows, cols)) { set_error("nvbx_integrate_color: invalid argument (image sides 1 .. 32768)"); return NVBX_E_INVALID; }
   if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_color: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
-  { int rc = NVBX_OK; const void* im = rgb_dev; if (defer_color(m, 0, 1, &im, rows, cols, T_L_C, camera, &rc)) return rc; }
+  { int rc = NVBX_OK; const void* im = rgb_dev; if (defer_color(m, ColorEnc::rgb8, 1, &im, rows, cols, T_L_C, camera, &rc)) return rc; }
   const PixRgb8 img{rgb_dev};
   return integrate_colors<PixRgb8, 1>(m, 1, &img, rows, cols, T_L_C, camera);
 }
@@ -319,7 +319,7 @@ extern "C" int nvbx_integrate_color_bgra8(nvbx_mapper* m, const uint8_t* bgra_de
                                           const nvbx_camera* camera) {
   if (!m || !bgra_dev || !T_L_C || !camera || !image_dims_ok(rows, cols) || ((uintptr_t)bgra_dev & 3)) { set_error("nvbx_integrate_color_bgra8: invalid argument"); return NVBX_E_INVALID; }
   if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_color_bgra8: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
-  { int rc = NVBX_OK; const void* im = bgra_dev; if (defer_color(m, 1, 1, &im, rows, cols, T_L_C, camera, &rc)) return rc; }
+  { int rc = NVBX_OK; const void* im = bgra_dev; if (defer_color(m, ColorEnc::bgra8, 1, &im, rows, cols, T_L_C, camera, &rc)) return rc; }
   const PixBgra8 img{reinterpret_cast<const uint32_t*>(bgra_dev)};
   return integrate_colors<PixBgra8, 1>(m, 1, &img, rows, cols, T_L_C, camera);
 }
@@ -346,7 +346,7 @@ extern "C" int nvbx_integrate_color_batch(nvbx_mapper* m, int32_t n, const uint8
   for (int c = 0; c < n; c++)
     if (!rgb_dev[c] || !nvbx_camera_matches(cameras + c, rows, cols)) { set_error("nvbx_integrate_color_batch: every camera's width/height must equal the images' cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
   if (n == 1) return nvbx_integrate_color(m, rgb_dev[0], rows, cols, T_L_C, cameras);
-  { int rc = NVBX_OK; if (defer_color(m, 0, n, reinterpret_cast<const void* const*>(rgb_dev), rows, cols, T_L_C, cameras, &rc)) return rc; }     // (held back: a depth batch carries it out)
+  { int rc = NVBX_OK; if (defer_color(m, ColorEnc::rgb8, n, reinterpret_cast<const void* const*>(rgb_dev), rows, cols, T_L_C, cameras, &rc)) return rc; }     // (held back: a depth batch carries it out)
   PixRgb8 imgs[MAX_BATCH];
   for (int c = 0; c < n; c++) imgs[c] = PixRgb8{rgb_dev[c]};
   return integrate_colors<PixRgb8, MAX_BATCH>(m, n, imgs, rows, cols, T_L_C, cameras);

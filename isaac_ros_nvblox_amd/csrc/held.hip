@@ -17,6 +17,7 @@
 // Two modes switch parts of this off while they last (nvbx_mapper::ModeScope): `replaying` (the replayed calls must not be held back again, nor replay)
 //   and `pipelined_order` (the carried-out calls run inside integrateDepth: no replay, and the marking pass empties its list itself -- EsdfArgs).
 #include "nvbx_mapper.h"
+#include "nvbx_color_worker.h"      // with_color_types
 using namespace nvbx;
 
 __global__ void k_reset_esdf_dirty_list(DMap m) { if (threadIdx.x < NSH) *shc_at(m, S_LIST_ESDF_DIRTY, threadIdx.x, 0) = 0; }
@@ -38,7 +39,10 @@ int nvbx_mapper::join_side(bool carry_out_held) {
   if (side_pending) { NVBX_HIP(hipStreamWaitEvent(stream, ev_side, 0)); side_pending = false; }
   return NVBX_OK;
 }
-// the held-back calls of colour deferral, carried out as they would have been at call time
+// the held-back calls of colour deferral, carried out as they would have been at call time: the entry point of each kind of colour call (with_color_types)
+static int replay_color(nvbx_mapper* m, const nvbx_mapper::ColorPending& c, PixRgb8, std::integral_constant<int, 1>) { return nvbx_integrate_color(m, (const uint8_t*)c.imgs[0], c.rows, c.cols, c.T, &c.cams[0]); }
+static int replay_color(nvbx_mapper* m, const nvbx_mapper::ColorPending& c, PixBgra8, std::integral_constant<int, 1>) { return nvbx_integrate_color_bgra8(m, (const uint8_t*)c.imgs[0], c.rows, c.cols, c.T, &c.cams[0]); }
+static int replay_color(nvbx_mapper* m, const nvbx_mapper::ColorPending& c, PixRgb8, std::integral_constant<int, MAX_BATCH>) { return nvbx_integrate_color_batch(m, c.n, reinterpret_cast<const uint8_t* const*>(c.imgs), c.rows, c.cols, c.T, c.cams); }
 int nvbx_mapper::replay_deferred() {
   if (!held.color_pending.on && !held.esdf_update_pending) return NVBX_OK;
   ModeScope mode(replaying);
@@ -46,9 +50,7 @@ int nvbx_mapper::replay_deferred() {
   if (replay_pair_applies()) { rc = replay_pair(); return rc == NVBX_OK ? NVBX_OK : NVBX_E_DEVICE; }
   if (held.color_pending.on) {
     const ColorPending c = take_pending();
-    if (c.n > 1) rc = nvbx_integrate_color_batch(this, c.n, reinterpret_cast<const uint8_t* const*>(c.imgs), c.rows, c.cols, c.T, c.cams);
-    else rc = c.kind == 0 ? nvbx_integrate_color(this, (const uint8_t*)c.imgs[0], c.rows, c.cols, c.T, &c.cams[0])
-                          : nvbx_integrate_color_bgra8(this, (const uint8_t*)c.imgs[0], c.rows, c.cols, c.T, &c.cams[0]);
+    rc = with_color_types(c.enc, c.n, [&](auto pix, auto nb) { return replay_color(this, c, pix, nb); });
   }
   if (rc == NVBX_OK && held.esdf_update_pending) { held.esdf_update_pending = false; rc = nvbx_update_esdf(this); }
   held.esdf_update_pending = false;

@@ -1,6 +1,8 @@
 // nvbx_color_worker.h -- the colour-integration worker of MultiMapper::integrateColor (ProjectiveColorIntegrator::integrateFrame restated),
 // shared by k_integrate_color (color.hip) and by the fused colour + TSDF launch of the pipelined order (tsdf.hip).
 #pragma once
+#include <type_traits>
+#include <variant>
 #include "nvbx_mapper.h"
 #include "nvbx_sphere_trace.h"
 
@@ -10,13 +12,28 @@ template <typename Pix, int NB> struct FrameSetC { FrameCore f[NB]; Pix img[NB];
 
 // colour source: rgb8 (nvblox::Color, 3 bytes) or bgra8 (4 bytes, channel reorder of ToRgba<Bgra> fused into the fetch)
 struct PixRgb8 {
+  static constexpr uint32_t kBytes = 3;      // per pixel
   const uint8_t* p;
   __device__ void tap(int32_t i, float* c) const { const uint8_t* q = p + (int64_t)i * 3; c[0] = (float)q[0]; c[1] = (float)q[1]; c[2] = (float)q[2]; }
 };
 struct PixBgra8 {
+  static constexpr uint32_t kBytes = 4;
   const uint32_t* p;     // little endian: b | g << 8 | r << 16 | a << 24
   __device__ void tap(int32_t i, float* c) const { const uint32_t v = p[i]; c[0] = (float)((v >> 16) & 0xFF); c[1] = (float)((v >> 8) & 0xFF); c[2] = (float)(v & 0xFF); }
 };
+
+// Host side.  The colour kernels exist for three (Pix, NB): one rgb8 image, one bgra8 image, a batch of up to MAX_BATCH rgb8 images.  THE mapping from
+// a colour call's {encoding, frame count} to them: f(Pix{}, std::integral_constant<int, NB>{}), both tags only.
+template <typename F> auto with_color_types(ColorEnc enc, int32_t n, F&& f) {
+  if (n > 1) return f(PixRgb8{}, std::integral_constant<int, MAX_BATCH>{});
+  return enc == ColorEnc::rgb8 ? f(PixRgb8{}, std::integral_constant<int, 1>{}) : f(PixBgra8{}, std::integral_constant<int, 1>{});
+}
+// A held-back colour call set up for the fused launch of a depth call of NB frames (tsdf.hip): its frames in their own pixel type (a batch is rgb8
+// only; nothing held back: rgb8, empty) and the size of its synthetic depth image.  std::visit picks the launch's instantiation.
+template <int NB> struct HeldColorFrames {
+  std::conditional_t<NB == 1, std::variant<FrameSetC<PixRgb8, NB>, FrameSetC<PixBgra8, NB>>, std::variant<FrameSetC<PixRgb8, NB>>> fs; int32_t srows = 0, scols = 0;
+};
+template <typename Pix, int NB> Pix pix_of(const FrameSetC<Pix, NB>&);      // (decltype only)
 
 __device__ inline uint32_t blend_u8(float c0, float w0, float c1, float w1) {
   const float tw = w0 + w1;

@@ -35,6 +35,8 @@ struct EsdfArgs {
 };
 
 struct MeshRecord { int32_t x, y, z, vbase, nvert, tbase, ntri, pad; };
+enum class ColorEnc { rgb8, bgra8 };      // a colour image's encoding
+template <int NB> struct TraceRiderT; template <int NB> struct HeldColorFrames;      // what color.hip hands to tsdf.hip of a held-back colour call (nvbx_sphere_trace.h, nvbx_color_worker.h)
 
 float log_odds(float p);
 // frames.hip: library-owned, reference-counted device frames (ownership transfer of input images)
@@ -157,9 +159,10 @@ struct nvbx_mapper {
   nvbx::DevBuf esdf3_scratch; int64_t esdf3_blocks_marked = 0, esdf3_window_voxels = 0;
   bool defer_edt = true;             // the EDT of an updateEsdf is held back (NVBX_DEFER_EDT=0 disables): see nvbx_update_esdf
   int flush_edt(); int flush_import();      // esdf.hip: launch the held-back EDT / union step now
-  // (n = 1: integrateColor, kind 0 = rgb8 / 1 = bgra8; n > 1: nvbx_integrate_color_batch, rgb8.  frames[i] != nullptr: imgs[i] lives in a library-owned
-  //  frame this mapper has RETAINED, let go of with a fence once the launches that read it are enqueued: frames.hip)
-  struct ColorPending { bool on = false; int kind = 0; int32_t n = 1; const void* imgs[nvbx::MAX_BATCH] = {}; void* frames[nvbx::MAX_BATCH] = {}; int32_t rows = 0, cols = 0; float T[16 * nvbx::MAX_BATCH]; nvbx_camera cams[nvbx::MAX_BATCH]; };
+  // (n = 1: integrateColor, rgb8 or bgra8; n > 1: nvbx_integrate_color_batch, rgb8 -- nvbx::with_color_types turns {enc, n} into the kernels' types.
+  //  frames[i] != nullptr: imgs[i] lives in a library-owned frame this mapper has RETAINED, let go of with a fence once the launches that read it are enqueued: frames.hip)
+  struct ColorPending { bool on = false; nvbx::ColorEnc enc = nvbx::ColorEnc::rgb8; int32_t n = 1; const void* imgs[nvbx::MAX_BATCH] = {}; void* frames[nvbx::MAX_BATCH] = {}; int32_t rows = 0, cols = 0; float T[16 * nvbx::MAX_BATCH]; nvbx_camera cams[nvbx::MAX_BATCH];
+    bool carried_by(int depth_frames) const { return (depth_frames == 1) == (n == 1); } };      // one depth frame carries one colour frame, a depth batch a batch
   struct Held {      // work an entry point has accepted but not launched yet: what, who carries it out and in which order -- the top of held.hip
     bool edt_pending = false; nvbx::EsdfArgs edt_args{};       // the distance transform of the last updateEsdf
     bool import_pending = false; const int32_t* import_ptr = nullptr; int32_t import_world = 0, import_rank = 0; int64_t import_max = 0;      // the union step of the multi-GPU exchange
@@ -200,7 +203,7 @@ struct nvbx_mapper {
   int join_side_keeping_held() { return join_side(false); }      // for an entry point that touches nothing the held-back work does: it all stays held back
   // a held-back updateEsdf with NO colour frame in front of it (depth-only hosts, occupancy mappers) that the next camera launch can carry in two-launch order
   bool esdf_only_carry() const { return held.esdf_update_pending && !held.color_pending.on && p.esdf_mode == 0 && p.esdf_propagation == 0 && !held.import_pending && !use_side && defer_edt; }
-  int pending_color_trace_rider(void* trace_rider_out);   // color.hip: set the held-back frame(s) up; the sphere tracing as a nvbx::TraceRiderT<1> (one frame) / <MAX_BATCH> (a batch)
+  template <int NB> int pending_color_trace_rider(nvbx::TraceRiderT<NB>* out);      // color.hip, for a depth call of NB frames (1 or MAX_BATCH; a held-back call of the other count is refused): set the held-back frame(s) up, the sphere tracing as a rider
   int launch_pending_color_after_trace();
   bool replay_pair_applies() const;  // color.hip: a held-back colour frame + updateEsdf can be replayed in two launches (replay_pair)
   int replay_pair();
@@ -208,10 +211,9 @@ struct nvbx_mapper {
   nvbx::DevBuf color_cand;           // int4 [2][capacity] candidate records {slot, block index} of the held-back colour frame (parity cand_parity)
   int cand_parity = 0;
   bool lidar_integrated = false;     // a LiDAR scan has been integrated since the last clear: blocks may be F_BAND_STALE -> no fused launches
-  // color.hip: the marking pass that rides in the view-marking launch (0 workgroups: none), and the held-back colour frame's set-up for the
-  // fused launch (FrameSetC<Pix, 1>: rgb8 / bgra8 share one layout; FrameSetC<PixRgb8, MAX_BATCH> for a held-back batch)
+  // color.hip: the marking pass that rides in the view-marking launch (0 workgroups: none), and the held-back colour frame's set-up for the fused launch, in its own pixel type
   void pending_marking_args(int32_t* mark_wg, nvbx::EsdfArgs* ea_out, bool single_frame);
-  int pending_color_fused_args(void* fsc_out, int* kind, int32_t* srows, int32_t* scols);
+  template <int NB> int pending_color_fused_args(nvbx::HeldColorFrames<NB>* out);
   void* table_spare = nullptr; void* table_dirty = nullptr; uint32_t table_mask_extra = 0xFFFFFFFFu;       // decay's rotating hash tables: the all-empty one k_decay builds the next table in, and the one it empties for the call after (maintenance.hip, round 6)
   nvbx::DevBuf view_class;           // LiDAR: per view record, 1 = updated by the beam-centric launch (lidar.hip k_lidar_sparse)
   // LiDAR view calculation over a dense grid (lidar.hip k_mark_view_grid): one byte per block of the box around the sensor (cell-major, 64 B per

@@ -278,7 +278,7 @@ static bool fused_colour_applies(const nvbx_mapper* m) {
 template <int NB> struct DepthSteps {
   int tiles = 0, edt_wg = 0; EsdfArgs ea{}; TraceRiderT<NB> tr{};                 // launch 1
   bool plain = true, has_color = false, pipelined = false, fused = false;
-  FrameSetC<PixRgb8, NB> fsc{}; int f_kind = 0; int32_t f_srows = 0, f_scols = 0;      // launch 2 (fused form)
+  HeldColorFrames<NB> col{};      // launch 2 (fused form): the held-back colour frame(s), if any
   int grid = 8; int32_t spec_lanes = 1;
   int32_t n_edt = 0; EsdfArgs ea_edt{}; const int4* cand = nullptr; int32_t cand_idx = 0; int cgrid = 0; ImportArgs imp{};
   nvbx_mapper::ModeScope pipelined_order;      // the mapper's flag: on in step 1, off in step 2 -- or wherever the frame is given up in between
@@ -308,7 +308,7 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
   st.has_color = m->held.color_pending.on;
   // (one frame carries a frame, a batch a batch; a held-back updateEsdf WITHOUT a colour frame -- depth-only and occupancy mappers -- is carried by
   //  any camera launch: integrate_cameras has checked that the two-launch order applies, nvbx_mapper::esdf_only_carry)
-  st.pipelined = Sensor::kRiders && (st.has_color ? ((NB == 1) == (m->held.color_pending.n == 1)) : m->held.esdf_update_pending);
+  st.pipelined = Sensor::kRiders && (st.has_color ? m->held.color_pending.carried_by(NB) : m->held.esdf_update_pending);
   st.fused = false;
   if (st.pipelined) {
     // TSDF mapper (with or without a freespace layer), 2-D ESDF by the exact transform (the marking pass / distance transform that ride are the
@@ -319,7 +319,7 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
     // (a distance transform armed outside the pipeline must precede the marking pass that rides in this launch: its own launch, rare)
     if (st.fused && st.edt_wg) { m->held.edt_pending = true; st.edt_wg = 0; if (m->flush_edt()) return NVBX_E_DEVICE; }
     st.pipelined_order.enter(m->pipelined_order);
-    if (st.has_color) { const int rc = m->pending_color_trace_rider(&st.tr); if (rc) return rc; }
+    if (st.has_color) { const int rc = m->pending_color_trace_rider<NB>(&st.tr); if (rc) return rc; }
     // riders before or after the tiles (A/B: NVBX_MARK_TILES_FIRST = 0 / 1).  One frame: tiles first (15.2 vs 15.8 us).  A batch of 8: riders first
     // (32.4 vs 42.0 us) -- its 2 688 single-wavefront tile workgroups, each holding its LDS key set, take most of the workgroup slots, and
     // sphere-tracing workgroups dispatched behind them start when the tiles are done: the launch took the SUM of its parts.
@@ -355,7 +355,7 @@ static int depth_step_between(nvbx_mapper* m, DepthSteps<NB>& st) {
     // of the update keeps it -- EsdfArgs), then updateEsdf (which only arms the next held-back EDT: the marking pass has been launched)
     if (!st.fused) m->premark_consumed = false;
     int rc = NVBX_OK;
-    if (st.fused) { if (st.has_color) rc = m->pending_color_fused_args(&st.fsc, &st.f_kind, &st.f_srows, &st.f_scols); }
+    if (st.fused) { if (st.has_color) rc = m->pending_color_fused_args<NB>(&st.col); }
     else rc = m->launch_pending_color_after_trace();
     if (rc == NVBX_OK && m->held.esdf_update_pending) { m->held.esdf_update_pending = false; rc = nvbx_update_esdf(m); }
     st.pipelined_order.leave();
@@ -411,10 +411,11 @@ static int depth_step_after(nvbx_mapper* m, int n_frames) {
   return m->mark_main();
 }
 
+// (frames of a held-back colour image a depth call carries out: let go of on every way out, behind the launches that read them)
+struct ReleaseFrames { nvbx_mapper* m; ~ReleaseFrames() { m->release_consumed_frames(); } };
 template <typename Img, typename Sensor, int NB>
 static int integrate_depth_impl(nvbx_mapper* m, FrameSet<Img, NB> fs, const Sensor& sensor) {
-  // (frames of a held-back colour image this call carries out: let go of on every way out, behind the launches that read them)
-  struct ReleaseFrames { nvbx_mapper* m; ~ReleaseFrames() { m->release_consumed_frames(); } } release_frames{m};
+  ReleaseFrames release_frames{m};
   DepthSteps<NB> st;
   { const int rc = depth_step_before_mark_view<Img, Sensor, NB>(m, fs, st); if (rc) return rc; }
   bool grid_view = false;
@@ -431,14 +432,12 @@ static int integrate_depth_impl(nvbx_mapper* m, FrameSet<Img, NB> fs, const Sens
     if constexpr (Sensor::kRiders) {
       depth_step_fused_riders<NB>(m, st);
       const dim3 g((unsigned)(st.n_edt + grid + st.cgrid + st.imp.n_wg));
-#define NVBX_FUSED_LAUNCH(PIX, PLAIN, FC) NVBX_LAUNCH(m, (k_integrate_tsdf_color<Img, PIX, NB, PLAIN>), g, dim3(512), m->d, fs, sensor, (const int4*)m->view_list, (int32_t)m->capacity, \
-        m->mesh_list_live(), m->view_export, (int32_t)m->view_export_cap, spec_lanes, (int32_t)grid, FC, m->synth.as<const float>(), st.f_srows, st.f_scols, st.cand, st.cand_idx, st.n_edt, st.ea_edt, st.imp)
-      if (NB > 1 || st.f_kind == 0) {
-        if (plain) NVBX_FUSED_LAUNCH(PixRgb8, true, st.fsc); else NVBX_FUSED_LAUNCH(PixRgb8, false, st.fsc);
-      } else if constexpr (NB == 1) {
-        FrameSetC<PixBgra8, 1> fc; memcpy(&fc, &st.fsc, sizeof(fc));       // (one layout, color.hip static_assert)
-        if (plain) NVBX_FUSED_LAUNCH(PixBgra8, true, fc); else NVBX_FUSED_LAUNCH(PixBgra8, false, fc);
-      }
+#define NVBX_FUSED_LAUNCH(PIX, PLAIN) NVBX_LAUNCH(m, (k_integrate_tsdf_color<Img, PIX, NB, PLAIN>), g, dim3(512), m->d, fs, sensor, (const int4*)m->view_list, (int32_t)m->capacity, \
+        m->mesh_list_live(), m->view_export, (int32_t)m->view_export_cap, spec_lanes, (int32_t)grid, fsc, m->synth.as<const float>(), st.col.srows, st.col.scols, st.cand, st.cand_idx, st.n_edt, st.ea_edt, st.imp)
+      std::visit([&](const auto& fsc) {      // (each instantiation named in source text: that text is its name in the profile, NVBX_LAUNCH)
+        if constexpr (std::is_same_v<decltype(pix_of(fsc)), PixRgb8>) { if (plain) NVBX_FUSED_LAUNCH(PixRgb8, true); else NVBX_FUSED_LAUNCH(PixRgb8, false); }
+        else { if (plain) NVBX_FUSED_LAUNCH(PixBgra8, true); else NVBX_FUSED_LAUNCH(PixBgra8, false); }
+      }, st.col.fs);
 #undef NVBX_FUSED_LAUNCH
     }
   } else
@@ -454,7 +453,7 @@ static int integrate_depth_impl(nvbx_mapper* m, FrameSet<Img, NB> fs, const Sens
 // frames are camera frames that have passed integrate_cameras' own preparation (pair_prepare below).
 template <typename Img>
 static int integrate_depth_pair_impl(nvbx_mapper* ma, FrameSet<Img, 1> fa, nvbx_mapper* mb, FrameSet<Img, 1> fb) {
-  struct ReleaseFrames { nvbx_mapper* m; ~ReleaseFrames() { m->release_consumed_frames(); } } release_a{ma}, release_b{mb};
+  ReleaseFrames release_a{ma}, release_b{mb};
   DepthSteps<1> sa, sb;
   { const int rc = depth_step_before_mark_view<Img, CameraSensor, 1>(ma, fa, sa); if (rc) return rc; }
   { const int rc = depth_step_before_mark_view<Img, CameraSensor, 1>(mb, fb, sb); if (rc) return rc; }
@@ -476,23 +475,21 @@ static int integrate_depth_pair_impl(nvbx_mapper* ma, FrameSet<Img, 1> fa, nvbx_
   //  launch is residency-bound: every idle 8-wavefront workgroup holds a slot for ~1.5 us)
   static const int pair_b_edt = nvbx_knob_pair_b_edt_riders(getenv("NVBX_PAIR_B_EDT_RIDERS"));
   if (sb.n_edt > pair_b_edt) sb.n_edt = pair_b_edt;
-  const int kind = sa.has_color ? sa.f_kind : (sb.has_color ? sb.f_kind : 0);      // (both, in different encodings: the two calls, nvbx_integrate_depth_pair)
-  auto fused_args = [&](nvbx_mapper* m, const FrameSet<Img, 1>& f, const DepthSteps<1>& st, auto* out) {
-    using FA = std::remove_pointer_t<decltype(out)>;
-    FA x{}; x.m = m->d; x.fs = f; x.view_list = (const int4*)m->view_list; x.list_cap = (int32_t)m->capacity; x.mesh_list = m->mesh_list_live(); x.view_export = m->view_export;
-    x.view_export_cap = (int32_t)m->view_export_cap; x.spec_lanes = st.spec_lanes; x.n_tsdf_wg = (int32_t)st.grid; memcpy(&x.fsc, &st.fsc, sizeof(x.fsc));
-    x.synth = m->synth.as<const float>(); x.srows = st.f_srows; x.scols = st.f_scols; x.cand = st.cand; x.cand_cnt_idx = st.cand_idx; x.n_edt_wg = st.n_edt; x.ea = st.ea_edt; x.imp = st.imp;
+  // ONE pixel type for the pair: whichever mapper holds a colour frame, else rgb8; a mapper that holds none passes an empty set of that type
+  if (sa.has_color && sb.has_color && sa.col.fs.index() != sb.col.fs.index()) { set_error("nvbx_integrate_depth_pair: colour frames of two encodings"); return NVBX_E_INVALID; }
+  auto fused_args = [&](nvbx_mapper* m, const FrameSet<Img, 1>& f, const DepthSteps<1>& st, const auto& lead_fs) {
+    FusedArgs<Img, decltype(pix_of(lead_fs))> x{}; x.m = m->d; x.fs = f; x.view_list = (const int4*)m->view_list; x.list_cap = (int32_t)m->capacity; x.mesh_list = m->mesh_list_live(); x.view_export = m->view_export;
+    x.view_export_cap = (int32_t)m->view_export_cap; x.spec_lanes = st.spec_lanes; x.n_tsdf_wg = (int32_t)st.grid; if (auto* fsc = std::get_if<std::decay_t<decltype(lead_fs)>>(&st.col.fs)) x.fsc = *fsc;
+    x.synth = m->synth.as<const float>(); x.srows = st.col.srows; x.scols = st.col.scols; x.cand = st.cand; x.cand_cnt_idx = st.cand_idx; x.n_edt_wg = st.n_edt; x.ea = st.ea_edt; x.imp = st.imp;
     x.n_wg = st.n_edt + st.grid + st.cgrid + st.imp.n_wg;
-    *out = x;
+    return x;
   };
   mb->enqueue_seq++;
-  if (kind == 0) {
-    FusedArgs<Img, PixRgb8> FA_, FB_; fused_args(ma, fa, sa, &FA_); fused_args(mb, fb, sb, &FB_);
-    NVBX_LAUNCH(ma, (k_integrate_tsdf_color_pair<Img, PixRgb8>), dim3((unsigned)(FA_.n_wg + FB_.n_wg)), dim3(512), FA_, FB_);
-  } else {
-    FusedArgs<Img, PixBgra8> FA_, FB_; fused_args(ma, fa, sa, &FA_); fused_args(mb, fb, sb, &FB_);
-    NVBX_LAUNCH(ma, (k_integrate_tsdf_color_pair<Img, PixBgra8>), dim3((unsigned)(FA_.n_wg + FB_.n_wg)), dim3(512), FA_, FB_);
-  }
+  std::visit([&](const auto& lead_fs) {
+    const auto FA_ = fused_args(ma, fa, sa, lead_fs), FB_ = fused_args(mb, fb, sb, lead_fs);
+    if constexpr (std::is_same_v<decltype(pix_of(lead_fs)), PixRgb8>) NVBX_LAUNCH(ma, (k_integrate_tsdf_color_pair<Img, PixRgb8>), dim3((unsigned)(FA_.n_wg + FB_.n_wg)), dim3(512), FA_, FB_);
+    else NVBX_LAUNCH(ma, (k_integrate_tsdf_color_pair<Img, PixBgra8>), dim3((unsigned)(FA_.n_wg + FB_.n_wg)), dim3(512), FA_, FB_);
+  }, (sa.has_color ? sa.col : sb.col).fs);
   { const int rc = depth_step_after<CameraSensor>(ma, 1); if (rc) return rc; }
   return depth_step_after<CameraSensor>(mb, 1);
 }
@@ -541,7 +538,7 @@ static int cameras_prepare(nvbx_mapper* m, int32_t n, const float* T_L_C /* n x 
   NVBX_HIP(hipSetDevice(m->device));
   const bool dilate_first = m->p.do_depth_preprocessing && m->p.depth_preprocessing_num_dilations > 0;
   // held-back integrateColor / updateEsdf that this call cannot carry out in pipelined order are replayed NOW (the replayed calls launch / re-arm the EDT)
-  const bool carry = !dilate_first && (m->held.color_pending.on ? ((NB == 1) == (m->held.color_pending.n == 1)) : m->esdf_only_carry());      // this call can carry the held-back calls out in pipelined order
+  const bool carry = !dilate_first && (m->held.color_pending.on ? m->held.color_pending.carried_by(NB) : m->esdf_only_carry());      // this call can carry the held-back calls out in pipelined order
   if (!carry && m->replay_deferred()) return NVBX_E_DEVICE;
   // (join_side would launch a held-back EDT / union step; the EDT rides in k_mark_view instead, the union step stays held back for the next
   //  integrateColor -- it belongs to the NEXT ESDF update and touches nothing this launch reads.  What else is still held back, this call carries out)
@@ -610,8 +607,8 @@ static bool pair_can_fuse(const nvbx_mapper* m) {
 }
 // (the pair launch decodes ONE pixel type -- that of whichever mapper holds a colour frame: two held-back frames in different encodings, rgb8 and bgra8,
 //  cannot share it.  Checked before either mapper's preparation, which consumes host state)
-static bool pair_colour_kinds_differ(const nvbx_mapper* ma, const nvbx_mapper* mb) {
-  return ma->held.color_pending.on && mb->held.color_pending.on && ma->held.color_pending.kind != mb->held.color_pending.kind;
+static bool pair_colour_encodings_differ(const nvbx_mapper* ma, const nvbx_mapper* mb) {
+  return ma->held.color_pending.on && mb->held.color_pending.on && ma->held.color_pending.enc != mb->held.color_pending.enc;
 }
 extern "C" int nvbx_integrate_depth_pair(nvbx_mapper* ma, const float* depth_a_dev, nvbx_mapper* mb, const float* depth_b_dev, int32_t rows, int32_t cols,
                                          const float T_L_C[16], const nvbx_camera* camera) {
@@ -619,7 +616,7 @@ extern "C" int nvbx_integrate_depth_pair(nvbx_mapper* ma, const float* depth_a_d
   if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_depth_pair: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
   static const int pair_on = nvbx_knob_switch(getenv("NVBX_DEPTH_PAIR"));       // (A/B: 0 = always the two separate calls)
   if (!pair_on || ma->device != mb->device || ma->stream != mb->stream || !pair_can_fuse(ma) || !pair_can_fuse(mb) ||
-      pair_colour_kinds_differ(ma, mb)) {
+      pair_colour_encodings_differ(ma, mb)) {
     const int rc = nvbx_integrate_depth(ma, depth_a_dev, rows, cols, T_L_C, camera); if (rc) return rc;
     return nvbx_integrate_depth(mb, depth_b_dev, rows, cols, T_L_C, camera);
   }

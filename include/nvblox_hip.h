@@ -430,6 +430,44 @@ int nvbx_esdf_dense_grid(nvbx_mapper* m, const int32_t min_vox[3], const int32_t
 int nvbx_query_points(nvbx_mapper* m, uint32_t layer, const float* points_xyz_dev, int64_t n, float min_weight, float unknown_value,
                       float* distance_dev, float* gradient_xyz_dev, uint8_t* valid_dev);
 
+/* ---- rendering and ray casts ([U] SphereTracer::renderImageOnGPU / renderRgbdImageOnGPU / castOnGPU, nvblox/rays/sphere_tracer.h) -----
+ * The map seen along rays (SEMANTICS.md "Rendering and ray casts"): the sphere tracing of integrateColor's occlusion image -- nearest voxel,
+ * step = voxel distance, the truncation distance through unobserved space until something positive has been seen, hit when an observed
+ * sample is < sphere_tracing_surface_eps_vox * voxel_size after a positive one, stop at sphere_tracing_max_steps or the ray length -- from
+ * any pose, at any subsampling, into the caller's buffers.  One launch, read-only on the map, asynchronous on the mapper's stream.
+ * nvbx_render_view: ray (r, c) of the rows / s x cols / s image goes through the centre of full-resolution pixel (r s, c s) of `camera` at
+ *   pose T_L_C (row-major 4 x 4, camera -> layer).  depth = z of the hit in the camera frame (t * direction z), 0 = no surface.
+ * nvbx_cast_rays: origins / directions [n][3] in layer-frame metres, directions of unit length (the caller's contract); t_dev[n] = ray parameter of
+ *   the hit in metres, 0 = no hit; hit_dev[n] = 1 / 0.  A direction that is not finite or all-zero, or an origin that is not finite or
+ *   outside the addressable block range, reports no hit.
+ * Optional outputs of both (NULL: not computed, no loads spent): color_rgb_dev [..][3] = the colour voxel that contains the hit point
+ *   P = o + t d (grey 127 where that voxel has no colour, the mesh's rule; 0 0 0 on a miss); normal_xyz_dev [..][3] = the gradient of the trilinear
+ *   TSDF interpolant at P (nvbx_query_points with min_weight 1e-4), normalised; 0 0 0 on a miss, where a corner is missing or the gradient is 0.
+ * subsampling 0 / max_ray_length_m <= 0: the mapper's sphere_tracing_subsampling / sphere_tracing_max_ray_length_m.
+ * Errors: NVBX_E_INVALID (occupancy mapper, NULL required pointer, n < 0, rows / s < 2 or cols / s < 2, pose out of range, a ray length that
+ * reaches beyond the addressable block range from every origin); NVBX_E_CAPACITY when
+ * capacity_pixels < rows_out * cols_out, which are filled in (call with capacity 0 to size the buffers).  n == 0 launches nothing.
+ * Held-back work (nvbx_mapper_set_color_deferral): a call without a colour output leaves it held back (it reads TSDF voxels only), a call with
+ * one carries it out first (a held-back integrateColor writes the colour layer). */
+int nvbx_render_view(nvbx_mapper* m, const float T_L_C[16], const nvbx_camera* camera,
+                     int32_t subsampling,          /* >= 1; 0: the mapper's sphere_tracing_subsampling */
+                     float max_ray_length_m,       /* <= 0: the mapper's sphere_tracing_max_ray_length_m */
+                     float* depth_dev,             /* [rows/s][cols/s], 0 = no surface */
+                     uint8_t* color_rgb_dev,       /* [rows/s][cols/s][3] or NULL */
+                     float* normal_xyz_dev,        /* [rows/s][cols/s][3], map frame, or NULL */
+                     int64_t capacity_pixels, int32_t* rows_out, int32_t* cols_out);
+int nvbx_cast_rays(nvbx_mapper* m, const float* origins_xyz_dev, const float* directions_xyz_dev, int64_t n,
+                   float max_ray_length_m, float* t_dev, uint8_t* hit_dev /* or NULL */,
+                   uint8_t* color_rgb_dev /* or NULL */, float* normal_xyz_dev /* or NULL */);
+/* The same two calls with a tracer's own step limit and surface threshold instead of the mapper's parameters, which are left as they are
+ * (nvblox::SphereTracer keeps its own): max_steps <= 0 / surface_distance_epsilon_vox < 0 = the mapper's value; options NULL = both. */
+typedef struct { int32_t max_steps; float surface_distance_epsilon_vox; } nvbx_render_options;
+int nvbx_render_view_with(nvbx_mapper* m, const nvbx_render_options* options, const float T_L_C[16], const nvbx_camera* camera, int32_t subsampling,
+                          float max_ray_length_m, float* depth_dev, uint8_t* color_rgb_dev, float* normal_xyz_dev, int64_t capacity_pixels,
+                          int32_t* rows_out, int32_t* cols_out);
+int nvbx_cast_rays_with(nvbx_mapper* m, const nvbx_render_options* options, const float* origins_xyz_dev, const float* directions_xyz_dev, int64_t n,
+                        float max_ray_length_m, float* t_dev, uint8_t* hit_dev, uint8_t* color_rgb_dev, float* normal_xyz_dev);
+
 /* ---- map file (Mapper::saveLayerCake(path) -> bool, loadMap(path) -> bool: nvblox_node.cpp:1663-1668,1698-1703) -----------------
  * A path ending in .nvblx is written as an SQLITE database, like the reference's layer cake: table layers(layer_type, voxel_size,
  * block_size, voxel_bytes, num_blocks) + one table <layer_type>_blocks(index_x, index_y, index_z, data BLOB) per layer (tsdf_layer,

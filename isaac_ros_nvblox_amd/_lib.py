@@ -78,6 +78,11 @@ class Camera(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class RenderOptions(C.Structure):
+    """nvbx_render_options: a tracer's own step limit / surface threshold (<= 0 / < 0: the mapper's)"""
+    _fields_ = [("max_steps", C.c_int32), ("surface_distance_epsilon_vox", C.c_float)]
+
+
 class Lidar(C.Structure):
     _fields_ = [("num_azimuth_divisions", C.c_int32), ("num_elevation_divisions", C.c_int32),
                 ("min_valid_range_m", C.c_float), ("min_elevation_rad", C.c_float), ("max_elevation_rad", C.c_float)]
@@ -162,6 +167,10 @@ SIGNATURES = {
     "nvbx_pointcloud_from_slice": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _f, _f, _vp, _pi32]),
     "nvbx_esdf_dense_grid": (C.c_int, [_vp, _vp, _vp, _f, _vp]),
     "nvbx_query_points": (C.c_int, [_vp, C.c_uint32, _vp, _i64, _f, _f, _vp, _vp, _vp]),
+    "nvbx_render_view": (C.c_int, [_vp, _vp, C.POINTER(Camera), _i32, _f, _vp, _vp, _vp, _i64, _pi32, _pi32]),
+    "nvbx_cast_rays": (C.c_int, [_vp, _vp, _vp, _i64, _f, _vp, _vp, _vp, _vp]),
+    "nvbx_render_view_with": (C.c_int, [_vp, C.POINTER(RenderOptions), _vp, C.POINTER(Camera), _i32, _f, _vp, _vp, _vp, _i64, _pi32, _pi32]),
+    "nvbx_cast_rays_with": (C.c_int, [_vp, C.POINTER(RenderOptions), _vp, _vp, _i64, _f, _vp, _vp, _vp, _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),
     "nvbx_block_indices": (_i64, [_vp, C.c_uint32, _vp, _i64]),
     "nvbx_get_block": (C.c_int, [_vp, C.c_uint32, Index3D, _vp]),

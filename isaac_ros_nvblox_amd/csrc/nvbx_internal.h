@@ -282,6 +282,13 @@ __device__ inline uint32_t find_slot(const DMap& m, int32_t x, int32_t y, int32_
 // slot that lacks the layer reads as "nothing there": the TSDF and colour pools and site_bits of such slots are all-zero
 // (zeroed on free, never written otherwise), and weight 0 means unobserved / uncoloured exactly like a missing block.
 __device__ inline uint4 ld_entry(const DMap& m, uint32_t h) { return *reinterpret_cast<const uint4*>(&m.table[h]); }
+// two voxels adjacent in a block's linear order (TSDF: z, z + 1; ESDF: x, x + 1) in one 16-B load (8-B aligned: the first may be any voxel but the
+// block's last) -- the interpolating readers (query.hip, render.hip)
+__device__ inline uint4 ld_pair(const uint2* p) {
+  typedef unsigned int u4a8 __attribute__((ext_vector_type(4), aligned(8)));
+  const u4a8 v = *reinterpret_cast<const u4a8*>(p);
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
 // finish a lookup whose first probe `e` at `h` is already loaded: slot of any block with `key`, or SLOT_NONE
 __device__ inline uint32_t resolve_any(const DMap& m, u64 key, uint32_t h, uint4 e) {
   for (uint32_t probe = 0; probe <= m.mask; ++probe) {

@@ -60,6 +60,8 @@ static inline int nvbx_knob_st_lanes(const char* s) {
   const int v = nvbx_knob_int(s, 0, 1, 8);
   return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0;
 }
+/* NVBX_RENDER_LANES: lanes per ray of nvbx_render_view / nvbx_cast_rays, 1 / 2 / 4 / 8; 0 = by ray count */
+static inline int nvbx_knob_render_lanes(const char* s) { return nvbx_knob_st_lanes(s); }
 /* NVBX_FUSED_TRACE_LANES: lanes per ray of one frame's riding sphere tracing, 4 or 8 */
 static inline int nvbx_knob_fused_trace_lanes(const char* s) { return nvbx_knob_int(s, 8, 4, 8) == 4 ? 4 : 8; }
 /* NVBX_LIDAR_SPARSE_GRID: workgroups of the beam-centric LiDAR launch */

@@ -25,6 +25,72 @@ namespace nvbx {
 // The colour frames of one launch set: one frame, or a batch of up to MAX_BATCH (nvbx_integrate_color_batch); kernel arguments.
 template <int NB> struct PoseSet { FrameCore f[NB]; int32_t n; };
 
+// The march of one ray per group of RAY_LANES lanes, shared by sphere_trace_worker below (the colour frame's occlusion image) and by the render /
+// ray-cast kernel (render.hip): origin o, unit direction dl (map frame), `valid` = the group has a ray.  Every lane of the wavefront calls it
+// (ballots / shuffles); sub = the lane's sample index in its group, gsh = the group's first lane.  *t_out = the ray parameter of the hit
+// (group-uniform), returns whether the ray hit; n_rounds_out: round trips of this wavefront (instrumentation).
+template <int RAY_LANES>
+__device__ inline bool sphere_trace_march(const DMap& m, const float* o, const float* dl, float voxel_size, float trunc, int32_t max_steps, float max_len,
+                                          float eps_m, bool valid, int sub, int gsh, float* t_out, int* n_rounds_out) {
+  // group-uniform march state (replicated in the group's lanes)
+  bool last_positive = false, hit = false, done = !valid;
+  float t = 0.0f, ps = trunc;
+  int i = 0;
+  int n_rounds = 0;
+  while (__ballot(!done)) {                              // wave-uniform loop: ballots / shuffles below need all lanes
+    n_rounds++;
+    // this lane's sample: t advanced `sub` times by the predicted step (the serial march's additions, replayed)
+    float tc = t;
+    for (int j = 0; j < RAY_LANES - 1; j++) if (j < sub) tc = tc + ps;
+    const float px = o[0] + tc * dl[0], py = o[1] + tc * dl[1], pz = o[2] + tc * dl[2];
+    const int32_t gx = (int32_t)floorf(NVBX_DIV(px, voxel_size)), gy = (int32_t)floorf(NVBX_DIV(py, voxel_size)), gz = (int32_t)floorf(NVBX_DIV(pz, voxel_size));
+    const int32_t bx = gx >> 3, by = gy >> 3, bz = gz >> 3;
+    const uint32_t h = done ? 0u : table_pos(m, bx, by, bz);
+    const uint4 e = *reinterpret_cast<const uint4*>(&m.table[h]);
+    const uint32_t slot = done ? SLOT_NONE : resolve_any(m, pack_key(bx, by, bz), h, e);
+    const float2 v = m.tsdf[slot_ok(slot) ? (size_t)slot * 512 + (gz & 7) + 8 * (gy & 7) + 64 * (gx & 7) : 0];
+    // classify the sample as the serial loop body would, assuming every earlier sample of the round kept the prediction
+    const bool in_bounds = (i + sub < max_steps) && (tc < max_len);
+    const bool observed = slot_ok(slot) && (v.y > 1e-4f);
+    const bool surf = observed && (v.x < eps_m);                     // hit test
+    const bool keep = observed && !surf && (v.x == ps);              // observed, step == prediction
+    const u64 obs_mask = __ballot(observed && !surf);                 // samples that set last_positive
+    const uint32_t before = (uint32_t)((obs_mask >> gsh) & ((1u << sub) - 1u));
+    const bool pos_before = last_positive || before != 0;            // last_positive when the serial loop reaches this sample
+    const bool unobs_keep = !observed && !pos_before && (ps == trunc);   // unobserved: step = trunc, if that is the prediction
+    const bool event = !done && !(in_bounds && (keep || unobs_keep));
+    const uint32_t ev = (uint32_t)((__ballot(event) >> gsh) & (uint32_t)((1ull << RAY_LANES) - 1ull));
+    const int e_sub = ev ? (__ffs((int)ev) - 1) : RAY_LANES;         // first sample that breaks the prediction
+    const int src = gsh + (e_sub < RAY_LANES ? e_sub : RAY_LANES - 1);
+    // values at the event sample (or at the last sample if the whole round kept the prediction)
+    const float e_tc = __shfl(tc, src);
+    const float e_vx = __shfl(v.x, src);
+    const int e_inb = __shfl((int)in_bounds, src), e_obs = __shfl((int)observed, src), e_surf = __shfl((int)surf, src);
+    const int e_posb = __shfl((int)pos_before, src);
+    const int pos_last = __shfl((int)(pos_before || (observed && !surf)), gsh + RAY_LANES - 1);   // last_positive after a fully kept round
+    if (!done) {
+      if (e_sub == RAY_LANES) {                      // all samples consumed with the predicted step
+        t = e_tc + ps; i += RAY_LANES; last_positive = pos_last != 0;
+      } else {
+        i += e_sub;                                  // samples before the event were regular steps
+        last_positive = e_posb != 0;
+        if (!e_inb) { done = true; }
+        else if (!e_obs) {                           // unobserved / missing
+          if (!last_positive) { t = e_tc + trunc; i += 1; ps = trunc; }   // (prediction was not trunc)
+          else done = true;
+        } else if (e_surf) {
+          if (last_positive) { t = e_tc + e_vx; hit = true; }
+          done = true;
+        } else {                                     // observed, step differs from the prediction
+          t = e_tc + e_vx; i += 1; last_positive = true; ps = e_vx;
+        }
+      }
+    }
+  }
+  *t_out = t; *n_rounds_out = n_rounds;
+  return hit;
+}
+
 // worker `wgi` (a 256-thread workgroup) of NSH * ceil(patches / NSH) * n workers; every thread of the workgroup calls
 template <int NB, int RAY_LANES>
 __device__ inline void sphere_trace_worker(const DMap& m, const PoseSet<NB>& poses, float* synth_all, int32_t srows, int32_t scols, int32_t max_steps,
@@ -57,61 +123,8 @@ __device__ inline void sphere_trace_worker(const DMap& m, const PoseSet<NB>& pos
   const float dcx = NVBX_DIV(rx, n), dcy = NVBX_DIV(ry, n), dcz = NVBX_DIV(1.0f, n);
   float dl[3];
   rotate(f.R_LC, dcx, dcy, dcz, dl);
-  // group-uniform march state (replicated in the group's lanes)
-  bool last_positive = false, hit = false, done = !valid;
-  float t = 0.0f, ps = f.trunc;
-  int i = 0;
-  int n_rounds = 0;
-  while (__ballot(!done)) {                              // wave-uniform loop: ballots / shuffles below need all lanes
-    n_rounds++;
-    // this lane's sample: t advanced `sub` times by the predicted step (the serial march's additions, replayed)
-    float tc = t;
-    for (int j = 0; j < RAY_LANES - 1; j++) if (j < sub) tc = tc + ps;
-    const float px = f.t_LC[0] + tc * dl[0], py = f.t_LC[1] + tc * dl[1], pz = f.t_LC[2] + tc * dl[2];
-    const int32_t gx = (int32_t)floorf(NVBX_DIV(px, f.voxel_size)), gy = (int32_t)floorf(NVBX_DIV(py, f.voxel_size)), gz = (int32_t)floorf(NVBX_DIV(pz, f.voxel_size));
-    const int32_t bx = gx >> 3, by = gy >> 3, bz = gz >> 3;
-    const uint32_t h = done ? 0u : table_pos(m, bx, by, bz);
-    const uint4 e = *reinterpret_cast<const uint4*>(&m.table[h]);
-    const uint32_t slot = done ? SLOT_NONE : resolve_any(m, pack_key(bx, by, bz), h, e);
-    const float2 v = m.tsdf[slot_ok(slot) ? (size_t)slot * 512 + (gz & 7) + 8 * (gy & 7) + 64 * (gx & 7) : 0];
-    // classify the sample as the serial loop body would, assuming every earlier sample of the round kept the prediction
-    const bool in_bounds = (i + sub < max_steps) && (tc < max_len);
-    const bool observed = slot_ok(slot) && (v.y > 1e-4f);
-    const bool surf = observed && (v.x < eps_m);                     // hit test
-    const bool keep = observed && !surf && (v.x == ps);              // observed, step == prediction
-    const u64 obs_mask = __ballot(observed && !surf);                 // samples that set last_positive
-    const uint32_t before = (uint32_t)((obs_mask >> gsh) & ((1u << sub) - 1u));
-    const bool pos_before = last_positive || before != 0;            // last_positive when the serial loop reaches this sample
-    const bool unobs_keep = !observed && !pos_before && (ps == f.trunc);   // unobserved: step = trunc, if that is the prediction
-    const bool event = !done && !(in_bounds && (keep || unobs_keep));
-    const uint32_t ev = (uint32_t)((__ballot(event) >> gsh) & (uint32_t)((1ull << RAY_LANES) - 1ull));
-    const int e_sub = ev ? (__ffs((int)ev) - 1) : RAY_LANES;         // first sample that breaks the prediction
-    const int src = gsh + (e_sub < RAY_LANES ? e_sub : RAY_LANES - 1);
-    // values at the event sample (or at the last sample if the whole round kept the prediction)
-    const float e_tc = __shfl(tc, src);
-    const float e_vx = __shfl(v.x, src);
-    const int e_inb = __shfl((int)in_bounds, src), e_obs = __shfl((int)observed, src), e_surf = __shfl((int)surf, src);
-    const int e_posb = __shfl((int)pos_before, src);
-    const int pos_last = __shfl((int)(pos_before || (observed && !surf)), gsh + RAY_LANES - 1);   // last_positive after a fully kept round
-    if (!done) {
-      if (e_sub == RAY_LANES) {                      // all samples consumed with the predicted step
-        t = e_tc + ps; i += RAY_LANES; last_positive = pos_last != 0;
-      } else {
-        i += e_sub;                                  // samples before the event were regular steps
-        last_positive = e_posb != 0;
-        if (!e_inb) { done = true; }
-        else if (!e_obs) {                           // unobserved / missing
-          if (!last_positive) { t = e_tc + f.trunc; i += 1; ps = f.trunc; }   // (prediction was not trunc)
-          else done = true;
-        } else if (e_surf) {
-          if (last_positive) { t = e_tc + e_vx; hit = true; }
-          done = true;
-        } else {                                     // observed, step differs from the prediction
-          t = e_tc + e_vx; i += 1; last_positive = true; ps = e_vx;
-        }
-      }
-    }
-  }
+  float t = 0.0f; int n_rounds = 0;
+  const bool hit = sphere_trace_march<RAY_LANES>(m, f.t_LC, dl, f.voxel_size, f.trunc, max_steps, max_len, eps_m, valid, sub, gsh, &t, &n_rounds);
   if (valid && sub == 0) synth[(int64_t)r * scols + c] = hit ? t * dcz : 0.0f;
   NVBX_TV(0, 6, n_rounds); (void)n_rounds;
 }

@@ -56,13 +56,6 @@ __device__ inline uint32_t q_lookup(const DMap& m, bool need, int32_t x, int32_t
   return s;
 }
 
-// two voxels adjacent in a block's linear order (TSDF: z, z + 1; ESDF: x, x + 1) in one 16-B load
-__device__ inline uint4 ld_pair(const uint2* p) {
-  typedef unsigned int u4a8 __attribute__((ext_vector_type(4), aligned(8)));
-  const u4a8 v = *reinterpret_cast<const u4a8*>(p);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
 // corner (i, j, k) of the lane: block offset o = (i & cx) | (j & cy) << 1 | (k & cz) << 2 from the base block
 template <int KIND, bool DEDUP>
 __global__ __launch_bounds__(256) void k_query_points(DMap m, const float* __restrict__ pts, int64_t n, float vs, float min_weight, float unknown,

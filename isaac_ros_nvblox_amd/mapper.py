@@ -700,17 +700,107 @@ class Mapper:
                     raise ValueError("out tensor %s %s does not fit %d points" % (tuple(t.shape), t.dtype, n))
             if d is None:
                 raise ValueError("out needs a distance tensor")
-        cur = torch.cuda.current_stream(self.device); ms = self.torch_stream()
-        other = ms.cuda_stream != cur.cuda_stream
-        if other and n:
-            ms.wait_stream(cur)
-        self._check(self.lib.nvbx_query_points(self._h, layer, C.c_void_p(p.data_ptr()), n, float(min_weight), float(unknown_value),
-                                               C.c_void_p(d.data_ptr()), C.c_void_p(g.data_ptr()) if g is not None else None,
-                                               C.c_void_p(v.data_ptr()) if v is not None else None))
-        if other and n:
-            cur.wait_stream(ms)
+        self._around_torch_stream(lambda: self.lib.nvbx_query_points(
+            self._h, layer, C.c_void_p(p.data_ptr()), n, float(min_weight), float(unknown_value), C.c_void_p(d.data_ptr()),
+            C.c_void_p(g.data_ptr()) if g is not None else None, C.c_void_p(v.data_ptr()) if v is not None else None), order=n > 0)
         self._hold("_keep_q", [p])      # (the kernel reads the points: they, and an uploaded copy, live until the next query)
         return d, g, v
+
+    # -- rendering and ray casts (nvbx_render_view / nvbx_cast_rays; SEMANTICS.md "Rendering and ray casts")
+    def _out_tensor(self, t, shape, dtypes, what):
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        if t.device != dev or tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous():
+            raise ValueError("out tensor for %s must be contiguous %s %s on %s, got %s %s" % (what, shape, dtypes[0], dev, tuple(t.shape), t.dtype))
+        return t
+
+    def _around_torch_stream(self, call, order=True):
+        """`call` enqueues on the mapper's stream, ordered behind torch's current stream (which produced the inputs) and ahead of it (which reads
+        the results): no host synchronisation either way.  order=False: a call that launches nothing."""
+        torch = self._torch
+        cur = torch.cuda.current_stream(self.device); ms = self.torch_stream()
+        other = order and ms.cuda_stream != cur.cuda_stream
+        if other:
+            ms.wait_stream(cur)
+        self._check(call())
+        if other:
+            cur.wait_stream(ms)
+
+    def render(self, T_L_C, cam, subsampling=None, max_ray_length_m=None, color=True, normals=False, out=None):
+        """The map seen from camera `cam` at pose T_L_C: -> (depth [rows/s, cols/s] f32, color [.., 3] u8 | None, normals [.., 3] f32 | None) on the
+        mapper's device.  depth 0 = no surface.  subsampling / max_ray_length_m None: the mapper's sphere_tracing_* parameters.
+        out=(depth, color | None, normals | None): preallocated tensors, nothing is allocated; `out` then decides what is computed (a None
+        entry is not) and the color / normals flags are not looked at."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        k = self._cam(cam); T = self._T(T_L_C)
+        s = int(subsampling) if subsampling is not None else 0
+        if s < 0 or (subsampling is not None and s < 1):
+            raise ValueError("subsampling must be >= 1")
+        s_eff = s if s > 0 else max(1, self.params.sphere_tracing_subsampling)
+        rows, cols = k.height // s_eff, k.width // s_eff
+        if out is None:
+            d = torch.empty((rows, cols), dtype=torch.float32, device=dev)
+            c = torch.empty((rows, cols, 3), dtype=torch.uint8, device=dev) if color else None
+            nr = torch.empty((rows, cols, 3), dtype=torch.float32, device=dev) if normals else None
+        else:
+            d, c, nr = out
+            if d is None:
+                raise ValueError("out needs a depth tensor")
+            self._out_tensor(d, (rows, cols), (torch.float32,), "depth")
+            if c is not None:
+                self._out_tensor(c, (rows, cols, 3), (torch.uint8,), "color")
+            if nr is not None:
+                self._out_tensor(nr, (rows, cols, 3), (torch.float32,), "normals")
+        r_, c_ = C.c_int32(), C.c_int32()
+        self._around_torch_stream(lambda: self.lib.nvbx_render_view(
+            self._h, _np_ptr(T), C.byref(k), s, float(max_ray_length_m) if max_ray_length_m is not None else 0.0, C.c_void_p(d.data_ptr()),
+            C.c_void_p(c.data_ptr()) if c is not None else None, C.c_void_p(nr.data_ptr()) if nr is not None else None, d.numel(),
+            C.byref(r_), C.byref(c_)))
+        assert (r_.value, c_.value) == (rows, cols)
+        return d, c, nr
+
+    def cast_rays(self, origins, directions, max_ray_length_m=None, color=False, normals=False, out=None):
+        """Cast n rays (origins, directions: (n, 3) float32 torch tensors or numpy arrays, map-frame metres, directions of unit length):
+        -> (t [n] f32 metres, 0 = no hit; hit [n] bool; color [n, 3] u8 | None; normals [n, 3] f32 | None) on the mapper's device.
+        out=(t, hit | None, color | None, normals | None): preallocated tensors, nothing is allocated; `out` then decides what is computed
+        (a None entry is not) and the color / normals flags are not looked at."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+
+        def rays(a, what):
+            if isinstance(a, torch.Tensor):
+                p = (a if a.device == dev else a.to(dev)).contiguous()
+            else:
+                p = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 3))).to(dev)
+            if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
+                raise ValueError("%s must be an (n, 3) float32 array, got %s %s" % (what, tuple(p.shape), p.dtype))
+            return p
+        o = rays(origins, "origins"); dr = rays(directions, "directions")
+        if o.shape != dr.shape:
+            raise ValueError("origins %s and directions %s differ in shape" % (tuple(o.shape), tuple(dr.shape)))
+        n = o.shape[0]
+        if out is None:
+            t = torch.empty(n, dtype=torch.float32, device=dev)
+            h = torch.empty(n, dtype=torch.bool, device=dev)
+            c = torch.empty((n, 3), dtype=torch.uint8, device=dev) if color else None
+            nr = torch.empty((n, 3), dtype=torch.float32, device=dev) if normals else None
+        else:
+            t, h, c, nr = out
+            if t is None:
+                raise ValueError("out needs a t tensor")
+            self._out_tensor(t, (n,), (torch.float32,), "t")
+            if h is not None:
+                self._out_tensor(h, (n,), (torch.bool, torch.uint8), "hit")
+            if c is not None:
+                self._out_tensor(c, (n, 3), (torch.uint8,), "color")
+            if nr is not None:
+                self._out_tensor(nr, (n, 3), (torch.float32,), "normals")
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None      # noqa: E731
+        self._around_torch_stream(lambda: self.lib.nvbx_cast_rays(
+            self._h, ptr(o), ptr(dr), n, float(max_ray_length_m) if max_ray_length_m is not None else 0.0, ptr(t), ptr(h), ptr(c), ptr(nr)))
+        self._hold("_keep_r", [o, dr])      # (the kernel reads the rays: they, and an uploaded copy, live until the next cast)
+        return t, h, c, nr
 
     def mesh(self):
         """Mesh of the last update_color_mesh: dict block index tuple -> dict(vertices, normals, colors, triangles)."""

@@ -49,7 +49,7 @@ constexpr Param<float>::Description kWorkspaceBoundsMinCornerYParamDesc{"workspa
 constexpr Param<float>::Description kWorkspaceBoundsMaxCornerYParamDesc{"workspace_bounds_max_corner_y_m", 0.0f, "Workspace bounds [m]."};
 constexpr Param<float>::Description kEsdfIntegratorMinWeightParamDesc{"esdf_integrator_min_weight", 0.1f, "Minimum TSDF weight for a voxel to count as observed."};
 constexpr Param<float>::Description kEsdfIntegratorMaxSiteDistanceVoxParamDesc{"esdf_integrator_max_site_distance_vox", 2.0f, "Maximum |TSDF| of a site [voxels]."};
-constexpr Param<float>::Description kEsdfIntegratorMaxDistanceMParamDesc{"esdf_integrator_max_distance_m", 2.0f, "ESDF cut-off distance [m]."};
+constexpr Param<float>::Description kEsdfIntegratorMaxDistanceMParamDesc{"esdf_integrator_max_distance_m", 2.0f, "ESDF cut-off distance [m]; divided by the voxel size it must be below 64 voxels (updateEsdf fails otherwise); below one voxel only the sites have a distance."};
 constexpr Param<float>::Description kMeshIntegratorMinWeightParamDesc{"mesh_integrator_min_weight", 0.1f, "Minimum TSDF weight of a meshed corner."};
 constexpr Param<bool>::Description kMeshIntegratorWeldVerticesParamDesc{"mesh_integrator_weld_vertices", true, "Weld vertices per block."};
 constexpr Param<bool>::Description kDecayIntegratorDeallocateDecayedBlocks{"decay_integrator_deallocate_decayed_blocks", true, "Deallocate fully decayed blocks (false: they stay allocated with their decayed voxels)."};
@@ -87,6 +87,8 @@ struct ViewCalculatorParams {
 struct EsdfIntegratorParams {
   float esdf_integrator_min_weight = 0.1f;
   float esdf_integrator_max_site_distance_vox = 2.0f;
+  // esdf_integrator_max_distance_m / voxel_size must be below 64 voxels: updateEsdf fails otherwise (and leaves the map as it is); a radius below one
+  // voxel gives a distance (0) to the sites only, the cut-off value to every other voxel (SEMANTICS.md "Limits of the cut-off radius")
   float esdf_integrator_max_distance_m = 2.0f;
   float esdf_slice_min_height = 0.0f, esdf_slice_max_height = 1.0f, esdf_slice_height = 1.0f;
   float slice_height_above_plane_m = 0.0f, slice_height_thickness_m = 0.0f;

@@ -77,7 +77,10 @@ typedef struct {
   int32_t raycast_subsampling_factor;     /* raycast_subsampling_factor */
   float esdf_min_weight;                  /* esdf_integrator_min_weight */
   float esdf_max_site_distance_vox;       /* esdf_integrator_max_site_distance_vox */
-  float esdf_max_distance_m;              /* esdf_integrator_max_distance_m */
+  float esdf_max_distance_m;              /* esdf_integrator_max_distance_m: the ESDF cut-off radius.  esdf_max_distance_m / voxel_size (in float) must
+                                             be below 64 voxels: nvbx_update_esdf fails with NVBX_E_INVALID otherwise, in both ESDF modes, and leaves the
+                                             map as it is.  Below one voxel only the sites themselves have a distance (0); every other voxel reads the
+                                             cut-off value (esdf_max_distance_m / voxel_size)^2 -- SEMANTICS.md "Limits of the cut-off radius" */
   float esdf_slice_height;                /* esdf_slice_height */
   float esdf_slice_min_height;            /* esdf_slice_min_height */
   float esdf_slice_max_height;            /* esdf_slice_max_height */

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from esdf_independent import numpy_propagation
 from isaac_ros_nvblox_amd import synthetic as S
 from test_gpu_parity import TOL, compare_layer, make_pair
 
@@ -116,32 +117,6 @@ def test_colour_occlusion_threshold(oracle_mod, hip_lib, thresh):
     if len(test_colour_occlusion_threshold.n) == 3:
         n_ = test_colour_occlusion_threshold.n
         assert n_[0.5] < n_[-1.0] < n_[8.0], n_           # a tighter occlusion test colours fewer voxels (-1 = truncation = 4 vox)
-
-
-def numpy_propagation(sites, dom, max_sq):
-    """Independent restatement (numpy, whole-array) of esdf_propagation = 1: synchronous 4-neighbour parent propagation, key
-    (sq, dy, dx), cut-off max_sq, restricted to `dom`.  Returns sq (float, max_sq where no site is known)."""
-    H_, W_ = sites.shape
-    NONE = np.int64(2 ** 31 - 1)
-    cur = np.where(sites, np.int64((64 << 7) | 64), NONE)
-    for _ in range(4096):
-        best = cur.copy()
-        for ox, oy in ((-1, 0), (1, 0), (0, -1), (0, 1)):
-            nb = np.full_like(cur, NONE)
-            # neighbour at (x + ox, y + oy)
-            ys = slice(max(0, -oy), H_ - max(0, oy)); xs = slice(max(0, -ox), W_ - max(0, ox))
-            ysn = slice(max(0, oy), H_ - max(0, -oy)); xsn = slice(max(0, ox), W_ - max(0, -ox))
-            nb[ys, xs] = np.where(dom[ysn, xsn], cur[ysn, xsn], NONE)
-            dx = (nb & 127) - 64 + ox; dy = ((nb >> 7) & 127) - 64 + oy
-            sq = dx * dx + dy * dy
-            ok = (nb != NONE) & (sq.astype(np.float32) <= np.float32(max_sq)) & (np.abs(dx) <= 63) & (np.abs(dy) <= 63)
-            cand = np.where(ok, (sq << 14) | ((dy + 64) << 7) | (dx + 64), NONE)
-            best = np.minimum(best, cand)
-        best = np.where(dom, best, NONE)
-        if np.array_equal(best, cur):
-            break
-        cur = best
-    return np.where(cur == NONE, np.float32(max_sq), (cur >> 14).astype(np.float32))
 
 
 @pytest.mark.parametrize("prop", [0, 1])

@@ -44,6 +44,7 @@ extern "C" {
 #define NVBX_LAYER_MESH 8u
 #define NVBX_LAYER_OCCUPANCY 16u   /* occupancy mappers only; shares the projective voxel pool with TSDF */
 #define NVBX_LAYER_FREESPACE 32u   /* projective_layer_type 2 only */
+#define NVBX_LAYER_FEATURE 64u     /* after nvbx_enable_features; listed by nvbx_block_indices, read by nvbx_get_feature_blocks / nvbx_query_features */
 
 typedef struct nvbx_mapper nvbx_mapper; /* replaces nvblox::Mapper (one per GPU / stream) */
 
@@ -470,6 +471,39 @@ int nvbx_render_view_with(nvbx_mapper* m, const nvbx_render_options* options, co
                           int32_t* rows_out, int32_t* cols_out);
 int nvbx_cast_rays_with(nvbx_mapper* m, const nvbx_render_options* options, const float* origins_xyz_dev, const float* directions_xyz_dev, int64_t n,
                         float max_ray_length_m, float* t_dev, uint8_t* hit_dev, uint8_t* color_rgb_dev, float* normal_xyz_dev);
+
+/* ---- feature layer ([U] upstream's FeatureLayer / projective feature integrator; SEMANTICS.md "Feature layer") -----------------------
+ * A vision backbone emits a coarse grid of C-channel fp16 vectors per colour frame; the mapper averages them into the voxels the frame
+ * sees, and the caller reads them back at 3-D points.  The rules are the colour integrator's, item by item.
+ * nvbx_enable_features: turns the layer on.  channels = a multiple of 8, 8 .. 256 (else NVBX_E_INVALID); again with the same value: no-op,
+ *   with another: NVBX_E_INVALID; an occupancy mapper: NVBX_E_INVALID; pools that do not fit in free device memory: NVBX_E_DEVICE, the mapper
+ *   stays usable.  Pools: capacity x 512 x C x 2 B of values + capacity x 2048 B of weights, carried by pool growth.  A mapper that never calls
+ *   this allocates nothing for features and behaves bit for bit as without the layer.
+ * nvbx_integrate_features: feat_dev = rows_f x cols_f x C fp16, row-major HWC, 16-byte aligned device memory; `camera` = the full-resolution
+ *   camera the features were computed from; stride >= 1: feature pixel (i, j) is centred on full-resolution pixel coordinate
+ *   ((j + 0.5) stride, (i + 0.5) stride); cols_f stride <= camera.width and rows_f stride <= camera.height (else NVBX_E_INVALID).
+ *   Candidate blocks, synthetic depth (sphere-traced at sphere_tracing_subsampling into a scratch image of this call's own:
+ *   nvbx_get_synthetic_depth, nvbx_last_color_view and color_blocks_updated stay the last colour frame's) and the per-voxel projection and
+ *   occlusion test are nvbx_integrate_color's.  Feature taps: uf = u / stride - 0.5, vf = v / stride - 0.5, x0 = floor(uf), y0 = floor(vf),
+ *   all four taps inside [0, cols_f - 1] x [0, rows_f - 1] or the voxel is skipped; per channel f = bilinear in f32 (top, bottom, then
+ *   vertical, no contraction).  Blend: w0 = stored weight, tw = w0 + 1, v = old (w0 / tw) + f (1 / tw), rounded to fp16 to nearest even;
+ *   weight = min(w0 + 1, max_weight).  A voxel that fails a test is not written.  The mesh is not marked dirty, no work list is touched.
+ *   A block carries features while its slot has NVBX_LAYER_FEATURE: the first feature frame that reaches a voxel of a block without it
+ *   treats the whole block as empty (unreached voxels: weight 0, zero values); whatever deallocates the block's TSDF (decay, radius
+ *   clearing, nvbx_mapper_clear) takes its features with it.
+ * nvbx_query_features: the voxel that contains p (floor(p / voxel_size) per axis); feat_out_dev [n][C] fp16 (16-byte aligned), weight_out_dev [n].
+ *   Weight 0 and zero values -- never an error -- where the block is absent or carries no features, p is not finite, or p lies outside the
+ *   addressable range.  Chained behind nvbx_cast_rays / nvbx_render_view it gives a feature image of the map from any pose.
+ * nvbx_get_feature_blocks: whole blocks in the public layout -- voxel t = vx 64 + vy 8 + vz, C contiguous halfs per voxel: feat_out [n][512][C]
+ *   fp16, weight_out [n][512] f32, found_out [n] (NULL: not written); pointer conventions of nvbx_get_blocks (host memory, synchronous).
+ * All three carry held-back work out first (as nvbx_flush) and run in classic order on the mapper's stream; integrate and query are
+ * asynchronous.  Before nvbx_enable_features they return NVBX_E_INVALID.  Not covered: map files, mesh vertices, multi-GPU exchange,
+ * batches, LiDAR, nvbx_device_view. */
+int nvbx_enable_features(nvbx_mapper* m, int32_t channels);
+int nvbx_integrate_features(nvbx_mapper* m, const void* feat_dev, int32_t rows_f, int32_t cols_f, int32_t stride, const float T_L_C[16],
+                            const nvbx_camera* camera);
+int nvbx_query_features(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, void* feat_out_dev, float* weight_out_dev);
+int nvbx_get_feature_blocks(nvbx_mapper* m, const nvbx_index3d* idx, int64_t n, void* feat_out, float* weight_out, int32_t* found_out);
 
 /* ---- map file (Mapper::saveLayerCake(path) -> bool, loadMap(path) -> bool: nvblox_node.cpp:1663-1668,1698-1703) -----------------
  * A path ending in .nvblx is written as an SQLITE database, like the reference's layer cake: table layers(layer_type, voxel_size,

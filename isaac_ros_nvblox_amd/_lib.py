@@ -171,6 +171,10 @@ SIGNATURES = {
     "nvbx_cast_rays": (C.c_int, [_vp, _vp, _vp, _i64, _f, _vp, _vp, _vp, _vp]),
     "nvbx_render_view_with": (C.c_int, [_vp, C.POINTER(RenderOptions), _vp, C.POINTER(Camera), _i32, _f, _vp, _vp, _vp, _i64, _pi32, _pi32]),
     "nvbx_cast_rays_with": (C.c_int, [_vp, C.POINTER(RenderOptions), _vp, _vp, _i64, _f, _vp, _vp, _vp, _vp]),
+    "nvbx_enable_features": (C.c_int, [_vp, _i32]),
+    "nvbx_integrate_features": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, C.POINTER(Camera)]),
+    "nvbx_query_features": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "nvbx_get_feature_blocks": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),
     "nvbx_block_indices": (_i64, [_vp, C.c_uint32, _vp, _i64]),
     "nvbx_get_block": (C.c_int, [_vp, C.c_uint32, Index3D, _vp]),

@@ -1,0 +1,327 @@
+// features.hip -- the feature layer: per-pixel fp16 feature images (a vision backbone's coarse grid of C-channel vectors) averaged into the
+// voxels a frame sees, and read back at 3-D points (SEMANTICS.md "Feature layer").
+// [U] Upstream's FeatureLayer / projective feature integrator are not readable in the reference tree: the rules are the colour integrator's
+// (nvbx_color_worker.h), restated here for a payload of C halfs per voxel.
+//
+// Storage (allocated by nvbx_enable_features, carried by pool growth; the pointers travel in the kernels' own argument structs, not in DMap):
+//   feat_val : capacity x (C / 8) x 512 x 16 B -- block-major, then [chunk of 8 channels][voxel z + 8y + 64x][8 halfs]: the 64 lanes of a wavefront
+//              (lane = voxel) touch 1 KiB contiguous per access, whatever C is
+//   feat_w   : capacity x 512 x f32
+// A block's payload counts only while its slot carries F_FEATURE.  Whoever takes the block's TSDF away clears the flag (one more constant in
+// the atomicAnd that clears F_COLOR) and moves no byte of it; the first feature frame that reaches a voxel of an unflagged slot treats the
+// whole block as empty, sets the flag and writes all 512 voxels.
+//
+// Two launches per frame, classic order (nothing rides anywhere):
+//   k_feature_trace      the colour frame's sphere tracing (sphere_trace_march, nvbx_sphere_trace.h) into a scratch image of this path's own;
+//                        the colour path's synthetic depth, its work list and its counters are left alone
+//   k_integrate_features one 512-thread workgroup per candidate block (lane = voxel), candidates found as color_integrate_worker finds them
+//                        (chunked slot scan, ballot on the flags, frustum vote of 8 lanes).  Projection, synthetic-depth taps and the
+//                        occlusion verdict once per voxel; then a loop over chunks of 8 channels: four 16-B tap loads, one 16-B voxel load,
+//                        one 16-B voxel store per lane.  Registers do not scale with C.
+#include <algorithm>
+#include <cstring>
+#include "nvbx_mapper.h"
+#include "nvbx_sphere_trace.h"
+
+using namespace nvbx;
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));      // one chunk: 8 channels, 16 bytes
+
+struct FeatTraceArgs { FrameCore f; float* synth; int32_t srows, scols, max_steps; float max_len, eps_m; };
+struct FeatArgs {
+  FrameCore f;                   // the full-resolution camera (rows, cols = its height, width), pose, parameters
+  const half8* img;              // rows_f x cols_f x nch chunks, row-major HWC
+  int32_t rows_f, cols_f, nch;   // nch = C / 8
+  float stride;
+  const float* synth; int32_t srows, scols;
+  half8* val; float* w;          // the pools
+  int32_t chunk;                 // slots per workgroup iteration of the candidate scan (1 .. 64)
+};
+
+// color.hip's sphere tracing launch for one camera, 8 lanes per ray, without the colour work list's reset: ray (r, c) of the srows x scols image
+// goes through the centre of full-resolution pixel (r s, c s); the same expressions, so the image is the colour frame's (and nvbx_render_view's)
+__global__ __launch_bounds__(256) void k_feature_trace(DMap m, FeatTraceArgs a) {
+  constexpr int RL = 8, PW = 8, PH = (256 / RL) / PW;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int sub = lane & (RL - 1), gsh = lane & ~(RL - 1);
+  const FrameCore& f = a.f;
+  const int patches_x = (a.scols + PW - 1) / PW, patches_y = (a.srows + PH - 1) / PH;
+  const int n_patch = patches_x * patches_y, per_xcd = (n_patch + NSH - 1) / NSH;
+  const int wg = (int)blockIdx.x;
+  const int patch = (wg & (NSH - 1)) * per_xcd + (wg >> 3);      // the workgroups of one XCD own a band of patch rows (sphere_trace_worker)
+  const int pr = tid / RL;
+  const int py = patch / patches_x, px = patch - py * patches_x;
+  const int r = py * PH + pr / PW, c = px * PW + pr % PW;
+  const bool valid = patch < n_patch && (wg >> 3) < per_xcd && r < a.srows && c < a.scols;
+  const float rx = (((float)((valid ? c : 0) * f.subsample) + 0.5f) - f.cu) / f.fu;
+  const float ry = (((float)((valid ? r : 0) * f.subsample) + 0.5f) - f.cv) / f.fv;
+  const float n = NVBX_SQRT((rx * rx + ry * ry) + 1.0f);
+  const float dcx = NVBX_DIV(rx, n), dcy = NVBX_DIV(ry, n), dcz = NVBX_DIV(1.0f, n);
+  float dl[3];
+  rotate(f.R_LC, dcx, dcy, dcz, dl);
+  float t = 0.0f; int n_rounds = 0;
+  const bool hit = sphere_trace_march<RL>(m, f.t_LC, dl, f.voxel_size, f.trunc, a.max_steps, a.max_len, a.eps_m, valid, sub, gsh, &t, &n_rounds);
+  if (valid && sub == 0) a.synth[(int64_t)r * a.scols + c] = hit ? t * dcz : 0.0f;
+}
+
+// one candidate block: every thread of the workgroup calls (barriers); `flags` = the slot's flags as this launch found them
+__device__ inline void feature_integrate_block(const DMap& m, const FeatArgs& a, int32_t slot, int32_t bx, int32_t by, int32_t bz, uint32_t flags) {
+  const int tid = threadIdx.x;
+  const int vx = tid >> 6, vy = (tid >> 3) & 7, vz = tid & 7;
+  const FrameCore& f = a.f;
+  // ---- once per voxel: the colour integrator's tests in its expressions (color_integrate_block), the feature grid in place of the colour image
+  bool pass = false;
+  float ax = 0.0f, ay = 0.0f; int32_t i00 = 0;
+  {
+    const float lx = voxel_center(bx, vx, f.block_size, f.voxel_size), ly = voxel_center(by, vy, f.block_size, f.voxel_size),
+                lz = voxel_center(bz, vz, f.block_size, f.voxel_size);
+    float pc[3];
+    apply_rt(f.R_CL, f.t_CL, lx, ly, lz, pc);
+    float u, v;
+    bool ok = cam_project(f, pc, &u, &v);
+    const float vd = pc[2];
+    if (f.max_dist > 0.0f && vd > f.max_dist) ok = false;
+    const float uf = NVBX_DIV(u, a.stride) - 0.5f, vf = NVBX_DIV(v, a.stride) - 0.5f;
+    const float fx = floorf(uf), fy = floorf(vf);
+    const int x0 = (int)fx, y0 = (int)fy;
+    const bool c_ok = !(x0 < 0 || y0 < 0 || x0 + 1 > a.cols_f - 1 || y0 + 1 > a.rows_f - 1);
+    const float us = NVBX_DIV(u, (float)f.subsample), vs_ = NVBX_DIV(v, (float)f.subsample);
+    const float usc = us - 0.5f, vsc = vs_ - 0.5f;
+    const float sfx = floorf(usc), sfy = floorf(vsc);
+    const int sx0 = (int)sfx, sy0 = (int)sfy;
+    const bool s_ok = !(sx0 < 0 || sy0 < 0 || sx0 + 1 > a.scols - 1 || sy0 + 1 > a.srows - 1);
+    if (ok && c_ok && s_ok) {
+      const float* sp = a.synth + pix(sy0, sx0, a.scols);
+      const float s00 = sp[0], s10 = sp[1], s01 = sp[a.scols], s11 = sp[a.scols + 1];
+      if (s00 > 0.0f && s10 > 0.0f && s01 > 0.0f && s11 > 0.0f) {
+        const float sax = usc - sfx, say = vsc - sfy;
+        const float stop = (1.0f - sax) * s00 + sax * s10;
+        const float sbot = (1.0f - sax) * s01 + sax * s11;
+        const float sd = (1.0f - say) * stop + say * sbot;
+        if (!(fabsf(sd - vd) > f.occlusion_thresh)) { pass = true; ax = uf - fx; ay = vf - fy; i00 = pix(y0, x0, a.cols_f); }
+      }
+    }
+  }
+  if (!__syncthreads_or(pass ? 1 : 0)) return;         // no voxel of the block is reached: nothing is written, the slot is not flagged
+  const bool fresh = !(flags & F_FEATURE);             // uniform: the block holds nothing yet -- every voxel is written
+  if (fresh && tid == 0) atomicOr(&m.slot_flags[slot], F_FEATURE);
+  float* wp = a.w + (size_t)slot * 512 + tid;
+  const float w0 = (fresh || !pass) ? 0.0f : *wp;
+  const float tw = w0 + 1.0f;
+  const float ca = NVBX_DIV(w0, tw), cb = NVBX_DIV(1.0f, tw);      // blend_u8's weights (w1 = 1)
+  if (pass) *wp = fminf(w0 + 1.0f, f.max_weight);
+  else if (fresh) *wp = 0.0f;
+  if (!pass && !fresh) return;                         // (no barrier below)
+  const int nch = a.nch;
+  const half8* t0 = a.img + (size_t)i00 * nch;         // tap (x0, y0); (x0 + 1, y0) is nch chunks on, the next row cols_f * nch
+  const size_t row = (size_t)a.cols_f * nch;
+  half8* vp = a.val + (size_t)slot * nch * 512 + tid;
+  const float bx0 = 1.0f - ax, by0 = 1.0f - ay;
+#pragma unroll 2
+  for (int k = 0; k < nch; k++) {
+    half8 o;
+    if (pass) {
+      const half8 t00 = t0[k], t10 = t0[nch + k], t01 = t0[row + k], t11 = t0[row + nch + k];
+      half8 old;
+      if (fresh) { for (int q = 0; q < 8; q++) old[q] = (_Float16)0.0f; } else old = vp[(size_t)k * 512];
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const float top = bx0 * (float)t00[q] + ax * (float)t10[q];
+        const float bot = bx0 * (float)t01[q] + ax * (float)t11[q];
+        const float fv = by0 * top + ay * bot;
+        const float nv = (float)old[q] * ca + fv * cb;
+        o[q] = (_Float16)nv;                           // round to nearest even
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; q++) o[q] = (_Float16)0.0f;
+    }
+    vp[(size_t)k * 512] = o;
+  }
+}
+
+// candidate discovery of color_integrate_worker (nvbx_color_worker.h) for one camera; a block a LiDAR scan left F_BAND_STALE is voted from its
+// TSDF and NOT repaired (this launch writes nothing but the feature pools and F_FEATURE)
+__global__ __launch_bounds__(512) void k_integrate_features(DMap m, FeatArgs a) {
+  __shared__ int s_out[6];
+  const int tid = threadIdx.x;
+  const FrameCore& f = a.f;
+  const int chunk = a.chunk;
+  const int lane_c = tid & 63;
+  const int32_t cap = (int32_t)m.capacity;
+  const int32_t n_wg = (int32_t)gridDim.x;
+  const int32_t wg = xcd_chunked((int32_t)blockIdx.x, n_wg);
+  const int32_t hw = m.counters[C_HIGH_WATER];
+  for (int32_t base = wg * chunk; base < hw; base += n_wg * chunk) {
+    const int32_t ls = min(base + lane_c, cap - 1);
+    const uint32_t lflags = lane_c < chunk ? m.slot_flags[ls] : 0u;
+    int32_t lbx = 0, lby = 0, lbz = 0;
+    if (lane_c < chunk) { lbx = m.slot_index[3 * ls]; lby = m.slot_index[3 * ls + 1]; lbz = m.slot_index[3 * ls + 2]; }
+    u64 cand = __ballot(lane_c < chunk && base + lane_c < hw && (lflags & F_TSDF) && (lflags & (F_BAND | F_BAND_STALE)));      // (the same in all eight wavefronts: nobody writes these bits here)
+    while (cand) {
+      const int cj = __ffsll((long long)cand) - 1;
+      cand &= cand - 1ull;
+      const int32_t slot = base + cj;
+      const uint32_t flags = __shfl(lflags, cj);
+      const int32_t bx = __shfl(lbx, cj), by = __shfl(lby, cj), bz = __shfl(lbz, cj);
+      if (flags & F_BAND_STALE) {      // uniform
+        const float2 tv = m.tsdf[(size_t)slot * 512 + tid];
+        if (!__syncthreads_or(in_band(tv.x, tv.y, f.trunc) ? 1 : 0)) continue;
+      }
+      __syncthreads();
+      if (tid < 6) s_out[tid] = 0;
+      __syncthreads();
+      if (tid < 8) {            // frustum: count corners outside each plane
+        const int q = tid;
+        float pc[3];
+        apply_rt(f.R_CL, f.t_CL, (float)(bx + (q & 1)) * f.block_size, (float)(by + ((q >> 1) & 1)) * f.block_size,
+                 (float)(bz + ((q >> 2) & 1)) * f.block_size, pc);
+        if (f.fu * pc[0] + f.cu * pc[2] < 0.0f) atomicAdd(&s_out[0], 1);
+        if (f.fu * pc[0] + (f.cu - (float)f.w) * pc[2] > 0.0f) atomicAdd(&s_out[1], 1);
+        if (f.fv * pc[1] + f.cv * pc[2] < 0.0f) atomicAdd(&s_out[2], 1);
+        if (f.fv * pc[1] + (f.cv - (float)f.h) * pc[2] > 0.0f) atomicAdd(&s_out[3], 1);
+        if (pc[2] < 0.0f) atomicAdd(&s_out[4], 1);
+        if (f.max_dist > 0.0f && pc[2] > f.max_dist) atomicAdd(&s_out[5], 1);
+      }
+      __syncthreads();
+      bool iv = true;
+#pragma unroll
+      for (int q = 0; q < 6; q++) if (s_out[q] == 8) iv = false;
+      if (!iv) continue;        // uniform
+      feature_integrate_block(m, a, slot, bx, by, bz, flags);
+    }
+  }
+}
+
+// ---- readers
+// voxel that contains p: floor(p / vs) per axis (the renderer's colour rule); false: not finite / outside the addressable range
+__device__ inline bool feature_voxel_of(float px, float py, float pz, float vs, int32_t* g) {
+  const float fx = floorf(NVBX_DIV(px, vs)), fy = floorf(NVBX_DIV(py, vs)), fz = floorf(NVBX_DIV(pz, vs));
+  const float L = 8388608.0f;      // 2^20 blocks x 8 voxels
+  if (!(fx >= -L && fx < L && fy >= -L && fy < L && fz >= -L && fz < L)) return false;      // (a NaN fails every comparison)
+  g[0] = (int32_t)fx; g[1] = (int32_t)fy; g[2] = (int32_t)fz;
+  return true;
+}
+// one lane per (point, chunk): the nch lanes of a point write its C halfs as consecutive 16-B stores
+__global__ __launch_bounds__(256) void k_query_features(DMap m, const half8* __restrict__ val, const float* __restrict__ w, int32_t nch, const float* __restrict__ pts,
+                                                        int64_t n, float vs, half8* __restrict__ feat_out, float* __restrict__ w_out) {
+  const int64_t total = n * nch;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = i / nch; const int k = (int)(i - p * nch);
+    int32_t g[3] = {0, 0, 0};
+    uint32_t slot = SLOT_NONE;
+    if (feature_voxel_of(pts[3 * p], pts[3 * p + 1], pts[3 * p + 2], vs, g)) slot = find_slot(m, g[0] >> 3, g[1] >> 3, g[2] >> 3, F_FEATURE);
+    half8 o; float wv = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 8; q++) o[q] = (_Float16)0.0f;
+    if (slot_ok(slot)) {
+      const int t = (g[2] & 7) + 8 * (g[1] & 7) + 64 * (g[0] & 7);
+      o = val[((size_t)slot * nch + k) * 512 + t];
+      if (k == 0) wv = w[(size_t)slot * 512 + t];
+    }
+    feat_out[i] = o;
+    if (k == 0) w_out[p] = wv;
+  }
+}
+// block i of the list -> the public layout: voxel t = vx 64 + vy 8 + vz, C contiguous halfs per voxel; an absent / unflagged block reads as zeros
+__global__ __launch_bounds__(512) void k_gather_feature_blocks(DMap m, const half8* val, const float* w, int32_t nch, const int32_t* idx, int32_t n, half8* feat_out,
+                                                               float* w_out, int32_t* found) {
+  const int i = blockIdx.x; if (i >= n) return;
+  const int t = threadIdx.x;
+  const uint32_t s = find_slot(m, idx[3 * i], idx[3 * i + 1], idx[3 * i + 2], F_FEATURE);
+  if (t == 0) found[i] = slot_ok(s) ? 1 : 0;
+  w_out[(size_t)i * 512 + t] = slot_ok(s) ? w[(size_t)s * 512 + t] : 0.0f;
+  half8 z;
+#pragma unroll
+  for (int q = 0; q < 8; q++) z[q] = (_Float16)0.0f;
+  for (int k = 0; k < nch; k++) feat_out[((size_t)i * 512 + t) * nch + k] = slot_ok(s) ? val[((size_t)s * nch + k) * 512 + t] : z;
+}
+
+// ------------------------------------------------------------------------------------------------ C-ABI
+extern "C" int nvbx_enable_features(nvbx_mapper* m, int32_t channels) {
+  if (!m) return NVBX_E_INVALID;
+  if (channels < 8 || channels > 256 || (channels & 7)) { set_error("nvbx_enable_features: channels must be a multiple of 8, 8 .. 256"); return NVBX_E_INVALID; }
+  if (m->p.projective_layer_type == 1) { set_error("nvbx_enable_features: an occupancy mapper carries no feature layer (the occlusion test sphere-traces a TSDF)"); return NVBX_E_INVALID; }
+  if (m->feat_channels) {
+    if (m->feat_channels == channels) return NVBX_OK;
+    set_error("nvbx_enable_features: the layer is already on with another channel count"); return NVBX_E_INVALID;
+  }
+  if (m->join_side()) return NVBX_E_DEVICE;
+  const size_t vb = (size_t)m->capacity * 1024 * (size_t)channels, wb = (size_t)m->capacity * 2048;
+  size_t free_b = 0, total_b = 0; NVBX_HIP(hipMemGetInfo(&free_b, &total_b));
+  if (free_b < vb + wb + (64u << 20)) { set_error("nvbx_enable_features: the pools do not fit in free device memory"); return NVBX_E_DEVICE; }
+  void* v = nullptr; void* w = nullptr;
+  if (hipMalloc(&v, vb) != hipSuccess || hipMalloc(&w, wb) != hipSuccess) {
+    (void)hipGetLastError(); if (v) (void)hipFree(v);
+    set_error("nvbx_enable_features: device allocation failed"); return NVBX_E_DEVICE;
+  }
+  // (no fill: nothing reads a block's payload before the launch that flags its slot has written all of it)
+  m->feat_val = v; m->feat_w = static_cast<float*>(w); m->feat_channels = channels;
+  return NVBX_OK;
+}
+
+extern "C" int nvbx_integrate_features(nvbx_mapper* m, const void* feat_dev, int32_t rows_f, int32_t cols_f, int32_t stride, const float T_L_C[16],
+                                       const nvbx_camera* camera) {
+  if (!m || !feat_dev || !T_L_C || !camera || ((uintptr_t)feat_dev & 15)) { set_error("nvbx_integrate_features: invalid argument (the feature image is 16-byte aligned)"); return NVBX_E_INVALID; }
+  if (!m->feat_channels) { set_error("nvbx_integrate_features: call nvbx_enable_features first"); return NVBX_E_INVALID; }
+  if (!image_dims_ok(camera->height, camera->width) || !(camera->fu > 0.0f) || !(camera->fv > 0.0f)) { set_error("nvbx_integrate_features: camera sides 1 .. 32768, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (stride < 1 || rows_f < 1 || cols_f < 1 || (int64_t)cols_f * stride > camera->width || (int64_t)rows_f * stride > camera->height) {
+    set_error("nvbx_integrate_features: stride >= 1, cols_f * stride <= camera width, rows_f * stride <= camera height"); return NVBX_E_INVALID; }
+  if (!nvbx_pose_in_range(T_L_C, m->p.voxel_size * 8.0f, m->p.sphere_tracing_max_ray_length_m + m->p.max_integration_distance_m)) {
+    set_error("nvbx_integrate_features: T_L_C is not finite or lies outside the addressable block range (+-2^20 blocks)"); return NVBX_E_INVALID; }
+  const int sub = std::max(1, m->p.sphere_tracing_subsampling);
+  const int32_t srows = camera->height / sub, scols = camera->width / sub;
+  if (srows < 2 || scols < 2) { set_error("nvbx_integrate_features: camera too small for the sphere-tracing subsampling"); return NVBX_E_INVALID; }
+  if (m->join_side()) return NVBX_E_DEVICE;            // held-back work is carried out first: classic order from here on
+  if (m->feat_synth.ensure(m->stream, (size_t)srows * scols * 4)) return NVBX_E_DEVICE;
+  const Frame fr = m->make_frame(T_L_C, camera, camera->height, camera->width, m->p.sphere_tracing_subsampling);
+  FeatTraceArgs ta{}; ta.f = fr; ta.synth = m->feat_synth.as<float>(); ta.srows = srows; ta.scols = scols; ta.max_steps = m->p.sphere_tracing_max_steps;
+  ta.max_len = m->p.sphere_tracing_max_ray_length_m; ta.eps_m = m->p.sphere_tracing_surface_eps_vox * m->p.voxel_size;
+  const int st_patches = ((scols + 7) / 8) * ((srows + 3) / 4);      // 8 x 4 rays per 256-thread workgroup at 8 lanes per ray
+  NVBX_LAUNCH(m, k_feature_trace, dim3((unsigned)(NSH * ((st_patches + NSH - 1) / NSH))), dim3(256), m->d, ta);
+  FeatArgs a{}; a.f = fr; a.img = static_cast<const half8*>(feat_dev); a.rows_f = rows_f; a.cols_f = cols_f; a.nch = m->feat_channels / 8; a.stride = (float)stride;
+  a.synth = ta.synth; a.srows = srows; a.scols = scols; a.val = static_cast<half8*>(m->feat_val); a.w = m->feat_w;
+  const int grid = (int)std::min<int64_t>(m->capacity, 1024);
+  { const int64_t hw_seen = std::max<int64_t>(1, __atomic_load_n(&m->h_mirror[1], __ATOMIC_RELAXED));      // (color_setup's rule; a hint only)
+    int ch = 1; while (ch < 64 && (int64_t)ch * grid * 4 < hw_seen) ch *= 2;
+    a.chunk = ch; }
+  NVBX_LAUNCH(m, k_integrate_features, dim3((unsigned)grid), dim3(512), m->d, a);
+  NVBX_HIP(hipGetLastError());
+  return NVBX_OK;
+}
+
+extern "C" int nvbx_query_features(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, void* feat_out_dev, float* weight_out_dev) {
+  if (!m || n < 0 || (n > 0 && (!points_xyz_dev || !feat_out_dev || !weight_out_dev)) || ((uintptr_t)feat_out_dev & 15)) {
+    set_error("nvbx_query_features: invalid argument (the feature output is 16-byte aligned)"); return NVBX_E_INVALID; }
+  if (!m->feat_channels) { set_error("nvbx_query_features: call nvbx_enable_features first"); return NVBX_E_INVALID; }
+  if (n == 0) return NVBX_OK;
+  if (m->join_side()) return NVBX_E_DEVICE;
+  const int32_t nch = m->feat_channels / 8;
+  NVBX_LAUNCH(m, k_query_features, dim3((unsigned)std::min<int64_t>((n * nch + 255) / 256, 8192)), dim3(256), m->d, static_cast<const half8*>(m->feat_val),
+              (const float*)m->feat_w, nch, points_xyz_dev, n, m->p.voxel_size, static_cast<half8*>(feat_out_dev), weight_out_dev);
+  NVBX_HIP(hipGetLastError());
+  return NVBX_OK;
+}
+
+extern "C" int nvbx_get_feature_blocks(nvbx_mapper* m, const nvbx_index3d* idx, int64_t n, void* feat_out, float* weight_out, int32_t* found_out) {
+  if (!m || n < 0 || (n > 0 && (!idx || !feat_out || !weight_out))) { set_error("nvbx_get_feature_blocks: invalid argument"); return NVBX_E_INVALID; }
+  if (!m->feat_channels) { set_error("nvbx_get_feature_blocks: call nvbx_enable_features first"); return NVBX_E_INVALID; }
+  if (m->join_side()) return NVBX_E_DEVICE;
+  const int32_t nch = m->feat_channels / 8;
+  const size_t fb = (size_t)512 * 16 * nch, wb = 2048;
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)((m->staging.bytes - 65536) / (fb + wb + 16)));
+  for (int64_t o = 0; o < n; o += chunk) {
+    const int64_t c = std::min(chunk, n - o);
+    int32_t* d_idx = m->staging.as<int32_t>(); int32_t* d_found = d_idx + 3 * c;
+    uint8_t* d_w = m->staging.as<uint8_t>() + (((size_t)c * 16 + 255) & ~(size_t)255);
+    uint8_t* d_f = d_w + (size_t)c * wb;                         // (256-byte aligned: wb is)
+    NVBX_HIP(hipMemcpyAsync(d_idx, idx + o, (size_t)c * 12, hipMemcpyHostToDevice, m->stream));
+    NVBX_LAUNCH(m, k_gather_feature_blocks, dim3((unsigned)c), dim3(512), m->d, static_cast<const half8*>(m->feat_val), (const float*)m->feat_w, nch, (const int32_t*)d_idx,
+                (int32_t)c, reinterpret_cast<half8*>(d_f), reinterpret_cast<float*>(d_w), d_found);
+    NVBX_HIP(hipMemcpyAsync((uint8_t*)feat_out + (size_t)o * fb, d_f, (size_t)c * fb, hipMemcpyDeviceToHost, m->stream));
+    NVBX_HIP(hipMemcpyAsync((uint8_t*)weight_out + (size_t)o * wb, d_w, (size_t)c * wb, hipMemcpyDeviceToHost, m->stream));
+    if (found_out) NVBX_HIP(hipMemcpyAsync(found_out + o, d_found, (size_t)c * 4, hipMemcpyDeviceToHost, m->stream));
+    NVBX_HIP(hipStreamSynchronize(m->stream));
+  }
+  return NVBX_OK;
+}

@@ -14,7 +14,7 @@
 
 using namespace nvbx;
 
-constexpr uint32_t LAYER_MASK = F_TSDF | F_COLOR | F_ESDF | F_MESH | F_ESDF_PENDING | F_FREESPACE;   // a slot carrying any of these is live
+constexpr uint32_t LAYER_MASK = F_TSDF | F_COLOR | F_ESDF | F_MESH | F_ESDF_PENDING | F_FREESPACE;   // a slot carrying any of these is live (not F_FEATURE: it goes with the TSDF)
 
 __device__ inline void free_slot(DMap& m, uint32_t slot) {   // one thread
   const int32_t pos = atomicAdd(&m.counters[C_FREE_TOP], 1);
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       } else {
         if (!OCC) old = atomicOr(&m.slot_flags[slot], F_DIRTY_MESH);
         push_cleared = true;                             // Mapper::getClearedBlocks (layer_publishing.cpp:716): the viewer deletes it
-        atomicAnd(&m.slot_flags[slot], ~(F_TSDF | F_COLOR | F_MESH | F_FREESPACE | F_BAND | F_BAND_STALE));
+        atomicAnd(&m.slot_flags[slot], ~(F_TSDF | F_COLOR | F_FEATURE | F_MESH | F_FREESPACE | F_BAND | F_BAND_STALE));
         const int32_t bx = m.slot_index[3 * slot], by = m.slot_index[3 * slot + 1], bz = m.slot_index[3 * slot + 2];
         if (bz >= bz_lo && bz <= bz_hi) {
           const uint32_t es = bz_out == INT32_MIN ? (uint32_t)slot : any_slot(m, bx, by, bz_out);   // 3-D ESDF: the block's own slot (the table is rebuilt after this kernel, not during it)
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(512) void k_clear_outside(DMap m, float cx, float c
         atomicMin(shc_at(m, srec, sh, 0), bx); atomicMin(shc_at(m, srec, sh, 1), by);
         atomicMax(shc_at(m, srec, sh, 2), bx); atomicMax(shc_at(m, srec, sh, 3), by);
       }
-      atomicAnd(&m.slot_flags[slot], ~(LAYER_MASK | F_DIRTY_ESDF | F_DIRTY_MESH | F_ESDF_REMARK | F_BAND | F_BAND_STALE));
+      atomicAnd(&m.slot_flags[slot], ~(LAYER_MASK | F_FEATURE | F_DIRTY_ESDF | F_DIRTY_MESH | F_ESDF_REMARK | F_BAND | F_BAND_STALE));
       m.site_bits[slot] = 0ull; m.obs_bits[slot] = 0ull; m.inside_bits[slot] = 0ull; free_slot(m, (uint32_t)slot);
     }
     }
@@ -484,7 +484,8 @@ int nvbx_mapper::grow_map(int64_t new_cap) {
   if (fetch_counters()) return NVBX_E_DEVICE;                // (synchronises; the mesh arena cursors are needed below)
   // enough HBM?  (voxel pools dominate: 3-4 x 4 KiB per block; old and new copies of ONE array coexist at a time)
   { size_t free_b = 0, total_b = 0; NVBX_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t need = (size_t)new_cap * 4096 + ((size_t)new_cap - (size_t)old_cap) * (3 * 4096 + (d.freespace ? 8192 : 0) + 512) + (64u << 20);
+    const size_t need = (size_t)new_cap * 4096 + ((size_t)new_cap - (size_t)old_cap) * (3 * 4096 + (d.freespace ? 8192 : 0) + 512) + (64u << 20) +
+                        (feat_val ? (size_t)new_cap * (1024 * (size_t)feat_channels + 2048) : 0);      // (the feature pools' new copies)
     if (free_b < need) { set_error("pool growth: not enough free HBM, the block pools stay at their size"); max_capacity = capacity; return NVBX_OK; } }
   // Failure-atomic: EVERY new array is allocated first; if one allocation fails they are all released and the map is untouched
   // (the pools stay at their size).  Only then are the contents copied and the pointers / capacity swapped in one commit step.

@@ -60,6 +60,8 @@ std::vector<PoolArr> nvbx_mapper::pool_arrays(int64_t cap) {
       per_block(&export_idx, 12, -1), per_block(&cleared_idx, 12, -1), per_block(&d.site_bits, 8, 0), per_block(&d.obs_bits, 8, 0), per_block(&d.inside_bits, 8, 0),
       per_block(&mesh_rec, sizeof(MeshRecord), -1),
       PoolArr{reinterpret_cast<void**>(&d.freespace), 512 * 16, 0, 0},       // on first use: ensure_freespace_pool (dynamics.hip)
+      // the feature layer, on nvbx_enable_features (features.hip); no fill: a block's payload is written whole before its slot is flagged
+      PoolArr{&feat_val, 1024 * (size_t)feat_channels, -1, 0}, PoolArr{reinterpret_cast<void**>(&feat_w), feat_channels ? (size_t)2048 : 0, -1, 0},
       // grow_map has code of its own for these: the hash table is rebuilt, the work lists and mesh arenas move segment by segment
       other(&d.table, hash_slots(cap) * sizeof(Entry)), other(&d.lists, (size_t)N_LISTS * NSH * n * 4),
       other(&mesh_vert, mv * 12), other(&mesh_nrm, mv * 12), other(&mesh_col, mv * 4), other(&mesh_tri, mv * 2 * 12),

@@ -31,6 +31,10 @@ __host__ __device__ inline bool slot_ok(uint32_t s) { return s < SLOT_NONE; }
 // slot_flags bits
 constexpr uint32_t F_TSDF = 1u, F_COLOR = 2u, F_ESDF = 4u, F_MESH = 8u;
 constexpr uint32_t F_FREESPACE = 32u;      // (16 is the API id of the occupancy layer, which lives under F_TSDF)
+// on a TSDF slot: the block's feature voxels (features.hip) count.  Set by the first feature frame that reaches the block, which writes all 512
+// voxels; cleared -- and no byte of the payload touched -- by whoever takes the block's TSDF away, in the atomicAnd that clears F_COLOR.  Not part
+// of LAYER_MASK (maintenance.hip): features do not keep a block alive.
+constexpr uint32_t F_FEATURE = 64u;
 constexpr uint32_t F_DIRTY_ESDF = 1u << 8, F_DIRTY_MESH = 1u << 9;
 // the block was given an ESDF column by a marking pass but joins the ESDF layer (F_ESDF, layer AABB) only when the distance
 // transform of that update runs: marking never changes anything the API can observe

@@ -52,7 +52,7 @@ size_t ref_voxel_bytes(uint32_t layer);
 // API layer ids by what can be done with them: written block by block (nvbx_set_blocks, map files) / read block by block / listed
 static inline bool layer_writable(uint32_t l) { return l == F_TSDF || l == F_COLOR || l == F_ESDF || l == NVBX_LAYER_OCCUPANCY; }
 static inline bool layer_readable(uint32_t l) { return layer_writable(l) || l == F_FREESPACE; }
-static inline bool layer_listable(uint32_t l) { return layer_readable(l) || l == F_MESH; }
+static inline bool layer_listable(uint32_t l) { return layer_readable(l) || l == F_MESH || l == F_FEATURE; }      // (feature blocks are read by nvbx_get_feature_blocks)
 
 }  // namespace nvbx
 
@@ -118,6 +118,11 @@ struct nvbx_mapper {
   nvbx::DevBuf depth_pre;
   // colour scratch
   nvbx::DevBuf synth; int32_t synth_rows = 0, synth_cols = 0, synth_last = 0;
+  // feature layer (features.hip): null / 0 until nvbx_enable_features.  feat_val: capacity x (channels / 8) x 512 x 8 halfs, feat_w: capacity x 512 f32;
+  // both in pool_arrays (pool growth carries them), handed to the feature kernels in their own argument structs.  feat_synth: the synthetic depth of
+  // the last feature frame -- the colour path's `synth` stays the last colour frame's.
+  void* feat_val = nullptr; float* feat_w = nullptr; int32_t feat_channels = 0;
+  nvbx::DevBuf feat_synth;
   // mesh arena
   float* mesh_vert = nullptr; float* mesh_nrm = nullptr; uint8_t* mesh_col = nullptr; int32_t* mesh_tri = nullptr;
   nvbx::MeshRecord* mesh_rec = nullptr;

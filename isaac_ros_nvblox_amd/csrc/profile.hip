@@ -48,6 +48,8 @@ extern "C" int nvbx_get_profile(nvbx_mapper* m, char* json_out, int64_t capacity
     for (hipEvent_t e : ev) m->event_pool.push_back(e);
     if (n_ok) acc.push_back({"_empty_event_pair", n_ok, ms_sum, 0.0});
   }
+  // a mapper with a feature layer (features.hip) reports its pools: count = bytes allocated.  No entry: nothing was ever allocated for features
+  if (m->feat_val) acc.push_back({"_feature_pool_bytes", (int64_t)m->capacity * (1024 * (int64_t)m->feat_channels + 2048), 0.0, 0.0});
   std::string out = "{";
   for (size_t i = 0; i < acc.size(); i++) {
     char buf[256];

@@ -12,6 +12,7 @@ from . import _lib
 from ._lib import BoundingShape, Camera, Counters, Index3D, Lidar, Params
 
 LAYER_TSDF, LAYER_COLOR, LAYER_ESDF, LAYER_MESH, LAYER_OCCUPANCY, LAYER_FREESPACE = 1, 2, 4, 8, 16, 32
+LAYER_FEATURE = 64
 
 TSDF_DT = np.dtype([("distance", "<f4"), ("weight", "<f4")])
 COLOR_DT = np.dtype([("r", "u1"), ("g", "u1"), ("b", "u1"), ("pad", "u1"), ("weight", "<f4")])
@@ -801,6 +802,64 @@ class Mapper:
             self._h, ptr(o), ptr(dr), n, float(max_ray_length_m) if max_ray_length_m is not None else 0.0, ptr(t), ptr(h), ptr(c), ptr(nr)))
         self._hold("_keep_r", [o, dr])      # (the kernel reads the rays: they, and an uploaded copy, live until the next cast)
         return t, h, c, nr
+
+    # -- feature layer (nvbx_enable_features / nvbx_integrate_features / nvbx_query_features; SEMANTICS.md "Feature layer")
+    def enable_features(self, channels):
+        """Turn the feature layer on with `channels` fp16 values per voxel (a multiple of 8, 8 .. 256).  Again with the same value: no-op."""
+        self._check(self.lib.nvbx_enable_features(self._h, int(channels)))
+        self.feature_channels = int(channels)
+
+    def integrate_features(self, feat, T_L_C, cam, stride):
+        """Average a feature image into the voxels the frame sees.  feat: (rows_f, cols_f, C) torch.float16 device tensor or numpy float16 array;
+        `cam` is the full-resolution camera the features were computed from, feature pixel (i, j) is centred on its pixel coordinate
+        ((j + 0.5) stride, (i + 0.5) stride)."""
+        torch = self._torch
+        if not isinstance(feat, torch.Tensor):
+            feat = np.asarray(feat)
+        if feat.dtype not in (torch.float16, np.float16) or len(feat.shape) != 3:
+            raise ValueError("feat must be a (rows_f, cols_f, C) float16 array, got %s %s" % (tuple(feat.shape), feat.dtype))
+        f = self._dev(feat, torch.float16)
+        ch = getattr(self, "feature_channels", 0)      # (0: not enabled -- the library refuses the call)
+        if ch and f.shape[2] != ch:
+            raise NvbxError("integrate_features: the image has %d channels, the layer %d (enable_features)" % (f.shape[2], ch))
+        T = self._T(T_L_C); k = self._cam(cam)
+        self._around_torch_stream(lambda: self.lib.nvbx_integrate_features(
+            self._h, C.c_void_p(f.data_ptr()), f.shape[0], f.shape[1], int(stride), _np_ptr(T), C.byref(k)))
+        self._hold("_keep_f", [f])      # (the kernel reads the image: it, and an uploaded copy, live until the next feature frame)
+
+    def query_features(self, points, out=None):
+        """The feature voxel that contains each of `points` ((n, 3) float32 torch tensor or numpy array, metres): -> (features [n, C] f16,
+        weights [n] f32) on the mapper's device; weight 0 and zeros where the map holds no features (never an error).
+        out=(features, weights): preallocated tensors, nothing is allocated."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(points, torch.Tensor):
+            p = (points if points.device == dev else points.to(dev)).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
+        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError("points must be an (n, 3) float32 array, got %s %s" % (tuple(p.shape), p.dtype))
+        n = p.shape[0]; ch = getattr(self, "feature_channels", 0)
+        if out is None:
+            f = torch.empty((n, ch), dtype=torch.float16, device=dev)
+            w = torch.empty(n, dtype=torch.float32, device=dev)
+        else:
+            f, w = out
+            self._out_tensor(f, (n, ch), (torch.float16,), "features")
+            self._out_tensor(w, (n,), (torch.float32,), "weights")
+        self._around_torch_stream(lambda: self.lib.nvbx_query_features(
+            self._h, C.c_void_p(p.data_ptr()), n, C.c_void_p(f.data_ptr()), C.c_void_p(w.data_ptr())), order=n > 0)
+        self._hold("_keep_fq", [p])
+        return f, w
+
+    def feature_blocks(self, indices):
+        """Whole feature blocks: -> (features [n, 512, C] f16, weights [n, 512] f32, found [n] bool) as numpy arrays; voxel t = vx 64 + vy 8 + vz."""
+        idx = np.ascontiguousarray(np.asarray(indices, np.int32).reshape(-1, 3))
+        ch = getattr(self, "feature_channels", 0)
+        f = np.zeros((idx.shape[0], 512, max(ch, 1)), np.float16); w = np.zeros((idx.shape[0], 512), np.float32)
+        found = np.zeros(idx.shape[0], np.int32)
+        self._check(self.lib.nvbx_get_feature_blocks(self._h, _np_ptr(idx), idx.shape[0], _np_ptr(f), _np_ptr(w), _np_ptr(found)))
+        return f, w, found.astype(bool)
 
     def mesh(self):
         """Mesh of the last update_color_mesh: dict block index tuple -> dict(vertices, normals, colors, triangles)."""

@@ -498,12 +498,39 @@ int nvbx_cast_rays_with(nvbx_mapper* m, const nvbx_render_options* options, cons
  *   fp16, weight_out [n][512] f32, found_out [n] (NULL: not written); pointer conventions of nvbx_get_blocks (host memory, synchronous).
  * All three carry held-back work out first (as nvbx_flush) and run in classic order on the mapper's stream; integrate and query are
  * asynchronous.  Before nvbx_enable_features they return NVBX_E_INVALID.  Not covered: map files, mesh vertices, multi-GPU exchange,
- * batches, LiDAR, nvbx_device_view. */
+ * batches, LiDAR, nvbx_device_view.  Scoring the layer against query embeddings: "feature matching" below. */
 int nvbx_enable_features(nvbx_mapper* m, int32_t channels);
 int nvbx_integrate_features(nvbx_mapper* m, const void* feat_dev, int32_t rows_f, int32_t cols_f, int32_t stride, const float T_L_C[16],
                             const nvbx_camera* camera);
 int nvbx_query_features(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, void* feat_out_dev, float* weight_out_dev);
 int nvbx_get_feature_blocks(nvbx_mapper* m, const nvbx_index3d* idx, int64_t n, void* feat_out, float* weight_out, int32_t* found_out);
+
+/* ---- feature matching (open-vocabulary search over the feature layer; SEMANTICS.md "Feature matching") -------------------------------
+ * Scores feature voxels against Q query embeddings on the matrix cores, without moving the layer anywhere.
+ * Common to both calls: queries_dev = [Q][C] fp16, row-major, 16-byte aligned device memory, C = the layer's channel count, 1 <= Q <= 128.
+ *   NVBX_MATCH_DOT:    s(v, q) = sum_c f_v[c] q[c] -- the fp16 products are exact in f32, the sum is in f32 in the order the matrix instruction takes it.
+ *   NVBX_MATCH_COSINE: dot / sqrt(|f_v|^2 |q|^2), the norms summed in f32; 0 where either norm is 0.
+ *   Scores are NOT bit-specified (the library's only such output).  The contract is an error bound against exact arithmetic on the stored fp16
+ *   values: dot within C 2^-23 sum_c |f_c q_c| (+ the products that have an fp16-subnormal factor, which the hardware may take as 0), cosine within
+ *   (C + 16) 2^-23.
+ *   Both carry held-back work out first (as nvbx_flush), run in classic order on the mapper's stream, are asynchronous and write nothing to the map.
+ *   NVBX_E_INVALID (nvbx_last_error set, the mapper stays usable): before nvbx_enable_features; Q outside 1 .. 128; an unknown metric; a NULL or
+ *   misaligned queries_dev; a NULL required output while capacity_blocks / n is above 0 (count_dev is always required).
+ * nvbx_match_features: every block that carries features, one entry per block, entry order unspecified.  block_idx_dev[e] = the block's index;
+ *   label_dev[e][512], score_dev[e][512] in the public voxel order t = vx 64 + vy 8 + vz.  A voxel counts when its weight is > 0 and >= min_weight:
+ *   label = the query with the highest score (a tie: the lowest query index), score = that score; a voxel that does not count: label -1, score 0.
+ *   all_scores_dev: NULL, or [e][512][Q] f32 (0 for voxels that do not count).  *count_dev = the number of feature blocks in the map, also when it
+ *   exceeds capacity_blocks; entries at capacity_blocks and beyond are written nowhere; capacity_blocks 0 with NULL outputs only counts.
+ * nvbx_match_points: the voxel that contains each point (nvbx_query_features' rule: floor(p / voxel_size) per axis); scores_dev [n][Q],
+ *   weight_dev [n] = nvbx_query_features' weight.  Weight 0 and zero scores -- never an error -- where nvbx_query_features returns weight 0.
+ *   n == 0 launches nothing.  Chained behind nvbx_cast_rays / nvbx_render_view it gives a relevance image of the map from any pose. */
+#define NVBX_MATCH_DOT    0
+#define NVBX_MATCH_COSINE 1
+int nvbx_match_features(nvbx_mapper* m, const void* queries_dev, int32_t n_queries, int32_t metric, float min_weight,
+                        nvbx_index3d* block_idx_dev, int32_t* label_dev, float* score_dev, float* all_scores_dev,
+                        int64_t capacity_blocks, int64_t* count_dev);
+int nvbx_match_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const void* queries_dev, int32_t n_queries,
+                      int32_t metric, float* scores_dev, float* weight_dev);
 
 /* ---- map file (Mapper::saveLayerCake(path) -> bool, loadMap(path) -> bool: nvblox_node.cpp:1663-1668,1698-1703) -----------------
  * A path ending in .nvblx is written as an SQLITE database, like the reference's layer cake: table layers(layer_type, voxel_size,

@@ -175,6 +175,8 @@ SIGNATURES = {
     "nvbx_integrate_features": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, C.POINTER(Camera)]),
     "nvbx_query_features": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "nvbx_get_feature_blocks": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "nvbx_match_features": (C.c_int, [_vp, _vp, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "nvbx_match_points": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),
     "nvbx_block_indices": (_i64, [_vp, C.c_uint32, _vp, _i64]),
     "nvbx_get_block": (C.c_int, [_vp, C.c_uint32, Index3D, _vp]),

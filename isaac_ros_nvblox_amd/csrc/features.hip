@@ -22,10 +22,9 @@
 #include <cstring>
 #include "nvbx_mapper.h"
 #include "nvbx_sphere_trace.h"
+#include "nvbx_feature.h"      // half8, feature_voxel_of
 
 using namespace nvbx;
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));      // one chunk: 8 channels, 16 bytes
 
 struct FeatTraceArgs { FrameCore f; float* synth; int32_t srows, scols, max_steps; float max_len, eps_m; };
 struct FeatArgs {
@@ -194,14 +193,6 @@ __global__ __launch_bounds__(512) void k_integrate_features(DMap m, FeatArgs a) 
 }
 
 // ---- readers
-// voxel that contains p: floor(p / vs) per axis (the renderer's colour rule); false: not finite / outside the addressable range
-__device__ inline bool feature_voxel_of(float px, float py, float pz, float vs, int32_t* g) {
-  const float fx = floorf(NVBX_DIV(px, vs)), fy = floorf(NVBX_DIV(py, vs)), fz = floorf(NVBX_DIV(pz, vs));
-  const float L = 8388608.0f;      // 2^20 blocks x 8 voxels
-  if (!(fx >= -L && fx < L && fy >= -L && fy < L && fz >= -L && fz < L)) return false;      // (a NaN fails every comparison)
-  g[0] = (int32_t)fx; g[1] = (int32_t)fy; g[2] = (int32_t)fz;
-  return true;
-}
 // one lane per (point, chunk): the nch lanes of a point write its C halfs as consecutive 16-B stores
 __global__ __launch_bounds__(256) void k_query_features(DMap m, const half8* __restrict__ val, const float* __restrict__ w, int32_t nch, const float* __restrict__ pts,
                                                         int64_t n, float vs, half8* __restrict__ feat_out, float* __restrict__ w_out) {

@@ -861,6 +861,86 @@ class Mapper:
         self._check(self.lib.nvbx_get_feature_blocks(self._h, _np_ptr(idx), idx.shape[0], _np_ptr(f), _np_ptr(w), _np_ptr(found)))
         return f, w, found.astype(bool)
 
+    # -- feature matching (nvbx_match_features / nvbx_match_points; SEMANTICS.md "Feature matching")
+    _METRICS = {"dot": 0, "cosine": 1}
+
+    def _queries(self, queries, metric):
+        """-> (fp16 [Q, C] tensor on the mapper's device, Q, metric id)"""
+        torch = self._torch
+        if metric not in self._METRICS:
+            raise ValueError("metric must be 'dot' or 'cosine', got %r" % (metric,))
+        if not isinstance(queries, torch.Tensor):
+            queries = np.asarray(queries)
+        if queries.dtype not in (torch.float16, np.float16) or len(queries.shape) != 2:
+            raise ValueError("queries must be a (Q, C) float16 array, got %s %s" % (tuple(queries.shape), queries.dtype))
+        q = self._dev(queries, torch.float16)
+        ch = getattr(self, "feature_channels", 0)      # (0: not enabled -- the library refuses the call)
+        if ch and q.shape[1] != ch:
+            raise NvbxError("queries have %d channels, the layer %d (enable_features)" % (q.shape[1], ch))
+        return q, int(q.shape[0]), self._METRICS[metric]
+
+    def match_features(self, queries, metric="cosine", min_weight=1.0, all_scores=False, out=None):
+        """Score every feature voxel of the map against `queries` ((Q, C) torch.float16 device tensor or numpy float16 array, Q <= 128):
+        -> (indices [n, 3] i32, labels [n, 512] i32, scores [n, 512] f32, all [n, 512, Q] f32 | None) on the mapper's device, one entry per feature
+        block in no particular order, voxel t = vx 64 + vy 8 + vz.  label = the best query of a voxel whose weight is > 0 and >= min_weight (a tie:
+        the lowest index), score = its score; -1 and 0 elsewhere.  Buffers are sized from block_indices(LAYER_FEATURE); the call waits once for the count.
+        out=(indices, labels, scores, all | None, count): preallocated tensors of any capacity n_cap (count: one int64), nothing is allocated and
+        nothing waited for: -> (indices, labels, scores, all | None, count) untrimmed; count (a device tensor) may exceed n_cap, entries from n_cap on
+        are not written; `out` then decides whether the score matrix is computed and the all_scores flag is not looked at."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        q, nq, mid = self._queries(queries, metric)
+        if out is None:
+            cap = self.num_blocks(LAYER_FEATURE)
+            idx = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+            lab = torch.empty((cap, 512), dtype=torch.int32, device=dev)
+            sc = torch.empty((cap, 512), dtype=torch.float32, device=dev)
+            al = torch.empty((cap, 512, nq), dtype=torch.float32, device=dev) if all_scores else None
+            cnt = torch.empty(1, dtype=torch.int64, device=dev)
+        else:
+            idx, lab, sc, al, cnt = out
+            cap = int(idx.shape[0])
+            self._out_tensor(idx, (cap, 3), (torch.int32,), "indices")
+            self._out_tensor(lab, (cap, 512), (torch.int32,), "labels")
+            self._out_tensor(sc, (cap, 512), (torch.float32,), "scores")
+            if al is not None:
+                self._out_tensor(al, (cap, 512, nq), (torch.float32,), "all scores")
+            self._out_tensor(cnt, (1,), (torch.int64,), "count")
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
+        self._around_torch_stream(lambda: self.lib.nvbx_match_features(
+            self._h, C.c_void_p(q.data_ptr()), nq, mid, float(min_weight), ptr(idx), ptr(lab), ptr(sc), ptr(al), cap, C.c_void_p(cnt.data_ptr())))
+        self._hold("_keep_mq", [q])      # (the kernel reads the queries: they, and an uploaded copy, live until the next match)
+        if out is not None:
+            return idx, lab, sc, al, cnt
+        n = min(int(cnt.item()), cap)
+        return idx[:n], lab[:n], sc[:n], (al[:n] if al is not None else None)
+
+    def match_points(self, points, queries, metric="cosine", out=None):
+        """Score the feature voxel that contains each of `points` ((n, 3) float32 torch tensor or numpy array, metres) against `queries`:
+        -> (scores [n, Q] f32, weights [n] f32) on the mapper's device; weight 0 and zero scores where query_features would return weight 0.
+        out=(scores, weights): preallocated tensors, nothing is allocated."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        q, nq, mid = self._queries(queries, metric)
+        if isinstance(points, torch.Tensor):
+            p = (points if points.device == dev else points.to(dev)).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
+        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError("points must be an (n, 3) float32 array, got %s %s" % (tuple(p.shape), p.dtype))
+        n = p.shape[0]
+        if out is None:
+            s = torch.empty((n, nq), dtype=torch.float32, device=dev)
+            w = torch.empty(n, dtype=torch.float32, device=dev)
+        else:
+            s, w = out
+            self._out_tensor(s, (n, nq), (torch.float32,), "scores")
+            self._out_tensor(w, (n,), (torch.float32,), "weights")
+        self._around_torch_stream(lambda: self.lib.nvbx_match_points(
+            self._h, C.c_void_p(p.data_ptr()), n, C.c_void_p(q.data_ptr()), nq, mid, C.c_void_p(s.data_ptr()), C.c_void_p(w.data_ptr())), order=n > 0)
+        self._hold("_keep_mp", [p, q])
+        return s, w
+
     def mesh(self):
         """Mesh of the last update_color_mesh: dict block index tuple -> dict(vertices, normals, colors, triangles)."""
         nb, nv, nt = C.c_int64(), C.c_int64(), C.c_int64()

@@ -532,6 +532,49 @@ int nvbx_match_features(nvbx_mapper* m, const void* queries_dev, int32_t n_queri
 int nvbx_match_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const void* queries_dev, int32_t n_queries,
                       int32_t metric, float* scores_dev, float* weight_dev);
 
+/* ---- feature segmentation (from matched voxels to a table of 3-D objects; SEMANTICS.md "Feature segmentation") ----------------------
+ * nvbx_label_components: connected components of a labelled sparse voxel volume of the shape nvbx_match_features returns -- one entry per
+ *   block, distinct block indices in any order, label_dev[e][512] / score_dev[e][512] in the public voxel order t = vx 64 + vy 8 + vz; a label
+ *   < 0 is background.  Two voxels are adjacent when their GLOBAL voxel coordinates g = 8 block + v differ by at most 1 on every axis
+ *   (connectivity 26) or by exactly 1 on exactly one axis (6), across block borders too; a block that is not in the list separates what lies on
+ *   either side of it.  A component is a maximal set of voxels of one label >= 0 connected through adjacent voxels of that label.
+ *   component_id_dev[e][512] = the component's index in [0, *count_dev) for every voxel of a component of at least min_voxels voxels, -1 for
+ *   background and for smaller components; components_dev[index] = its record.  Index order is unspecified; volume and table agree.
+ *   *count_dev = the number of kept components, also when it exceeds capacity_components; records from the capacity on are written nowhere
+ *   (the id volume still carries their indices); capacity 0 with a NULL table only counts and labels.  Every record field is an integer, or a
+ *   maximum / comparison of stored floats: apart from the index order the result is bit-specified.  Scores compare as floats (-0 as +0, a NaN
+ *   as -infinity); without scores (NULL) every score is 0 and peak_xyz is the component's lowest voxel.
+ *   n_blocks_dev: NULL, or a device count -- min(n_blocks, *n_blocks_dev) entries are read, the entries behind them neither read nor written.
+ *   The call reads nothing from the map, carries out no held-back work and is asynchronous on the mapper's stream.  Its scratch (about 4.1 KiB
+ *   per entry) belongs to the mapper and grows on demand: the first call and every call with more entries than any before allocate (and wait
+ *   for the stream once).  NVBX_E_INVALID (nvbx_last_error set, nothing launched, the mapper stays usable): connectivity other than 6 / 26;
+ *   min_voxels < 1; n_blocks < 0 or > 2^22 (voxel ids are int32); a NULL block_idx_dev / label_dev / component_id_dev while n_blocks > 0; a
+ *   NULL count_dev; capacity_components < 0, or > 0 with a NULL or not 8-byte aligned components_dev.  n_blocks == 0 writes a count of 0 and
+ *   launches nothing else.  A repeated block index is a precondition violation: the result is still a valid partition, which copy the
+ *   neighbours see is unspecified.  Record fields of blocks outside the addressable index range (nvbx_index3d) are unspecified.
+ * nvbx_segment_features: queries in, objects out -- nvbx_match_features without the score matrix, then the threshold, then
+ *   nvbx_label_components over min(*block_count_dev, capacity_blocks) entries (read on the device), all in stream order without a host wait.
+ *   Threshold, in place: where score < min_score_dev[label] (f32; a NaN threshold drops nothing) label becomes -1 and score 0;
+ *   min_score_dev: [Q] device floats, or NULL for no threshold.  Refusals: those of both calls (capacity_blocks takes n_blocks' part);
+ *   held-back work is handled as in nvbx_match_features. */
+typedef struct {
+  int32_t label;          /* the common label of its voxels, >= 0 */
+  int32_t voxels;         /* how many */
+  int32_t min_xyz[3];     /* box in global voxel coordinates g = 8 block + v, inclusive */
+  int32_t max_xyz[3];
+  int64_t sum_xyz[3];     /* sum of g over its voxels: centroid = (sum / voxels + 0.5) voxel_size */
+  float   peak_score;     /* highest score among its voxels (0 without scores) */
+  int32_t peak_xyz[3];    /* global voxel of that score; a tie: the lexicographically lowest (x, then y, then z) */
+} nvbx_component;         /* 72 bytes, 8-byte aligned; offsets 0 4 8 20 32 56 60 */
+int nvbx_label_components(nvbx_mapper* m, const nvbx_index3d* block_idx_dev, const int32_t* label_dev, const float* score_dev,
+                          int64_t n_blocks, const int64_t* n_blocks_dev, int32_t connectivity, int32_t min_voxels,
+                          int32_t* component_id_dev, nvbx_component* components_dev, int64_t capacity_components, int64_t* count_dev);
+int nvbx_segment_features(nvbx_mapper* m, const void* queries_dev, int32_t n_queries, int32_t metric, float min_weight,
+                          const float* min_score_dev, int32_t connectivity, int32_t min_voxels, nvbx_index3d* block_idx_dev,
+                          int32_t* label_dev, float* score_dev, int32_t* component_id_dev, int64_t capacity_blocks,
+                          int64_t* block_count_dev, nvbx_component* components_dev, int64_t capacity_components,
+                          int64_t* component_count_dev);
+
 /* ---- map file (Mapper::saveLayerCake(path) -> bool, loadMap(path) -> bool: nvblox_node.cpp:1663-1668,1698-1703) -----------------
  * A path ending in .nvblx is written as an SQLITE database, like the reference's layer cake: table layers(layer_type, voxel_size,
  * block_size, voxel_bytes, num_blocks) + one table <layer_type>_blocks(index_x, index_y, index_z, data BLOB) per layer (tsdf_layer,

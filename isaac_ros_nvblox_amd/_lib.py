@@ -96,6 +96,12 @@ class Index3D(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32)]
 
 
+class Component(C.Structure):
+    """nvbx_component: one connected component of nvbx_label_components / nvbx_segment_features (72 bytes)"""
+    _fields_ = [("label", C.c_int32), ("voxels", C.c_int32), ("min_xyz", C.c_int32 * 3), ("max_xyz", C.c_int32 * 3),
+                ("sum_xyz", C.c_int64 * 3), ("peak_score", C.c_float), ("peak_xyz", C.c_int32 * 3)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("table", C.c_void_p), ("table_mask", C.c_uint32), ("table_shift", C.c_uint32), ("slot_flags", C.c_void_p),
                 ("slot_index", C.c_void_p), ("tsdf", C.c_void_p), ("color", C.c_void_p), ("esdf", C.c_void_p),
@@ -177,6 +183,8 @@ SIGNATURES = {
     "nvbx_get_feature_blocks": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "nvbx_match_features": (C.c_int, [_vp, _vp, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i64, _vp]),
     "nvbx_match_points": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
+    "nvbx_label_components": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "nvbx_segment_features": (C.c_int, [_vp, _vp, _i32, _i32, _f, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),
     "nvbx_block_indices": (_i64, [_vp, C.c_uint32, _vp, _i64]),
     "nvbx_get_block": (C.c_int, [_vp, C.c_uint32, Index3D, _vp]),

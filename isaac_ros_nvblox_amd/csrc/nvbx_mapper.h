@@ -123,6 +123,8 @@ struct nvbx_mapper {
   // the last feature frame -- the colour path's `synth` stays the last colour frame's.
   void* feat_val = nullptr; float* feat_w = nullptr; int32_t feat_channels = 0;
   nvbx::DevBuf feat_synth;
+  // feature segmentation (segment.hip): the entry table, parent[n][512] and count[n][512] of the largest block list labelled so far
+  nvbx::DevBuf seg_scratch;
   // mesh arena
   float* mesh_vert = nullptr; float* mesh_nrm = nullptr; uint8_t* mesh_col = nullptr; int32_t* mesh_tri = nullptr;
   nvbx::MeshRecord* mesh_rec = nullptr;

@@ -4,6 +4,7 @@ Method names follow the reference call sites (nvblox_ros/src/lib/nvblox_node.cpp
 layer_publishing.cpp:686-689).  Images are torch CUDA tensors (device memory, like the reference's
 MemoryType::kDevice images) or numpy arrays (uploaded first).
 """
+import collections
 import ctypes as C
 import os
 import numpy as np
@@ -13,6 +14,11 @@ from ._lib import BoundingShape, Camera, Counters, Index3D, Lidar, Params
 
 LAYER_TSDF, LAYER_COLOR, LAYER_ESDF, LAYER_MESH, LAYER_OCCUPANCY, LAYER_FREESPACE = 1, 2, 4, 8, 16, 32
 LAYER_FEATURE = 64
+
+# nvbx_component (label_components / segment_features): the fields of a record table as tensors that view it, one row per component; centroid_m is
+# derived -- (sum_xyz / voxels + 0.5) voxel_size, float64 metres.  A record is COMPONENT_WORDS int32 words (72 bytes).
+Components = collections.namedtuple("Components", "label voxels min_xyz max_xyz sum_xyz peak_score peak_xyz centroid_m")
+COMPONENT_WORDS = C.sizeof(_lib.Component) // 4
 
 TSDF_DT = np.dtype([("distance", "<f4"), ("weight", "<f4")])
 COLOR_DT = np.dtype([("r", "u1"), ("g", "u1"), ("b", "u1"), ("pad", "u1"), ("weight", "<f4")])
@@ -940,6 +946,135 @@ class Mapper:
             self._h, C.c_void_p(p.data_ptr()), n, C.c_void_p(q.data_ptr()), nq, mid, C.c_void_p(s.data_ptr()), C.c_void_p(w.data_ptr())), order=n > 0)
         self._hold("_keep_mp", [p, q])
         return s, w
+
+    # -- feature segmentation (nvbx_label_components / nvbx_segment_features; SEMANTICS.md "Feature segmentation")
+    def component_records(self, capacity):
+        """An uninitialised table of `capacity` nvbx_component records for out=: an int32 [capacity, 18] device tensor (72 bytes a record)."""
+        torch = self._torch
+        return torch.empty((int(capacity), COMPONENT_WORDS), dtype=torch.int32, device=torch.device("cuda", self.device))
+
+    def components_view(self, records, n=None, centroid=True):
+        """The fields of a record table (component_records) as device tensors viewing it, trimmed to the first n records: -> Components.  centroid_m
+        = (sum / voxels + 0.5) voxel_size in float64 is the one field that is computed (and allocated), None with centroid=False."""
+        torch = self._torch
+        r = records if n is None else records[:n]
+        sums = r[:, 8:14].view(torch.int64)
+        voxels = r[:, 1]
+        cm = (sums.double() / voxels.double()[:, None] + 0.5) * float(self.params.voxel_size) if centroid else None
+        return Components(r[:, 0], voxels, r[:, 2:5], r[:, 5:8], sums, r[:, 14:15].view(torch.float32)[:, 0], r[:, 15:18], cm)
+
+    def _volume(self, a, dtype, what):
+        """-> a contiguous [n, 512] tensor of `dtype` on the mapper's device"""
+        torch = self._torch
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+        if a.dtype != dtype or a.dim() != 2 or a.shape[1] != 512:
+            raise ValueError("%s must be an (n, 512) %s array, got %s %s" % (what, dtype, tuple(a.shape), a.dtype))
+        return self._dev(a, dtype)
+
+    @staticmethod
+    def _segment_options(connectivity, min_voxels):
+        if connectivity not in (6, 26):
+            raise ValueError("connectivity must be 6 or 26, got %r" % (connectivity,))
+        if int(min_voxels) < 1:
+            raise ValueError("min_voxels must be >= 1, got %r" % (min_voxels,))
+        return int(connectivity), int(min_voxels)
+
+    def _records_out(self, rec, cnt):
+        torch = self._torch
+        if rec is not None:
+            self._out_tensor(rec, (int(rec.shape[0]), COMPONENT_WORDS), (torch.int32,), "components")
+        self._out_tensor(cnt, (1,), (torch.int64,), "count")
+
+    def label_components(self, indices, labels, scores=None, connectivity=6, min_voxels=1, out=None):
+        """Connected components of a labelled sparse voxel volume of the shape match_features returns: indices (n, 3) int32 distinct block indices,
+        labels (n, 512) int32 (< 0: background), scores (n, 512) float32 or None -- torch device tensors or numpy arrays, voxel t = vx 64 + vy 8 + vz.
+        Voxels are adjacent across faces (connectivity 6) or faces, edges and corners (26) of the GLOBAL voxel grid, block borders included; a block
+        that is not listed separates its sides.  -> (ids [n, 512] i32: the component's row in the table, -1 for background and for components of fewer
+        than min_voxels voxels; Components, one row per kept component in no particular order) on the mapper's device.  The table is sized for the
+        worst case (n 512 / min_voxels records of 72 bytes), the call waits once for the count.  Reads nothing from the map.
+        out=(ids, records | None, count): preallocated tensors (records: component_records(capacity), count: one int64), nothing is allocated and
+        nothing waited for: -> (ids, records, count) as given; count (a device tensor) may exceed the capacity, records from the capacity on are
+        not written (ids still name them); components_view(records) gives the fields."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        conn, mv = self._segment_options(connectivity, min_voxels)
+        if not isinstance(indices, torch.Tensor):
+            indices = torch.from_numpy(np.ascontiguousarray(np.asarray(indices, np.int32).reshape(-1, 3)))
+        if indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[1] != 3:
+            raise ValueError("indices must be an (n, 3) int32 array, got %s %s" % (tuple(indices.shape), indices.dtype))
+        idx = self._dev(indices, torch.int32)
+        lab = self._volume(labels, torch.int32, "labels")
+        sc = self._volume(scores, torch.float32, "scores") if scores is not None else None
+        n = int(idx.shape[0])
+        if lab.shape[0] != n or (sc is not None and sc.shape[0] != n):
+            raise ValueError("indices, labels and scores differ in their number of blocks")
+        if out is None:
+            ids = torch.empty((n, 512), dtype=torch.int32, device=dev)
+            rec = self.component_records(n * 512 // mv)
+            cnt = torch.empty(1, dtype=torch.int64, device=dev)
+        else:
+            ids, rec, cnt = out
+            self._out_tensor(ids, (n, 512), (torch.int32,), "ids")
+            self._records_out(rec, cnt)
+        cap = int(rec.shape[0]) if rec is not None else 0
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
+        self._around_torch_stream(lambda: self.lib.nvbx_label_components(
+            self._h, ptr(idx), ptr(lab), ptr(sc), n, None, conn, mv, ptr(ids), ptr(rec), cap, C.c_void_p(cnt.data_ptr())))
+        self._hold("_keep_lc", [idx, lab, sc])      # (the kernels read the volume: it, and an uploaded copy, live until the next call)
+        if out is not None:
+            return ids, rec, cnt
+        return ids, self.components_view(rec, min(int(cnt.item()), cap))
+
+    def segment_features(self, queries, metric="cosine", min_weight=1.0, min_score=None, connectivity=6, min_voxels=1, out=None):
+        """From query embeddings to 3-D objects in one call: match_features without the score matrix, then a threshold (where score <
+        min_score[label] the voxel becomes background: label -1, score 0; min_score: None, a float for all queries, or a length-Q float32 array /
+        device tensor; a NaN drops nothing), then label_components over the result.  -> (indices [n, 3] i32, labels [n, 512] i32, scores [n, 512] f32,
+        ids [n, 512] i32, Components) on the mapper's device, trimmed; buffers are sized from block_indices(LAYER_FEATURE) and the worst-case
+        component count, the call waits once for the two counts.
+        out=(indices, labels, scores, ids, block_count, records | None, component_count): preallocated tensors of any capacities (the counts: one
+        int64 each), nothing is allocated -- give min_score as a device tensor -- and nothing waited for: -> the same tuple, untrimmed."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        conn, mv = self._segment_options(connectivity, min_voxels)
+        q, nq, mid = self._queries(queries, metric)
+        if min_score is None:
+            thr = None
+        elif isinstance(min_score, torch.Tensor):
+            thr = self._dev(min_score.reshape(-1), torch.float32)
+        else:
+            thr = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, np.float32).reshape(-1), (nq,)))).to(dev)
+        if thr is not None and tuple(thr.shape) != (nq,):
+            raise ValueError("min_score must be a number or hold one value per query (%d), got %s" % (nq, tuple(thr.shape)))
+        if out is None:
+            cap = self.num_blocks(LAYER_FEATURE)
+            idx = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+            lab = torch.empty((cap, 512), dtype=torch.int32, device=dev)
+            sc = torch.empty((cap, 512), dtype=torch.float32, device=dev)
+            ids = torch.empty((cap, 512), dtype=torch.int32, device=dev)
+            rec = self.component_records(cap * 512 // mv)
+            both = torch.empty(2, dtype=torch.int64, device=dev)
+            bcnt, ccnt = both[0:1], both[1:2]
+        else:
+            idx, lab, sc, ids, bcnt, rec, ccnt = out
+            cap = int(idx.shape[0])
+            self._out_tensor(idx, (cap, 3), (torch.int32,), "indices")
+            self._out_tensor(lab, (cap, 512), (torch.int32,), "labels")
+            self._out_tensor(sc, (cap, 512), (torch.float32,), "scores")
+            self._out_tensor(ids, (cap, 512), (torch.int32,), "ids")
+            self._out_tensor(bcnt, (1,), (torch.int64,), "block count")
+            self._records_out(rec, ccnt)
+        ccap = int(rec.shape[0]) if rec is not None else 0
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
+        self._around_torch_stream(lambda: self.lib.nvbx_segment_features(
+            self._h, C.c_void_p(q.data_ptr()), nq, mid, float(min_weight), ptr(thr), conn, mv, ptr(idx), ptr(lab), ptr(sc), ptr(ids), cap,
+            C.c_void_p(bcnt.data_ptr()), ptr(rec), ccap, C.c_void_p(ccnt.data_ptr())))
+        self._hold("_keep_sq", [q, thr])      # (the kernels read the queries and thresholds: they live until the next call)
+        if out is not None:
+            return idx, lab, sc, ids, bcnt, rec, ccnt
+        nb, nc = (int(v) for v in both.tolist())
+        nb = min(nb, cap)
+        return idx[:nb], lab[:nb], sc[:nb], ids[:nb], self.components_view(rec, min(nc, ccap))
 
     def mesh(self):
         """Mesh of the last update_color_mesh: dict block index tuple -> dict(vertices, normals, colors, triangles)."""

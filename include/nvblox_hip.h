@@ -598,6 +598,74 @@ int nvbx_backproject_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows,
  * out == in; asynchronous on the mapper's stream) */
 int nvbx_transform_pointcloud(nvbx_mapper* m, const float T_L_C[16], const float* points_in_dev, int64_t n_points, float* points_out_dev);
 
+/* ---- pose alignment ([U] frame-to-model refinement against the TSDF; SEMANTICS.md "Pose alignment") ---------------------------------
+ * Refines a sensor pose so that the sensor's points lie on the TSDF's zero level: Gauss-Newton on sum w r^2 with r = the trilinear TSDF
+ * interpolant of nvbx_query_points at T x and its analytic gradient.  A refinement from a guess within the truncation band, not a
+ * relocalisation.  The pose is held in f64 on the device; every iteration is an accumulate launch (one lane per point, 29 f64 sums, a
+ * fixed reduction order: bit-identical from run to run) and a one-workgroup solve launch (6 x 6 Cholesky, exponential map, pose update,
+ * status).  All launches of a call are enqueued at once on the mapper's stream: no host wait, the launches behind a final status
+ * return at once.  The calls read TSDF voxels only and leave held-back work held back (as a TSDF nvbx_query_points does).
+ * One linearization at T, over the n sensor-frame points x: Tf = T rounded to f32; p = Tf x in nvbx_transform_pointcloud's f32
+ * arithmetic; (d, g, valid) = nvbx_query_points(TSDF, min_weight) at p; then in f64 r = d, q = p - Tf.t, J = [g, q x g],
+ * w = 1 if huber_delta_m <= 0 or |r| <= huber_delta_m else huber_delta_m / |r|; over the valid points H += (w J) J^T (upper triangle,
+ * row-major: 21 numbers), b += (w J) r, cost += (w r) r, n_valid += 1.
+ * One step: (H + damping diag(H)) xi = -b by Cholesky, xi = (v, omega); R <- exp([omega]x) R, t <- t + V(omega) v.
+ * Status: NVBX_ALIGN_TOO_FEW when n_valid < min_valid, NVBX_ALIGN_DEGENERATE when a pivot is <= min_pivot_ratio x max diag(H) -- neither
+ * applies a step, a failure in the first iteration returns the guess bit for bit; NVBX_ALIGN_CONVERGED after an applied step with
+ * |v| <= stop_translation_m and |omega| <= stop_rotation_rad; NVBX_ALIGN_MAX_ITERATIONS after max_iterations linearizations. */
+#define NVBX_ALIGN_CONVERGED      1
+#define NVBX_ALIGN_MAX_ITERATIONS 2
+#define NVBX_ALIGN_TOO_FEW        3
+#define NVBX_ALIGN_DEGENERATE     4
+#define NVBX_ALIGN_LINEARIZED     5   /* nvbx_linearize_points: one linearization, a solvable system, no step applied */
+typedef struct {
+  int32_t max_iterations;       /* 1 .. 64 linearizations */
+  int32_t subsampling;          /* nvbx_align_depth: pixels (r s, c s); >= 1 */
+  float   min_weight;           /* a TSDF corner counts with weight >= this */
+  float   huber_delta_m;        /* <= 0: plain least squares */
+  double  damping;              /* >= 0: (H + damping diag(H)) */
+  double  min_pivot_ratio;      /* >= 0 */
+  double  stop_translation_m;
+  double  stop_rotation_rad;
+  int32_t min_valid;            /* >= 1 */
+  float   max_depth_m;          /* nvbx_align_depth: pixels with 0 < depth <= this; <= 0: no limit */
+} nvbx_align_options;           /* 56 bytes; offsets 0 4 8 12 16 24 32 40 48 52 */
+typedef struct {
+  double  H[21];                /* upper triangle, row-major */
+  double  b[6];
+  double  cost;                 /* sum w r^2 */
+  int32_t n_valid;
+  int32_t pad;
+} nvbx_align_sums;              /* 232 bytes */
+typedef struct {
+  float   T_L_S[16];            /* the refined pose, row-major 4 x 4, rounded to f32 */
+  double  T64[16];              /* the same in f64 */
+  double  step[6];              /* the last step solved for, (v, omega); 0 where none was */
+  nvbx_align_sums first;        /* the sums of the first linearization (at the guess) ... */
+  nvbx_align_sums last;         /* ... and of the last one (the pose it was taken at: T64 before the last applied step) */
+  int32_t iterations;           /* linearizations carried out */
+  int32_t status;               /* NVBX_ALIGN_* */
+} nvbx_align_result;            /* 712 bytes, 8-byte aligned DEVICE memory; offsets 0 64 192 240 472 704 708 */
+/* defaults: 10 iterations, subsampling 4, min_weight 1e-4, huber 0, damping 0, min_pivot_ratio 1e-9, stop 1e-5 m / 1e-5 rad, min_valid 50, no depth limit */
+void nvbx_default_align_options(nvbx_align_options* options);
+/* nvbx_align_points: any sensor-frame cloud points_xyz_dev[n][3] (LiDAR included), from T_L_S_guess (row-major 4 x 4, host memory).
+ * nvbx_align_depth: the pixels (r s, c s) of depth_dev[rows][cols] with 0 < depth <= max_depth_m, back-projected with
+ *   nvbx_backproject_depth's arithmetic inside the launch; no point buffer is written.
+ * nvbx_linearize_points: one linearization at T_L_S, no step is applied (result: T = T_L_S, step = what the solve gives, first = last,
+ *   iterations 1, status TOO_FEW / DEGENERATE / LINEARIZED); optional per-point outputs (NULL: not written): points_L_dev[n][3],
+ *   residual_dev[n], gradient_dev[n][3], valid_dev[n] -- bit for bit nvbx_transform_pointcloud and nvbx_query_points (unknown_value 0).
+ * options NULL: the defaults.  result_dev: 8-byte aligned device memory, written by the launches.  Asynchronous on the mapper's stream.
+ * n == 0: NVBX_ALIGN_TOO_FEW, the accumulate launch is skipped.  NVBX_E_INVALID (nvbx_last_error set, nothing launched, the mapper stays
+ * usable): an occupancy mapper; a NULL mapper, pose, result or (n > 0) point / depth pointer; n < 0; a misaligned result_dev; a pose that is
+ * not finite or out of range; a camera that does not match the image; max_iterations outside 1 .. 64; subsampling < 1; min_valid < 1;
+ * damping / min_pivot_ratio / a stop threshold negative or not finite; min_weight, huber_delta_m or max_depth_m not a number. */
+int nvbx_align_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float T_L_S_guess[16], const nvbx_align_options* options,
+                      nvbx_align_result* result_dev);
+int nvbx_align_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const float T_L_C_guess[16], const nvbx_camera* camera,
+                     const nvbx_align_options* options, nvbx_align_result* result_dev);
+int nvbx_linearize_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float T_L_S[16], const nvbx_align_options* options,
+                          nvbx_align_result* result_dev, float* points_L_dev, float* residual_dev, float* gradient_dev, uint8_t* valid_dev);
+
 /* ---- mask splitting (human / people-segmentation mapping) ------------------------------------------------------------
  * [U] ImageMasker::splitImageOnGPU as used by MultiMapper::integrateDepth(depth, mask, T_L_CD, T_CM_CD, depth_cam, mask_cam) --
  * nvblox_node.cpp:1018-1060: every valid depth pixel is lifted to 3-D, moved into the mask camera (T_CM_CD = T_L_CM^-1 T_L_CD)

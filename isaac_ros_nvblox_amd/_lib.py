@@ -102,6 +102,24 @@ class Component(C.Structure):
                 ("sum_xyz", C.c_int64 * 3), ("peak_score", C.c_float), ("peak_xyz", C.c_int32 * 3)]
 
 
+class AlignOptions(C.Structure):
+    """nvbx_align_options (56 bytes); nvbx_default_align_options fills it"""
+    _fields_ = [("max_iterations", C.c_int32), ("subsampling", C.c_int32), ("min_weight", C.c_float), ("huber_delta_m", C.c_float),
+                ("damping", C.c_double), ("min_pivot_ratio", C.c_double), ("stop_translation_m", C.c_double), ("stop_rotation_rad", C.c_double),
+                ("min_valid", C.c_int32), ("max_depth_m", C.c_float)]
+
+
+class AlignSums(C.Structure):
+    """nvbx_align_sums: the 29 sums of one linearization (232 bytes)"""
+    _fields_ = [("H", C.c_double * 21), ("b", C.c_double * 6), ("cost", C.c_double), ("n_valid", C.c_int32), ("pad", C.c_int32)]
+
+
+class AlignResult(C.Structure):
+    """nvbx_align_result: what the alignment launches leave in DEVICE memory (712 bytes)"""
+    _fields_ = [("T_L_S", C.c_float * 16), ("T64", C.c_double * 16), ("step", C.c_double * 6), ("first", AlignSums), ("last", AlignSums),
+                ("iterations", C.c_int32), ("status", C.c_int32)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("table", C.c_void_p), ("table_mask", C.c_uint32), ("table_shift", C.c_uint32), ("slot_flags", C.c_void_p),
                 ("slot_index", C.c_void_p), ("tsdf", C.c_void_p), ("color", C.c_void_p), ("esdf", C.c_void_p),
@@ -185,6 +203,10 @@ SIGNATURES = {
     "nvbx_match_points": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
     "nvbx_label_components": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
     "nvbx_segment_features": (C.c_int, [_vp, _vp, _i32, _i32, _f, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "nvbx_default_align_options": (None, [C.POINTER(AlignOptions)]),
+    "nvbx_align_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp]),
+    "nvbx_align_depth": (C.c_int, [_vp, _vp, _i32, _i32, _vp, C.POINTER(Camera), C.POINTER(AlignOptions), _vp]),
+    "nvbx_linearize_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp, _vp, _vp, _vp, _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),
     "nvbx_block_indices": (_i64, [_vp, C.c_uint32, _vp, _i64]),
     "nvbx_get_block": (C.c_int, [_vp, C.c_uint32, Index3D, _vp]),

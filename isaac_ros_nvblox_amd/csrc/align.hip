@@ -1,0 +1,259 @@
+// align.hip -- frame-to-model pose refinement against the TSDF (nvbx_align_points / nvbx_align_depth / nvbx_linearize_points;
+// SEMANTICS.md "Pose alignment").  [U] KinectFusion's tracking step and voxblox's ICP refinement serve the same request;
+// nothing of the kind is readable in the reference tree.
+//
+// An iteration is two launches in stream order, and nothing waits for another workgroup inside a launch:
+//   k_align_accumulate  one lane = one sensor-frame point, grid-stride: transform (apply_rt, f32), the TSDF point query of k_query_points
+//                       (q_point, nvbx_query_point.h: the same inline code), then 29 f64 products per valid lane -- 21 of H, 6 of b, the cost and
+//                       the count -- summed in the lane, across the wavefront with shuffles, across the workgroup through LDS, all in a fixed
+//                       order; one store of 29 doubles into partial slot blockIdx.x.  Grid = min(ceil(n / 256), 256) workgroups of 256: a
+//                       function of n alone, so the sums are bit-identical from run to run.
+//   k_align_solve       one workgroup: the partials are summed per entry in a fixed order (eight groups of lanes take every eighth slot, then
+//                       the groups in order), lane 0 runs the Cholesky solve, the exponential map and the pose update (nvbx_align_math.h),
+//                       writes the f64 pose state, the status word and the caller's result record.
+// All max_iterations pairs are enqueued up front; the pose of iteration 0 and the options travel as kernel arguments, the pose of the later
+// ones is the state the previous solve left.  Once the status is final the remaining launches read it and return at once.
+#include <algorithm>
+#include <cmath>
+#include "nvbx_mapper.h"
+#include "nvbx_query_point.h"
+#include "nvbx_align_math.h"
+
+using namespace nvbx;
+
+constexpr int ALIGN_TERMS = 29;              // H 21, b 6, cost, n_valid
+constexpr int ALIGN_MAX_WG = 256, ALIGN_TPB = 256;
+enum { ALIGN_RUNNING = 0 };
+enum { MODE_ALIGN = 0, MODE_LINEARIZE = 1 };
+
+struct AlignState { double R[9], t[3]; int32_t status, iterations; };      // 104 bytes, at the front of nvbx_mapper::align_buf
+constexpr size_t ALIGN_PARTIAL_OFFSET = 128;
+constexpr size_t ALIGN_BUF_BYTES = ALIGN_PARTIAL_OFFSET + (size_t)ALIGN_MAX_WG * ALIGN_TERMS * sizeof(double);
+
+struct AlignArgs {
+  const float* pts;                                             // [n][3], or ...
+  const float* depth; int32_t cols, cs, s; float fu, fv, cu, cv, max_d;      // ... the pixels (r s, c s): n = rs x cs of them
+  int64_t n;
+  float R0[9], t0[3];                                           // the pose of iteration 0
+  int32_t iter, max_iter, mode, min_valid, nblocks;
+  float vs, min_weight;
+  double huber, damping, min_pivot, stop_t, stop_r;
+  AlignState* st; double* partial; nvbx_align_result* res;
+  float* out_p; float* out_r; float* out_g; uint8_t* out_v;     // per-point outputs of nvbx_linearize_points (each may be null)
+};
+
+template <bool DEPTH>
+__global__ __launch_bounds__(ALIGN_TPB) void k_align_accumulate(DMap m, AlignArgs a) {
+  __shared__ double s_part[ALIGN_TPB / 64][ALIGN_TERMS];
+  float R[9], t[3];
+  if (a.iter == 0) {
+    for (int k = 0; k < 9; k++) R[k] = a.R0[k];
+    for (int k = 0; k < 3; k++) t[k] = a.t0[k];
+  } else {
+    if (a.st->status != ALIGN_RUNNING) return;                  // (uniform: the whole grid leaves)
+    for (int k = 0; k < 9; k++) R[k] = (float)a.st->R[k];
+    for (int k = 0; k < 3; k++) t[k] = (float)a.st->t[k];
+  }
+  const uint2* pool = reinterpret_cast<const uint2*>(m.tsdf);
+  double acc[ALIGN_TERMS];
+#pragma unroll
+  for (int k = 0; k < ALIGN_TERMS; k++) acc[k] = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
+    float x[3];
+    if (DEPTH) {
+      const int32_t r = (int32_t)(i / a.cs) * a.s, c = (int32_t)(i % a.cs) * a.s;
+      const float d = a.depth[(int64_t)r * a.cols + c];
+      if (!backproject_takes(d, a.max_d)) continue;
+      backproject_pixel(r, c, d, a.fu, a.fv, a.cu, a.cv, x);
+    } else {
+      x[0] = a.pts[3 * i]; x[1] = a.pts[3 * i + 1]; x[2] = a.pts[3 * i + 2];
+    }
+    float p[3], g[3], d;
+    apply_rt(R, t, x[0], x[1], x[2], p);
+    const bool valid = q_point<Q_TSDF, false>(m, pool, p, a.vs, a.min_weight, 0.0f, 0, &d, g);
+    if (!DEPTH) {
+      if (a.out_p) { a.out_p[3 * i] = p[0]; a.out_p[3 * i + 1] = p[1]; a.out_p[3 * i + 2] = p[2]; }
+      if (a.out_r) a.out_r[i] = d;
+      if (a.out_g) { a.out_g[3 * i] = g[0]; a.out_g[3 * i + 1] = g[1]; a.out_g[3 * i + 2] = g[2]; }
+      if (a.out_v) a.out_v[i] = valid ? 1 : 0;
+    }
+    if (!valid) continue;
+    const double r = (double)d;
+    const double q[3] = {(double)p[0] - (double)t[0], (double)p[1] - (double)t[1], (double)p[2] - (double)t[2]};
+    const double gd[3] = {(double)g[0], (double)g[1], (double)g[2]};
+    const double J[6] = {gd[0], gd[1], gd[2], q[1] * gd[2] - q[2] * gd[1], q[2] * gd[0] - q[0] * gd[2], q[0] * gd[1] - q[1] * gd[0]};
+    const double ar = fabs(r);
+    const double w = (a.huber <= 0.0 || ar <= a.huber) ? 1.0 : a.huber / ar;
+    double wJ[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) wJ[k] = w * J[k];
+    int e = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+#pragma unroll
+      for (int l = k; l < 6; l++) { acc[e] = acc[e] + wJ[k] * J[l]; e++; }
+#pragma unroll
+    for (int k = 0; k < 6; k++) acc[21 + k] = acc[21 + k] + wJ[k] * r;
+    acc[27] = acc[27] + (w * r) * r;
+    acc[28] = acc[28] + 1.0;
+  }
+  // wavefront: lane l takes lane l + off, off = 32 .. 1; workgroup: the four wavefronts in order
+#pragma unroll
+  for (int k = 0; k < ALIGN_TERMS; k++) {
+    double v = acc[k];
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off);
+    acc[k] = v;
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < ALIGN_TERMS; k++) s_part[wave][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < ALIGN_TERMS) {
+    double v = s_part[0][threadIdx.x];
+    for (int wv = 1; wv < ALIGN_TPB / 64; wv++) v = v + s_part[wv][threadIdx.x];
+    a.partial[(size_t)blockIdx.x * ALIGN_TERMS + threadIdx.x] = v;
+  }
+}
+
+constexpr int SOLVE_TPB = 256, SOLVE_GROUPS = SOLVE_TPB / 32;
+__global__ __launch_bounds__(SOLVE_TPB) void k_align_solve(AlignArgs a) {
+  __shared__ double s_grp[SOLVE_GROUPS][32];
+  __shared__ double s_sum[ALIGN_TERMS];
+  if (a.iter > 0 && a.st->status != ALIGN_RUNNING) return;
+  // entry j of the partials: group g of 32 lanes takes the slots g, g + 8, .. in order (chains of at most 32 loads instead of one of 256), then the
+  // eight groups in order -- a fixed order again
+  const int j = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  double v = 0.0;
+  if (j < ALIGN_TERMS)
+    for (int32_t b = grp; b < a.nblocks; b += SOLVE_GROUPS) v = v + a.partial[(size_t)b * ALIGN_TERMS + j];
+  s_grp[grp][j] = v;
+  __syncthreads();
+  if (threadIdx.x < ALIGN_TERMS) {
+    double t = s_grp[0][threadIdx.x];
+    for (int g = 1; g < SOLVE_GROUPS; g++) t = t + s_grp[g][threadIdx.x];
+    s_sum[threadIdx.x] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double R[9], t[3];
+  if (a.iter == 0) {
+    for (int k = 0; k < 9; k++) R[k] = (double)a.R0[k];
+    for (int k = 0; k < 3; k++) t[k] = (double)a.t0[k];
+  } else {
+    for (int k = 0; k < 9; k++) R[k] = a.st->R[k];
+    for (int k = 0; k < 3; k++) t[k] = a.st->t[k];
+  }
+  nvbx_align_sums cur;
+  for (int k = 0; k < 21; k++) cur.H[k] = s_sum[k];
+  for (int k = 0; k < 6; k++) cur.b[k] = s_sum[21 + k];
+  cur.cost = s_sum[27]; cur.n_valid = (int32_t)s_sum[28]; cur.pad = 0;
+  double xi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int32_t status = ALIGN_RUNNING;
+  if (cur.n_valid < a.min_valid) status = NVBX_ALIGN_TOO_FEW;
+  else if (!nvbx_align_solve6(cur.H, cur.b, a.damping, a.min_pivot, xi, nullptr)) { status = NVBX_ALIGN_DEGENERATE; for (int k = 0; k < 6; k++) xi[k] = 0.0; }
+  else if (a.mode == MODE_LINEARIZE) status = NVBX_ALIGN_LINEARIZED;
+  else {
+    nvbx_align_apply(R, t, xi);
+    const double nv = sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]), nw = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
+    if (nv <= a.stop_t && nw <= a.stop_r) status = NVBX_ALIGN_CONVERGED;
+    else if (a.iter + 1 >= a.max_iter) status = NVBX_ALIGN_MAX_ITERATIONS;
+  }
+  for (int k = 0; k < 9; k++) a.st->R[k] = R[k];
+  for (int k = 0; k < 3; k++) a.st->t[k] = t[k];
+  a.st->status = status; a.st->iterations = a.iter + 1;
+  nvbx_align_result* o = a.res;
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) { o->T64[4 * i + j] = R[3 * i + j]; o->T_L_S[4 * i + j] = (float)R[3 * i + j]; }
+    o->T64[4 * i + 3] = t[i]; o->T_L_S[4 * i + 3] = (float)t[i];
+    o->T64[12 + i] = 0.0; o->T_L_S[12 + i] = 0.0f;
+  }
+  o->T64[15] = 1.0; o->T_L_S[15] = 1.0f;
+  for (int k = 0; k < 6; k++) o->step[k] = xi[k];
+  if (a.iter == 0) o->first = cur;
+  o->last = cur;
+  o->iterations = a.iter + 1; o->status = status;
+}
+
+static int align_fail(const char* who, const char* why) { set_error((std::string(who) + ": " + why).c_str()); return NVBX_E_INVALID; }
+
+// the checks and the launches of the three entry points.  depth != null: the depth form (pts null), else the point form.
+static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
+              const float T[16], const nvbx_align_options* options, nvbx_align_result* res, int mode, float* out_p, float* out_r, float* out_g,
+              uint8_t* out_v) {
+  if (!m) return NVBX_E_INVALID;
+  nvbx_align_options o;
+  if (options) o = *options; else nvbx_default_align_options(&o);
+  if (!T || !res) return align_fail(who, "the pose and result_dev are required");
+  if ((uintptr_t)res & 7) return align_fail(who, "result_dev must be 8-byte aligned");
+  if (m->p.projective_layer_type == 1) return align_fail(who, "an occupancy mapper has no TSDF layer");
+  if (o.max_iterations < 1 || o.max_iterations > 64) return align_fail(who, "max_iterations must be 1 .. 64");
+  if (o.min_valid < 1) return align_fail(who, "min_valid must be >= 1");
+  if (!(o.damping >= 0.0) || !(o.min_pivot_ratio >= 0.0) || !(o.stop_translation_m >= 0.0) || !(o.stop_rotation_rad >= 0.0) ||
+      !std::isfinite(o.damping) || !std::isfinite(o.min_pivot_ratio) || !std::isfinite(o.stop_translation_m) || !std::isfinite(o.stop_rotation_rad))
+    return align_fail(who, "damping, min_pivot_ratio and the stop thresholds must be finite and >= 0");
+  if (o.min_weight != o.min_weight || o.huber_delta_m != o.huber_delta_m || o.max_depth_m != o.max_depth_m)
+    return align_fail(who, "min_weight / huber_delta_m / max_depth_m is not a number");
+  if (!nvbx_pose_in_range(T, m->p.voxel_size * 8.0f, 0.0f)) return align_fail(who, "the pose is not finite or out of range");
+  AlignArgs a{};
+  if (depth || cam) {
+    if (!depth || rows <= 0 || cols <= 0 || !nvbx_camera_matches(cam, rows, cols)) return align_fail(who, "the depth image and a camera of its size are required");
+    if (o.subsampling < 1) return align_fail(who, "subsampling must be >= 1");
+    const int32_t rs = (rows + o.subsampling - 1) / o.subsampling, cs = (cols + o.subsampling - 1) / o.subsampling;
+    a.depth = depth; a.cols = cols; a.cs = cs; a.s = o.subsampling;
+    a.fu = cam->fu; a.fv = cam->fv; a.cu = cam->cu; a.cv = cam->cv; a.max_d = o.max_depth_m;
+    n = (int64_t)rs * cs;
+  } else {
+    if (n < 0 || (n > 0 && !pts)) return align_fail(who, "n points need points_xyz_dev");
+    a.pts = pts;
+  }
+  NVBX_HIP(hipSetDevice(m->device));
+  // reads TSDF voxels and the TSDF flags only: held-back work stays held back, as for the TSDF point query (query.hip)
+  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (m->align_buf.ensure(m->stream, ALIGN_BUF_BYTES)) return NVBX_E_DEVICE;
+  a.n = n;
+  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) a.R0[3 * i + j] = T[4 * i + j]; a.t0[i] = T[4 * i + 3]; }
+  a.max_iter = mode == MODE_LINEARIZE ? 1 : o.max_iterations; a.mode = mode; a.min_valid = o.min_valid;
+  a.nblocks = (int32_t)std::min<int64_t>((n + ALIGN_TPB - 1) / ALIGN_TPB, ALIGN_MAX_WG);
+  a.vs = m->p.voxel_size; a.min_weight = o.min_weight;
+  a.huber = (double)o.huber_delta_m; a.damping = o.damping; a.min_pivot = o.min_pivot_ratio; a.stop_t = o.stop_translation_m; a.stop_r = o.stop_rotation_rad;
+  a.st = reinterpret_cast<AlignState*>(m->align_buf.as<unsigned char>());
+  a.partial = reinterpret_cast<double*>(m->align_buf.as<unsigned char>() + ALIGN_PARTIAL_OFFSET);
+  a.res = res; a.out_p = out_p; a.out_r = out_r; a.out_g = out_g; a.out_v = out_v;
+  for (int32_t it = 0; it < a.max_iter; it++) {
+    a.iter = it;
+    if (a.nblocks > 0) {
+      if (a.depth) NVBX_LAUNCH(m, k_align_accumulate<true>, dim3((unsigned)a.nblocks), dim3(ALIGN_TPB), m->d, a);
+      else NVBX_LAUNCH(m, k_align_accumulate<false>, dim3((unsigned)a.nblocks), dim3(ALIGN_TPB), m->d, a);
+    }
+    NVBX_LAUNCH(m, k_align_solve, dim3(1), dim3(SOLVE_TPB), a);
+    if (a.nblocks == 0) break;      // (an empty cloud: the first solve says TOO_FEW)
+  }
+  NVBX_HIP(hipGetLastError());
+  return NVBX_OK;
+}
+
+extern "C" void nvbx_default_align_options(nvbx_align_options* o) {
+  if (!o) return;
+  o->max_iterations = 10; o->subsampling = 4; o->min_weight = 1e-4f; o->huber_delta_m = 0.0f;
+  o->damping = 0.0; o->min_pivot_ratio = 1e-9; o->stop_translation_m = 1e-5; o->stop_rotation_rad = 1e-5;
+  o->min_valid = 50; o->max_depth_m = 0.0f;
+}
+
+extern "C" int nvbx_align_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float T_L_S_guess[16], const nvbx_align_options* options,
+                                 nvbx_align_result* result_dev) {
+  return align_run("nvbx_align_points", m, points_xyz_dev, n, nullptr, 0, 0, nullptr, T_L_S_guess, options, result_dev, MODE_ALIGN, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int nvbx_align_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const float T_L_C_guess[16], const nvbx_camera* camera,
+                                const nvbx_align_options* options, nvbx_align_result* result_dev) {
+  if (m && (!depth_dev || !camera)) return align_fail("nvbx_align_depth", "the depth image and the camera are required");
+  return align_run("nvbx_align_depth", m, nullptr, 0, depth_dev, rows, cols, camera, T_L_C_guess, options, result_dev, MODE_ALIGN, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int nvbx_linearize_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float T_L_S[16], const nvbx_align_options* options,
+                                     nvbx_align_result* result_dev, float* points_L_dev, float* residual_dev, float* gradient_dev, uint8_t* valid_dev) {
+  return align_run("nvbx_linearize_points", m, points_xyz_dev, n, nullptr, 0, 0, nullptr, T_L_S, options, result_dev, MODE_LINEARIZE, points_L_dev, residual_dev,
+                   gradient_dev, valid_dev);
+}

@@ -18,7 +18,7 @@ __global__ __launch_bounds__(256) void k_backproject(const float* depth, int32_t
     const int64_t i = base + lane;
     float d = 0.0f;
     if (i < n) d = depth[i];
-    const bool ok = i < n && d > 0.0f && !(max_d > 0.0f && d > max_d);
+    const bool ok = i < n && backproject_takes(d, max_d);
     const u64 mask = __ballot(ok);
     if (!mask) continue;
     int32_t b = 0;
@@ -29,8 +29,8 @@ __global__ __launch_bounds__(256) void k_backproject(const float* depth, int32_t
       const int64_t pos = (int64_t)b + __popcll(mask & ((1ull << lane) - 1ull));
       if (pos < cap) {
         const int32_t r = (int32_t)(i / cols), c = (int32_t)(i - (int64_t)r * cols);
-        const float rx = (((float)c + 0.5f) - cu) / fu, ry = (((float)r + 0.5f) - cv) / fv;
-        out[3 * pos] = d * rx; out[3 * pos + 1] = d * ry; out[3 * pos + 2] = d;
+        float p[3]; backproject_pixel(r, c, d, fu, fv, cu, cv, p);
+        out[3 * pos] = p[0]; out[3 * pos + 1] = p[1]; out[3 * pos + 2] = p[2];
       }
     }
   }

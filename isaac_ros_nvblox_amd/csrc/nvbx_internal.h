@@ -357,6 +357,13 @@ __device__ inline void apply_rt(const float* R, const float* t, float x, float y
     o[i] = s + t[i];
   }
 }
+// DepthImageBackProjector's point of pixel (r, c) at depth d, camera frame (k_backproject, and nvbx_align_depth inside its launch)
+__device__ inline void backproject_pixel(int32_t r, int32_t c, float d, float fu, float fv, float cu, float cv, float* o) {
+  const float rx = (((float)c + 0.5f) - cu) / fu, ry = (((float)r + 0.5f) - cv) / fv;
+  o[0] = d * rx; o[1] = d * ry; o[2] = d;
+}
+// which pixels it takes: 0 < depth <= max_d (max_d <= 0: no limit)
+__device__ inline bool backproject_takes(float d, float max_d) { return d > 0.0f && !(max_d > 0.0f && d > max_d); }
 __device__ inline void rotate(const float* R, float x, float y, float z, float* o) {
 #pragma unroll
   for (int i = 0; i < 3; i++) {

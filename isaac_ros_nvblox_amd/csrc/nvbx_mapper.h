@@ -125,6 +125,8 @@ struct nvbx_mapper {
   nvbx::DevBuf feat_synth;
   // feature segmentation (segment.hip): the entry table, parent[n][512] and count[n][512] of the largest block list labelled so far
   nvbx::DevBuf seg_scratch;
+  // pose alignment (align.hip): the f64 pose state and the 256 x 29 partial sums of the accumulate launches, about 60 KB
+  nvbx::DevBuf align_buf;
   // mesh arena
   float* mesh_vert = nullptr; float* mesh_nrm = nullptr; uint8_t* mesh_col = nullptr; int32_t* mesh_tri = nullptr;
   nvbx::MeshRecord* mesh_rec = nullptr;

@@ -20,6 +20,11 @@ LAYER_FEATURE = 64
 Components = collections.namedtuple("Components", "label voxels min_xyz max_xyz sum_xyz peak_score peak_xyz centroid_m")
 COMPONENT_WORDS = C.sizeof(_lib.Component) // 4
 
+# nvbx_align_result.status (align_points / align_depth / linearize_points)
+ALIGN_CONVERGED, ALIGN_MAX_ITERATIONS, ALIGN_TOO_FEW, ALIGN_DEGENERATE, ALIGN_LINEARIZED = 1, 2, 3, 4, 5
+ALIGN_STATUS_NAMES = {1: "CONVERGED", 2: "MAX_ITERATIONS", 3: "TOO_FEW", 4: "DEGENERATE", 5: "LINEARIZED"}
+ALIGN_RESULT_BYTES = C.sizeof(_lib.AlignResult)
+
 TSDF_DT = np.dtype([("distance", "<f4"), ("weight", "<f4")])
 COLOR_DT = np.dtype([("r", "u1"), ("g", "u1"), ("b", "u1"), ("pad", "u1"), ("weight", "<f4")])
 ESDF_DT = np.dtype([("squared_distance_vox", "<f4"), ("parent_direction", "<i4", (3,)),
@@ -132,6 +137,49 @@ class ColorFrame:
             self.close()
         except Exception:
             pass
+
+
+class AlignResult:
+    """What an alignment call left behind: `buffer` is the nvbx_align_result record on the device (a uint8 tensor, written by the launches);
+    the first field that is read copies it to the host once (torch's current stream is ordered behind the launches by then)."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        self._host = None
+
+    def _r(self):
+        if self._host is None:
+            self._host = _lib.AlignResult.from_buffer_copy(self.buffer.cpu().numpy().tobytes())
+        return self._host
+
+    @staticmethod
+    def _full(tri):
+        H = np.zeros((6, 6)); H[np.triu_indices(6)] = np.array(tri, np.float64)
+        return H + np.triu(H, 1).T
+
+    @staticmethod
+    def _rmse(sums):
+        return float(np.sqrt(sums.cost / sums.n_valid)) if sums.n_valid > 0 else 0.0
+
+    T_L_S = property(lambda self: np.array(self._r().T_L_S, np.float32).reshape(4, 4), doc="the refined pose, f32")
+    T64 = property(lambda self: np.array(self._r().T64, np.float64).reshape(4, 4), doc="the refined pose, f64")
+    step = property(lambda self: np.array(self._r().step, np.float64), doc="the last step solved for, (v, omega)")
+    iterations = property(lambda self: int(self._r().iterations))
+    status = property(lambda self: int(self._r().status))
+    status_name = property(lambda self: ALIGN_STATUS_NAMES.get(int(self._r().status), "?"))
+    n_valid = property(lambda self: int(self._r().last.n_valid), doc="valid points of the last linearization")
+    n_valid_first = property(lambda self: int(self._r().first.n_valid))
+    cost_first = property(lambda self: float(self._r().first.cost))
+    cost_last = property(lambda self: float(self._r().last.cost))
+    rmse_first = property(lambda self: self._rmse(self._r().first), doc="sqrt(cost / n_valid) at the guess")
+    rmse_last = property(lambda self: self._rmse(self._r().last), doc="... at the last linearization")
+    H = property(lambda self: self._full(self._r().last.H), doc="6 x 6 normal matrix of the last linearization")
+    b = property(lambda self: np.array(self._r().last.b, np.float64))
+    H_first = property(lambda self: self._full(self._r().first.H))
+    b_first = property(lambda self: np.array(self._r().first.b, np.float64))
+
+    def __repr__(self):
+        return "AlignResult(%s, iterations=%d, n_valid=%d, rmse %.4g -> %.4g)" % (self.status_name, self.iterations, self.n_valid, self.rmse_first, self.rmse_last)
 
 
 class Mapper:
@@ -732,6 +780,88 @@ class Mapper:
         self._check(call())
         if other:
             cur.wait_stream(ms)
+
+    # -- pose alignment (nvbx_align_points / nvbx_align_depth / nvbx_linearize_points; SEMANTICS.md "Pose alignment")
+    def align_options(self, **kw):
+        """nvbx_align_options: the library's defaults with the given fields replaced (max_iterations, subsampling, min_weight, huber_delta_m,
+        damping, min_pivot_ratio, stop_translation_m, stop_rotation_rad, min_valid, max_depth_m)."""
+        o = _lib.AlignOptions()
+        self.lib.nvbx_default_align_options(C.byref(o))
+        names = [f for f, _ in _lib.AlignOptions._fields_]
+        for k, v in kw.items():
+            if k not in names:
+                raise TypeError("unknown alignment option %r" % k)
+            setattr(o, k, v)
+        return o
+
+    def _align_buffer(self, out):
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            return torch.empty(ALIGN_RESULT_BYTES, dtype=torch.uint8, device=dev)
+        if out.device != dev or out.dtype != torch.uint8 or out.numel() != ALIGN_RESULT_BYTES or not out.is_contiguous() or out.data_ptr() % 8:
+            raise ValueError("the result buffer must be a contiguous 8-byte aligned uint8 tensor of %d bytes on %s" % (ALIGN_RESULT_BYTES, dev))
+        return out
+
+    def _points(self, points):
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(points, torch.Tensor):
+            p = (points if points.device == dev else points.to(dev)).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
+        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError("points must be an (n, 3) float32 array, got %s %s" % (tuple(p.shape), p.dtype))
+        return p
+
+    def align_points(self, points, T_L_S_guess, out=None, **options):
+        """Refine the pose of a sensor-frame cloud ((n, 3) float32 torch tensor or numpy array) against the TSDF, from T_L_S_guess: -> AlignResult.
+        Every launch is enqueued at once on the mapper's stream, nothing waits on the host.  options: see align_options.
+        out: a preallocated result buffer (uint8 tensor of ALIGN_RESULT_BYTES bytes), nothing is allocated."""
+        p = self._points(points); T = self._T(T_L_S_guess); o = self.align_options(**options); buf = self._align_buffer(out)
+        self._around_torch_stream(lambda: self.lib.nvbx_align_points(self._h, C.c_void_p(p.data_ptr()), p.shape[0], _np_ptr(T), C.byref(o),
+                                                                     C.c_void_p(buf.data_ptr())))
+        self._hold("_keep_a", [p])      # (the launches read the points: they, and an uploaded copy, live until the next alignment)
+        return AlignResult(buf)
+
+    def align_depth(self, depth, T_L_C_guess, cam, out=None, **options):
+        """Refine a camera pose from a float32 depth image (metres; torch tensor or numpy array): the pixels (r s, c s) with
+        0 < depth <= max_depth_m are back-projected inside the launch, no point buffer is written.  -> AlignResult; out as for align_points."""
+        d = self._dev(depth, self._torch.float32)
+        if d.dim() != 2:
+            raise ValueError("depth must be a (rows, cols) image")
+        T = self._T(T_L_C_guess); o = self.align_options(**options); buf = self._align_buffer(out); k = self._cam(cam)
+        self._around_torch_stream(lambda: self.lib.nvbx_align_depth(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k),
+                                                                    C.byref(o), C.c_void_p(buf.data_ptr())))
+        self._hold("_keep_a", [d])
+        return AlignResult(buf)
+
+    def linearize_points(self, points, T_L_S, per_point=True, out=None, **options):
+        """One linearization at T_L_S, no step applied: -> (AlignResult, points_L [n, 3] f32, residual [n] f32, gradient [n, 3] f32, valid [n] bool)
+        on the mapper's device; the per-point tensors are None with per_point=False.  They are bit for bit nvbx_transform_pointcloud and
+        query_tsdf(unknown_value=0) at those points.  out=(buffer | None, points_L | None, residual | None, gradient | None, valid | None):
+        preallocated tensors, `out` then decides what is written (a None per-point entry is not) and per_point is not looked at."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        p = self._points(points); n = p.shape[0]
+        T = self._T(T_L_S); o = self.align_options(**options)
+        if out is None:
+            buf = self._align_buffer(None)
+            pl = torch.empty((n, 3), dtype=torch.float32, device=dev) if per_point else None
+            r = torch.empty(n, dtype=torch.float32, device=dev) if per_point else None
+            g = torch.empty((n, 3), dtype=torch.float32, device=dev) if per_point else None
+            v = torch.empty(n, dtype=torch.bool, device=dev) if per_point else None
+        else:
+            buf, pl, r, g, v = out
+            buf = self._align_buffer(buf)
+            for t, shape, dts, what in ((pl, (n, 3), (torch.float32,), "points_L"), (r, (n,), (torch.float32,), "residual"),
+                                        (g, (n, 3), (torch.float32,), "gradient"), (v, (n,), (torch.bool, torch.uint8), "valid")):
+                if t is not None:
+                    self._out_tensor(t, shape, dts, what)
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None      # noqa: E731
+        self._around_torch_stream(lambda: self.lib.nvbx_linearize_points(self._h, ptr(p), n, _np_ptr(T), C.byref(o), ptr(buf), ptr(pl), ptr(r), ptr(g), ptr(v)))
+        self._hold("_keep_a", [p])
+        return AlignResult(buf), pl, r, g, v
 
     def render(self, T_L_C, cam, subsampling=None, max_ray_length_m=None, color=True, normals=False, out=None):
         """The map seen from camera `cam` at pose T_L_C: -> (depth [rows/s, cols/s] f32, color [.., 3] u8 | None, normals [.., 3] f32 | None) on the

@@ -666,6 +666,43 @@ int nvbx_align_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32
 int nvbx_linearize_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float T_L_S[16], const nvbx_align_options* options,
                           nvbx_align_result* result_dev, float* points_L_dev, float* residual_dev, float* gradient_dev, uint8_t* valid_dev);
 
+/* ---- map merging ([U] submap fusion under a rigid transform; SEMANTICS.md "Map merging") ----------------------------------------------
+ * Brings the TSDF and colour of `src` into `dst` under p_D = T_D_S p_S: every voxel of every candidate block of dst (the blocks whose voxel
+ * centres can fall into the sampling cube of a TSDF block of src; missing ones are allocated) samples src at R_SD p_D + t_SD with the rule of
+ * the TSDF point query (eight corners, each with weight >= min_weight), the weights interpolated the same way and multiplied by
+ * weight_scale; a valid sample is fused as a weighted mean, clamped to +-truncation and dst's max_weight; an invalid one leaves the voxel
+ * untouched.  With merge_color the nearest source colour voxel is blended into dst's.  Band flags, ESDF-dirty and mesh-dirty lists of dst
+ * are kept as by any TSDF writer; src is not modified.  Both mappers: TSDF mappers (projective_layer_type 0) on one device with one
+ * voxel_size.  Feature voxels, ESDF, occupancy and freespace are not merged.
+ * Launches run on dst's stream, ordered behind everything enqueued on src's so far; work enqueued on src afterwards is ordered behind the
+ * merge's reads.  A maintenance call: it waits on the host for src's block count and, once, between enumerating the candidates and
+ * allocating them (dst's pools grow if they must).  NVBX_E_CAPACITY (dst unchanged): dst's max_capacity cannot hold the candidates.
+ * NVBX_E_INVALID (nvbx_last_error set, dst unchanged): src == dst; different devices or voxel sizes; an occupancy or freespace mapper; a
+ * pose that is not finite, out of range or no rotation (|R^T R - I| > 1e-5 or det <= 0); min_weight not a number; weight_scale not finite
+ * or <= 0; a NULL or misaligned result_dev. */
+#define NVBX_MERGE_OK           0
+#define NVBX_MERGE_EMPTY_SOURCE 1   /* src has no TSDF block: nothing is allocated */
+#define NVBX_MERGE_NO_OVERLAP   2   /* no voxel fused (the candidates stay allocated) */
+typedef struct {
+  float   min_weight;           /* a source corner counts with weight >= this */
+  float   weight_scale;         /* the sampled TSDF weight is multiplied by this; finite, > 0 */
+  int32_t merge_color;          /* != 0: colour is merged too */
+  int32_t pad;
+} nvbx_merge_options;           /* 16 bytes; offsets 0 4 8 12 */
+typedef struct {
+  int64_t source_blocks;        /* TSDF blocks of src */
+  int64_t candidate_blocks;     /* blocks of dst the merge went over */
+  int64_t blocks_allocated;     /* ... of which dst did not have before */
+  int64_t voxels_fused;
+  int64_t color_voxels_fused;
+  int32_t status;               /* NVBX_MERGE_* */
+  int32_t pad[5];
+} nvbx_merge_result;            /* 64 bytes, 8-byte aligned DEVICE memory; offsets 0 8 16 24 32 40 44 */
+/* defaults: min_weight 1e-4, weight_scale 1, merge_color 1 */
+void nvbx_default_merge_options(nvbx_merge_options* options);
+/* T_D_S: row-major 4 x 4, host memory.  options NULL: the defaults.  result_dev: written by the last launch, not waited for. */
+int nvbx_merge_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S[16], const nvbx_merge_options* options, nvbx_merge_result* result_dev);
+
 /* ---- mask splitting (human / people-segmentation mapping) ------------------------------------------------------------
  * [U] ImageMasker::splitImageOnGPU as used by MultiMapper::integrateDepth(depth, mask, T_L_CD, T_CM_CD, depth_cam, mask_cam) --
  * nvblox_node.cpp:1018-1060: every valid depth pixel is lifted to 3-D, moved into the mask camera (T_CM_CD = T_L_CM^-1 T_L_CD)

@@ -120,6 +120,17 @@ class AlignResult(C.Structure):
                 ("iterations", C.c_int32), ("status", C.c_int32)]
 
 
+class MergeOptions(C.Structure):
+    """nvbx_merge_options (16 bytes); nvbx_default_merge_options fills it"""
+    _fields_ = [("min_weight", C.c_float), ("weight_scale", C.c_float), ("merge_color", C.c_int32), ("pad", C.c_int32)]
+
+
+class MergeResult(C.Structure):
+    """nvbx_merge_result: what nvbx_merge_map's last launch leaves in DEVICE memory (64 bytes)"""
+    _fields_ = [("source_blocks", C.c_int64), ("candidate_blocks", C.c_int64), ("blocks_allocated", C.c_int64), ("voxels_fused", C.c_int64),
+                ("color_voxels_fused", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32 * 5)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("table", C.c_void_p), ("table_mask", C.c_uint32), ("table_shift", C.c_uint32), ("slot_flags", C.c_void_p),
                 ("slot_index", C.c_void_p), ("tsdf", C.c_void_p), ("color", C.c_void_p), ("esdf", C.c_void_p),
@@ -207,6 +218,8 @@ SIGNATURES = {
     "nvbx_align_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp]),
     "nvbx_align_depth": (C.c_int, [_vp, _vp, _i32, _i32, _vp, C.POINTER(Camera), C.POINTER(AlignOptions), _vp]),
     "nvbx_linearize_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp, _vp, _vp, _vp, _vp]),
+    "nvbx_default_merge_options": (None, [C.POINTER(MergeOptions)]),
+    "nvbx_merge_map": (C.c_int, [_vp, _vp, _vp, C.POINTER(MergeOptions), _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),
     "nvbx_block_indices": (_i64, [_vp, C.c_uint32, _vp, _i64]),
     "nvbx_get_block": (C.c_int, [_vp, C.c_uint32, Index3D, _vp]),

@@ -1,0 +1,333 @@
+// merge.hip -- one mapper's TSDF and colour brought into another under a rigid transform (nvbx_merge_map; SEMANTICS.md "Map merging",
+// DESIGN.md 2.17).  [U] submap fusion after loop closure / multi-session / multi-robot mapping: nothing of the kind is readable in the reference tree.
+//
+// Launches, all on dst's stream, src read-only throughout:
+//   k_merge_count   one thread per (source slot, candidate 0 .. 26): the candidate box of the slot's block (nvbx_merge_math.h) and, for every
+//                   candidate dst lacks, an insert into a scratch key set -- the distinct ones are counted.  Nothing of dst is written: the host
+//                   waits for the counts, grows dst's pools if it must, or refuses (NVBX_E_CAPACITY) with dst untouched.
+//   k_merge_index   the same enumeration again, now with mark_block on dst: missing blocks are allocated, every candidate is stamped with
+//                   the call's frame id and appended to dst's view list exactly once -- the work list of the next launch (k_apply_index is the pattern).
+//   k_merge_fuse    one 512-thread workgroup per candidate block, lane = voxel z + 8y + 64x.  The lanes' sample positions reach at most
+//                   3 x 3 x 3 source blocks: the workgroup finds the lowest block index per axis, 27 lanes probe src's table once and leave the
+//                   slots (and whether they carry colour) in LDS; every lane then takes its eight corners -- a z pair is one 16-B load inside a
+//                   block, as in q_point -- through that table, interpolates distance and weight, fuses, blends the nearest colour voxel and
+//                   writes its own voxel: no two lanes write one voxel, the result does not depend on scheduling.  Band bits per wavefront
+//                   (publish_band), dirty flags and lists per block as in k_apply_fuse.
+//   k_merge_result  one thread: the caller's result record from the counters the launches left.
+#include "nvbx_view.h"
+#include "nvbx_query_point.h"
+#include "nvbx_merge_math.h"
+
+struct MergeArgs {
+  float R_DS[9], t_DS[3];       // p_D = R_DS p_S + t_DS: the candidate boxes
+  float R_SD[9], t_SD[3];       // p_S = R_SD p_D + t_SD: the samples
+  float vs, min_weight, weight_scale, trunc, max_weight;
+  int32_t merge_color, mesh_list;
+  uint32_t frame_id;
+};
+// head of nvbx_mapper::merge_buf (zeroed per call); the key set follows at MERGE_KEYS_OFFSET
+struct MergeScratch { int32_t src_blocks, need_slots, need_tsdf, dst_free; unsigned long long voxels, colors; };
+constexpr size_t MERGE_KEYS_OFFSET = 64;
+static_assert(sizeof(MergeScratch) <= MERGE_KEYS_OFFSET, "scratch head");
+static_assert(sizeof(nvbx_merge_result) == 64 && sizeof(nvbx_merge_options) == 16, "C-ABI layout");
+
+// candidate c (0 .. 26) of source slot s: false if the slot holds no TSDF block or the box has no such block
+__device__ inline bool merge_candidate(const DMap& src, const MergeArgs& a, int32_t s, int c, int32_t* x, int32_t* y, int32_t* z) {
+  if (!(src.slot_flags[s] & F_TSDF)) return false;
+  const int32_t si[3] = {src.slot_index[3 * s], src.slot_index[3 * s + 1], src.slot_index[3 * s + 2]};
+  int32_t lo[3], hi[3];
+  if (!nvbx_merge_candidate_box(a.R_DS, a.t_DS, si, a.vs, lo, hi)) return false;
+  *x = lo[0] + c % 3; *y = lo[1] + (c / 3) % 3; *z = lo[2] + c / 9;
+  return *x <= hi[0] && *y <= hi[1] && *z <= hi[2];
+}
+
+__global__ void k_merge_count(DMap dst, DMap src, MergeArgs a, MergeScratch* sc, u64* keys, uint32_t kmask) {
+  const int64_t n = (int64_t)src.counters[C_HIGH_WATER] * 27;
+  if (blockIdx.x == 0 && threadIdx.x == 0) sc->dst_free = dst.counters[C_FREE_TOP];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t s = (int32_t)(i / 27); const int c = (int)(i - (int64_t)s * 27);
+    if (c == 0 && (src.slot_flags[s] & F_TSDF)) atomicAdd(&sc->src_blocks, 1);
+    int32_t x, y, z;
+    if (!merge_candidate(src, a, s, c, &x, &y, &z)) continue;
+    // what dst has: an entry with a slot (a block of any layer shares it), and whether that slot carries a TSDF block
+    const u64 key = pack_key(x, y, z);
+    bool has_slot = false, has_tsdf = false;
+    uint32_t h = table_pos(dst, x, y, z);
+    for (uint32_t probe = 0; probe <= dst.mask; ++probe) {
+      const uint4 e = ld_entry(dst, h);
+      const u64 k = ((u64)e.y << 32) | (u64)e.x;
+      if (k == key) { has_slot = true; has_tsdf = slot_ok(e.z) && (dst.slot_flags[e.z] & F_TSDF); break; }
+      if (k == KEY_EMPTY) break;
+      h = (h + 1) & dst.mask;
+    }
+    if (has_tsdf) continue;
+    uint32_t kh = (index_hash(x, y, z) * 2654435761u) & kmask;
+    for (uint32_t probe = 0; probe <= kmask; ++probe) {
+      const u64 old = atomicCAS(&keys[kh], KEY_EMPTY, key);
+      if (old == KEY_EMPTY) { atomicAdd(&sc->need_tsdf, 1); if (!has_slot) atomicAdd(&sc->need_slots, 1); break; }
+      if (old == key) break;
+      kh = (kh + 1) & kmask;
+    }
+  }
+}
+
+__global__ void k_merge_index(DMap dst, DMap src, MergeArgs a, int4* view_list, int32_t list_cap) {
+  int32_t* cnt = &dst.counters[C_VIEW_COUNT + (a.frame_id & 3)];
+  if (blockIdx.x == 0 && threadIdx.x == 0) dst.counters[C_VIEW_COUNT + ((a.frame_id + 1) & 3)] = 0;
+  const int64_t n = (int64_t)src.counters[C_HIGH_WATER] * 27;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t s = (int32_t)(i / 27); const int c = (int)(i - (int64_t)s * 27);
+    int32_t x, y, z;
+    if (!merge_candidate(src, a, s, c, &x, &y, &z)) continue;
+    int4 rec;
+    if (!mark_block(dst, pack_key(x, y, z), a.frame_id, 1u, &rec)) continue;      // (stamped already: another source block's candidate too)
+    const int32_t p = atomicAdd(cnt, 1);
+    if (p < list_cap) view_list[p] = rec;
+  }
+}
+
+__global__ __launch_bounds__(512) void k_merge_fuse(DMap dst, DMap src, MergeArgs a, const int4* view_list, int32_t list_cap, MergeScratch* sc) {
+  __shared__ uint32_t s_slot[27], s_color[27];
+  __shared__ int32_t s_min[3];
+  __shared__ uint32_t s_cnt[2];
+#ifdef NVBX_MERGE_STAGE_LDS            // -DNVBX_MERGE_STAGE_LDS variant (tools/build_variant.sh): the up to 27 source blocks copied into 108 KiB of dynamic LDS first
+  extern __shared__ __align__(16) uint2 s_vox[];
+#endif
+  int32_t n = dst.counters[C_VIEW_COUNT + (a.frame_id & 3)];
+  if (n > list_cap) n = list_cap;
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && tid == 64) __hip_atomic_store(&dst.host_mirror[0], dst.counters[C_FREE_TOP], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (tid < 2) s_cnt[tid] = 0u;
+  const int vx = tid >> 6, vy = (tid >> 3) & 7, vz = tid & 7;
+  const uint2* spool = reinterpret_cast<const uint2*>(src.tsdf);
+  uint32_t n_fused = 0u, n_color = 0u;
+  for (int32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const int4 rec = view_list[i];
+    const uint32_t slot = (uint32_t)rec.x;
+    if (!slot_ok(slot)) continue;                                   // (uniform)
+    if (tid < 3) s_min[tid] = INT32_MAX;
+    float2* vp = &dst.tsdf[(size_t)slot * 512 + tid];
+    float2 cur = *vp;
+    // the sample position and its base voxel
+    const float pd0 = ((float)(8 * rec.y + vx) + 0.5f) * a.vs, pd1 = ((float)(8 * rec.z + vy) + 0.5f) * a.vs, pd2 = ((float)(8 * rec.w + vz) + 0.5f) * a.vs;
+    float ps[3];
+    apply_rt(a.R_SD, a.t_SD, pd0, pd1, pd2, ps);
+    int32_t b[3] = {0, 0, 0}; float t[3] = {0.0f, 0.0f, 0.0f};
+    const bool ok0 = nvbx_interp_axis(ps[0], a.vs, &b[0], &t[0]), ok1 = nvbx_interp_axis(ps[1], a.vs, &b[1], &t[1]), ok2 = nvbx_interp_axis(ps[2], a.vs, &b[2], &t[2]);
+    const bool ok = ok0 && ok1 && ok2;
+    __syncthreads();                                                // s_min is reset, the last block's table has been read by everyone
+    {
+      int32_t m0 = ok ? (b[0] >> 3) : INT32_MAX, m1 = ok ? (b[1] >> 3) : INT32_MAX, m2 = ok ? (b[2] >> 3) : INT32_MAX;
+#pragma unroll
+      for (int o = 32; o; o >>= 1) { m0 = min(m0, __shfl_xor(m0, o)); m1 = min(m1, __shfl_xor(m1, o)); m2 = min(m2, __shfl_xor(m2, o)); }
+      if ((tid & 63) == 0) { atomicMin(&s_min[0], m0); atomicMin(&s_min[1], m1); atomicMin(&s_min[2], m2); }
+    }
+    __syncthreads();
+    const int32_t B0 = s_min[0], B1 = s_min[1], B2 = s_min[2];
+    if (tid < 27) {                                                 // the source blocks the samples can reach, resolved once
+      uint32_t s = SLOT_NONE, cf = 0u;
+      const int32_t x = B0 + tid % 3, y = B1 + (tid / 3) % 3, z = B2 + tid / 9;
+      constexpr int32_t L = 1 << 20;                                 // (block indices the hash key can hold)
+      if (B0 != INT32_MAX && x >= -L && x < L && y >= -L && y < L && z >= -L && z < L) {
+        s = q_probe(src, x, y, z, F_TSDF);
+        if (slot_ok(s)) cf = src.slot_flags[s] & F_COLOR;
+      }
+      s_slot[tid] = s; s_color[tid] = cf;
+    }
+    __syncthreads();
+#ifdef NVBX_MERGE_STAGE_LDS
+    for (int q = 0; q < 27; q++) { const uint32_t s = s_slot[q]; if (slot_ok(s)) s_vox[q * 512 + tid] = spool[(size_t)s * 512 + tid]; }      // (uniform branch; 4 KiB per block present)
+    __syncthreads();
+#endif
+    // corners: block offsets 0 .. 2 from (B0, B1, B2) per axis (ok lanes: never more, the block's centres span 7 voxels)
+    const int lx = b[0] & 7, ly = b[1] & 7, lz = b[2] & 7;
+    const int ox0 = ok ? (b[0] >> 3) - B0 : 0, oy0 = ok ? (b[1] >> 3) - B1 : 0, oz0 = ok ? (b[2] >> 3) - B2 : 0;
+    const int ox1 = ok ? ((b[0] + 1) >> 3) - B0 : 0, oy1 = ok ? ((b[1] + 1) >> 3) - B1 : 0, oz1 = ok ? ((b[2] + 1) >> 3) - B2 : 0;
+    bool all = ok && ox1 <= 2 && oy1 <= 2 && oz1 <= 2;
+    float cd[8], cw[8];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {                                   // q = i + 2j: corners (i, j, 0) and (i, j, 1)
+      const int i_ = q & 1, j_ = q >> 1;
+      const int ox = i_ ? ox1 : ox0, oy = j_ ? oy1 : oy0;
+      const int xx = (lx + i_) & 7, yy = (ly + j_) & 7;
+      uint2 e0 = make_uint2(0, 0), e1 = make_uint2(0, 0);
+      if (all) {
+        const int q0 = ox + 3 * oy + 9 * oz0, q1 = ox + 3 * oy + 9 * oz1;
+        const uint32_t s0 = s_slot[q0];
+#ifdef NVBX_MERGE_STAGE_LDS            // (experiment, EXPERIMENTS.md: the corners come from the staged copies)
+        const uint32_t s1 = s_slot[q1];
+        if (slot_ok(s0) && slot_ok(s1)) { e0 = s_vox[q0 * 512 + lz + 8 * yy + 64 * xx]; e1 = s_vox[q1 * 512 + ((lz + 1) & 7) + 8 * yy + 64 * xx]; }
+        else all = false;
+#else
+        if (lz != 7) {
+          if (slot_ok(s0)) { const uint4 w = ld_pair(spool + (size_t)s0 * 512 + lz + 8 * yy + 64 * xx); e0 = make_uint2(w.x, w.y); e1 = make_uint2(w.z, w.w); }
+          else all = false;
+        } else {
+          const uint32_t s1 = s_slot[q1];
+          if (slot_ok(s0) && slot_ok(s1)) { e0 = spool[(size_t)s0 * 512 + 7 + 8 * yy + 64 * xx]; e1 = spool[(size_t)s1 * 512 + 8 * yy + 64 * xx]; }
+          else all = false;
+        }
+#endif
+      }
+      cd[q] = __uint_as_float(e0.x); cw[q] = __uint_as_float(e0.y); cd[q + 4] = __uint_as_float(e1.x); cw[q + 4] = __uint_as_float(e1.y);
+      all = all && cw[q] >= a.min_weight && cw[q + 4] >= a.min_weight;
+    }
+    bool fused = false, colored = false;
+    if (all) {
+      float g[3];
+      const float ds = nvbx_interp_trilinear(cd, t[0], t[1], t[2], a.vs, g);
+      const float ws = nvbx_interp_trilinear(cw, t[0], t[1], t[2], a.vs, g) * a.weight_scale;
+      const float w = cur.y + ws;
+      if (w > 0.0f) {
+        float d = NVBX_DIV(ds * ws + cur.x * cur.y, w);
+        d = __builtin_amdgcn_fmed3f(d, -a.trunc, a.trunc);
+        cur = make_float2(d, fminf(w, a.max_weight));
+        *vp = cur;
+        fused = true;
+      }
+    }
+    if (a.merge_color && fused) {                                   // the nearest source colour voxel: floor(p / vs) per axis, one of b, b + 1
+      const int32_t n0 = (int32_t)floorf(ps[0] / a.vs), n1 = (int32_t)floorf(ps[1] / a.vs), n2 = (int32_t)floorf(ps[2] / a.vs);
+      const int o0 = (n0 >> 3) - B0, o1 = (n1 >> 3) - B1, o2 = (n2 >> 3) - B2;
+      if (o0 >= 0 && o0 <= 2 && o1 >= 0 && o1 <= 2 && o2 >= 0 && o2 <= 2) {
+        const int oi = o0 + 3 * o1 + 9 * o2;
+        const uint32_t cs = s_slot[oi];
+        if (slot_ok(cs) && s_color[oi]) {
+          const uint2 sv = src.color[(size_t)cs * 512 + (n2 & 7) + 8 * (n1 & 7) + 64 * (n0 & 7)];
+          const float sw = __uint_as_float(sv.y);
+          if (sw > 0.0f) {
+            uint2* cp = &dst.color[(size_t)slot * 512 + tid];
+            const uint2 dv = *cp;
+            const float w0 = __uint_as_float(dv.y);
+            const uint32_t r8 = blend_u8((float)(dv.x & 0xFF), w0, (float)(sv.x & 0xFF), sw);
+            const uint32_t g8 = blend_u8((float)((dv.x >> 8) & 0xFF), w0, (float)((sv.x >> 8) & 0xFF), sw);
+            const uint32_t b8 = blend_u8((float)((dv.x >> 16) & 0xFF), w0, (float)((sv.x >> 16) & 0xFF), sw);
+            *cp = make_uint2(r8 | (g8 << 8) | (b8 << 16), __float_as_uint(fminf(w0 + sw, a.max_weight)));
+            colored = true;
+          }
+        }
+      }
+    }
+    n_fused += fused ? 1u : 0u; n_color += colored ? 1u : 0u;
+    uint32_t old = 0u;
+    if (tid == 0) old = atomicOr(&dst.slot_flags[slot], F_TSDF | F_DIRTY_ESDF | F_DIRTY_MESH);
+    publish_band(dst.slot_flags, slot, tid, in_band(cur.x, cur.y, a.trunc));      // (every wavefront is here)
+    const int any_color = __syncthreads_or(colored ? 1 : 0);
+    if (tid == 0) {
+      if (any_color) atomicOr(&dst.slot_flags[slot], F_COLOR);
+      if (!(old & F_DIRTY_ESDF)) list_append(dst, S_LIST_ESDF_DIRTY, (int32_t)slot);
+      if (!(old & F_DIRTY_MESH)) list_append(dst, a.mesh_list, (int32_t)slot);
+    }
+  }
+  // the workgroup's counts: wavefront sums, LDS, one atomic each
+#pragma unroll
+  for (int o = 32; o; o >>= 1) { n_fused += __shfl_xor(n_fused, o); n_color += __shfl_xor(n_color, o); }
+  __syncthreads();
+  if ((tid & 63) == 0) { atomicAdd(&s_cnt[0], n_fused); atomicAdd(&s_cnt[1], n_color); }
+  __syncthreads();
+  if (tid == 0) { if (s_cnt[0]) atomicAdd(&sc->voxels, (unsigned long long)s_cnt[0]); if (s_cnt[1]) atomicAdd(&sc->colors, (unsigned long long)s_cnt[1]); }
+}
+
+// empty != 0: nothing was enumerated (src has no TSDF block)
+__global__ void k_merge_result(DMap dst, uint32_t frame_id, const MergeScratch* sc, int64_t src_blocks, int64_t allocated, int32_t empty, nvbx_merge_result* out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  nvbx_merge_result r;
+  r.source_blocks = src_blocks;
+  r.candidate_blocks = empty ? 0 : (int64_t)dst.counters[C_VIEW_COUNT + (frame_id & 3)];
+  r.blocks_allocated = allocated;
+  r.voxels_fused = empty ? 0 : (int64_t)sc->voxels;
+  r.color_voxels_fused = empty ? 0 : (int64_t)sc->colors;
+  r.status = empty ? NVBX_MERGE_EMPTY_SOURCE : (r.voxels_fused == 0 ? NVBX_MERGE_NO_OVERLAP : NVBX_MERGE_OK);
+  for (int k = 0; k < 5; k++) r.pad[k] = 0;
+  *out = r;
+}
+
+static int merge_fail(const char* why) { set_error((std::string("nvbx_merge_map: ") + why).c_str()); return NVBX_E_INVALID; }
+
+extern "C" void nvbx_default_merge_options(nvbx_merge_options* o) {
+  if (!o) return;
+  o->min_weight = 1e-4f; o->weight_scale = 1.0f; o->merge_color = 1; o->pad = 0;
+}
+
+extern "C" int nvbx_merge_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S[16], const nvbx_merge_options* options, nvbx_merge_result* result_dev) {
+  if (!dst || !src) return merge_fail("both mappers are required");
+  nvbx_merge_options o;
+  if (options) o = *options; else nvbx_default_merge_options(&o);
+  if (!T_D_S || !result_dev) return merge_fail("the pose and result_dev are required");
+  if ((uintptr_t)result_dev & 7) return merge_fail("result_dev must be 8-byte aligned");
+  if (src == dst) return merge_fail("src and dst are the same mapper");
+  if (src->device != dst->device) return merge_fail("the mappers are on different devices");
+  if (src->p.voxel_size != dst->p.voxel_size) return merge_fail("the mappers' voxel sizes differ");
+  if (src->p.projective_layer_type != 0 || dst->p.projective_layer_type != 0) return merge_fail("both mappers must be TSDF mappers without a freespace layer (projective_layer_type 0)");
+  if (!nvbx_pose_in_range(T_D_S, dst->p.voxel_size * 8.0f, 0.0f)) return merge_fail("the pose is not finite or out of range");
+  if (!nvbx_merge_rotation_ok(T_D_S, nullptr, nullptr)) return merge_fail("the upper-left 3 x 3 of T_D_S is not a rotation (|R^T R - I| > 1e-5 or det <= 0)");
+  if (o.min_weight != o.min_weight) return merge_fail("min_weight is not a number");
+  if (!std::isfinite(o.weight_scale) || !(o.weight_scale > 0.0f)) return merge_fail("weight_scale must be finite and > 0");
+  NVBX_HIP(hipSetDevice(dst->device));
+  // src: held-back work is carried out; its block count sizes the key set (waits for src's stream)
+  if (src->fetch_counters()) return NVBX_E_DEVICE;
+  const int64_t src_hw = src->h_counters[C_HIGH_WATER];
+  const int64_t src_live = std::max<int64_t>(1, (int64_t)src->capacity - (int64_t)src->h_counters[C_FREE_TOP]);
+  if (dst->join_side()) return NVBX_E_DEVICE;
+  { const int rc = nvbx_mapper_wait_for(dst, src); if (rc) return rc; }
+  MergeArgs a{};
+  nvbx_merge_transforms(T_D_S, a.R_DS, a.t_DS, a.R_SD, a.t_SD);
+  a.vs = dst->p.voxel_size; a.min_weight = o.min_weight; a.weight_scale = o.weight_scale;
+  a.trunc = dst->p.truncation_distance_vox * dst->p.voxel_size; a.max_weight = dst->p.max_weight;
+  a.merge_color = o.merge_color ? 1 : 0;
+  // the key set: distinct candidates are at most 27 per source block; load <= 1/2
+  uint64_t entries = 64; while (entries < (uint64_t)src_live * 54) entries <<= 1;
+  if (entries > (1ull << 31)) return merge_fail("the source map is too large to enumerate");
+  if (dst->merge_buf.ensure(dst->stream, MERGE_KEYS_OFFSET + (size_t)entries * 8)) return NVBX_E_DEVICE;
+  MergeScratch* sc = dst->merge_buf.as<MergeScratch>();
+  u64* keys = reinterpret_cast<u64*>(dst->merge_buf.as<unsigned char>() + MERGE_KEYS_OFFSET);
+  NVBX_HIP(hipMemsetAsync(sc, 0, MERGE_KEYS_OFFSET, dst->stream));
+  MergeScratch h{};
+  const unsigned enum_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((src_hw * 27 + 255) / 256, 2048));
+  if (src_hw > 0) {
+    NVBX_HIP(hipMemsetAsync(keys, 0xFF, (size_t)entries * 8, dst->stream));
+    NVBX_LAUNCH(dst, k_merge_count, dim3(enum_grid), dim3(256), dst->d, src->d, a, sc, keys, (uint32_t)(entries - 1));
+    NVBX_HIP(hipGetLastError());
+    NVBX_HIP(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, dst->stream));
+    NVBX_HIP(hipStreamSynchronize(dst->stream));                    // the one wait between enumerating and allocating
+  }
+  if (h.src_blocks == 0) {
+    NVBX_LAUNCH(dst, k_merge_result, dim3(1), dim3(64), dst->d, 0u, (const MergeScratch*)sc, (int64_t)0, (int64_t)0, 1, result_dev);
+    NVBX_HIP(hipGetLastError());
+    return nvbx_mapper_wait_for(src, dst);
+  }
+  // room for every candidate dst lacks, or nothing is touched
+  {
+    const int64_t need = h.need_slots, free_now = h.dst_free;
+    if (need > free_now + (dst->max_capacity - dst->capacity)) {
+      set_error("nvbx_merge_map: dst's max_capacity cannot hold the candidate blocks, nothing was merged");
+      return NVBX_E_CAPACITY;
+    }
+    const int64_t cap_before = dst->capacity;
+    if (dst->capacity < dst->max_capacity) {
+      dst->h_mirror[0] = (int32_t)free_now;
+      const int rc = dst->maybe_grow(need); if (rc) return rc;
+    }
+    if (need > free_now + (dst->capacity - cap_before)) {
+      set_error("nvbx_merge_map: dst's block pools could not grow to hold the candidate blocks, nothing was merged");
+      return NVBX_E_CAPACITY;
+    }
+  }
+  if (dst->begin_dirtying()) return NVBX_E_DEVICE;
+  { const int rc = next_frame_id(dst); if (rc) return rc; }
+  a.frame_id = dst->frame_id; a.mesh_list = dst->mesh_list_live();
+  NVBX_LAUNCH(dst, k_merge_index, dim3(enum_grid), dim3(256), dst->d, src->d, a, (int4*)dst->view_list, (int32_t)dst->capacity);
+  const unsigned fuse_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(dst->capacity, (int64_t)h.src_blocks * 27), 2048));
+#ifdef NVBX_MERGE_STAGE_LDS
+  constexpr size_t kStageBytes = 27 * 512 * sizeof(uint2);
+  NVBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_fuse), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStageBytes));
+  NVBX_LAUNCH_SMEM(dst, k_merge_fuse, dim3(fuse_grid), dim3(512), kStageBytes, dst->d, src->d, a, (const int4*)dst->view_list, (int32_t)dst->capacity, sc);
+#else
+  NVBX_LAUNCH(dst, k_merge_fuse, dim3(fuse_grid), dim3(512), dst->d, src->d, a, (const int4*)dst->view_list, (int32_t)dst->capacity, sc);
+#endif
+  NVBX_LAUNCH(dst, k_merge_result, dim3(1), dim3(64), dst->d, a.frame_id, (const MergeScratch*)sc, (int64_t)h.src_blocks, (int64_t)h.need_tsdf, 0, result_dev);
+  NVBX_HIP(hipGetLastError());
+  dst->last_view_frame = dst->frame_id; dst->last_view_batch = 1;      // (the view list now holds the candidates; the last CAMERA view stays what it was)
+  { const int rc = nvbx_mapper_wait_for(src, dst); if (rc) return rc; }      // later work on src runs behind the merge's reads
+  return dst->mark_main();
+}

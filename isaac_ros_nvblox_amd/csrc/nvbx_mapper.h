@@ -127,6 +127,8 @@ struct nvbx_mapper {
   nvbx::DevBuf seg_scratch;
   // pose alignment (align.hip): the f64 pose state and the 256 x 29 partial sums of the accumulate launches, about 60 KB
   nvbx::DevBuf align_buf;
+  // map merging (merge.hip), as the destination: a 64-byte head of counters and the key set that counts the distinct candidate blocks
+  nvbx::DevBuf merge_buf;
   // mesh arena
   float* mesh_vert = nullptr; float* mesh_nrm = nullptr; uint8_t* mesh_col = nullptr; int32_t* mesh_tri = nullptr;
   nvbx::MeshRecord* mesh_rec = nullptr;

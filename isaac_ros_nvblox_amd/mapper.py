@@ -25,6 +25,11 @@ ALIGN_CONVERGED, ALIGN_MAX_ITERATIONS, ALIGN_TOO_FEW, ALIGN_DEGENERATE, ALIGN_LI
 ALIGN_STATUS_NAMES = {1: "CONVERGED", 2: "MAX_ITERATIONS", 3: "TOO_FEW", 4: "DEGENERATE", 5: "LINEARIZED"}
 ALIGN_RESULT_BYTES = C.sizeof(_lib.AlignResult)
 
+# nvbx_merge_result.status (merge_from)
+MERGE_OK, MERGE_EMPTY_SOURCE, MERGE_NO_OVERLAP = 0, 1, 2
+MERGE_STATUS_NAMES = {0: "OK", 1: "EMPTY_SOURCE", 2: "NO_OVERLAP"}
+MERGE_RESULT_BYTES = C.sizeof(_lib.MergeResult)
+
 TSDF_DT = np.dtype([("distance", "<f4"), ("weight", "<f4")])
 COLOR_DT = np.dtype([("r", "u1"), ("g", "u1"), ("b", "u1"), ("pad", "u1"), ("weight", "<f4")])
 ESDF_DT = np.dtype([("squared_distance_vox", "<f4"), ("parent_direction", "<i4", (3,)),
@@ -180,6 +185,32 @@ class AlignResult:
 
     def __repr__(self):
         return "AlignResult(%s, iterations=%d, n_valid=%d, rmse %.4g -> %.4g)" % (self.status_name, self.iterations, self.n_valid, self.rmse_first, self.rmse_last)
+
+
+class MergeResult:
+    """What merge_from left behind: `buffer` is the nvbx_merge_result record on the device (a uint8 tensor, written by the call's last launch);
+    the first field that is read copies it to the host once."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        self._host = None
+
+    def _r(self):
+        if self._host is None:
+            self._host = _lib.MergeResult.from_buffer_copy(self.buffer.cpu().numpy().tobytes())
+        return self._host
+
+    source_blocks = property(lambda self: int(self._r().source_blocks), doc="TSDF blocks of the source")
+    candidate_blocks = property(lambda self: int(self._r().candidate_blocks), doc="blocks of this map the merge went over")
+    blocks_allocated = property(lambda self: int(self._r().blocks_allocated), doc="... of which it did not have before")
+    voxels_fused = property(lambda self: int(self._r().voxels_fused))
+    color_voxels_fused = property(lambda self: int(self._r().color_voxels_fused))
+    status = property(lambda self: int(self._r().status))
+    status_name = property(lambda self: MERGE_STATUS_NAMES.get(int(self._r().status), "?"))
+
+    def __repr__(self):
+        return "MergeResult(%s, %d source blocks -> %d candidates (%d new), %d voxels, %d colour voxels)" % (
+            self.status_name, self.source_blocks, self.candidate_blocks, self.blocks_allocated, self.voxels_fused, self.color_voxels_fused)
 
 
 class Mapper:
@@ -862,6 +893,36 @@ class Mapper:
         self._around_torch_stream(lambda: self.lib.nvbx_linearize_points(self._h, ptr(p), n, _np_ptr(T), C.byref(o), ptr(buf), ptr(pl), ptr(r), ptr(g), ptr(v)))
         self._hold("_keep_a", [p])
         return AlignResult(buf), pl, r, g, v
+
+    # -- map merging (nvbx_merge_map; SEMANTICS.md "Map merging")
+    def merge_options(self, **kw):
+        """nvbx_merge_options: the library's defaults with the given fields replaced (min_weight, weight_scale, merge_color)."""
+        o = _lib.MergeOptions()
+        self.lib.nvbx_default_merge_options(C.byref(o))
+        for k, v in kw.items():
+            if k not in ("min_weight", "weight_scale", "merge_color"):
+                raise TypeError("unknown merge option %r" % k)
+            setattr(o, k, int(bool(v)) if k == "merge_color" else v)
+        return o
+
+    def merge_from(self, other, T_D_S, out=None, **options):
+        """Bring `other`'s TSDF and colour into this map under p_D = T_D_S p_S (row-major 4 x 4): -> MergeResult.  Missing blocks are allocated
+        (the pools grow; NvbxError with code -3 if max_block_capacity cannot hold them, this map then unchanged); `other` is not modified.
+        The launches run on this mapper's stream behind everything enqueued on `other`'s.  options: see merge_options.
+        out: a preallocated result buffer (uint8 tensor of MERGE_RESULT_BYTES bytes)."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(other, Mapper):
+            raise TypeError("merge_from needs a Mapper")
+        T = self._T(T_D_S); o = self.merge_options(**options)
+        if out is None:
+            buf = torch.empty(MERGE_RESULT_BYTES, dtype=torch.uint8, device=dev)
+        else:
+            buf = out
+            if buf.device != dev or buf.dtype != torch.uint8 or buf.numel() != MERGE_RESULT_BYTES or not buf.is_contiguous() or buf.data_ptr() % 8:
+                raise ValueError("the result buffer must be a contiguous 8-byte aligned uint8 tensor of %d bytes on %s" % (MERGE_RESULT_BYTES, dev))
+        self._around_torch_stream(lambda: self.lib.nvbx_merge_map(self._h, other._h, _np_ptr(T), C.byref(o), C.c_void_p(buf.data_ptr())))
+        return MergeResult(buf)
 
     def render(self, T_L_C, cam, subsampling=None, max_ray_length_m=None, color=True, normals=False, out=None):
         """The map seen from camera `cam` at pose T_L_C: -> (depth [rows/s, cols/s] f32, color [.., 3] u8 | None, normals [.., 3] f32 | None) on the

@@ -575,6 +575,47 @@ int nvbx_segment_features(nvbx_mapper* m, const void* queries_dev, int32_t n_que
                           int64_t* block_count_dev, nvbx_component* components_dev, int64_t capacity_components,
                           int64_t* component_count_dev);
 
+/* ---- frontiers and view gain (exploration; SEMANTICS.md "Frontiers and view gain") -------------------------------------------------
+ * Where known free space ends and the unseen begins, and how much unseen space a pose would look into.  A voxel with stored {d, w} is
+ * OBSERVED iff its block carries the TSDF layer and w >= min_weight, FREE iff observed and d > free_distance_m (a NaN d is not free),
+ * OCCUPIED iff observed and not free, UNKNOWN otherwise -- every voxel of a block that is not allocated or lies outside the addressable
+ * block range included.  All three calls are for TSDF mappers (an occupancy mapper: NVBX_E_INVALID), read TSDF voxels only, leave held-back
+ * work held back (as a TSDF nvbx_query_points does), write nothing to the map and are asynchronous on the mapper's stream.  On a refusal
+ * (NVBX_E_INVALID, nvbx_last_error set) nothing is launched and the mapper stays usable.
+ * nvbx_find_frontiers: a frontier voxel is a free voxel with nu >= min_unknown_neighbours (1 .. 6), nu = the number of unknown voxels among
+ *   its six face neighbours in GLOBAL voxel coordinates g = 8 block + v (across block borders), that lies inside box_min_max_vox = {min x, y, z,
+ *   max x, y, z} (host memory, inclusive, global voxel coordinates; NULL: unbounded).  The output has the shape nvbx_match_features returns and
+ *   feeds nvbx_label_components unchanged: one entry per TSDF block with at least one frontier voxel, entry order unspecified;
+ *   block_idx_dev[e] = the block's index; label_dev[e][512] = 0 for a frontier voxel, -1 otherwise; score_dev[e][512] (NULL: not written) =
+ *   (float)nu for a frontier voxel, 0 otherwise; voxel order t = vx 64 + vy 8 + vz.  *count_dev = the number of such blocks, also when it
+ *   exceeds capacity_blocks; entries from the capacity on are written nowhere; capacity_blocks 0 with NULL arrays only counts; an empty map
+ *   writes a count of 0.  Apart from the entry order the result is bit-specified.  Refused: min_unknown_neighbours outside 1 .. 6; a NaN
+ *   min_weight or free_distance_m; capacity_blocks < 0 or > 2^22; a NULL count_dev; a NULL block_idx_dev or label_dev with capacity_blocks > 0;
+ *   a box with min > max on an axis.
+ * nvbx_frontier_clusters: nvbx_find_frontiers, then nvbx_label_components over min(*block_count_dev, capacity_blocks) entries (read on the
+ *   device), in stream order without a host wait (the labelling's scratch grows as documented there).  A component's centroid is an
+ *   exploration goal, `voxels` the frontier's size, peak_score / peak_xyz its most open voxel.  Refusals: those of both calls.
+ * nvbx_view_gain: for each of n_views poses T_L_C_dev[n_views][16] (DEVICE memory, row-major 4 x 4, camera -> layer) the rays of
+ *   nvbx_render_view for `camera` at `subsampling` are walked in steps of one voxel size: sample k = 0, 1, ... lies at t_k = (k + 0.5) voxel_size
+ *   while t_k < max_range_m, in the voxel that contains o + t_k d (floor(p / voxel_size) per axis, f32).  An unknown sample counts one
+ *   unknown_samples, a free one one free_samples, an occupied one ends the ray and counts one rays_hit.  The samples count voxels ALONG RAYS,
+ *   not distinct voxels: neighbouring rays may count one voxel twice, and a ray may count a voxel it crosses diagonally more than once.
+ *   gains_dev[v] = the sums over the view's rays, rays = rows / s x cols / s.  A pose that is not finite or out of range (nvbx_render_view's
+ *   rule) is never an error: its record is all zero with rays = -1.  subsampling 0 / max_range_m <= 0: the mapper's sphere_tracing_subsampling
+ *   / sphere_tracing_max_ray_length_m.  Refused: what nvbx_render_view refuses of camera, subsampling and range; n_views < 0; a NULL
+ *   T_L_C_dev or gains_dev with n_views > 0; a NaN min_weight or free_distance_m.  n_views == 0 launches nothing. */
+typedef struct { int32_t rays, unknown_samples, free_samples, rays_hit; } nvbx_gain;      /* 16 bytes; offsets 0 4 8 12 */
+int nvbx_find_frontiers(nvbx_mapper* m, float min_weight, float free_distance_m, int32_t min_unknown_neighbours,
+                        const int32_t box_min_max_vox[6], nvbx_index3d* block_idx_dev, int32_t* label_dev, float* score_dev,
+                        int64_t capacity_blocks, int64_t* count_dev);
+int nvbx_frontier_clusters(nvbx_mapper* m, float min_weight, float free_distance_m, int32_t min_unknown_neighbours,
+                           const int32_t box_min_max_vox[6], int32_t connectivity, int32_t min_voxels, nvbx_index3d* block_idx_dev,
+                           int32_t* label_dev, float* score_dev, int32_t* component_id_dev, int64_t capacity_blocks,
+                           int64_t* block_count_dev, nvbx_component* components_dev, int64_t capacity_components,
+                           int64_t* component_count_dev);
+int nvbx_view_gain(nvbx_mapper* m, const float* T_L_C_dev, int32_t n_views, const nvbx_camera* camera, int32_t subsampling,
+                   float max_range_m, float min_weight, float free_distance_m, nvbx_gain* gains_dev);
+
 /* ---- map file (Mapper::saveLayerCake(path) -> bool, loadMap(path) -> bool: nvblox_node.cpp:1663-1668,1698-1703) -----------------
  * A path ending in .nvblx is written as an SQLITE database, like the reference's layer cake: table layers(layer_type, voxel_size,
  * block_size, voxel_bytes, num_blocks) + one table <layer_type>_blocks(index_x, index_y, index_z, data BLOB) per layer (tsdf_layer,

@@ -102,6 +102,11 @@ class Component(C.Structure):
                 ("sum_xyz", C.c_int64 * 3), ("peak_score", C.c_float), ("peak_xyz", C.c_int32 * 3)]
 
 
+class Gain(C.Structure):
+    """nvbx_gain: one view's record of nvbx_view_gain (16 bytes)"""
+    _fields_ = [("rays", C.c_int32), ("unknown_samples", C.c_int32), ("free_samples", C.c_int32), ("rays_hit", C.c_int32)]
+
+
 class AlignOptions(C.Structure):
     """nvbx_align_options (56 bytes); nvbx_default_align_options fills it"""
     _fields_ = [("max_iterations", C.c_int32), ("subsampling", C.c_int32), ("min_weight", C.c_float), ("huber_delta_m", C.c_float),
@@ -214,6 +219,9 @@ SIGNATURES = {
     "nvbx_match_points": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
     "nvbx_label_components": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
     "nvbx_segment_features": (C.c_int, [_vp, _vp, _i32, _i32, _f, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "nvbx_find_frontiers": (C.c_int, [_vp, _f, _f, _i32, _pi32, _vp, _vp, _vp, _i64, _vp]),
+    "nvbx_frontier_clusters": (C.c_int, [_vp, _f, _f, _i32, _pi32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "nvbx_view_gain": (C.c_int, [_vp, _vp, _i32, C.POINTER(Camera), _i32, _f, _f, _f, _vp]),
     "nvbx_default_align_options": (None, [C.POINTER(AlignOptions)]),
     "nvbx_align_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp]),
     "nvbx_align_depth": (C.c_int, [_vp, _vp, _i32, _i32, _vp, C.POINTER(Camera), C.POINTER(AlignOptions), _vp]),

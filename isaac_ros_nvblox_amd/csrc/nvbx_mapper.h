@@ -129,6 +129,8 @@ struct nvbx_mapper {
   nvbx::DevBuf align_buf;
   // map merging (merge.hip), as the destination: a 64-byte head of counters and the key set that counts the distinct candidate blocks
   nvbx::DevBuf merge_buf;
+  // frontier scan (frontier.hip), -DNVBX_FRONTIER_TWO_PASS variant only: 128 bytes of voxel classes per slot; the product's single pass needs none
+  nvbx::DevBuf frontier_scratch;
   // mesh arena
   float* mesh_vert = nullptr; float* mesh_nrm = nullptr; uint8_t* mesh_col = nullptr; int32_t* mesh_tri = nullptr;
   nvbx::MeshRecord* mesh_rec = nullptr;

@@ -1267,6 +1267,131 @@ class Mapper:
         nb = min(nb, cap)
         return idx[:nb], lab[:nb], sc[:nb], ids[:nb], self.components_view(rec, min(nc, ccap))
 
+    # -- frontiers and view gain (nvbx_find_frontiers / nvbx_frontier_clusters / nvbx_view_gain; SEMANTICS.md "Frontiers and view gain")
+    def _frontier_options(self, min_weight, free_distance_m, min_unknown, box_m):
+        """-> (min_weight, free_distance_m, min_unknown, box pointer | None); box_m = ((x0, y0, z0), (x1, y1, z1)) in metres, inclusive: the
+        voxels that contain the two corners, floor(p / voxel_size) in float32, bound the box"""
+        fd = float(self.params.voxel_size) if free_distance_m is None else float(free_distance_m)
+        if int(min_unknown) < 1 or int(min_unknown) > 6:
+            raise ValueError("min_unknown must be 1 .. 6, got %r" % (min_unknown,))
+        box = None
+        if box_m is not None:
+            b = np.asarray(box_m, np.float32).reshape(2, 3)
+            box = np.ascontiguousarray(np.floor(b / np.float32(self.params.voxel_size)).astype(np.int32).reshape(6))
+            if np.any(box[:3] > box[3:]):
+                raise ValueError("box_m has min > max on an axis: %r" % (box_m,))
+        return float(min_weight), fd, int(min_unknown), box
+
+    def _frontier_count(self, mw, fd, mu, box):
+        """the number of blocks that hold a frontier voxel: a counting scan (capacity 0), waited for"""
+        torch = self._torch
+        cnt = torch.empty(1, dtype=torch.int64, device=torch.device("cuda", self.device))
+        self._around_torch_stream(lambda: self.lib.nvbx_find_frontiers(
+            self._h, mw, fd, mu, box.ctypes.data_as(C.POINTER(C.c_int32)) if box is not None else None, None, None, None, 0, C.c_void_p(cnt.data_ptr())))
+        return int(cnt.item())
+
+    def find_frontiers(self, min_weight=1e-4, free_distance_m=None, min_unknown=1, box_m=None, out=None):
+        """The frontier voxels of the TSDF layer: free voxels (weight >= min_weight, distance > free_distance_m; None: one voxel size) with at
+        least min_unknown unknown voxels among their six face neighbours, inside box_m (((x0, y0, z0), (x1, y1, z1)) metres; None: everywhere).
+        -> (indices [n, 3] i32, labels [n, 512] i32: 0 on a frontier voxel, -1 elsewhere; scores [n, 512] f32: the number of unknown neighbours, 0
+        elsewhere; count: one int64) on the mapper's device, one entry per block that holds a frontier voxel in no particular order, voxel
+        t = vx 64 + vy 8 + vz -- the shape label_components takes.  Buffers are sized by a counting scan first (the call scans twice and waits once
+        for the count; unlike num_blocks that leaves held-back work held back).
+        out=(indices, labels, scores | None, count): preallocated tensors of any capacity n_cap, nothing is allocated and nothing waited for:
+        -> the same tuple untrimmed; count may exceed n_cap, entries from n_cap on are not written."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        mw, fd, mu, box = self._frontier_options(min_weight, free_distance_m, min_unknown, box_m)
+        if out is None:
+            cap = self._frontier_count(mw, fd, mu, box)
+            idx = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+            lab = torch.empty((cap, 512), dtype=torch.int32, device=dev)
+            sc = torch.empty((cap, 512), dtype=torch.float32, device=dev)
+            cnt = torch.empty(1, dtype=torch.int64, device=dev)
+        else:
+            idx, lab, sc, cnt = out
+            cap = int(idx.shape[0])
+            self._out_tensor(idx, (cap, 3), (torch.int32,), "indices")
+            self._out_tensor(lab, (cap, 512), (torch.int32,), "labels")
+            if sc is not None:
+                self._out_tensor(sc, (cap, 512), (torch.float32,), "scores")
+            self._out_tensor(cnt, (1,), (torch.int64,), "count")
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
+        self._around_torch_stream(lambda: self.lib.nvbx_find_frontiers(
+            self._h, mw, fd, mu, box.ctypes.data_as(C.POINTER(C.c_int32)) if box is not None else None, ptr(idx), ptr(lab), ptr(sc), cap,
+            C.c_void_p(cnt.data_ptr())))
+        if out is not None:
+            return idx, lab, sc, cnt
+        n = min(int(cnt.item()), cap)
+        return idx[:n], lab[:n], sc[:n], cnt
+
+    def frontier_clusters(self, min_weight=1e-4, free_distance_m=None, min_unknown=1, box_m=None, connectivity=26, min_voxels=1, out=None):
+        """From the map to exploration goals in one call: find_frontiers, then label_components over the result.  -> (indices [n, 3] i32,
+        labels [n, 512] i32, scores [n, 512] f32, ids [n, 512] i32, Components) on the mapper's device, trimmed, as segment_features returns: a
+        component's centroid_m is a goal, voxels the frontier's size, peak_score / peak_xyz its most open voxel.  Buffers are sized by a counting
+        scan first and for the worst-case component count; the call waits for that count and once for the two counts of the result.
+        out=(indices, labels, scores | None, ids, block_count, records | None, component_count): preallocated tensors of any capacities (the counts:
+        one int64 each), nothing is allocated and nothing waited for: -> the same tuple, untrimmed."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        conn, mv = self._segment_options(connectivity, min_voxels)
+        mw, fd, mu, box = self._frontier_options(min_weight, free_distance_m, min_unknown, box_m)
+        if out is None:
+            cap = self._frontier_count(mw, fd, mu, box)
+            idx = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+            lab = torch.empty((cap, 512), dtype=torch.int32, device=dev)
+            sc = torch.empty((cap, 512), dtype=torch.float32, device=dev)
+            ids = torch.empty((cap, 512), dtype=torch.int32, device=dev)
+            rec = self.component_records(cap * 512 // mv)
+            both = torch.empty(2, dtype=torch.int64, device=dev)
+            bcnt, ccnt = both[0:1], both[1:2]
+        else:
+            idx, lab, sc, ids, bcnt, rec, ccnt = out
+            cap = int(idx.shape[0])
+            self._out_tensor(idx, (cap, 3), (torch.int32,), "indices")
+            self._out_tensor(lab, (cap, 512), (torch.int32,), "labels")
+            if sc is not None:
+                self._out_tensor(sc, (cap, 512), (torch.float32,), "scores")
+            self._out_tensor(ids, (cap, 512), (torch.int32,), "ids")
+            self._out_tensor(bcnt, (1,), (torch.int64,), "block count")
+            self._records_out(rec, ccnt)
+        ccap = int(rec.shape[0]) if rec is not None else 0
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
+        self._around_torch_stream(lambda: self.lib.nvbx_frontier_clusters(
+            self._h, mw, fd, mu, box.ctypes.data_as(C.POINTER(C.c_int32)) if box is not None else None, conn, mv, ptr(idx), ptr(lab), ptr(sc),
+            ptr(ids), cap, C.c_void_p(bcnt.data_ptr()), ptr(rec), ccap, C.c_void_p(ccnt.data_ptr())))
+        if out is not None:
+            return idx, lab, sc, ids, bcnt, rec, ccnt
+        nb, nc = (int(v) for v in both.tolist())
+        nb = min(nb, cap)
+        return idx[:nb], lab[:nb], sc[:nb], ids[:nb], self.components_view(rec, min(nc, ccap))
+
+    def view_gain(self, poses, cam, subsampling=None, max_range_m=None, min_weight=1e-4, free_distance_m=None, out=None):
+        """How much unseen space each candidate pose would look into: poses (n, 4, 4) or (n, 16) float32 T_L_C (torch device tensor or numpy
+        array), the rays of render() for `cam` at `subsampling`, walked one voxel size per sample up to max_range_m (None: the mapper's
+        sphere_tracing_* parameters).  -> int32 [n, 4] on the mapper's device: rays, unknown_samples, free_samples, rays_hit per pose; a pose
+        that is not finite or out of range has rays = -1 and zeros.  Samples count voxels along rays, not distinct voxels.
+        out: a preallocated int32 [n, 4] tensor, nothing is allocated."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        k = self._cam(cam)
+        if not isinstance(poses, torch.Tensor):
+            poses = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)))
+        if poses.dtype != torch.float32 or poses.numel() % 16:
+            raise ValueError("poses must be (n, 4, 4) float32, got %s %s" % (tuple(poses.shape), poses.dtype))
+        p = self._dev(poses.reshape(-1, 16), torch.float32)
+        n = int(p.shape[0])
+        s = int(subsampling) if subsampling is not None else 0
+        if s < 0 or (subsampling is not None and s < 1):
+            raise ValueError("subsampling must be >= 1")
+        mw, fd, _, _ = self._frontier_options(min_weight, free_distance_m, 1, None)
+        g = torch.empty((n, 4), dtype=torch.int32, device=dev) if out is None else self._out_tensor(out, (n, 4), (torch.int32,), "gains")
+        self._around_torch_stream(lambda: self.lib.nvbx_view_gain(
+            self._h, C.c_void_p(p.data_ptr()) if n else None, n, C.byref(k), s, float(max_range_m) if max_range_m is not None else 0.0, mw, fd,
+            C.c_void_p(g.data_ptr()) if n else None), order=n > 0)
+        self._hold("_keep_vg", [p])      # (the kernel reads the poses: they, and an uploaded copy, live until the next call)
+        return g
+
     def mesh(self):
         """Mesh of the last update_color_mesh: dict block index tuple -> dict(vertices, normals, colors, triangles)."""
         nb, nv, nt = C.c_int64(), C.c_int64(), C.c_int64()

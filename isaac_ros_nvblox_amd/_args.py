@@ -1,0 +1,114 @@
+"""Argument coercion and output buffers of the mapper's reader calls (mapper.py, from the point queries down to view_gain).
+
+Pure functions: the target torch.device is an argument, nothing here touches the library or a stream, so they run with torch.device("cpu")
+on a machine without a GPU (tests/test_wrapper_args.py).  A reader call declares its outputs as a spec for `outputs` and adds no coercion
+code of its own ("Host language").
+"""
+import ctypes as C
+import numpy as np
+import torch
+
+F32, F16, I32, I64, U8 = (torch.float32,), (torch.float16,), (torch.int32,), (torch.int64,), (torch.uint8,)
+FLAG = (torch.bool, torch.uint8)      # what a `valid` / `hit` output may be: the kernels write one byte, 0 or 1
+
+
+def points3(a, dev, what="points"):
+    """-> a contiguous (n, 3) float32 tensor on `dev`.  A tensor is moved and made contiguous, never converted or reshaped; anything else
+    goes through numpy (converted to float32, reshaped to (-1, 3)) and is uploaded."""
+    if isinstance(a, torch.Tensor):
+        p = (a if a.device == dev else a.to(dev)).contiguous()
+    else:
+        p = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 3))).to(dev)
+    if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError("%s must be an (n, 3) float32 array, got %s %s" % (what, tuple(p.shape), p.dtype))
+    return p
+
+
+def outputs(out, spec, dev):
+    """Allocate a call's outputs, or check the caller's.  spec: rows (name, shape, dtypes, required, wanted).
+    out=None: -> a tensor of dtypes[0] per wanted row, None for the others.  Otherwise `out` holds one entry per row: a None in a required
+    row is refused, every tensor must lie on `dev`, have the row's shape, one of its dtypes and be contiguous; -> tuple(out)."""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dtypes[0], device=dev) if wanted else None for _, shape, dtypes, _, wanted in spec)
+    out = tuple(out)
+    if len(out) != len(spec):
+        raise ValueError("out must hold %d entries (%s), got %d" % (len(spec), ", ".join(row[0] for row in spec), len(out)))
+    for t, (name, shape, dtypes, required, _) in zip(out, spec):
+        if t is None:
+            if required:
+                raise ValueError("out needs a %s tensor" % name)
+        elif t.device != dev or tuple(t.shape) != tuple(shape) or t.dtype not in dtypes or not t.is_contiguous():
+            raise ValueError("out tensor for %s must be contiguous %s %s on %s, got %s %s" % (name, tuple(shape), dtypes[0], dev, tuple(t.shape), t.dtype))
+    return out
+
+
+def sparse_volume(out, dev, count_blocks, scores_required=True, all_queries=None, want_all=False, record_words=0, min_voxels=1):
+    """THE spec of the sparse voxel volume (match_features, segment_features, find_frontiers, frontier_clusters), over `outputs`:
+    indices [cap, 3] i32, labels [cap, 512] i32, scores [cap, 512] f32 (optional unless scores_required), then with all_queries = Q the score
+    matrix [cap, 512, Q] f32 (optional; allocated if want_all), then with record_words > 0 the component ids [cap, 512] i32, then the block
+    count (one int64), then with record_words > 0 the record table [any, record_words] i32 (optional) and the component count (one int64).
+    out=None: cap = count_blocks() (which may wait), the table holds the worst case cap 512 / min_voxels records.  Otherwise cap is
+    out[0]'s and the table's capacity its own.  -> (the tensors in that order, cap, counts); counts, out=None only, is the tensor to wait
+    for once: the block count, or with records the two-element tensor that both counts view."""
+    if out is None:
+        cap = int(count_blocks()); rcap = cap * 512 // min_voxels
+    else:
+        out = tuple(out)
+        if not out or out[0] is None:
+            raise ValueError("out needs an indices tensor")
+        cap = int(out[0].shape[0])
+        rcap = int(out[-2].shape[0]) if record_words and len(out) > 1 and out[-2] is not None else 0
+    spec = [("indices", (cap, 3), I32, True, True), ("labels", (cap, 512), I32, True, True), ("scores", (cap, 512), F32, scores_required, True)]
+    if all_queries is not None:
+        spec.append(("all scores", (cap, 512, all_queries), F32, False, want_all))
+    if record_words:
+        spec.append(("ids", (cap, 512), I32, True, True))
+    spec.append(("block count" if record_words else "count", (1,), I64, True, not record_words))
+    if record_words:
+        spec += [("components", (rcap, record_words), I32, False, True), ("count", (1,), I64, True, False)]
+    t = list(outputs(out, spec, dev))
+    if out is not None:
+        return tuple(t), cap, None
+    counts = t[-1]
+    if record_words:      # one tensor for both counts: one wait
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        t[-3], t[-1] = counts[0:1], counts[1:2]
+    return tuple(t), cap, counts
+
+
+def ptr(x):
+    """THE tensor -> c_void_p conversion: None and an empty tensor become NULL.  Every entry point the reader calls use takes NULL where
+    the count or capacity that sizes the tensor is 0 (its first check reads `n > 0 && !pointer`), and NULL for an optional output means
+    'not wanted', which is what an empty one is."""
+    return C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None
+
+
+def result_buffer(out, nbytes, dev):
+    """The device record an alignment or a merge writes its result into: `out`, checked, or a new one -- a contiguous, 8-byte aligned
+    uint8 tensor of nbytes on `dev`."""
+    if out is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if out.device != dev or out.dtype != torch.uint8 or out.numel() != nbytes or not out.is_contiguous() or out.data_ptr() % 8:
+        raise ValueError("the result buffer must be a contiguous 8-byte aligned uint8 tensor of %d bytes on %s" % (nbytes, dev))
+    return out
+
+
+def struct_options(struct, defaults_fn, kw, what):
+    """-> struct() filled by defaults_fn(byref(it)), then the fields `kw` names replaced; a name that is no field: TypeError.
+    A field called merge_color is a flag (any truthy value: 1)."""
+    o = struct()
+    defaults_fn(C.byref(o))
+    names = [f for f, _ in struct._fields_ if f != "pad"]
+    for k, v in kw.items():
+        if k not in names:
+            raise TypeError("unknown %s option %r" % (what, k))
+        setattr(o, k, int(bool(v)) if k == "merge_color" else v)
+    return o
+
+
+def subsampling_arg(subsampling):
+    """render / view_gain: None -> 0 (the mapper's sphere_tracing_subsampling), else an int >= 1"""
+    s = int(subsampling) if subsampling is not None else 0
+    if s < 0 or (subsampling is not None and s < 1):
+        raise ValueError("subsampling must be >= 1")
+    return s

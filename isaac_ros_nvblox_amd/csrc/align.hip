@@ -176,8 +176,6 @@ __global__ __launch_bounds__(SOLVE_TPB) void k_align_solve(AlignArgs a) {
   o->iterations = a.iter + 1; o->status = status;
 }
 
-static int align_fail(const char* who, const char* why) { set_error((std::string(who) + ": " + why).c_str()); return NVBX_E_INVALID; }
-
 // the checks and the launches of the three entry points.  depth != null: the depth form (pts null), else the point form.
 static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
               const float T[16], const nvbx_align_options* options, nvbx_align_result* res, int mode, float* out_p, float* out_r, float* out_g,
@@ -185,27 +183,27 @@ static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t 
   if (!m) return NVBX_E_INVALID;
   nvbx_align_options o;
   if (options) o = *options; else nvbx_default_align_options(&o);
-  if (!T || !res) return align_fail(who, "the pose and result_dev are required");
-  if ((uintptr_t)res & 7) return align_fail(who, "result_dev must be 8-byte aligned");
-  if (m->p.projective_layer_type == 1) return align_fail(who, "an occupancy mapper has no TSDF layer");
-  if (o.max_iterations < 1 || o.max_iterations > 64) return align_fail(who, "max_iterations must be 1 .. 64");
-  if (o.min_valid < 1) return align_fail(who, "min_valid must be >= 1");
+  if (!T || !res) return refuse(who, ": the pose and result_dev are required");
+  if ((uintptr_t)res & 7) return refuse(who, ": result_dev must be 8-byte aligned");
+  if (tsdf_reader_refused(m, who)) return NVBX_E_INVALID;
+  if (o.max_iterations < 1 || o.max_iterations > 64) return refuse(who, ": max_iterations must be 1 .. 64");
+  if (o.min_valid < 1) return refuse(who, ": min_valid must be >= 1");
   if (!(o.damping >= 0.0) || !(o.min_pivot_ratio >= 0.0) || !(o.stop_translation_m >= 0.0) || !(o.stop_rotation_rad >= 0.0) ||
       !std::isfinite(o.damping) || !std::isfinite(o.min_pivot_ratio) || !std::isfinite(o.stop_translation_m) || !std::isfinite(o.stop_rotation_rad))
-    return align_fail(who, "damping, min_pivot_ratio and the stop thresholds must be finite and >= 0");
+    return refuse(who, ": damping, min_pivot_ratio and the stop thresholds must be finite and >= 0");
   if (o.min_weight != o.min_weight || o.huber_delta_m != o.huber_delta_m || o.max_depth_m != o.max_depth_m)
-    return align_fail(who, "min_weight / huber_delta_m / max_depth_m is not a number");
-  if (!nvbx_pose_in_range(T, m->p.voxel_size * 8.0f, 0.0f)) return align_fail(who, "the pose is not finite or out of range");
+    return refuse(who, ": min_weight / huber_delta_m / max_depth_m is not a number");
+  if (!nvbx_pose_in_range(T, m->p.voxel_size * 8.0f, 0.0f)) return refuse(who, ": the pose is not finite or out of range");
   AlignArgs a{};
   if (depth || cam) {
-    if (!depth || rows <= 0 || cols <= 0 || !nvbx_camera_matches(cam, rows, cols)) return align_fail(who, "the depth image and a camera of its size are required");
-    if (o.subsampling < 1) return align_fail(who, "subsampling must be >= 1");
+    if (!depth || rows <= 0 || cols <= 0 || !nvbx_camera_matches(cam, rows, cols)) return refuse(who, ": the depth image and a camera of its size are required");
+    if (o.subsampling < 1) return refuse(who, ": subsampling must be >= 1");
     const int32_t rs = (rows + o.subsampling - 1) / o.subsampling, cs = (cols + o.subsampling - 1) / o.subsampling;
     a.depth = depth; a.cols = cols; a.cs = cs; a.s = o.subsampling;
     a.fu = cam->fu; a.fv = cam->fv; a.cu = cam->cu; a.cv = cam->cv; a.max_d = o.max_depth_m;
     n = (int64_t)rs * cs;
   } else {
-    if (n < 0 || (n > 0 && !pts)) return align_fail(who, "n points need points_xyz_dev");
+    if (n < 0 || (n > 0 && !pts)) return refuse(who, ": n points need points_xyz_dev");
     a.pts = pts;
   }
   NVBX_HIP(hipSetDevice(m->device));
@@ -248,7 +246,7 @@ extern "C" int nvbx_align_points(nvbx_mapper* m, const float* points_xyz_dev, in
 
 extern "C" int nvbx_align_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const float T_L_C_guess[16], const nvbx_camera* camera,
                                 const nvbx_align_options* options, nvbx_align_result* result_dev) {
-  if (m && (!depth_dev || !camera)) return align_fail("nvbx_align_depth", "the depth image and the camera are required");
+  if (m && (!depth_dev || !camera)) return refuse("nvbx_align_depth", ": the depth image and the camera are required");
   return align_run("nvbx_align_depth", m, nullptr, 0, depth_dev, rows, cols, camera, T_L_C_guess, options, result_dev, MODE_ALIGN, nullptr, nullptr, nullptr, nullptr);
 }
 

@@ -239,10 +239,10 @@ template <int RT> __global__ __launch_bounds__(256) void k_match_points(DMap m, 
 // ------------------------------------------------------------------------------------------------ C-ABI
 static int match_common(nvbx_mapper* m, const char* who, const void* queries_dev, int32_t n_queries, int32_t metric, MatchArgs* a, size_t* smem, int* rt) {
   if (!m) return NVBX_E_INVALID;
-  if (!m->feat_channels) { set_error((std::string(who) + ": call nvbx_enable_features first").c_str()); return NVBX_E_INVALID; }
-  if (n_queries < 1 || n_queries > 128) { set_error((std::string(who) + ": n_queries must be 1 .. 128").c_str()); return NVBX_E_INVALID; }
-  if (metric != NVBX_MATCH_DOT && metric != NVBX_MATCH_COSINE) { set_error((std::string(who) + ": unknown metric").c_str()); return NVBX_E_INVALID; }
-  if (!queries_dev || ((uintptr_t)queries_dev & 15)) { set_error((std::string(who) + ": queries_dev is NULL or not 16-byte aligned").c_str()); return NVBX_E_INVALID; }
+  if (!m->feat_channels) return refuse(who, ": call nvbx_enable_features first");
+  if (n_queries < 1 || n_queries > 128) return refuse(who, ": n_queries must be 1 .. 128");
+  if (metric != NVBX_MATCH_DOT && metric != NVBX_MATCH_COSINE) return refuse(who, ": unknown metric");
+  if (!queries_dev || ((uintptr_t)queries_dev & 15)) return refuse(who, ": queries_dev is NULL or not 16-byte aligned");
   a->val = static_cast<const half8*>(m->feat_val); a->w = m->feat_w; a->q = static_cast<const half8*>(queries_dev);
   a->nch = m->feat_channels / 8; a->Q = n_queries; a->metric = metric; a->vec4 = 0; a->min_weight = 0.0f;
   *rt = n_queries <= 32 ? 1 : n_queries <= 64 ? 2 : 4;

@@ -255,7 +255,7 @@ extern "C" int nvbx_integrate_features(nvbx_mapper* m, const void* feat_dev, int
                                        const nvbx_camera* camera) {
   if (!m || !feat_dev || !T_L_C || !camera || ((uintptr_t)feat_dev & 15)) { set_error("nvbx_integrate_features: invalid argument (the feature image is 16-byte aligned)"); return NVBX_E_INVALID; }
   if (!m->feat_channels) { set_error("nvbx_integrate_features: call nvbx_enable_features first"); return NVBX_E_INVALID; }
-  if (!image_dims_ok(camera->height, camera->width) || !(camera->fu > 0.0f) || !(camera->fv > 0.0f)) { set_error("nvbx_integrate_features: camera sides 1 .. 32768, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (!nvbx_camera_valid(camera)) { set_error("nvbx_integrate_features: camera sides 1 .. 32768, focal lengths > 0"); return NVBX_E_INVALID; }
   if (stride < 1 || rows_f < 1 || cols_f < 1 || (int64_t)cols_f * stride > camera->width || (int64_t)rows_f * stride > camera->height) {
     set_error("nvbx_integrate_features: stride >= 1, cols_f * stride <= camera width, rows_f * stride <= camera height"); return NVBX_E_INVALID; }
   if (!nvbx_pose_in_range(T_L_C, m->p.voxel_size * 8.0f, m->p.sphere_tracing_max_ray_length_m + m->p.max_integration_distance_m)) {

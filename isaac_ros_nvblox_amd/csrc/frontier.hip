@@ -34,10 +34,6 @@ struct FrontierArgs {
 // distance > free_dist (a NaN distance is not free), unknown = not observed
 __device__ inline bool fr_observed(float2 v, float min_weight) { return v.y >= min_weight; }
 __device__ inline bool fr_free(float2 v, float min_weight, float free_dist) { return fr_observed(v, min_weight) && v.x > free_dist; }
-__device__ inline bool fr_index_ok(int32_t x, int32_t y, int32_t z) {
-  const int32_t L = 1 << 20;
-  return x >= -L && x < L && y >= -L && y < L && z >= -L && z < L;
-}
 __device__ inline int fr_bit(u64 w, int b) { return (int)((w >> b) & 1ull); }
 
 #ifdef NVBX_FRONTIER_TWO_PASS
@@ -81,7 +77,7 @@ __global__ __launch_bounds__(FR_TPB) void k_find_frontiers(DMap m, FrontierArgs 
     if (t < 6) {      // face neighbour t: axis t >> 1, direction -1 / +1
       const int d = (t & 1) ? 1 : -1;
       const int32_t nx = bx + ((t >> 1) == 0 ? d : 0), ny = by + ((t >> 1) == 1 ? d : 0), nz = bz + ((t >> 1) == 2 ? d : 0);
-      s_nb[t] = fr_index_ok(nx, ny, nz) ? find_slot(m, nx, ny, nz, F_TSDF) : SLOT_NONE;
+      s_nb[t] = nvbx_index_in_range(nx, ny, nz) ? find_slot(m, nx, ny, nz, F_TSDF) : SLOT_NONE;
     }
     __syncthreads();
     if (w < 6) {
@@ -181,7 +177,7 @@ __global__ __launch_bounds__(GAIN_TPB) void k_view_gain(DMap m, GainArgs a) {
         const int32_t gx = (int32_t)floorf(NVBX_DIV(px, a.voxel_size)), gy = (int32_t)floorf(NVBX_DIV(py, a.voxel_size)), gz = (int32_t)floorf(NVBX_DIV(pz, a.voxel_size));
         const int32_t bx = gx >> 3, by = gy >> 3, bz = gz >> 3;
         if (!have || bx != lbx || by != lby || bz != lbz) {
-          lslot = fr_index_ok(bx, by, bz) ? find_slot(m, bx, by, bz, F_TSDF) : SLOT_NONE;
+          lslot = nvbx_index_in_range(bx, by, bz) ? find_slot(m, bx, by, bz, F_TSDF) : SLOT_NONE;
           lbx = bx; lby = by; lbz = bz; have = true;
         }
         float2 v = make_float2(0.0f, 0.0f);
@@ -201,11 +197,9 @@ __global__ __launch_bounds__(GAIN_TPB) void k_view_gain(DMap m, GainArgs a) {
 // ------------------------------------------------------------------------------------------------ C-ABI
 namespace {
 
-int refuse(const char* who, const char* why) { set_error((std::string(who) + why).c_str()); return NVBX_E_INVALID; }
-
 int frontier_check(const nvbx_mapper* m, const char* who, float min_weight, float free_distance_m, int32_t min_unknown, const int32_t* box,
                    const void* block_idx, const void* label, int64_t capacity, const void* count) {
-  if (m->p.projective_layer_type == 1) return refuse(who, ": an occupancy mapper has no TSDF layer");
+  if (tsdf_reader_refused(m, who)) return NVBX_E_INVALID;
   if (min_unknown < 1 || min_unknown > 6) return refuse(who, ": min_unknown_neighbours must be 1 .. 6");
   if (std::isnan(min_weight) || std::isnan(free_distance_m)) return refuse(who, ": min_weight / free_distance_m is not a number");
   if (capacity < 0 || capacity > FR_MAX_BLOCKS) return refuse(who, ": capacity_blocks must be 0 .. 2^22");
@@ -259,12 +253,9 @@ extern "C" int nvbx_frontier_clusters(nvbx_mapper* m, float min_weight, float fr
   int rc = frontier_check(m, who, min_weight, free_distance_m, min_unknown_neighbours, box_min_max_vox, block_idx_dev, label_dev, capacity_blocks, block_count_dev);
   if (rc) return rc;
   // nvbx_label_components' refusals, looked at before the scan is launched: a refused call launches nothing
-  if (connectivity != 6 && connectivity != 26) return refuse(who, ": connectivity must be 6 or 26");
-  if (min_voxels < 1) return refuse(who, ": min_voxels must be >= 1");
-  if (capacity_blocks > 0 && !component_id_dev) return refuse(who, ": component_id_dev is required with capacity_blocks > 0");
-  if (!component_count_dev) return refuse(who, ": the component count pointer is required");
-  if (capacity_components < 0 || (capacity_components > 0 && (!components_dev || ((uintptr_t)components_dev & 7))))
-    return refuse(who, ": components_dev must be 8-byte aligned memory for capacity_components >= 0 records");
+  rc = seg_check(who, connectivity, min_voxels, capacity_blocks > 0 && !component_id_dev ? ": component_id_dev is required with capacity_blocks > 0" : nullptr,
+                 components_dev, capacity_components, component_count_dev);
+  if (rc) return rc;
   rc = frontier_launch(m, min_weight, free_distance_m, min_unknown_neighbours, box_min_max_vox, block_idx_dev, label_dev, score_dev, capacity_blocks, block_count_dev);
   if (rc) return rc;
   return nvbx_label_components(m, block_idx_dev, label_dev, score_dev, capacity_blocks, block_count_dev, connectivity, min_voxels, component_id_dev,
@@ -275,10 +266,10 @@ extern "C" int nvbx_view_gain(nvbx_mapper* m, const float* T_L_C_dev, int32_t n_
                               float min_weight, float free_distance_m, nvbx_gain* gains_dev) {
   if (!m) return NVBX_E_INVALID;
   const char* who = "nvbx_view_gain";
-  if (m->p.projective_layer_type == 1) return refuse(who, ": an occupancy mapper has no TSDF layer");
+  if (tsdf_reader_refused(m, who)) return NVBX_E_INVALID;
   if (!camera || subsampling < 0 || n_views < 0) return refuse(who, ": invalid argument");
   if (n_views > 0 && (!T_L_C_dev || !gains_dev)) return refuse(who, ": T_L_C_dev and gains_dev are required with n_views > 0");
-  if (!(camera->fu > 0.0f) || !(camera->fv > 0.0f) || !image_dims_ok(camera->height, camera->width)) return refuse(who, ": invalid camera");
+  if (!nvbx_camera_valid(camera)) return refuse(who, ": invalid camera");
   const int32_t s = subsampling > 0 ? subsampling : std::max(1, m->p.sphere_tracing_subsampling);
   const int32_t srows = camera->height / s, scols = camera->width / s;
   if (srows < 2 || scols < 2) return refuse(who, ": image too small for the subsampling");
@@ -292,7 +283,7 @@ extern "C" int nvbx_view_gain(nvbx_mapper* m, const float* T_L_C_dev, int32_t n_
   a.poses = T_L_C_dev; a.n_views = n_views;
   a.fu = camera->fu; a.fv = camera->fv; a.cu = camera->cu; a.cv = camera->cv; a.subsample = s; a.srows = srows; a.scols = scols;
   a.voxel_size = m->p.voxel_size; a.max_range = reach;
-  a.pose_lim = ((float)(1 << 20) - 2.0f) * (m->p.voxel_size * 8.0f) - reach;      // (nvbx_pose_in_range's bound)
+  a.pose_lim = nvbx_pose_limit(m->p.voxel_size * 8.0f, reach);      // (nvbx_pose_in_range's bound)
   a.min_weight = min_weight; a.free_dist = free_distance_m;
   a.gains = reinterpret_cast<int32_t*>(gains_dev);
   NVBX_HIP(hipMemsetAsync(gains_dev, 0, sizeof(nvbx_gain) * (size_t)n_views, m->stream));

@@ -242,7 +242,7 @@ __global__ void k_merge_result(DMap dst, uint32_t frame_id, const MergeScratch* 
   *out = r;
 }
 
-static int merge_fail(const char* why) { set_error((std::string("nvbx_merge_map: ") + why).c_str()); return NVBX_E_INVALID; }
+static const char* const MERGE_WHO = "nvbx_merge_map";
 
 extern "C" void nvbx_default_merge_options(nvbx_merge_options* o) {
   if (!o) return;
@@ -250,19 +250,19 @@ extern "C" void nvbx_default_merge_options(nvbx_merge_options* o) {
 }
 
 extern "C" int nvbx_merge_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S[16], const nvbx_merge_options* options, nvbx_merge_result* result_dev) {
-  if (!dst || !src) return merge_fail("both mappers are required");
+  if (!dst || !src) return refuse(MERGE_WHO, ": both mappers are required");
   nvbx_merge_options o;
   if (options) o = *options; else nvbx_default_merge_options(&o);
-  if (!T_D_S || !result_dev) return merge_fail("the pose and result_dev are required");
-  if ((uintptr_t)result_dev & 7) return merge_fail("result_dev must be 8-byte aligned");
-  if (src == dst) return merge_fail("src and dst are the same mapper");
-  if (src->device != dst->device) return merge_fail("the mappers are on different devices");
-  if (src->p.voxel_size != dst->p.voxel_size) return merge_fail("the mappers' voxel sizes differ");
-  if (src->p.projective_layer_type != 0 || dst->p.projective_layer_type != 0) return merge_fail("both mappers must be TSDF mappers without a freespace layer (projective_layer_type 0)");
-  if (!nvbx_pose_in_range(T_D_S, dst->p.voxel_size * 8.0f, 0.0f)) return merge_fail("the pose is not finite or out of range");
-  if (!nvbx_merge_rotation_ok(T_D_S, nullptr, nullptr)) return merge_fail("the upper-left 3 x 3 of T_D_S is not a rotation (|R^T R - I| > 1e-5 or det <= 0)");
-  if (o.min_weight != o.min_weight) return merge_fail("min_weight is not a number");
-  if (!std::isfinite(o.weight_scale) || !(o.weight_scale > 0.0f)) return merge_fail("weight_scale must be finite and > 0");
+  if (!T_D_S || !result_dev) return refuse(MERGE_WHO, ": the pose and result_dev are required");
+  if ((uintptr_t)result_dev & 7) return refuse(MERGE_WHO, ": result_dev must be 8-byte aligned");
+  if (src == dst) return refuse(MERGE_WHO, ": src and dst are the same mapper");
+  if (src->device != dst->device) return refuse(MERGE_WHO, ": the mappers are on different devices");
+  if (src->p.voxel_size != dst->p.voxel_size) return refuse(MERGE_WHO, ": the mappers' voxel sizes differ");
+  if (src->p.projective_layer_type != 0 || dst->p.projective_layer_type != 0) return refuse(MERGE_WHO, ": both mappers must be TSDF mappers without a freespace layer (projective_layer_type 0)");
+  if (!nvbx_pose_in_range(T_D_S, dst->p.voxel_size * 8.0f, 0.0f)) return refuse(MERGE_WHO, ": the pose is not finite or out of range");
+  if (!nvbx_merge_rotation_ok(T_D_S, nullptr, nullptr)) return refuse(MERGE_WHO, ": the upper-left 3 x 3 of T_D_S is not a rotation (|R^T R - I| > 1e-5 or det <= 0)");
+  if (o.min_weight != o.min_weight) return refuse(MERGE_WHO, ": min_weight is not a number");
+  if (!std::isfinite(o.weight_scale) || !(o.weight_scale > 0.0f)) return refuse(MERGE_WHO, ": weight_scale must be finite and > 0");
   NVBX_HIP(hipSetDevice(dst->device));
   // src: held-back work is carried out; its block count sizes the key set (waits for src's stream)
   if (src->fetch_counters()) return NVBX_E_DEVICE;
@@ -277,7 +277,7 @@ extern "C" int nvbx_merge_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_
   a.merge_color = o.merge_color ? 1 : 0;
   // the key set: distinct candidates are at most 27 per source block; load <= 1/2
   uint64_t entries = 64; while (entries < (uint64_t)src_live * 54) entries <<= 1;
-  if (entries > (1ull << 31)) return merge_fail("the source map is too large to enumerate");
+  if (entries > (1ull << 31)) return refuse(MERGE_WHO, ": the source map is too large to enumerate");
   if (dst->merge_buf.ensure(dst->stream, MERGE_KEYS_OFFSET + (size_t)entries * 8)) return NVBX_E_DEVICE;
   MergeScratch* sc = dst->merge_buf.as<MergeScratch>();
   u64* keys = reinterpret_cast<u64*>(dst->merge_buf.as<unsigned char>() + MERGE_KEYS_OFFSET);

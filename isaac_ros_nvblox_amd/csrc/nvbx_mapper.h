@@ -1,4 +1,4 @@
-// nvbx_mapper.h -- host-side state of one mapper (one GPU, one stream).  Host code only.
+// nvbx_mapper.h -- host-side state of one mapper (one GPU, one stream).  Host code only, but for nvbx_index_in_range, which kernels call too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,6 +46,11 @@ void frames_register_stream(int device, hipStream_t stream);
 void frames_forget_owner(const void* owner, int device, hipStream_t stream);
 void set_error(const char* what, hipError_t e);
 void set_error(const char* what);
+// THE refusal of a C-ABI argument check: the error becomes who + why (why carries its own ": "), the call returns NVBX_E_INVALID
+inline int refuse(const char* who, const char* why) { set_error((std::string(who) + why).c_str()); return NVBX_E_INVALID; }
+// segment.hip.  nvbx_label_components' refusals in their order, for every call that ends in it; volume_why: what the caller found wrong with its
+// block arrays (their count, their pointers), null = nothing -- the one refusal whose condition and text differ between the callers
+int seg_check(const char* who, int32_t connectivity, int32_t min_voxels, const char* volume_why, const void* comps, int64_t cap, const void* count);
 // layers.hip.  API layer id -> internal slot flag (0 = this mapper cannot hold that layer); bytes of one voxel in the reference's struct layout
 uint32_t internal_layer(const nvbx_mapper* m, uint32_t layer);
 size_t ref_voxel_bytes(uint32_t layer);
@@ -61,15 +66,21 @@ static inline bool layer_listable(uint32_t l) { return layer_readable(l) || l ==
 static inline bool nvbx_camera_matches(const nvbx_camera* c, int32_t rows, int32_t cols) {
   return c && c->width == cols && c->height == rows && c->fu > 0.0f && c->fv > 0.0f;
 }
+// ... and one that comes without an image (rendering, view gain, feature frames) must describe an image the C-ABI would accept
+static inline bool nvbx_camera_valid(const nvbx_camera* c) {
+  return c && c->fu > 0.0f && c->fv > 0.0f && nvbx::image_dims_ok(c->height, c->width);
+}
 
 // Block indices are 21 bits per axis in the hash key (pack_key): a sensor pose is accepted only if it is finite and everything
 // within `reach` metres of it stays inside [-2^20, 2^20) blocks (419 km at 0.05 m voxels) -- beyond that keys would alias.
+// nvbx_pose_limit: the bound on |translation| per axis, also handed to the kernels that test ray origins and candidate poses on the device.
+static inline float nvbx_pose_limit(float block_size, float reach) { return ((float)(1 << 20) - 2.0f) * block_size - reach; }
 static inline bool nvbx_pose_in_range(const float T[16], float block_size, float reach) {
   for (int i = 0; i < 16; i++) if (!std::isfinite(T[i])) return false;
-  const float lim = ((float)(1 << 20) - 2.0f) * block_size - reach;
+  const float lim = nvbx_pose_limit(block_size, reach);
   return std::fabs(T[3]) < lim && std::fabs(T[7]) < lim && std::fabs(T[11]) < lim;
 }
-static inline bool nvbx_index_in_range(int32_t x, int32_t y, int32_t z) {
+__host__ __device__ static inline bool nvbx_index_in_range(int32_t x, int32_t y, int32_t z) {
   const int32_t L = 1 << 20;
   return x >= -L && x < L && y >= -L && y < L && z >= -L && z < L;
 }
@@ -261,6 +272,11 @@ struct nvbx_mapper {
   void span_begin(const char* name, hipStream_t s);
   void span_end(hipStream_t s);
 };
+
+// every call that reads the TSDF layer refuses an occupancy mapper: -> 0, or NVBX_E_INVALID with the error set
+static inline int tsdf_reader_refused(const nvbx_mapper* m, const char* who) {
+  return m->p.projective_layer_type == 1 ? nvbx::refuse(who, ": an occupancy mapper has no TSDF layer") : 0;
+}
 
 // every kernel launch of the library goes through this macro (name = the kernel's name in rocprof output)
 #define NVBX_LAUNCH_ON(m, s, kernel, grid, block, ...)                               \

@@ -47,7 +47,7 @@ extern "C" int nvbx_query_points(nvbx_mapper* m, uint32_t layer, const float* po
   if (!m || (layer != NVBX_LAYER_TSDF && layer != NVBX_LAYER_ESDF) || n < 0 || (n > 0 && (!points_xyz_dev || !distance_dev))) {
     set_error("nvbx_query_points: invalid argument"); return NVBX_E_INVALID;
   }
-  if (layer == NVBX_LAYER_TSDF && m->p.projective_layer_type == 1) { set_error("nvbx_query_points: an occupancy mapper has no TSDF layer"); return NVBX_E_INVALID; }
+  if (layer == NVBX_LAYER_TSDF && tsdf_reader_refused(m, "nvbx_query_points")) return NVBX_E_INVALID;
   if (n == 0) return NVBX_OK;
   if (layer == NVBX_LAYER_ESDF) {
     if (m->join_side()) return NVBX_E_DEVICE;                 // a held-back updateEsdf (colour deferral, held-back EDT) is carried out first

@@ -227,14 +227,14 @@ int launch_render(nvbx_mapper* m, int rl, dim3 grid, const RenderArgs& a) {
 
 // checks common to both calls + the march's parameters (options: NULL or fields <= 0 / < 0 = the mapper's parameters)
 int render_begin(nvbx_mapper* m, const nvbx_render_options* opt, float max_ray_length_m, bool with_color, const char* who, RenderArgs* a) {
-  if (m->p.projective_layer_type == 1) { set_error((std::string(who) + ": an occupancy mapper has no TSDF layer").c_str()); return NVBX_E_INVALID; }
+  if (tsdf_reader_refused(m, who)) return NVBX_E_INVALID;
   *a = RenderArgs{};
   a->voxel_size = m->p.voxel_size;
   a->trunc = m->p.truncation_distance_vox * m->p.voxel_size;
   a->max_len = max_ray_length_m > 0.0f ? max_ray_length_m : m->p.sphere_tracing_max_ray_length_m;
   a->max_steps = (opt && opt->max_steps > 0) ? opt->max_steps : m->p.sphere_tracing_max_steps;
   a->eps_m = ((opt && opt->surface_distance_epsilon_vox >= 0.0f) ? opt->surface_distance_epsilon_vox : m->p.sphere_tracing_surface_eps_vox) * m->p.voxel_size;
-  if (!std::isfinite(a->max_len)) { set_error((std::string(who) + ": max_ray_length_m is not finite").c_str()); return NVBX_E_INVALID; }
+  if (!std::isfinite(a->max_len)) return refuse(who, ": max_ray_length_m is not finite");
   NVBX_HIP(hipSetDevice(m->device));
   // Without a colour output the launch reads TSDF voxels only, which nothing that is held back writes: the held-back work stays held back and
   // the next integrateDepth is still a two-launch pipelined frame (as for the TSDF point query, query.hip).  A colour output reads the colour
@@ -249,7 +249,7 @@ extern "C" int nvbx_render_view_with(nvbx_mapper* m, const nvbx_render_options* 
                                      float max_ray_length_m, float* depth_dev, uint8_t* color_rgb_dev, float* normal_xyz_dev, int64_t capacity_pixels,
                                      int32_t* rows_out, int32_t* cols_out) {
   if (!m || !T_L_C || !camera || !rows_out || !cols_out || subsampling < 0) { set_error("nvbx_render_view: invalid argument"); return NVBX_E_INVALID; }
-  if (!(camera->fu > 0.0f) || !(camera->fv > 0.0f) || !image_dims_ok(camera->height, camera->width)) { set_error("nvbx_render_view: invalid camera"); return NVBX_E_INVALID; }
+  if (!nvbx_camera_valid(camera)) { set_error("nvbx_render_view: invalid camera"); return NVBX_E_INVALID; }
   const int32_t s = subsampling > 0 ? subsampling : std::max(1, m->p.sphere_tracing_subsampling);
   const int32_t srows = camera->height / s, scols = camera->width / s;
   if (srows < 2 || scols < 2) { set_error("nvbx_render_view: image too small for the subsampling"); return NVBX_E_INVALID; }
@@ -279,12 +279,12 @@ extern "C" int nvbx_render_view(nvbx_mapper* m, const float T_L_C[16], const nvb
 extern "C" int nvbx_cast_rays_with(nvbx_mapper* m, const nvbx_render_options* options, const float* origins_xyz_dev, const float* directions_xyz_dev, int64_t n,
                                    float max_ray_length_m, float* t_dev, uint8_t* hit_dev, uint8_t* color_rgb_dev, float* normal_xyz_dev) {
   if (!m || n < 0 || (n > 0 && (!origins_xyz_dev || !directions_xyz_dev || !t_dev))) { set_error("nvbx_cast_rays: invalid argument"); return NVBX_E_INVALID; }
-  if (m->p.projective_layer_type == 1) { set_error("nvbx_cast_rays: an occupancy mapper has no TSDF layer"); return NVBX_E_INVALID; }
+  if (tsdf_reader_refused(m, "nvbx_cast_rays")) return NVBX_E_INVALID;
   if (n == 0) return NVBX_OK;
   RenderArgs a;
   { const int rc = render_begin(m, options, max_ray_length_m, color_rgb_dev != nullptr, "nvbx_cast_rays", &a); if (rc) return rc; }
   a.origins = origins_xyz_dev; a.dirs = directions_xyz_dev; a.n = n;
-  a.origin_lim = ((float)(1 << 20) - 2.0f) * (m->p.voxel_size * 8.0f) - a.max_len;        // (nvbx_pose_in_range's bound, per ray)
+  a.origin_lim = nvbx_pose_limit(m->p.voxel_size * 8.0f, a.max_len);        // (nvbx_pose_in_range's bound, per ray)
   if (!(a.origin_lim > 0.0f)) { set_error("nvbx_cast_rays: max_ray_length_m reaches beyond the addressable block range (+-2^20 blocks)"); return NVBX_E_INVALID; }
   a.depth = t_dev; a.hit = hit_dev; a.color = color_rgb_dev; a.normal = normal_xyz_dev;
   const int rl = render_lanes(n);

@@ -338,18 +338,20 @@ __global__ __launch_bounds__(256) void k_seg_threshold(int32_t* label, float* sc
 // ------------------------------------------------------------------------------------------------ C-ABI
 constexpr int64_t SEG_MAX_BLOCKS = 1ll << 22;      // 2^22 x 512 voxel ids fill int32
 
-static int seg_check(const char* who, const void* block_idx, const void* label, int64_t n, int32_t connectivity, int32_t min_voxels, const void* ids,
-                     const void* comps, int64_t cap, const void* count) {
-  const char* why = nullptr;
-  if (connectivity != 6 && connectivity != 26) why = ": connectivity must be 6 or 26";
-  else if (min_voxels < 1) why = ": min_voxels must be >= 1";
-  else if (n < 0 || n > SEG_MAX_BLOCKS) why = ": the number of blocks must be 0 .. 2^22";
-  else if (n > 0 && (!block_idx || !label || !ids)) why = ": block_idx_dev, label_dev and component_id_dev are required";
-  else if (!count) why = ": the component count pointer is required";
-  else if (cap < 0 || (cap > 0 && (!comps || ((uintptr_t)comps & 7)))) why = ": components_dev must be 8-byte aligned memory for capacity_components >= 0 records";
-  if (!why) return NVBX_OK;
-  set_error((std::string(who) + why).c_str());
-  return NVBX_E_INVALID;
+// what is wrong with a call's n blocks of indices, labels and ids (null: nothing) -- seg_check's volume_why
+static const char* seg_volume_why(const void* block_idx, const void* label, int64_t n, const void* ids) {
+  if (n < 0 || n > SEG_MAX_BLOCKS) return ": the number of blocks must be 0 .. 2^22";
+  if (n > 0 && (!block_idx || !label || !ids)) return ": block_idx_dev, label_dev and component_id_dev are required";
+  return nullptr;
+}
+
+int nvbx::seg_check(const char* who, int32_t connectivity, int32_t min_voxels, const char* volume_why, const void* comps, int64_t cap, const void* count) {
+  if (connectivity != 6 && connectivity != 26) return refuse(who, ": connectivity must be 6 or 26");
+  if (min_voxels < 1) return refuse(who, ": min_voxels must be >= 1");
+  if (volume_why) return refuse(who, volume_why);
+  if (!count) return refuse(who, ": the component count pointer is required");
+  if (cap < 0 || (cap > 0 && (!comps || ((uintptr_t)comps & 7)))) return refuse(who, ": components_dev must be 8-byte aligned memory for capacity_components >= 0 records");
+  return NVBX_OK;
 }
 
 // the launches of nvbx_label_components; the arguments have been checked
@@ -383,7 +385,7 @@ extern "C" int nvbx_label_components(nvbx_mapper* m, const nvbx_index3d* block_i
                                      const int64_t* n_blocks_dev, int32_t connectivity, int32_t min_voxels, int32_t* component_id_dev,
                                      nvbx_component* components_dev, int64_t capacity_components, int64_t* count_dev) {
   if (!m) return NVBX_E_INVALID;
-  const int rc = seg_check("nvbx_label_components", block_idx_dev, label_dev, n_blocks, connectivity, min_voxels, component_id_dev, components_dev,
+  const int rc = seg_check("nvbx_label_components", connectivity, min_voxels, seg_volume_why(block_idx_dev, label_dev, n_blocks, component_id_dev), components_dev,
                            capacity_components, count_dev);
   if (rc) return rc;
   NVBX_HIP(hipSetDevice(m->device));
@@ -396,7 +398,7 @@ extern "C" int nvbx_segment_features(nvbx_mapper* m, const void* queries_dev, in
                                      int32_t* component_id_dev, int64_t capacity_blocks, int64_t* block_count_dev, nvbx_component* components_dev,
                                      int64_t capacity_components, int64_t* component_count_dev) {
   if (!m) return NVBX_E_INVALID;
-  int rc = seg_check("nvbx_segment_features", block_idx_dev, label_dev, capacity_blocks, connectivity, min_voxels, component_id_dev, components_dev,
+  int rc = seg_check("nvbx_segment_features", connectivity, min_voxels, seg_volume_why(block_idx_dev, label_dev, capacity_blocks, component_id_dev), components_dev,
                      capacity_components, component_count_dev);
   if (rc) return rc;
   rc = nvbx_match_features(m, queries_dev, n_queries, metric, min_weight, block_idx_dev, label_dev, score_dev, nullptr, capacity_blocks, block_count_dev);

@@ -9,7 +9,8 @@ import ctypes as C
 import os
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import F16, F32, FLAG, I32, I64, U8, ptr
 from ._lib import BoundingShape, Camera, Counters, Index3D, Lidar, Params
 
 LAYER_TSDF, LAYER_COLOR, LAYER_ESDF, LAYER_MESH, LAYER_OCCUPANCY, LAYER_FREESPACE = 1, 2, 4, 8, 16, 32
@@ -749,6 +750,33 @@ class Mapper:
         self.synchronize()
         return out.cpu().numpy()
 
+    # -- Reader calls, from the point queries down to view_gain.  Their argument coercion and output buffers live in _args.py: a call declares its
+    #    outputs as a spec of (name, shape, dtypes, required, wanted) rows and adds no coercion code of its own ("Host language").
+    @property
+    def _cuda(self):
+        return self._torch.device("cuda", self.device)
+
+    def _around_torch_stream(self, call, order=True):
+        """`call` enqueues on the mapper's stream, ordered behind torch's current stream (which produced the inputs) and ahead of it (which reads
+        the results): no host synchronisation either way.  order=False: a call that launches nothing."""
+        torch = self._torch
+        cur = torch.cuda.current_stream(self.device); ms = self.torch_stream()
+        other = order and ms.cuda_stream != cur.cuda_stream
+        if other:
+            ms.wait_stream(cur)
+        self._check(call())
+        if other:
+            cur.wait_stream(ms)
+
+    def _trim(self, counts, cap, volume, records=None):
+        """The tail of a call that allocated its own sparse volume: ONE wait, for `counts` (the block count, or the two-element tensor of block and
+        component count) -> the volume's tensors cut to min(block count, cap) blocks and, with a record table, its first min(component count,
+        its capacity) records as Components."""
+        c = counts.tolist()
+        n = min(c[0], cap)
+        cut = tuple(t[:n] if t is not None else None for t in volume)
+        return cut if records is None else cut + (self.components_view(records, min(c[-1], int(records.shape[0]))),)
+
     # -- interpolated point queries (nvbx_query_points; SEMANTICS.md "Point queries")
     def query_tsdf(self, points, min_weight=None, unknown_value=1000.0, out=None):
         """Trilinear TSDF distance and its gradient per metre at `points` ((n, 3) float32 torch tensor or numpy array, metres):
@@ -765,93 +793,27 @@ class Mapper:
     def _query(self, layer, points, min_weight, unknown_value, out):
         """Runs on the mapper's stream, ordered behind torch's current stream (which produced the points) and ahead of it (which
         reads the results): no host synchronisation either way."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(points, torch.Tensor):
-            p = points if points.device == dev else points.to(dev)
-            p = p.contiguous()
-        else:
-            p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
-        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
-            raise ValueError("points must be an (n, 3) float32 array, got %s %s" % (tuple(p.shape), p.dtype))
-        n = p.shape[0]
-        if out is None:
-            d = torch.empty(n, dtype=torch.float32, device=dev)
-            g = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            v = torch.empty(n, dtype=torch.bool, device=dev)
-        else:
-            d, g, v = out
-            for t, shape, dts in ((d, (n,), (torch.float32,)), (g, (n, 3), (torch.float32,)), (v, (n,), (torch.bool, torch.uint8))):
-                if t is not None and (t.device != dev or tuple(t.shape) != shape or t.dtype not in dts or not t.is_contiguous()):
-                    raise ValueError("out tensor %s %s does not fit %d points" % (tuple(t.shape), t.dtype, n))
-            if d is None:
-                raise ValueError("out needs a distance tensor")
-        self._around_torch_stream(lambda: self.lib.nvbx_query_points(
-            self._h, layer, C.c_void_p(p.data_ptr()), n, float(min_weight), float(unknown_value), C.c_void_p(d.data_ptr()),
-            C.c_void_p(g.data_ptr()) if g is not None else None, C.c_void_p(v.data_ptr()) if v is not None else None), order=n > 0)
+        dev = self._cuda
+        p = _args.points3(points, dev); n = p.shape[0]
+        d, g, v = _args.outputs(out, (("distance", (n,), F32, True, True), ("gradient", (n, 3), F32, False, True), ("valid", (n,), FLAG, False, True)), dev)
+        self._around_torch_stream(lambda: self.lib.nvbx_query_points(self._h, layer, ptr(p), n, float(min_weight), float(unknown_value), ptr(d), ptr(g), ptr(v)),
+                                  order=n > 0)
         self._hold("_keep_q", [p])      # (the kernel reads the points: they, and an uploaded copy, live until the next query)
         return d, g, v
-
-    # -- rendering and ray casts (nvbx_render_view / nvbx_cast_rays; SEMANTICS.md "Rendering and ray casts")
-    def _out_tensor(self, t, shape, dtypes, what):
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
-        if t.device != dev or tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous():
-            raise ValueError("out tensor for %s must be contiguous %s %s on %s, got %s %s" % (what, shape, dtypes[0], dev, tuple(t.shape), t.dtype))
-        return t
-
-    def _around_torch_stream(self, call, order=True):
-        """`call` enqueues on the mapper's stream, ordered behind torch's current stream (which produced the inputs) and ahead of it (which reads
-        the results): no host synchronisation either way.  order=False: a call that launches nothing."""
-        torch = self._torch
-        cur = torch.cuda.current_stream(self.device); ms = self.torch_stream()
-        other = order and ms.cuda_stream != cur.cuda_stream
-        if other:
-            ms.wait_stream(cur)
-        self._check(call())
-        if other:
-            cur.wait_stream(ms)
 
     # -- pose alignment (nvbx_align_points / nvbx_align_depth / nvbx_linearize_points; SEMANTICS.md "Pose alignment")
     def align_options(self, **kw):
         """nvbx_align_options: the library's defaults with the given fields replaced (max_iterations, subsampling, min_weight, huber_delta_m,
         damping, min_pivot_ratio, stop_translation_m, stop_rotation_rad, min_valid, max_depth_m)."""
-        o = _lib.AlignOptions()
-        self.lib.nvbx_default_align_options(C.byref(o))
-        names = [f for f, _ in _lib.AlignOptions._fields_]
-        for k, v in kw.items():
-            if k not in names:
-                raise TypeError("unknown alignment option %r" % k)
-            setattr(o, k, v)
-        return o
-
-    def _align_buffer(self, out):
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            return torch.empty(ALIGN_RESULT_BYTES, dtype=torch.uint8, device=dev)
-        if out.device != dev or out.dtype != torch.uint8 or out.numel() != ALIGN_RESULT_BYTES or not out.is_contiguous() or out.data_ptr() % 8:
-            raise ValueError("the result buffer must be a contiguous 8-byte aligned uint8 tensor of %d bytes on %s" % (ALIGN_RESULT_BYTES, dev))
-        return out
-
-    def _points(self, points):
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(points, torch.Tensor):
-            p = (points if points.device == dev else points.to(dev)).contiguous()
-        else:
-            p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
-        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
-            raise ValueError("points must be an (n, 3) float32 array, got %s %s" % (tuple(p.shape), p.dtype))
-        return p
+        return _args.struct_options(_lib.AlignOptions, self.lib.nvbx_default_align_options, kw, "alignment")
 
     def align_points(self, points, T_L_S_guess, out=None, **options):
         """Refine the pose of a sensor-frame cloud ((n, 3) float32 torch tensor or numpy array) against the TSDF, from T_L_S_guess: -> AlignResult.
         Every launch is enqueued at once on the mapper's stream, nothing waits on the host.  options: see align_options.
         out: a preallocated result buffer (uint8 tensor of ALIGN_RESULT_BYTES bytes), nothing is allocated."""
-        p = self._points(points); T = self._T(T_L_S_guess); o = self.align_options(**options); buf = self._align_buffer(out)
-        self._around_torch_stream(lambda: self.lib.nvbx_align_points(self._h, C.c_void_p(p.data_ptr()), p.shape[0], _np_ptr(T), C.byref(o),
-                                                                     C.c_void_p(buf.data_ptr())))
+        p = _args.points3(points, self._cuda); T = self._T(T_L_S_guess); o = self.align_options(**options)
+        buf = _args.result_buffer(out, ALIGN_RESULT_BYTES, self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_align_points(self._h, ptr(p), p.shape[0], _np_ptr(T), C.byref(o), ptr(buf)))
         self._hold("_keep_a", [p])      # (the launches read the points: they, and an uploaded copy, live until the next alignment)
         return AlignResult(buf)
 
@@ -861,9 +823,11 @@ class Mapper:
         d = self._dev(depth, self._torch.float32)
         if d.dim() != 2:
             raise ValueError("depth must be a (rows, cols) image")
-        T = self._T(T_L_C_guess); o = self.align_options(**options); buf = self._align_buffer(out); k = self._cam(cam)
+        T = self._T(T_L_C_guess); o = self.align_options(**options); k = self._cam(cam)
+        buf = _args.result_buffer(out, ALIGN_RESULT_BYTES, self._cuda)
+        # (a non-collapsing pointer: nvbx_align_depth refuses a NULL image before it looks at its size)
         self._around_torch_stream(lambda: self.lib.nvbx_align_depth(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k),
-                                                                    C.byref(o), C.c_void_p(buf.data_ptr())))
+                                                                    C.byref(o), ptr(buf)))
         self._hold("_keep_a", [d])
         return AlignResult(buf)
 
@@ -872,24 +836,13 @@ class Mapper:
         on the mapper's device; the per-point tensors are None with per_point=False.  They are bit for bit nvbx_transform_pointcloud and
         query_tsdf(unknown_value=0) at those points.  out=(buffer | None, points_L | None, residual | None, gradient | None, valid | None):
         preallocated tensors, `out` then decides what is written (a None per-point entry is not) and per_point is not looked at."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
-        p = self._points(points); n = p.shape[0]
+        dev = self._cuda
+        p = _args.points3(points, dev); n = p.shape[0]
         T = self._T(T_L_S); o = self.align_options(**options)
-        if out is None:
-            buf = self._align_buffer(None)
-            pl = torch.empty((n, 3), dtype=torch.float32, device=dev) if per_point else None
-            r = torch.empty(n, dtype=torch.float32, device=dev) if per_point else None
-            g = torch.empty((n, 3), dtype=torch.float32, device=dev) if per_point else None
-            v = torch.empty(n, dtype=torch.bool, device=dev) if per_point else None
-        else:
-            buf, pl, r, g, v = out
-            buf = self._align_buffer(buf)
-            for t, shape, dts, what in ((pl, (n, 3), (torch.float32,), "points_L"), (r, (n,), (torch.float32,), "residual"),
-                                        (g, (n, 3), (torch.float32,), "gradient"), (v, (n,), (torch.bool, torch.uint8), "valid")):
-                if t is not None:
-                    self._out_tensor(t, shape, dts, what)
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None      # noqa: E731
+        buf_out, rest = (None, None) if out is None else (out[0], out[1:])
+        buf = _args.result_buffer(buf_out, ALIGN_RESULT_BYTES, dev)
+        pl, r, g, v = _args.outputs(rest, (("points_L", (n, 3), F32, False, per_point), ("residual", (n,), F32, False, per_point),
+                                           ("gradient", (n, 3), F32, False, per_point), ("valid", (n,), FLAG, False, per_point)), dev)
         self._around_torch_stream(lambda: self.lib.nvbx_linearize_points(self._h, ptr(p), n, _np_ptr(T), C.byref(o), ptr(buf), ptr(pl), ptr(r), ptr(g), ptr(v)))
         self._hold("_keep_a", [p])
         return AlignResult(buf), pl, r, g, v
@@ -897,63 +850,35 @@ class Mapper:
     # -- map merging (nvbx_merge_map; SEMANTICS.md "Map merging")
     def merge_options(self, **kw):
         """nvbx_merge_options: the library's defaults with the given fields replaced (min_weight, weight_scale, merge_color)."""
-        o = _lib.MergeOptions()
-        self.lib.nvbx_default_merge_options(C.byref(o))
-        for k, v in kw.items():
-            if k not in ("min_weight", "weight_scale", "merge_color"):
-                raise TypeError("unknown merge option %r" % k)
-            setattr(o, k, int(bool(v)) if k == "merge_color" else v)
-        return o
+        return _args.struct_options(_lib.MergeOptions, self.lib.nvbx_default_merge_options, kw, "merge")
 
     def merge_from(self, other, T_D_S, out=None, **options):
         """Bring `other`'s TSDF and colour into this map under p_D = T_D_S p_S (row-major 4 x 4): -> MergeResult.  Missing blocks are allocated
         (the pools grow; NvbxError with code -3 if max_block_capacity cannot hold them, this map then unchanged); `other` is not modified.
         The launches run on this mapper's stream behind everything enqueued on `other`'s.  options: see merge_options.
         out: a preallocated result buffer (uint8 tensor of MERGE_RESULT_BYTES bytes)."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
         if not isinstance(other, Mapper):
             raise TypeError("merge_from needs a Mapper")
         T = self._T(T_D_S); o = self.merge_options(**options)
-        if out is None:
-            buf = torch.empty(MERGE_RESULT_BYTES, dtype=torch.uint8, device=dev)
-        else:
-            buf = out
-            if buf.device != dev or buf.dtype != torch.uint8 or buf.numel() != MERGE_RESULT_BYTES or not buf.is_contiguous() or buf.data_ptr() % 8:
-                raise ValueError("the result buffer must be a contiguous 8-byte aligned uint8 tensor of %d bytes on %s" % (MERGE_RESULT_BYTES, dev))
-        self._around_torch_stream(lambda: self.lib.nvbx_merge_map(self._h, other._h, _np_ptr(T), C.byref(o), C.c_void_p(buf.data_ptr())))
+        buf = _args.result_buffer(out, MERGE_RESULT_BYTES, self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_merge_map(self._h, other._h, _np_ptr(T), C.byref(o), ptr(buf)))
         return MergeResult(buf)
 
+    # -- rendering and ray casts (nvbx_render_view / nvbx_cast_rays; SEMANTICS.md "Rendering and ray casts")
     def render(self, T_L_C, cam, subsampling=None, max_ray_length_m=None, color=True, normals=False, out=None):
         """The map seen from camera `cam` at pose T_L_C: -> (depth [rows/s, cols/s] f32, color [.., 3] u8 | None, normals [.., 3] f32 | None) on the
         mapper's device.  depth 0 = no surface.  subsampling / max_ray_length_m None: the mapper's sphere_tracing_* parameters.
         out=(depth, color | None, normals | None): preallocated tensors, nothing is allocated; `out` then decides what is computed (a None
         entry is not) and the color / normals flags are not looked at."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
         k = self._cam(cam); T = self._T(T_L_C)
-        s = int(subsampling) if subsampling is not None else 0
-        if s < 0 or (subsampling is not None and s < 1):
-            raise ValueError("subsampling must be >= 1")
+        s = _args.subsampling_arg(subsampling)
         s_eff = s if s > 0 else max(1, self.params.sphere_tracing_subsampling)
         rows, cols = k.height // s_eff, k.width // s_eff
-        if out is None:
-            d = torch.empty((rows, cols), dtype=torch.float32, device=dev)
-            c = torch.empty((rows, cols, 3), dtype=torch.uint8, device=dev) if color else None
-            nr = torch.empty((rows, cols, 3), dtype=torch.float32, device=dev) if normals else None
-        else:
-            d, c, nr = out
-            if d is None:
-                raise ValueError("out needs a depth tensor")
-            self._out_tensor(d, (rows, cols), (torch.float32,), "depth")
-            if c is not None:
-                self._out_tensor(c, (rows, cols, 3), (torch.uint8,), "color")
-            if nr is not None:
-                self._out_tensor(nr, (rows, cols, 3), (torch.float32,), "normals")
+        d, c, nr = _args.outputs(out, (("depth", (rows, cols), F32, True, True), ("color", (rows, cols, 3), U8, False, color),
+                                       ("normals", (rows, cols, 3), F32, False, normals)), self._cuda)
         r_, c_ = C.c_int32(), C.c_int32()
         self._around_torch_stream(lambda: self.lib.nvbx_render_view(
-            self._h, _np_ptr(T), C.byref(k), s, float(max_ray_length_m) if max_ray_length_m is not None else 0.0, C.c_void_p(d.data_ptr()),
-            C.c_void_p(c.data_ptr()) if c is not None else None, C.c_void_p(nr.data_ptr()) if nr is not None else None, d.numel(),
+            self._h, _np_ptr(T), C.byref(k), s, float(max_ray_length_m) if max_ray_length_m is not None else 0.0, ptr(d), ptr(c), ptr(nr), d.numel(),
             C.byref(r_), C.byref(c_)))
         assert (r_.value, c_.value) == (rows, cols)
         return d, c, nr
@@ -963,38 +888,13 @@ class Mapper:
         -> (t [n] f32 metres, 0 = no hit; hit [n] bool; color [n, 3] u8 | None; normals [n, 3] f32 | None) on the mapper's device.
         out=(t, hit | None, color | None, normals | None): preallocated tensors, nothing is allocated; `out` then decides what is computed
         (a None entry is not) and the color / normals flags are not looked at."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
-
-        def rays(a, what):
-            if isinstance(a, torch.Tensor):
-                p = (a if a.device == dev else a.to(dev)).contiguous()
-            else:
-                p = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 3))).to(dev)
-            if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
-                raise ValueError("%s must be an (n, 3) float32 array, got %s %s" % (what, tuple(p.shape), p.dtype))
-            return p
-        o = rays(origins, "origins"); dr = rays(directions, "directions")
+        dev = self._cuda
+        o = _args.points3(origins, dev, "origins"); dr = _args.points3(directions, dev, "directions")
         if o.shape != dr.shape:
             raise ValueError("origins %s and directions %s differ in shape" % (tuple(o.shape), tuple(dr.shape)))
         n = o.shape[0]
-        if out is None:
-            t = torch.empty(n, dtype=torch.float32, device=dev)
-            h = torch.empty(n, dtype=torch.bool, device=dev)
-            c = torch.empty((n, 3), dtype=torch.uint8, device=dev) if color else None
-            nr = torch.empty((n, 3), dtype=torch.float32, device=dev) if normals else None
-        else:
-            t, h, c, nr = out
-            if t is None:
-                raise ValueError("out needs a t tensor")
-            self._out_tensor(t, (n,), (torch.float32,), "t")
-            if h is not None:
-                self._out_tensor(h, (n,), (torch.bool, torch.uint8), "hit")
-            if c is not None:
-                self._out_tensor(c, (n, 3), (torch.uint8,), "color")
-            if nr is not None:
-                self._out_tensor(nr, (n, 3), (torch.float32,), "normals")
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None      # noqa: E731
+        t, h, c, nr = _args.outputs(out, (("t", (n,), F32, True, True), ("hit", (n,), FLAG, False, True), ("color", (n, 3), U8, False, color),
+                                          ("normals", (n, 3), F32, False, normals)), dev)
         self._around_torch_stream(lambda: self.lib.nvbx_cast_rays(
             self._h, ptr(o), ptr(dr), n, float(max_ray_length_m) if max_ray_length_m is not None else 0.0, ptr(t), ptr(h), ptr(c), ptr(nr)))
         self._hold("_keep_r", [o, dr])      # (the kernel reads the rays: they, and an uploaded copy, live until the next cast)
@@ -1028,24 +928,10 @@ class Mapper:
         """The feature voxel that contains each of `points` ((n, 3) float32 torch tensor or numpy array, metres): -> (features [n, C] f16,
         weights [n] f32) on the mapper's device; weight 0 and zeros where the map holds no features (never an error).
         out=(features, weights): preallocated tensors, nothing is allocated."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(points, torch.Tensor):
-            p = (points if points.device == dev else points.to(dev)).contiguous()
-        else:
-            p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
-        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
-            raise ValueError("points must be an (n, 3) float32 array, got %s %s" % (tuple(p.shape), p.dtype))
-        n = p.shape[0]; ch = getattr(self, "feature_channels", 0)
-        if out is None:
-            f = torch.empty((n, ch), dtype=torch.float16, device=dev)
-            w = torch.empty(n, dtype=torch.float32, device=dev)
-        else:
-            f, w = out
-            self._out_tensor(f, (n, ch), (torch.float16,), "features")
-            self._out_tensor(w, (n,), (torch.float32,), "weights")
-        self._around_torch_stream(lambda: self.lib.nvbx_query_features(
-            self._h, C.c_void_p(p.data_ptr()), n, C.c_void_p(f.data_ptr()), C.c_void_p(w.data_ptr())), order=n > 0)
+        dev = self._cuda
+        p = _args.points3(points, dev); n = p.shape[0]; ch = getattr(self, "feature_channels", 0)
+        f, w = _args.outputs(out, (("features", (n, ch), F16, True, True), ("weights", (n,), F32, True, True)), dev)
+        self._around_torch_stream(lambda: self.lib.nvbx_query_features(self._h, ptr(p), n, ptr(f), ptr(w)), order=n > 0)
         self._hold("_keep_fq", [p])
         return f, w
 
@@ -1084,65 +970,28 @@ class Mapper:
         out=(indices, labels, scores, all | None, count): preallocated tensors of any capacity n_cap (count: one int64), nothing is allocated and
         nothing waited for: -> (indices, labels, scores, all | None, count) untrimmed; count (a device tensor) may exceed n_cap, entries from n_cap on
         are not written; `out` then decides whether the score matrix is computed and the all_scores flag is not looked at."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
         q, nq, mid = self._queries(queries, metric)
-        if out is None:
-            cap = self.num_blocks(LAYER_FEATURE)
-            idx = torch.empty((cap, 3), dtype=torch.int32, device=dev)
-            lab = torch.empty((cap, 512), dtype=torch.int32, device=dev)
-            sc = torch.empty((cap, 512), dtype=torch.float32, device=dev)
-            al = torch.empty((cap, 512, nq), dtype=torch.float32, device=dev) if all_scores else None
-            cnt = torch.empty(1, dtype=torch.int64, device=dev)
-        else:
-            idx, lab, sc, al, cnt = out
-            cap = int(idx.shape[0])
-            self._out_tensor(idx, (cap, 3), (torch.int32,), "indices")
-            self._out_tensor(lab, (cap, 512), (torch.int32,), "labels")
-            self._out_tensor(sc, (cap, 512), (torch.float32,), "scores")
-            if al is not None:
-                self._out_tensor(al, (cap, 512, nq), (torch.float32,), "all scores")
-            self._out_tensor(cnt, (1,), (torch.int64,), "count")
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
-        self._around_torch_stream(lambda: self.lib.nvbx_match_features(
-            self._h, C.c_void_p(q.data_ptr()), nq, mid, float(min_weight), ptr(idx), ptr(lab), ptr(sc), ptr(al), cap, C.c_void_p(cnt.data_ptr())))
+        (idx, lab, sc, al, cnt), cap, counts = _args.sparse_volume(out, self._cuda, lambda: self.num_blocks(LAYER_FEATURE), all_queries=nq, want_all=all_scores)
+        self._around_torch_stream(lambda: self.lib.nvbx_match_features(self._h, ptr(q), nq, mid, float(min_weight), ptr(idx), ptr(lab), ptr(sc), ptr(al), cap, ptr(cnt)))
         self._hold("_keep_mq", [q])      # (the kernel reads the queries: they, and an uploaded copy, live until the next match)
-        if out is not None:
-            return idx, lab, sc, al, cnt
-        n = min(int(cnt.item()), cap)
-        return idx[:n], lab[:n], sc[:n], (al[:n] if al is not None else None)
+        return (idx, lab, sc, al, cnt) if out is not None else self._trim(counts, cap, (idx, lab, sc, al))
 
     def match_points(self, points, queries, metric="cosine", out=None):
         """Score the feature voxel that contains each of `points` ((n, 3) float32 torch tensor or numpy array, metres) against `queries`:
         -> (scores [n, Q] f32, weights [n] f32) on the mapper's device; weight 0 and zero scores where query_features would return weight 0.
         out=(scores, weights): preallocated tensors, nothing is allocated."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
+        dev = self._cuda
         q, nq, mid = self._queries(queries, metric)
-        if isinstance(points, torch.Tensor):
-            p = (points if points.device == dev else points.to(dev)).contiguous()
-        else:
-            p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
-        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
-            raise ValueError("points must be an (n, 3) float32 array, got %s %s" % (tuple(p.shape), p.dtype))
-        n = p.shape[0]
-        if out is None:
-            s = torch.empty((n, nq), dtype=torch.float32, device=dev)
-            w = torch.empty(n, dtype=torch.float32, device=dev)
-        else:
-            s, w = out
-            self._out_tensor(s, (n, nq), (torch.float32,), "scores")
-            self._out_tensor(w, (n,), (torch.float32,), "weights")
-        self._around_torch_stream(lambda: self.lib.nvbx_match_points(
-            self._h, C.c_void_p(p.data_ptr()), n, C.c_void_p(q.data_ptr()), nq, mid, C.c_void_p(s.data_ptr()), C.c_void_p(w.data_ptr())), order=n > 0)
+        p = _args.points3(points, dev); n = p.shape[0]
+        s, w = _args.outputs(out, (("scores", (n, nq), F32, True, True), ("weights", (n,), F32, True, True)), dev)
+        self._around_torch_stream(lambda: self.lib.nvbx_match_points(self._h, ptr(p), n, ptr(q), nq, mid, ptr(s), ptr(w)), order=n > 0)
         self._hold("_keep_mp", [p, q])
         return s, w
 
     # -- feature segmentation (nvbx_label_components / nvbx_segment_features; SEMANTICS.md "Feature segmentation")
     def component_records(self, capacity):
         """An uninitialised table of `capacity` nvbx_component records for out=: an int32 [capacity, 18] device tensor (72 bytes a record)."""
-        torch = self._torch
-        return torch.empty((int(capacity), COMPONENT_WORDS), dtype=torch.int32, device=torch.device("cuda", self.device))
+        return self._torch.empty((int(capacity), COMPONENT_WORDS), dtype=self._torch.int32, device=self._cuda)
 
     def components_view(self, records, n=None, centroid=True):
         """The fields of a record table (component_records) as device tensors viewing it, trimmed to the first n records: -> Components.  centroid_m
@@ -1171,12 +1020,6 @@ class Mapper:
             raise ValueError("min_voxels must be >= 1, got %r" % (min_voxels,))
         return int(connectivity), int(min_voxels)
 
-    def _records_out(self, rec, cnt):
-        torch = self._torch
-        if rec is not None:
-            self._out_tensor(rec, (int(rec.shape[0]), COMPONENT_WORDS), (torch.int32,), "components")
-        self._out_tensor(cnt, (1,), (torch.int64,), "count")
-
     def label_components(self, indices, labels, scores=None, connectivity=6, min_voxels=1, out=None):
         """Connected components of a labelled sparse voxel volume of the shape match_features returns: indices (n, 3) int32 distinct block indices,
         labels (n, 512) int32 (< 0: background), scores (n, 512) float32 or None -- torch device tensors or numpy arrays, voxel t = vx 64 + vy 8 + vz.
@@ -1188,7 +1031,6 @@ class Mapper:
         nothing waited for: -> (ids, records, count) as given; count (a device tensor) may exceed the capacity, records from the capacity on are
         not written (ids still name them); components_view(records) gives the fields."""
         torch = self._torch
-        dev = torch.device("cuda", self.device)
         conn, mv = self._segment_options(connectivity, min_voxels)
         if not isinstance(indices, torch.Tensor):
             indices = torch.from_numpy(np.ascontiguousarray(np.asarray(indices, np.int32).reshape(-1, 3)))
@@ -1201,21 +1043,14 @@ class Mapper:
         if lab.shape[0] != n or (sc is not None and sc.shape[0] != n):
             raise ValueError("indices, labels and scores differ in their number of blocks")
         if out is None:
-            ids = torch.empty((n, 512), dtype=torch.int32, device=dev)
-            rec = self.component_records(n * 512 // mv)
-            cnt = torch.empty(1, dtype=torch.int64, device=dev)
+            cap = n * 512 // mv
         else:
-            ids, rec, cnt = out
-            self._out_tensor(ids, (n, 512), (torch.int32,), "ids")
-            self._records_out(rec, cnt)
-        cap = int(rec.shape[0]) if rec is not None else 0
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
-        self._around_torch_stream(lambda: self.lib.nvbx_label_components(
-            self._h, ptr(idx), ptr(lab), ptr(sc), n, None, conn, mv, ptr(ids), ptr(rec), cap, C.c_void_p(cnt.data_ptr())))
+            cap = int(out[1].shape[0]) if len(out) > 1 and out[1] is not None else 0
+        ids, rec, cnt = _args.outputs(out, (("ids", (n, 512), I32, True, True), ("components", (cap, COMPONENT_WORDS), I32, False, True),
+                                            ("count", (1,), I64, True, True)), self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_label_components(self._h, ptr(idx), ptr(lab), ptr(sc), n, None, conn, mv, ptr(ids), ptr(rec), cap, ptr(cnt)))
         self._hold("_keep_lc", [idx, lab, sc])      # (the kernels read the volume: it, and an uploaded copy, live until the next call)
-        if out is not None:
-            return ids, rec, cnt
-        return ids, self.components_view(rec, min(int(cnt.item()), cap))
+        return (ids, rec, cnt) if out is not None else (ids,) + self._trim(cnt, 0, (), rec)
 
     def segment_features(self, queries, metric="cosine", min_weight=1.0, min_score=None, connectivity=6, min_voxels=1, out=None):
         """From query embeddings to 3-D objects in one call: match_features without the score matrix, then a threshold (where score <
@@ -1226,7 +1061,7 @@ class Mapper:
         out=(indices, labels, scores, ids, block_count, records | None, component_count): preallocated tensors of any capacities (the counts: one
         int64 each), nothing is allocated -- give min_score as a device tensor -- and nothing waited for: -> the same tuple, untrimmed."""
         torch = self._torch
-        dev = torch.device("cuda", self.device)
+        dev = self._cuda
         conn, mv = self._segment_options(connectivity, min_voxels)
         q, nq, mid = self._queries(queries, metric)
         if min_score is None:
@@ -1237,40 +1072,18 @@ class Mapper:
             thr = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, np.float32).reshape(-1), (nq,)))).to(dev)
         if thr is not None and tuple(thr.shape) != (nq,):
             raise ValueError("min_score must be a number or hold one value per query (%d), got %s" % (nq, tuple(thr.shape)))
-        if out is None:
-            cap = self.num_blocks(LAYER_FEATURE)
-            idx = torch.empty((cap, 3), dtype=torch.int32, device=dev)
-            lab = torch.empty((cap, 512), dtype=torch.int32, device=dev)
-            sc = torch.empty((cap, 512), dtype=torch.float32, device=dev)
-            ids = torch.empty((cap, 512), dtype=torch.int32, device=dev)
-            rec = self.component_records(cap * 512 // mv)
-            both = torch.empty(2, dtype=torch.int64, device=dev)
-            bcnt, ccnt = both[0:1], both[1:2]
-        else:
-            idx, lab, sc, ids, bcnt, rec, ccnt = out
-            cap = int(idx.shape[0])
-            self._out_tensor(idx, (cap, 3), (torch.int32,), "indices")
-            self._out_tensor(lab, (cap, 512), (torch.int32,), "labels")
-            self._out_tensor(sc, (cap, 512), (torch.float32,), "scores")
-            self._out_tensor(ids, (cap, 512), (torch.int32,), "ids")
-            self._out_tensor(bcnt, (1,), (torch.int64,), "block count")
-            self._records_out(rec, ccnt)
-        ccap = int(rec.shape[0]) if rec is not None else 0
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
+        vol, cap, counts = _args.sparse_volume(out, dev, lambda: self.num_blocks(LAYER_FEATURE), record_words=COMPONENT_WORDS, min_voxels=mv)
+        idx, lab, sc, ids, bcnt, rec, ccnt = vol
         self._around_torch_stream(lambda: self.lib.nvbx_segment_features(
-            self._h, C.c_void_p(q.data_ptr()), nq, mid, float(min_weight), ptr(thr), conn, mv, ptr(idx), ptr(lab), ptr(sc), ptr(ids), cap,
-            C.c_void_p(bcnt.data_ptr()), ptr(rec), ccap, C.c_void_p(ccnt.data_ptr())))
+            self._h, ptr(q), nq, mid, float(min_weight), ptr(thr), conn, mv, ptr(idx), ptr(lab), ptr(sc), ptr(ids), cap, ptr(bcnt), ptr(rec),
+            int(rec.shape[0]) if rec is not None else 0, ptr(ccnt)))
         self._hold("_keep_sq", [q, thr])      # (the kernels read the queries and thresholds: they live until the next call)
-        if out is not None:
-            return idx, lab, sc, ids, bcnt, rec, ccnt
-        nb, nc = (int(v) for v in both.tolist())
-        nb = min(nb, cap)
-        return idx[:nb], lab[:nb], sc[:nb], ids[:nb], self.components_view(rec, min(nc, ccap))
+        return vol if out is not None else self._trim(counts, cap, (idx, lab, sc, ids), rec)
 
     # -- frontiers and view gain (nvbx_find_frontiers / nvbx_frontier_clusters / nvbx_view_gain; SEMANTICS.md "Frontiers and view gain")
     def _frontier_options(self, min_weight, free_distance_m, min_unknown, box_m):
-        """-> (min_weight, free_distance_m, min_unknown, box pointer | None); box_m = ((x0, y0, z0), (x1, y1, z1)) in metres, inclusive: the
-        voxels that contain the two corners, floor(p / voxel_size) in float32, bound the box"""
+        """-> (min_weight, free_distance_m, min_unknown, box | None); box_m = ((x0, y0, z0), (x1, y1, z1)) in metres, inclusive: the
+        voxels that contain the two corners, floor(p / voxel_size) in float32, bound the box (six int32, _box_ptr makes the argument of them)"""
         fd = float(self.params.voxel_size) if free_distance_m is None else float(free_distance_m)
         if int(min_unknown) < 1 or int(min_unknown) > 6:
             raise ValueError("min_unknown must be 1 .. 6, got %r" % (min_unknown,))
@@ -1282,12 +1095,14 @@ class Mapper:
                 raise ValueError("box_m has min > max on an axis: %r" % (box_m,))
         return float(min_weight), fd, int(min_unknown), box
 
+    @staticmethod
+    def _box_ptr(box):
+        return box.ctypes.data_as(C.POINTER(C.c_int32)) if box is not None else None
+
     def _frontier_count(self, mw, fd, mu, box):
         """the number of blocks that hold a frontier voxel: a counting scan (capacity 0), waited for"""
-        torch = self._torch
-        cnt = torch.empty(1, dtype=torch.int64, device=torch.device("cuda", self.device))
-        self._around_torch_stream(lambda: self.lib.nvbx_find_frontiers(
-            self._h, mw, fd, mu, box.ctypes.data_as(C.POINTER(C.c_int32)) if box is not None else None, None, None, None, 0, C.c_void_p(cnt.data_ptr())))
+        cnt = self._torch.empty(1, dtype=self._torch.int64, device=self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_find_frontiers(self._h, mw, fd, mu, self._box_ptr(box), None, None, None, 0, ptr(cnt)))
         return int(cnt.item())
 
     def find_frontiers(self, min_weight=1e-4, free_distance_m=None, min_unknown=1, box_m=None, out=None):
@@ -1299,31 +1114,11 @@ class Mapper:
         for the count; unlike num_blocks that leaves held-back work held back).
         out=(indices, labels, scores | None, count): preallocated tensors of any capacity n_cap, nothing is allocated and nothing waited for:
         -> the same tuple untrimmed; count may exceed n_cap, entries from n_cap on are not written."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
         mw, fd, mu, box = self._frontier_options(min_weight, free_distance_m, min_unknown, box_m)
-        if out is None:
-            cap = self._frontier_count(mw, fd, mu, box)
-            idx = torch.empty((cap, 3), dtype=torch.int32, device=dev)
-            lab = torch.empty((cap, 512), dtype=torch.int32, device=dev)
-            sc = torch.empty((cap, 512), dtype=torch.float32, device=dev)
-            cnt = torch.empty(1, dtype=torch.int64, device=dev)
-        else:
-            idx, lab, sc, cnt = out
-            cap = int(idx.shape[0])
-            self._out_tensor(idx, (cap, 3), (torch.int32,), "indices")
-            self._out_tensor(lab, (cap, 512), (torch.int32,), "labels")
-            if sc is not None:
-                self._out_tensor(sc, (cap, 512), (torch.float32,), "scores")
-            self._out_tensor(cnt, (1,), (torch.int64,), "count")
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
-        self._around_torch_stream(lambda: self.lib.nvbx_find_frontiers(
-            self._h, mw, fd, mu, box.ctypes.data_as(C.POINTER(C.c_int32)) if box is not None else None, ptr(idx), ptr(lab), ptr(sc), cap,
-            C.c_void_p(cnt.data_ptr())))
-        if out is not None:
-            return idx, lab, sc, cnt
-        n = min(int(cnt.item()), cap)
-        return idx[:n], lab[:n], sc[:n], cnt
+        vol, cap, counts = _args.sparse_volume(out, self._cuda, lambda: self._frontier_count(mw, fd, mu, box), scores_required=False)
+        idx, lab, sc, cnt = vol
+        self._around_torch_stream(lambda: self.lib.nvbx_find_frontiers(self._h, mw, fd, mu, self._box_ptr(box), ptr(idx), ptr(lab), ptr(sc), cap, ptr(cnt)))
+        return vol if out is not None else self._trim(counts, cap, (idx, lab, sc)) + (cnt,)
 
     def frontier_clusters(self, min_weight=1e-4, free_distance_m=None, min_unknown=1, box_m=None, connectivity=26, min_voxels=1, out=None):
         """From the map to exploration goals in one call: find_frontiers, then label_components over the result.  -> (indices [n, 3] i32,
@@ -1332,39 +1127,15 @@ class Mapper:
         scan first and for the worst-case component count; the call waits for that count and once for the two counts of the result.
         out=(indices, labels, scores | None, ids, block_count, records | None, component_count): preallocated tensors of any capacities (the counts:
         one int64 each), nothing is allocated and nothing waited for: -> the same tuple, untrimmed."""
-        torch = self._torch
-        dev = torch.device("cuda", self.device)
         conn, mv = self._segment_options(connectivity, min_voxels)
         mw, fd, mu, box = self._frontier_options(min_weight, free_distance_m, min_unknown, box_m)
-        if out is None:
-            cap = self._frontier_count(mw, fd, mu, box)
-            idx = torch.empty((cap, 3), dtype=torch.int32, device=dev)
-            lab = torch.empty((cap, 512), dtype=torch.int32, device=dev)
-            sc = torch.empty((cap, 512), dtype=torch.float32, device=dev)
-            ids = torch.empty((cap, 512), dtype=torch.int32, device=dev)
-            rec = self.component_records(cap * 512 // mv)
-            both = torch.empty(2, dtype=torch.int64, device=dev)
-            bcnt, ccnt = both[0:1], both[1:2]
-        else:
-            idx, lab, sc, ids, bcnt, rec, ccnt = out
-            cap = int(idx.shape[0])
-            self._out_tensor(idx, (cap, 3), (torch.int32,), "indices")
-            self._out_tensor(lab, (cap, 512), (torch.int32,), "labels")
-            if sc is not None:
-                self._out_tensor(sc, (cap, 512), (torch.float32,), "scores")
-            self._out_tensor(ids, (cap, 512), (torch.int32,), "ids")
-            self._out_tensor(bcnt, (1,), (torch.int64,), "block count")
-            self._records_out(rec, ccnt)
-        ccap = int(rec.shape[0]) if rec is not None else 0
-        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None      # noqa: E731
+        vol, cap, counts = _args.sparse_volume(out, self._cuda, lambda: self._frontier_count(mw, fd, mu, box), scores_required=False,
+                                               record_words=COMPONENT_WORDS, min_voxels=mv)
+        idx, lab, sc, ids, bcnt, rec, ccnt = vol
         self._around_torch_stream(lambda: self.lib.nvbx_frontier_clusters(
-            self._h, mw, fd, mu, box.ctypes.data_as(C.POINTER(C.c_int32)) if box is not None else None, conn, mv, ptr(idx), ptr(lab), ptr(sc),
-            ptr(ids), cap, C.c_void_p(bcnt.data_ptr()), ptr(rec), ccap, C.c_void_p(ccnt.data_ptr())))
-        if out is not None:
-            return idx, lab, sc, ids, bcnt, rec, ccnt
-        nb, nc = (int(v) for v in both.tolist())
-        nb = min(nb, cap)
-        return idx[:nb], lab[:nb], sc[:nb], ids[:nb], self.components_view(rec, min(nc, ccap))
+            self._h, mw, fd, mu, self._box_ptr(box), conn, mv, ptr(idx), ptr(lab), ptr(sc), ptr(ids), cap, ptr(bcnt), ptr(rec),
+            int(rec.shape[0]) if rec is not None else 0, ptr(ccnt)))
+        return vol if out is not None else self._trim(counts, cap, (idx, lab, sc, ids), rec)
 
     def view_gain(self, poses, cam, subsampling=None, max_range_m=None, min_weight=1e-4, free_distance_m=None, out=None):
         """How much unseen space each candidate pose would look into: poses (n, 4, 4) or (n, 16) float32 T_L_C (torch device tensor or numpy
@@ -1373,7 +1144,6 @@ class Mapper:
         that is not finite or out of range has rays = -1 and zeros.  Samples count voxels along rays, not distinct voxels.
         out: a preallocated int32 [n, 4] tensor, nothing is allocated."""
         torch = self._torch
-        dev = torch.device("cuda", self.device)
         k = self._cam(cam)
         if not isinstance(poses, torch.Tensor):
             poses = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)))
@@ -1381,14 +1151,11 @@ class Mapper:
             raise ValueError("poses must be (n, 4, 4) float32, got %s %s" % (tuple(poses.shape), poses.dtype))
         p = self._dev(poses.reshape(-1, 16), torch.float32)
         n = int(p.shape[0])
-        s = int(subsampling) if subsampling is not None else 0
-        if s < 0 or (subsampling is not None and s < 1):
-            raise ValueError("subsampling must be >= 1")
+        s = _args.subsampling_arg(subsampling)
         mw, fd, _, _ = self._frontier_options(min_weight, free_distance_m, 1, None)
-        g = torch.empty((n, 4), dtype=torch.int32, device=dev) if out is None else self._out_tensor(out, (n, 4), (torch.int32,), "gains")
+        g, = _args.outputs(None if out is None else (out,), (("gains", (n, 4), I32, True, True),), self._cuda)
         self._around_torch_stream(lambda: self.lib.nvbx_view_gain(
-            self._h, C.c_void_p(p.data_ptr()) if n else None, n, C.byref(k), s, float(max_range_m) if max_range_m is not None else 0.0, mw, fd,
-            C.c_void_p(g.data_ptr()) if n else None), order=n > 0)
+            self._h, ptr(p), n, C.byref(k), s, float(max_range_m) if max_range_m is not None else 0.0, mw, fd, ptr(g)), order=n > 0)
         self._hold("_keep_vg", [p])      # (the kernel reads the poses: they, and an uploaded copy, live until the next call)
         return g
 

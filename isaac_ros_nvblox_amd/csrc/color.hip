@@ -76,8 +76,7 @@ static int color_precheck(nvbx_mapper* m, int32_t n, int32_t rows, int32_t cols,
   for (int c = 0; c < n; c++)
     if (!nvbx_pose_in_range(T_L_C + 16 * c, m->p.voxel_size * 8.0f, m->p.sphere_tracing_max_ray_length_m + m->p.max_integration_distance_m)) {
       set_error("integrate color: T_L_C is not finite or lies outside the addressable block range (+-2^20 blocks)"); return NVBX_E_INVALID; }
-  const int sub = std::max(1, m->p.sphere_tracing_subsampling);
-  if (rows / sub < 2 || cols / sub < 2) { set_error("colour image too small for the sphere-tracing subsampling"); return NVBX_E_INVALID; }
+  if (!subsampled_size(m, 0, rows, cols).ok()) { set_error("colour image too small for the sphere-tracing subsampling"); return NVBX_E_INVALID; }
   return NVBX_OK;
 }
 template <typename Pix, int NB>
@@ -86,30 +85,18 @@ static int color_setup(nvbx_mapper* m, int32_t n, const Pix* imgs, int32_t rows,
   *fs = FrameSetC<Pix, NB>{}; fs->n = n;
   *ps = PoseSet<NB>{}; ps->n = n;
   for (int c = 0; c < n; c++) { fs->f[c] = m->make_frame(T_L_C + 16 * c, cameras + c, rows, cols, m->p.sphere_tracing_subsampling); fs->img[c] = imgs[c]; ps->f[c] = fs->f[c]; }
-  const FrameCore& f = fs->f[0];
-  { // slots per workgroup iteration of k_integrate_color's candidate scan: from the high-water mark the GPU last reported (a hint only)
-    const int64_t hw_seen = std::max<int64_t>(1, __atomic_load_n(&m->h_mirror[1], __ATOMIC_RELAXED));
-    int ch = 1; while (ch < 64 && (int64_t)ch * std::min<int64_t>(m->capacity, 1024) * 4 < hw_seen) ch *= 2;     // (up to 4 iterations of single slots: a room-sized map keeps
-                                                                                                        //  the stride-grid pairing, which balances the in-band blocks better than runs of neighbours)
-    fs->chunk = ch; }
-  const int32_t srows = rows / f.subsample, scols = cols / f.subsample;
-  if (srows < 2 || scols < 2) { set_error("colour image too small for the sphere-tracing subsampling"); return NVBX_E_INVALID; }
-  if (m->synth.ensure(m->stream, (size_t)srows * scols * n * 4)) return NVBX_E_DEVICE;
-  m->synth_rows = srows; m->synth_cols = scols; m->synth_last = n - 1;
-  *srows_out = srows; *scols_out = scols;
+  fs->chunk = candidate_scan_chunk(m);
+  const SubsampledSize ss = subsampled_size(m, 0, rows, cols);      // (ss.s = the frames' subsample: make_frame's clamp)
+  if (!ss.ok()) { set_error("colour image too small for the sphere-tracing subsampling"); return NVBX_E_INVALID; }
+  if (m->synth.ensure(m->stream, (size_t)ss.rows * ss.cols * n * 4)) return NVBX_E_DEVICE;
+  m->synth_rows = ss.rows; m->synth_cols = ss.cols; m->synth_last = n - 1;
+  *srows_out = ss.rows; *scols_out = ss.cols;
   return NVBX_OK;
-}
-// workgroups of the sphere-tracing launch / rider: one 256-thread workgroup per 8 x (32 / lanes) patch of rays, NSH x ceil(patches / NSH)
-// per camera (XCD-banded numbering, see the worker)
-static int sphere_trace_workgroups(int rl, int32_t srows, int32_t scols, int n) {
-  const int ph = 256 / rl / 8;
-  const int st_patches = ((scols + 7) / 8) * ((srows + ph - 1) / ph);
-  return NSH * ((st_patches + NSH - 1) / NSH) * n;
 }
 template <int NB>
 static int color_launch_trace(nvbx_mapper* m, const PoseSet<NB>& ps, int32_t n, int32_t srows, int32_t scols, int32_t mark_wg = 0, const EsdfArgs& ea = EsdfArgs{}) {
   const int rl = sphere_trace_lanes(n);
-  const int32_t n_trace = sphere_trace_workgroups(rl, srows, scols, n);
+  const int32_t n_trace = trace_patch_workgroups(rl, srows, scols) * n;
   const dim3 st_grid((unsigned)(n_trace + mark_wg));
 #define NVBX_ST_LAUNCH(RL) NVBX_LAUNCH(m, (k_sphere_trace<NB, RL>), st_grid, dim3(256), m->d, ps, m->synth.as<float>(), srows, scols, m->p.sphere_tracing_max_steps, \
                                        m->p.sphere_tracing_max_ray_length_m, m->p.sphere_tracing_surface_eps_vox * m->p.voxel_size, n_trace, mark_wg, ea)
@@ -119,7 +106,7 @@ static int color_launch_trace(nvbx_mapper* m, const PoseSet<NB>& ps, int32_t n, 
 }
 template <typename Pix, int NB>
 static int color_launch_integrate(nvbx_mapper* m, const FrameSetC<Pix, NB>& fs, int32_t srows, int32_t scols, bool take_edt = false) {
-  const int grid = (int)std::min<int64_t>(m->capacity, 1024);     // one resident batch of 512-thread workgroups
+  const int grid = candidate_scan_grid(m);
   // ESDF site marking of the blocks dirtied since the last marking pass rides in this launch (256 extra single-wavefront
   // workers): it reads only the TSDF, like the colour pass, and a following updateEsdf then needs the EDT kernel only
   int mark_wg = 0;
@@ -237,7 +224,7 @@ template <int NB> int nvbx_mapper::pending_color_trace_rider(TraceRiderT<NB>* tr
   tr->max_len = p.sphere_tracing_max_ray_length_m; tr->eps_m = p.sphere_tracing_surface_eps_vox * p.voxel_size;
   static const int fused_lanes = nvbx_knob_fused_trace_lanes(getenv("NVBX_FUSED_TRACE_LANES"));       // (A/B, one frame: 4 or 8 lanes per ray)
   tr->lanes = NB == 1 ? fused_lanes : std::max(2, sphere_trace_lanes(c.n));
-  tr->n_wg = sphere_trace_workgroups(tr->lanes, srows, scols, c.n);
+  tr->n_wg = trace_patch_workgroups(tr->lanes, srows, scols) * c.n;
   return NVBX_OK;
 }
 template int nvbx_mapper::pending_color_trace_rider<1>(TraceRiderT<1>*);  template int nvbx_mapper::pending_color_trace_rider<MAX_BATCH>(TraceRiderT<MAX_BATCH>*);

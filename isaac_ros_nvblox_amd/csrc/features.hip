@@ -12,7 +12,7 @@
 // whole block as empty, sets the flag and writes all 512 voxels.
 //
 // Two launches per frame, classic order (nothing rides anywhere):
-//   k_feature_trace      the colour frame's sphere tracing (sphere_trace_march, nvbx_sphere_trace.h) into a scratch image of this path's own;
+//   k_feature_trace      the colour frame's sphere tracing (sphere_trace_camera, nvbx_sphere_trace.h) into a scratch image of this path's own;
 //                        the colour path's synthetic depth, its work list and its counters are left alone
 //   k_integrate_features one 512-thread workgroup per candidate block (lane = voxel), candidates found as color_integrate_worker finds them
 //                        (chunked slot scan, ballot on the flags, frustum vote of 8 lanes).  Projection, synthetic-depth taps and the
@@ -37,30 +37,11 @@ struct FeatArgs {
   int32_t chunk;                 // slots per workgroup iteration of the candidate scan (1 .. 64)
 };
 
-// color.hip's sphere tracing launch for one camera, 8 lanes per ray, without the colour work list's reset: ray (r, c) of the srows x scols image
-// goes through the centre of full-resolution pixel (r s, c s); the same expressions, so the image is the colour frame's (and nvbx_render_view's)
+// color.hip's sphere tracing launch for one camera, 8 lanes per ray, without the colour work list's reset: the same function
+// (sphere_trace_camera), so the image is the colour frame's (and nvbx_render_view's)
+constexpr int FEAT_TRACE_LANES = 8;
 __global__ __launch_bounds__(256) void k_feature_trace(DMap m, FeatTraceArgs a) {
-  constexpr int RL = 8, PW = 8, PH = (256 / RL) / PW;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int sub = lane & (RL - 1), gsh = lane & ~(RL - 1);
-  const FrameCore& f = a.f;
-  const int patches_x = (a.scols + PW - 1) / PW, patches_y = (a.srows + PH - 1) / PH;
-  const int n_patch = patches_x * patches_y, per_xcd = (n_patch + NSH - 1) / NSH;
-  const int wg = (int)blockIdx.x;
-  const int patch = (wg & (NSH - 1)) * per_xcd + (wg >> 3);      // the workgroups of one XCD own a band of patch rows (sphere_trace_worker)
-  const int pr = tid / RL;
-  const int py = patch / patches_x, px = patch - py * patches_x;
-  const int r = py * PH + pr / PW, c = px * PW + pr % PW;
-  const bool valid = patch < n_patch && (wg >> 3) < per_xcd && r < a.srows && c < a.scols;
-  const float rx = (((float)((valid ? c : 0) * f.subsample) + 0.5f) - f.cu) / f.fu;
-  const float ry = (((float)((valid ? r : 0) * f.subsample) + 0.5f) - f.cv) / f.fv;
-  const float n = NVBX_SQRT((rx * rx + ry * ry) + 1.0f);
-  const float dcx = NVBX_DIV(rx, n), dcy = NVBX_DIV(ry, n), dcz = NVBX_DIV(1.0f, n);
-  float dl[3];
-  rotate(f.R_LC, dcx, dcy, dcz, dl);
-  float t = 0.0f; int n_rounds = 0;
-  const bool hit = sphere_trace_march<RL>(m, f.t_LC, dl, f.voxel_size, f.trunc, a.max_steps, a.max_len, a.eps_m, valid, sub, gsh, &t, &n_rounds);
-  if (valid && sub == 0) a.synth[(int64_t)r * a.scols + c] = hit ? t * dcz : 0.0f;
+  (void)sphere_trace_camera<FEAT_TRACE_LANES>(m, a.f, a.synth, a.srows, a.scols, a.max_steps, a.max_len, a.eps_m, (int)blockIdx.x, true);
 }
 
 // one candidate block: every thread of the workgroup calls (barriers); `flags` = the slot's flags as this launch found them
@@ -68,7 +49,7 @@ __device__ inline void feature_integrate_block(const DMap& m, const FeatArgs& a,
   const int tid = threadIdx.x;
   const int vx = tid >> 6, vy = (tid >> 3) & 7, vz = tid & 7;
   const FrameCore& f = a.f;
-  // ---- once per voxel: the colour integrator's tests in its expressions (color_integrate_block), the feature grid in place of the colour image
+  // ---- once per voxel: the colour integrator's tests (color_integrate_block; the occlusion test is the shared one), the feature grid in place of the colour image
   bool pass = false;
   float ax = 0.0f, ay = 0.0f; int32_t i00 = 0;
   {
@@ -80,25 +61,13 @@ __device__ inline void feature_integrate_block(const DMap& m, const FeatArgs& a,
     bool ok = cam_project(f, pc, &u, &v);
     const float vd = pc[2];
     if (f.max_dist > 0.0f && vd > f.max_dist) ok = false;
-    const float uf = NVBX_DIV(u, a.stride) - 0.5f, vf = NVBX_DIV(v, a.stride) - 0.5f;
-    const float fx = floorf(uf), fy = floorf(vf);
-    const int x0 = (int)fx, y0 = (int)fy;
-    const bool c_ok = !(x0 < 0 || y0 < 0 || x0 + 1 > a.cols_f - 1 || y0 + 1 > a.rows_f - 1);
-    const float us = NVBX_DIV(u, (float)f.subsample), vs_ = NVBX_DIV(v, (float)f.subsample);
-    const float usc = us - 0.5f, vsc = vs_ - 0.5f;
-    const float sfx = floorf(usc), sfy = floorf(vsc);
-    const int sx0 = (int)sfx, sy0 = (int)sfy;
-    const bool s_ok = !(sx0 < 0 || sy0 < 0 || sx0 + 1 > a.scols - 1 || sy0 + 1 > a.srows - 1);
+    int32_t fi00, si00; float fax, fay, sax, say;
+    const bool c_ok = scaled_taps(u, v, a.stride, a.rows_f, a.cols_f, &fi00, &fax, &fay);
+    const bool s_ok = scaled_taps(u, v, (float)f.subsample, a.srows, a.scols, &si00, &sax, &say);
     if (ok && c_ok && s_ok) {
-      const float* sp = a.synth + pix(sy0, sx0, a.scols);
+      const float* sp = a.synth + si00;
       const float s00 = sp[0], s10 = sp[1], s01 = sp[a.scols], s11 = sp[a.scols + 1];
-      if (s00 > 0.0f && s10 > 0.0f && s01 > 0.0f && s11 > 0.0f) {
-        const float sax = usc - sfx, say = vsc - sfy;
-        const float stop = (1.0f - sax) * s00 + sax * s10;
-        const float sbot = (1.0f - sax) * s01 + sax * s11;
-        const float sd = (1.0f - say) * stop + say * sbot;
-        if (!(fabsf(sd - vd) > f.occlusion_thresh)) { pass = true; ax = uf - fx; ay = vf - fy; i00 = pix(y0, x0, a.cols_f); }
-      }
+      if (synth_depth_agrees(s00, s10, s01, s11, sax, say, vd, f.occlusion_thresh)) { pass = true; ax = fax; ay = fay; i00 = fi00; }
     }
   }
   if (!__syncthreads_or(pass ? 1 : 0)) return;         // no voxel of the block is reached: nothing is written, the slot is not flagged
@@ -142,7 +111,7 @@ __device__ inline void feature_integrate_block(const DMap& m, const FeatArgs& a,
 // candidate discovery of color_integrate_worker (nvbx_color_worker.h) for one camera; a block a LiDAR scan left F_BAND_STALE is voted from its
 // TSDF and NOT repaired (this launch writes nothing but the feature pools and F_FEATURE)
 __global__ __launch_bounds__(512) void k_integrate_features(DMap m, FeatArgs a) {
-  __shared__ int s_out[6];
+  __shared__ int s_out[1][6];
   const int tid = threadIdx.x;
   const FrameCore& f = a.f;
   const int chunk = a.chunk;
@@ -167,26 +136,7 @@ __global__ __launch_bounds__(512) void k_integrate_features(DMap m, FeatArgs a) 
         const float2 tv = m.tsdf[(size_t)slot * 512 + tid];
         if (!__syncthreads_or(in_band(tv.x, tv.y, f.trunc) ? 1 : 0)) continue;
       }
-      __syncthreads();
-      if (tid < 6) s_out[tid] = 0;
-      __syncthreads();
-      if (tid < 8) {            // frustum: count corners outside each plane
-        const int q = tid;
-        float pc[3];
-        apply_rt(f.R_CL, f.t_CL, (float)(bx + (q & 1)) * f.block_size, (float)(by + ((q >> 1) & 1)) * f.block_size,
-                 (float)(bz + ((q >> 2) & 1)) * f.block_size, pc);
-        if (f.fu * pc[0] + f.cu * pc[2] < 0.0f) atomicAdd(&s_out[0], 1);
-        if (f.fu * pc[0] + (f.cu - (float)f.w) * pc[2] > 0.0f) atomicAdd(&s_out[1], 1);
-        if (f.fv * pc[1] + f.cv * pc[2] < 0.0f) atomicAdd(&s_out[2], 1);
-        if (f.fv * pc[1] + (f.cv - (float)f.h) * pc[2] > 0.0f) atomicAdd(&s_out[3], 1);
-        if (pc[2] < 0.0f) atomicAdd(&s_out[4], 1);
-        if (f.max_dist > 0.0f && pc[2] > f.max_dist) atomicAdd(&s_out[5], 1);
-      }
-      __syncthreads();
-      bool iv = true;
-#pragma unroll
-      for (int q = 0; q < 6; q++) if (s_out[q] == 8) iv = false;
-      if (!iv) continue;        // uniform
+      if (!frustum_vote<1>(&f, 1, bx, by, bz, s_out)) continue;        // uniform
       feature_integrate_block(m, a, slot, bx, by, bz, flags);
     }
   }
@@ -260,23 +210,18 @@ extern "C" int nvbx_integrate_features(nvbx_mapper* m, const void* feat_dev, int
     set_error("nvbx_integrate_features: stride >= 1, cols_f * stride <= camera width, rows_f * stride <= camera height"); return NVBX_E_INVALID; }
   if (!nvbx_pose_in_range(T_L_C, m->p.voxel_size * 8.0f, m->p.sphere_tracing_max_ray_length_m + m->p.max_integration_distance_m)) {
     set_error("nvbx_integrate_features: T_L_C is not finite or lies outside the addressable block range (+-2^20 blocks)"); return NVBX_E_INVALID; }
-  const int sub = std::max(1, m->p.sphere_tracing_subsampling);
-  const int32_t srows = camera->height / sub, scols = camera->width / sub;
-  if (srows < 2 || scols < 2) { set_error("nvbx_integrate_features: camera too small for the sphere-tracing subsampling"); return NVBX_E_INVALID; }
+  const SubsampledSize ss = subsampled_size(m, 0, camera->height, camera->width);
+  if (!ss.ok()) { set_error("nvbx_integrate_features: camera too small for the sphere-tracing subsampling"); return NVBX_E_INVALID; }
   if (m->join_side()) return NVBX_E_DEVICE;            // held-back work is carried out first: classic order from here on
-  if (m->feat_synth.ensure(m->stream, (size_t)srows * scols * 4)) return NVBX_E_DEVICE;
+  if (m->feat_synth.ensure(m->stream, (size_t)ss.rows * ss.cols * 4)) return NVBX_E_DEVICE;
   const Frame fr = m->make_frame(T_L_C, camera, camera->height, camera->width, m->p.sphere_tracing_subsampling);
-  FeatTraceArgs ta{}; ta.f = fr; ta.synth = m->feat_synth.as<float>(); ta.srows = srows; ta.scols = scols; ta.max_steps = m->p.sphere_tracing_max_steps;
+  FeatTraceArgs ta{}; ta.f = fr; ta.synth = m->feat_synth.as<float>(); ta.srows = ss.rows; ta.scols = ss.cols; ta.max_steps = m->p.sphere_tracing_max_steps;
   ta.max_len = m->p.sphere_tracing_max_ray_length_m; ta.eps_m = m->p.sphere_tracing_surface_eps_vox * m->p.voxel_size;
-  const int st_patches = ((scols + 7) / 8) * ((srows + 3) / 4);      // 8 x 4 rays per 256-thread workgroup at 8 lanes per ray
-  NVBX_LAUNCH(m, k_feature_trace, dim3((unsigned)(NSH * ((st_patches + NSH - 1) / NSH))), dim3(256), m->d, ta);
+  NVBX_LAUNCH(m, k_feature_trace, dim3((unsigned)trace_patch_workgroups(FEAT_TRACE_LANES, ss.rows, ss.cols)), dim3(256), m->d, ta);
   FeatArgs a{}; a.f = fr; a.img = static_cast<const half8*>(feat_dev); a.rows_f = rows_f; a.cols_f = cols_f; a.nch = m->feat_channels / 8; a.stride = (float)stride;
-  a.synth = ta.synth; a.srows = srows; a.scols = scols; a.val = static_cast<half8*>(m->feat_val); a.w = m->feat_w;
-  const int grid = (int)std::min<int64_t>(m->capacity, 1024);
-  { const int64_t hw_seen = std::max<int64_t>(1, __atomic_load_n(&m->h_mirror[1], __ATOMIC_RELAXED));      // (color_setup's rule; a hint only)
-    int ch = 1; while (ch < 64 && (int64_t)ch * grid * 4 < hw_seen) ch *= 2;
-    a.chunk = ch; }
-  NVBX_LAUNCH(m, k_integrate_features, dim3((unsigned)grid), dim3(512), m->d, a);
+  a.synth = ta.synth; a.srows = ss.rows; a.scols = ss.cols; a.val = static_cast<half8*>(m->feat_val); a.w = m->feat_w;
+  a.chunk = candidate_scan_chunk(m);
+  NVBX_LAUNCH(m, k_integrate_features, dim3((unsigned)candidate_scan_grid(m)), dim3(512), m->d, a);
   NVBX_HIP(hipGetLastError());
   return NVBX_OK;
 }

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include "nvbx_mapper.h"
+#include "nvbx_projective.h"
 
 using namespace nvbx;
 
@@ -160,13 +161,8 @@ __global__ __launch_bounds__(GAIN_TPB) void k_view_gain(DMap m, GainArgs a) {
     const int ray = (int)blockIdx.x * GAIN_TPB + tid;
     const bool valid = ray < n_rays;
     const int r = valid ? ray / a.scols : 0, c = valid ? ray - r * a.scols : 0;
-    // the ray of nvbx_render_view (k_render, render.hip), expression for expression
-    const float rx = (((float)(c * a.subsample) + 0.5f) - a.cu) / a.fu;
-    const float ry = (((float)(r * a.subsample) + 0.5f) - a.cv) / a.fv;
-    const float n = NVBX_SQRT((rx * rx + ry * ry) + 1.0f);
-    const float dcx = NVBX_DIV(rx, n), dcy = NVBX_DIV(ry, n), dcz = NVBX_DIV(1.0f, n);
-    float dl[3];
-    rotate(R, dcx, dcy, dcz, dl);
+    float dl[3];      // the ray of nvbx_render_view (k_render, render.hip): the same function
+    (void)pinhole_ray(a.fu, a.fv, a.cu, a.cv, a.subsample, R, r, c, dl);
     int32_t n_unknown = 0, n_free = 0, n_hit = 0;
     if (valid) {
       int32_t lbx = 0, lby = 0, lbz = 0; uint32_t lslot = SLOT_NONE; bool have = false;
@@ -174,7 +170,7 @@ __global__ __launch_bounds__(GAIN_TPB) void k_view_gain(DMap m, GainArgs a) {
         const float t = ((float)k + 0.5f) * a.voxel_size;
         if (!(t < a.max_range)) break;
         const float px = o[0] + t * dl[0], py = o[1] + t * dl[1], pz = o[2] + t * dl[2];
-        const int32_t gx = (int32_t)floorf(NVBX_DIV(px, a.voxel_size)), gy = (int32_t)floorf(NVBX_DIV(py, a.voxel_size)), gz = (int32_t)floorf(NVBX_DIV(pz, a.voxel_size));
+        const int32_t gx = voxel_of(px, a.voxel_size), gy = voxel_of(py, a.voxel_size), gz = voxel_of(pz, a.voxel_size);
         const int32_t bx = gx >> 3, by = gy >> 3, bz = gz >> 3;
         if (!have || bx != lbx || by != lby || bz != lbz) {
           lslot = nvbx_index_in_range(bx, by, bz) ? find_slot(m, bx, by, bz, F_TSDF) : SLOT_NONE;
@@ -270,9 +266,8 @@ extern "C" int nvbx_view_gain(nvbx_mapper* m, const float* T_L_C_dev, int32_t n_
   if (!camera || subsampling < 0 || n_views < 0) return refuse(who, ": invalid argument");
   if (n_views > 0 && (!T_L_C_dev || !gains_dev)) return refuse(who, ": T_L_C_dev and gains_dev are required with n_views > 0");
   if (!nvbx_camera_valid(camera)) return refuse(who, ": invalid camera");
-  const int32_t s = subsampling > 0 ? subsampling : std::max(1, m->p.sphere_tracing_subsampling);
-  const int32_t srows = camera->height / s, scols = camera->width / s;
-  if (srows < 2 || scols < 2) return refuse(who, ": image too small for the subsampling");
+  const SubsampledSize ss = subsampled_size(m, subsampling, camera->height, camera->width);
+  if (!ss.ok()) return refuse(who, ": image too small for the subsampling");
   const float reach = max_range_m > 0.0f ? max_range_m : m->p.sphere_tracing_max_ray_length_m;
   if (!std::isfinite(reach)) return refuse(who, ": max_range_m is not finite");
   if (std::isnan(min_weight) || std::isnan(free_distance_m)) return refuse(who, ": min_weight / free_distance_m is not a number");
@@ -281,13 +276,13 @@ extern "C" int nvbx_view_gain(nvbx_mapper* m, const float* T_L_C_dev, int32_t n_
   if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
   GainArgs a{};
   a.poses = T_L_C_dev; a.n_views = n_views;
-  a.fu = camera->fu; a.fv = camera->fv; a.cu = camera->cu; a.cv = camera->cv; a.subsample = s; a.srows = srows; a.scols = scols;
+  a.fu = camera->fu; a.fv = camera->fv; a.cu = camera->cu; a.cv = camera->cv; a.subsample = ss.s; a.srows = ss.rows; a.scols = ss.cols;
   a.voxel_size = m->p.voxel_size; a.max_range = reach;
   a.pose_lim = nvbx_pose_limit(m->p.voxel_size * 8.0f, reach);      // (nvbx_pose_in_range's bound)
   a.min_weight = min_weight; a.free_dist = free_distance_m;
   a.gains = reinterpret_cast<int32_t*>(gains_dev);
   NVBX_HIP(hipMemsetAsync(gains_dev, 0, sizeof(nvbx_gain) * (size_t)n_views, m->stream));
-  const dim3 grid((unsigned)(((int64_t)srows * scols + GAIN_TPB - 1) / GAIN_TPB), (unsigned)std::min<int32_t>(n_views, 65535));
+  const dim3 grid((unsigned)(((int64_t)ss.rows * ss.cols + GAIN_TPB - 1) / GAIN_TPB), (unsigned)std::min<int32_t>(n_views, 65535));
   NVBX_LAUNCH(m, k_view_gain, grid, dim3(GAIN_TPB), m->d, a);
   NVBX_HIP(hipGetLastError());
   return NVBX_OK;

@@ -82,13 +82,10 @@ __device__ inline void color_integrate_block(const DMap& m, const FrameSetC<Pix,
     const float fx = floorf(uc), fy = floorf(vc);
     const int x0 = (int)fx, y0 = (int)fy;
     const bool c_ok = !(x0 < 0 || y0 < 0 || x0 + 1 > f.cols - 1 || y0 + 1 > f.rows - 1);
-    const float us = NVBX_DIV(u, (float)f.subsample), vs_ = NVBX_DIV(v, (float)f.subsample);
-    const float usc = us - 0.5f, vsc = vs_ - 0.5f;
-    const float sfx = floorf(usc), sfy = floorf(vsc);
-    const int sx0 = (int)sfx, sy0 = (int)sfy;
-    const bool s_ok = !(sx0 < 0 || sy0 < 0 || sx0 + 1 > scols - 1 || sy0 + 1 > srows - 1);
+    int32_t si00; float sax, say;
+    const bool s_ok = scaled_taps(u, v, (float)f.subsample, srows, scols, &si00, &sax, &say);
     if (!c_ok || !s_ok) continue;
-    const float* sp = synth + pix(sy0, sx0, scols);
+    const float* sp = synth + si00;
     const int32_t i00 = pix(y0, x0, f.cols);
     // (the colour voxel is only needed for the blend: it travels with the taps, not with the vote's inputs -- blocks
     // outside the truncation band or the frustum, most of the map, never fetch it)
@@ -98,12 +95,7 @@ __device__ inline void color_integrate_block(const DMap& m, const FrameSetC<Pix,
     fs.img[c].tap(i00, t00); fs.img[c].tap(i00 + 1, t10); fs.img[c].tap(i00 + f.cols, t01); fs.img[c].tap(i00 + f.cols + 1, t11);
     // (the compiler sinks the colour taps below the occlusion test -- two round trips for a voxel that passes, none for the many that
     // fail; pinning them above it was measured: 9.5 -> 10.9 us)
-    if (!(s00 > 0.0f) || !(s10 > 0.0f) || !(s01 > 0.0f) || !(s11 > 0.0f)) continue;
-    const float sax = usc - sfx, say = vsc - sfy;
-    const float stop = (1.0f - sax) * s00 + sax * s10;
-    const float sbot = (1.0f - sax) * s01 + sax * s11;
-    const float sd = (1.0f - say) * stop + say * sbot;
-    if (fabsf(sd - vd) > f.occlusion_thresh) continue;      // [U] occlusion test (color_occlusion_threshold_vox)
+    if (!synth_depth_agrees(s00, s10, s01, s11, sax, say, vd, f.occlusion_thresh)) continue;
     const float ax = uc - fx, ay = vc - fy;
     float cc[3];
 #pragma unroll
@@ -171,30 +163,7 @@ __device__ inline void color_integrate_worker(const DMap& m, const FrameSetC<Pix
       publish_band(m.slot_flags, (uint32_t)slot, tid, pred);
       if (!__syncthreads_or(pred ? 1 : 0)) continue;
     }
-    __syncthreads();
-    if (tid < 6 * NB) (&s_out[0][0])[tid] = 0;
-    __syncthreads();
-    if (tid < 8 * ncam) {   // frustum: count corners outside each plane, 8 lanes per camera
-      const int c = NB == 1 ? 0 : (tid >> 3), q = tid & 7;      // (one camera: a constant index -- a per-lane index into the argument block is a vector load from memory)
-      const FrameCore& f = fs.f[c];
-      float pc[3];
-      apply_rt(f.R_CL, f.t_CL, (float)(bx + (q & 1)) * f.block_size, (float)(by + ((q >> 1) & 1)) * f.block_size,
-               (float)(bz + ((q >> 2) & 1)) * f.block_size, pc);
-      if (f.fu * pc[0] + f.cu * pc[2] < 0.0f) atomicAdd(&s_out[c][0], 1);
-      if (f.fu * pc[0] + (f.cu - (float)f.w) * pc[2] > 0.0f) atomicAdd(&s_out[c][1], 1);
-      if (f.fv * pc[1] + f.cv * pc[2] < 0.0f) atomicAdd(&s_out[c][2], 1);
-      if (f.fv * pc[1] + (f.cv - (float)f.h) * pc[2] > 0.0f) atomicAdd(&s_out[c][3], 1);
-      if (pc[2] < 0.0f) atomicAdd(&s_out[c][4], 1);
-      if (f.max_dist > 0.0f && pc[2] > f.max_dist) atomicAdd(&s_out[c][5], 1);
-    }
-    __syncthreads();
-    uint32_t in_view = 0u;               // cameras whose frustum the block touches (uniform)
-    for (int c = 0; c < ncam; c++) {
-      bool iv = true;
-#pragma unroll
-      for (int q = 0; q < 6; q++) if (s_out[c][q] == 8) iv = false;
-      if (iv) in_view |= 1u << c;
-    }
+    const uint32_t in_view = frustum_vote<NB>(fs.f, ncam, bx, by, bz, s_out);      // cameras whose frustum the block touches (uniform)
     if (!in_view) continue;                // uniform
     color_integrate_block<Pix, NB>(m, fs, synth_all, srows, scols, mesh_list, slot, bx, by, bz, in_view);
   }
@@ -205,7 +174,7 @@ __device__ inline void color_integrate_worker(const DMap& m, const FrameSetC<Pix
 // PREVIOUS launch (view marking of depth frame i + 1 -- nothing writes block flags or TSDF voxels there), so that the colour integration
 // itself reads no flag the TSDF update of frame i + 1, running beside it, is changing (F_BAND).
 // Candidate records {slot | camera mask << 24, block index}: exactly the blocks color_integrate_worker would visit -- TSDF layer, truncation-band
-// flag, inside the frustum of at least one camera (the same expressions; the mask names which).  One wavefront per 64 consecutive slots
+// flag, inside the frustum of at least one camera (frustum_vote's verdict; the mask names which).  One wavefront per 64 consecutive slots
 // (lane = slot), wave-aggregated append.  Slot ids stay below 2^24 (mapper.hip: max_capacity).
 // Requires: no block flagged F_BAND_STALE (the host does not take this path once a LiDAR scan has been integrated into the mapper).
 template <int NB>
@@ -228,7 +197,10 @@ __device__ inline void color_scan_worker(const DMap& m, const PoseSet<NB>& ps, i
     uint32_t in_view = 0u;
     if (base + lane < hw && (flags & F_TSDF) && (flags & F_BAND)) {
 #pragma unroll 1
-      for (int c = 0; c < ncam; c++) {          // frustum: corners outside each plane (color_integrate_worker's test, one lane per block)
+      // frustum: corners outside each plane, one lane per block.  The corner and the six planes below MUST EQUAL frustum_vote's corner and
+      // frustum_planes_outside (nvbx_projective.h), line for line.  They stay a copy: this worker rides in k_mark_view, which is register-starved, and
+      // the shared callback -- though it expands to these statements -- took k_mark_view<DepthF32, CameraSensor, 8> from 68 to 196 B/lane of scratch.
+      for (int c = 0; c < ncam; c++) {
         const FrameCore& f = ps.f[NB == 1 ? 0 : c];
         int out[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll

@@ -4,6 +4,7 @@
 // TSDF and the insert-only hash, view marking inserts hash entries whose pool slots are all-zero (= unobserved, exactly like a missing block).
 #pragma once
 #include "nvbx_mapper.h"
+#include "nvbx_projective.h"
 
 namespace nvbx {
 
@@ -43,7 +44,7 @@ __device__ inline bool sphere_trace_march(const DMap& m, const float* o, const f
     float tc = t;
     for (int j = 0; j < RAY_LANES - 1; j++) if (j < sub) tc = tc + ps;
     const float px = o[0] + tc * dl[0], py = o[1] + tc * dl[1], pz = o[2] + tc * dl[2];
-    const int32_t gx = (int32_t)floorf(NVBX_DIV(px, voxel_size)), gy = (int32_t)floorf(NVBX_DIV(py, voxel_size)), gz = (int32_t)floorf(NVBX_DIV(pz, voxel_size));
+    const int32_t gx = voxel_of(px, voxel_size), gy = voxel_of(py, voxel_size), gz = voxel_of(pz, voxel_size);
     const int32_t bx = gx >> 3, by = gy >> 3, bz = gz >> 3;
     const uint32_t h = done ? 0u : table_pos(m, bx, by, bz);
     const uint4 e = *reinterpret_cast<const uint4*>(&m.table[h]);
@@ -91,44 +92,38 @@ __device__ inline bool sphere_trace_march(const DMap& m, const float* o, const f
   return hit;
 }
 
-// worker `wgi` (a 256-thread workgroup) of NSH * ceil(patches / NSH) * n workers; every thread of the workgroup calls
-template <int NB, int RAY_LANES>
-__device__ inline void sphere_trace_worker(const DMap& m, const PoseSet<NB>& poses, float* synth_all, int32_t srows, int32_t scols, int32_t max_steps,
-                                           float max_len, float eps_m, int wgi) {
-  const int tid = threadIdx.x;
-  NVBX_INV_TSDF_READER(m);
-  if (wgi == 0 && tid == 0) list_reset(m, S_LIST_COLOR);
-  const int lane = tid & 63;
+// One camera's workgroup `wg` (256 threads, of trace_patch_workgroups(RAY_LANES, srows, scols)): patch, ray, march, store -- the synthetic depth
+// image of frame f, synth[r * scols + c] = depth of the hit along ray (r, c), 0 = no hit.  live = false: the workgroup has no camera (a batch with
+// fewer frames than MAX_BATCH).  Every thread calls; returns the wavefront's round trips (instrumentation).  Also the whole of k_feature_trace.
+template <int RAY_LANES>
+__device__ inline int sphere_trace_camera(const DMap& m, const FrameCore& f, float* synth, int32_t srows, int32_t scols, int32_t max_steps, float max_len,
+                                          float eps_m, int wg, bool live) {
+  const int tid = threadIdx.x, lane = tid & 63;
   const int sub = lane & (RAY_LANES - 1);              // sample index within the ray's group
   const int gsh = lane & ~(RAY_LANES - 1);             // first lane of the group (= shift of its bits in a ballot)
-  // XCD-aware ray -> workgroup mapping.  Workgroups are dispatched round-robin over the 8 XCDs, each with its own L2: with rays
-  // dealt out in row-major order every XCD marches through EVERY part of the frustum and fetches its own copy of every TSDF block
-  // and hash line (PMC: 6.6 MB of HBM traffic for 1.0 MB of blocks).  Instead a workgroup takes an 8 x 4 patch of rays, and the
-  // patches are numbered so that the workgroups of one XCD (blockIdx.x & 7) own a contiguous band of patch rows.
-  constexpr int PW = 8, PH = (256 / RAY_LANES) / PW;       // 256 / RAY_LANES rays per 256-thread workgroup (32 at 8 lanes per ray)
-  const int patches_x = (scols + PW - 1) / PW, patches_y = (srows + PH - 1) / PH;
-  const int n_patch = patches_x * patches_y, per_xcd = (n_patch + NSH - 1) / NSH;
-  const int cam = NB > 1 ? wgi / (NSH * per_xcd) : 0;          // batch: NSH * per_xcd workgroups per camera, camera after camera
-  const int wg = wgi - cam * (NSH * per_xcd);
-  const FrameCore& f = poses.f[cam];
-  float* synth = synth_all + (size_t)cam * srows * scols;
-  const int patch = (wg & (NSH - 1)) * per_xcd + (wg >> 3);
-  const int pr = tid / RAY_LANES;                            // ray within the patch
-  const int py = patch / patches_x, px = patch - py * patches_x;
-  const int r = py * PH + pr / PW, c = px * PW + pr % PW;
-  const bool valid = cam < poses.n && patch < n_patch && (wg >> 3) < per_xcd && r < srows && c < scols;
-  const float rx = (((float)((valid ? c : 0) * f.subsample) + 0.5f) - f.cu) / f.fu;
-  const float ry = (((float)((valid ? r : 0) * f.subsample) + 0.5f) - f.cv) / f.fv;
-  const float n = NVBX_SQRT((rx * rx + ry * ry) + 1.0f);          // (NVBX_SQRT / NVBX_DIV: the IEEE results, shorter sequences -- nvbx_arith.h)
-  const float dcx = NVBX_DIV(rx, n), dcy = NVBX_DIV(ry, n), dcz = NVBX_DIV(1.0f, n);
+  int r, c;
+  const bool valid = trace_patch_pixel<RAY_LANES>(wg, tid, srows, scols, &r, &c) && live;
   float dl[3];
-  rotate(f.R_LC, dcx, dcy, dcz, dl);
+  const float dcz = pinhole_ray(f.fu, f.fv, f.cu, f.cv, f.subsample, f.R_LC, valid ? r : 0, valid ? c : 0, dl);
   float t = 0.0f; int n_rounds = 0;
   const bool hit = sphere_trace_march<RAY_LANES>(m, f.t_LC, dl, f.voxel_size, f.trunc, max_steps, max_len, eps_m, valid, sub, gsh, &t, &n_rounds);
   if (valid && sub == 0) synth[(int64_t)r * scols + c] = hit ? t * dcz : 0.0f;
-  NVBX_TV(0, 6, n_rounds); (void)n_rounds;
+  return n_rounds;
 }
 
+// worker `wgi` of the colour frame's tracing launch / rider, trace_patch_workgroups() x n workers: the colour work list's reset, the camera of a
+// batch (its workgroups follow the previous camera's), invariants and timeline; every thread of the workgroup calls
+template <int NB, int RAY_LANES>
+__device__ inline void sphere_trace_worker(const DMap& m, const PoseSet<NB>& poses, float* synth_all, int32_t srows, int32_t scols, int32_t max_steps,
+                                           float max_len, float eps_m, int wgi) {
+  NVBX_INV_TSDF_READER(m);
+  if (wgi == 0 && threadIdx.x == 0) list_reset(m, S_LIST_COLOR);
+  const int per_cam = trace_patch_workgroups(RAY_LANES, srows, scols);
+  const int cam = NB > 1 ? wgi / per_cam : 0;
+  const int n_rounds = sphere_trace_camera<RAY_LANES>(m, poses.f[cam], synth_all + (size_t)cam * srows * scols, srows, scols, max_steps, max_len, eps_m,
+                                                      wgi - cam * per_cam, cam < poses.n);
+  NVBX_TV(0, 6, n_rounds); (void)n_rounds;
+}
 
 // The sphere tracing of a held-back colour frame riding in the next depth frame's k_mark_view launch (kernel argument; n_wg = 0: none).
 // n_tile_wg > 0: the launch's first n_tile_wg workgroups are the view-marking tiles and the riders (EDT, then sphere tracing) follow; 0: riders first.

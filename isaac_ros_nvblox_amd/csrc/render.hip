@@ -65,7 +65,7 @@ __device__ inline void render_epilogue(const DMap& m, const RenderArgs& a, const
     // the colour voxel that contains P, found as the march finds its TSDF voxel.  No layer-flag load: the colour pool of a slot without a colour
     // block is all-zero (nvbx_internal.h, "lookups without a layer-flag check"), and weight 0 is "no colour" -- grey 127, the mesh's rule
     const bool mine = sub == RL - 1;
-    const int32_t gx = (int32_t)floorf(NVBX_DIV(P[0], vs)), gy = (int32_t)floorf(NVBX_DIV(P[1], vs)), gz = (int32_t)floorf(NVBX_DIV(P[2], vs));
+    const int32_t gx = voxel_of(P[0], vs), gy = voxel_of(P[1], vs), gz = voxel_of(P[2], vs);
     const int32_t bx = gx >> 3, by = gy >> 3, bz = gz >> 3;
     const bool need = on && mine;
     const uint32_t h = need ? table_pos(m, bx, by, bz) : 0u;
@@ -161,22 +161,11 @@ __global__ __launch_bounds__(256) void k_render(DMap m, RenderArgs a) {
   constexpr int RPW = 256 / RL;                 // rays per workgroup
   int n_rounds = 0;      // (the march reports its round trips to the occlusion image's instrumentation; not used here)
   if (SRC == SRC_VIEW) {
-    // rays -> workgroups: the XCD-banded 8 x PH patches of sphere_trace_worker (nvbx_sphere_trace.h), one camera; ray set-up in its order
-    constexpr int PW = 8, PH = RPW / PW;
-    const int wg = (int)blockIdx.x;
-    const int patches_x = (a.scols + PW - 1) / PW, patches_y = (a.srows + PH - 1) / PH;
-    const int n_patch = patches_x * patches_y, per_xcd = (n_patch + NSH - 1) / NSH;
-    const int patch = (wg & (NSH - 1)) * per_xcd + (wg >> 3);
-    const int pr = tid / RL;
-    const int py = patch / patches_x, px = patch - py * patches_x;
-    const int r = py * PH + pr / PW, c = px * PW + pr % PW;
-    const bool valid = patch < n_patch && (wg >> 3) < per_xcd && r < a.srows && c < a.scols;
-    const float rx = (((float)((valid ? c : 0) * a.subsample) + 0.5f) - a.cu) / a.fu;
-    const float ry = (((float)((valid ? r : 0) * a.subsample) + 0.5f) - a.cv) / a.fv;
-    const float n = NVBX_SQRT((rx * rx + ry * ry) + 1.0f);
-    const float dcx = NVBX_DIV(rx, n), dcy = NVBX_DIV(ry, n), dcz = NVBX_DIV(1.0f, n);
+    // rays -> workgroups and the ray of a pixel: the colour frame's (sphere_trace_camera, nvbx_sphere_trace.h), one camera
+    int r, c;
+    const bool valid = trace_patch_pixel<RL>((int)blockIdx.x, tid, a.srows, a.scols, &r, &c);
     float dl[3];
-    rotate(a.R_LC, dcx, dcy, dcz, dl);
+    const float dcz = pinhole_ray(a.fu, a.fv, a.cu, a.cv, a.subsample, a.R_LC, valid ? r : 0, valid ? c : 0, dl);
     float t = 0.0f;
     const bool hit = sphere_trace_march<RL>(m, a.t_LC, dl, a.voxel_size, a.trunc, a.max_steps, a.max_len, a.eps_m, valid, sub, gsh, &t, &n_rounds);
     render_epilogue<RL, COLOR, NORMAL>(m, a, a.t_LC, dl, t, hit, valid, sub, gsh, (int64_t)r * a.scols + c, dcz);
@@ -250,11 +239,10 @@ extern "C" int nvbx_render_view_with(nvbx_mapper* m, const nvbx_render_options* 
                                      int32_t* rows_out, int32_t* cols_out) {
   if (!m || !T_L_C || !camera || !rows_out || !cols_out || subsampling < 0) { set_error("nvbx_render_view: invalid argument"); return NVBX_E_INVALID; }
   if (!nvbx_camera_valid(camera)) { set_error("nvbx_render_view: invalid camera"); return NVBX_E_INVALID; }
-  const int32_t s = subsampling > 0 ? subsampling : std::max(1, m->p.sphere_tracing_subsampling);
-  const int32_t srows = camera->height / s, scols = camera->width / s;
-  if (srows < 2 || scols < 2) { set_error("nvbx_render_view: image too small for the subsampling"); return NVBX_E_INVALID; }
-  *rows_out = srows; *cols_out = scols;
-  if (capacity_pixels < (int64_t)srows * scols) { set_error("nvbx_render_view: capacity_pixels is smaller than the rendered image"); return NVBX_E_CAPACITY; }
+  const SubsampledSize ss = subsampled_size(m, subsampling, camera->height, camera->width);
+  if (!ss.ok()) { set_error("nvbx_render_view: image too small for the subsampling"); return NVBX_E_INVALID; }
+  *rows_out = ss.rows; *cols_out = ss.cols;
+  if (capacity_pixels < (int64_t)ss.rows * ss.cols) { set_error("nvbx_render_view: capacity_pixels is smaller than the rendered image"); return NVBX_E_CAPACITY; }
   if (!depth_dev) { set_error("nvbx_render_view: depth_dev is NULL"); return NVBX_E_INVALID; }
   const float reach = max_ray_length_m > 0.0f ? max_ray_length_m : m->p.sphere_tracing_max_ray_length_m;
   if (!nvbx_pose_in_range(T_L_C, m->p.voxel_size * 8.0f, reach)) {
@@ -263,12 +251,10 @@ extern "C" int nvbx_render_view_with(nvbx_mapper* m, const nvbx_render_options* 
   { const int rc = render_begin(m, options, max_ray_length_m, color_rgb_dev != nullptr, "nvbx_render_view", &a); if (rc) return rc; }
   for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) a.R_LC[3 * i + j] = T_L_C[4 * i + j]; a.t_LC[i] = T_L_C[4 * i + 3]; }
   a.fu = camera->fu; a.fv = camera->fv; a.cu = camera->cu; a.cv = camera->cv;
-  a.subsample = s; a.srows = srows; a.scols = scols;
+  a.subsample = ss.s; a.srows = ss.rows; a.scols = ss.cols;
   a.depth = depth_dev; a.color = color_rgb_dev; a.normal = normal_xyz_dev;
-  const int rl = render_lanes((int64_t)srows * scols);
-  const int ph = 256 / rl / 8;
-  const int patches = ((scols + 7) / 8) * ((srows + ph - 1) / ph);
-  return launch_render<SRC_VIEW>(m, rl, dim3((unsigned)(NSH * ((patches + NSH - 1) / NSH))), a);
+  const int rl = render_lanes((int64_t)ss.rows * ss.cols);
+  return launch_render<SRC_VIEW>(m, rl, dim3((unsigned)trace_patch_workgroups(rl, ss.rows, ss.cols)), a);
 }
 
 extern "C" int nvbx_render_view(nvbx_mapper* m, const float T_L_C[16], const nvbx_camera* camera, int32_t subsampling, float max_ray_length_m, float* depth_dev,

@@ -118,6 +118,39 @@ def test_weights_equal_the_colour_layers(room_frames):
     m.close()
 
 
+def test_weights_equal_the_colour_layers_on_an_odd_image():
+    """The same identity where the tracing launches' ray numbering has its edge cases: a 37 x 29 camera at sphere_tracing_subsampling 4 gives a
+    9 x 7 synthetic image -- no multiple of the 8 x 4 ray patch on either side, and its four patches are fewer than the eight bands of the
+    numbering, so partial patches and workgroups without a patch run on the colour path and on the feature path."""
+    M, S = _mods()
+    cam = (18.5, 18.5, 18.0, 14.0, 37, 29)      # CAM's field of view
+    p = M.default_params()
+    assert p.sphere_tracing_subsampling == 4
+    m = M.Mapper(p, block_capacity=1 << 12)
+    m.set_color_deferral(False)
+    m.enable_features(8)
+    sc = S.Scene()
+    frames = []
+    for i in range(3):
+        T = S.trajectory_pose(i * 9)
+        d, rgb = S.render(sc, T, cam)
+        frames.append((rgb, T))
+        m.integrate_depth(d, T, cam)
+    for rgb, T in frames:
+        feat = np.zeros((cam[5], cam[4], 8), np.float16); feat[:, :, :3] = rgb
+        m.integrate_color(rgb, T, cam)
+        m.integrate_features(feat, T, cam, 1)
+    assert m.synthetic_depth().shape == (7, 9)
+    idx = m.block_indices(M.LAYER_TSDF)
+    col, _ = m.get_blocks(M.LAYER_COLOR, idx)
+    _, w, _ = m.feature_blocks(idx)
+    assert np.array_equal(col["weight"].view(np.uint32), w.view(np.uint32))
+    # not trivially empty: the occlusion test passes only inside the synthetic image's interior (8 x 6 of its 9 x 7 pixels, about 3/4 of the
+    # view), where each of the ~1 000 depth pixels of a frame has at least one voxel of the truncation band behind it
+    assert (w > 0).sum() > 500 and (w == 3).any()
+    m.close()
+
+
 # ---- hand-made walls (set_blocks): a one-sided wall at x = 1 and, behind it, a two-sided slab at x = 2.2
 def _wall_blocks(M, plane_x, two_sided, y_rng, z_rng, extra_bx=()):
     """TSDF blocks (weight 1) around the plane x = plane_x; extra_bx: further block columns of observed space beside it (the sphere tracer steps

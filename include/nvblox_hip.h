@@ -707,6 +707,66 @@ int nvbx_align_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32
 int nvbx_linearize_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float T_L_S[16], const nvbx_align_options* options,
                           nvbx_align_result* result_dev, float* points_L_dev, float* residual_dev, float* gradient_dev, uint8_t* valid_dev);
 
+/* ---- relocalisation ([U] scoring pose hypotheses against the TSDF; SEMANTICS.md "Relocalisation") ----------------------------------------
+ * Where nvbx_align_* refine a guess within the truncation band, these calls find such a guess: they score many sensor poses against the
+ * TSDF in one launch, and nvbx_relocalize_* score a lattice of poses around T0, select the best and refine it with the alignment's own
+ * iterations, without a host wait in between.
+ * One pose, one taken point x (nvbx_score_poses_points: all n points; nvbx_score_poses_depth: the pixels (r s, c s) with
+ * 0 < depth <= max_depth_m, back-projected with nvbx_backproject_depth's arithmetic inside the launch): p = T x in
+ * nvbx_transform_pointcloud's f32 arithmetic with the pose's f32 entries; (d, valid) = nvbx_query_points(TSDF, min_weight) at p, bit for
+ * bit (a non-finite point or a missing corner is not valid).  The record of the pose, all integers, so that every summation order gives the
+ * same bits: points = the taken points, valid = the valid ones, inliers = valid with |d| <= inlier_distance_m, conflicts = valid with
+ * d > conflict_distance_m (a measured surface point in observed free space: evidence against the pose), abs_residual_q20 = the sum over
+ * the valid points of (int64)rintf(|d| * 1048576.0f) (round to even).
+ * A pose that is not finite or out of range (nvbx_render_view's rule) is never an error: its record is all zero with points = -1.
+ * Options: a threshold <= 0 selects its default -- inlier_distance_m one voxel size, conflict_distance_m half the truncation distance,
+ * min_weight 1e-4; max_depth_m <= 0: no limit; options NULL: the defaults.  n_poses == 0 launches nothing.  Asynchronous on the mapper's
+ * stream; TSDF voxels are read, nothing is written to the map, held-back work stays held back.
+ * NVBX_E_INVALID (nvbx_last_error set, nothing launched, the mapper stays usable): an occupancy mapper; a NULL mapper, or a NULL point /
+ * depth, pose or score pointer that a count > 0 needs; n < 0 or n_poses < 0; a misaligned scores_dev; subsampling < 1; a camera that does
+ * not match the image; an option that is not a number. */
+typedef struct { int32_t points, valid, inliers, conflicts; int64_t abs_residual_q20; } nvbx_pose_score;   /* 24 bytes, 8-byte aligned; offsets 0 4 8 12 16 */
+typedef struct { float min_weight, inlier_distance_m, conflict_distance_m, max_depth_m; int32_t subsampling; } nvbx_score_options;   /* 20 bytes; offsets 0 4 8 12 16 */
+/* defaults: the three thresholds 0 (= their defaults, above), no depth limit, subsampling 4 */
+void nvbx_default_score_options(nvbx_score_options* options);
+/* T_L_S_dev / T_L_C_dev: [n_poses][16] f32, row-major 4 x 4, DEVICE memory; scores_dev[n_poses]: 8-byte aligned device memory */
+int nvbx_score_poses_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float* T_L_S_dev, int32_t n_poses,
+                            const nvbx_score_options* options, nvbx_pose_score* scores_dev);
+int nvbx_score_poses_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const nvbx_camera* camera, const float* T_L_C_dev,
+                           int32_t n_poses, const nvbx_score_options* options, nvbx_pose_score* scores_dev);
+/* The lattice around T0 (row-major 4 x 4, host memory): steps[0..3] = (nx, ny, nz, nyaw), each 1 .. 64, product K <= 2^20.  Hypothesis
+ * h = ((ix ny + iy) nz + iz) nyaw + iw has t_h = t0 + (dx[ix], dy[iy], dz[iz]) (three f32 additions; offsets along the layer's axes) and
+ * R_h = Rz(yaw[iw]) R0 (about the layer's z through the sensor origin).  Offset i of s steps over +-half: 0 for s == 1, else
+ * -half + (2 half i) / (s - 1) in f64, rounded once to f32 for the translations.  R_h in f64 from R0's f32 entries, c = cos(yaw), s = sin(yaw):
+ * row 0 = c R0[0] - s R0[1], row 1 = s R0[0] + c R0[1], row 2 = R0[2], rounded once to f32.  The tables are made on the host
+ * (csrc/nvbx_relocalize_math.h); the device only picks entries and adds.  nvbx_search_lattice_poses writes the K poses [K][16] into host
+ * memory and returns K, or NVBX_E_INVALID for a lattice or T0 the relocalisation would refuse (but for the range of T0). */
+typedef struct { float half_extent_m[3]; float half_yaw_rad; int32_t steps[4]; } nvbx_search_lattice;   /* 32 bytes; offsets 0 12 16 */
+#define NVBX_RELOC_OK           0
+#define NVBX_RELOC_NO_CANDIDATE 1
+typedef struct {
+  int32_t status;               /* NVBX_RELOC_* */
+  int32_t best_index;           /* h of the selected hypothesis */
+  nvbx_pose_score coarse;       /* its record */
+  float   T_coarse[16];         /* its pose */
+  nvbx_pose_score refined;      /* the record of align.T_L_S; zero with NVBX_RELOC_NO_CANDIDATE */
+  nvbx_align_result align;      /* what nvbx_align_* from T_coarse leaves; zero with NVBX_RELOC_NO_CANDIDATE */
+} nvbx_relocalize_result;       /* 832 bytes, 8-byte aligned DEVICE memory; offsets 0 4 8 32 96 120 */
+/* nvbx_relocalize_points / _depth: four steps enqueued at once.  (1) The lattice is scored as above (score_options), into scores_dev[K]
+ * if that is not NULL.  (2) Selection: the hypothesis with the largest key = inliers - conflicts; ties go to more inliers, then to the
+ * lowest h.  If its inliers < min_inliers (<= 0: the default 50) the status is NVBX_RELOC_NO_CANDIDATE, best_index / coarse / T_coarse
+ * still describe it, refined and align are zero and nothing further runs.  (3) The iterations of nvbx_align_points / _depth
+ * (align_options) from T_coarse, read on the device: `align` is bit for bit what that call leaves with T_coarse as the host guess.
+ * (4) One scoring launch of align.T_L_S into `refined`.  Refused: what scoring and alignment refuse; steps outside 1 .. 64 or a product
+ * above 2^20; a half-extent that is negative or not finite; a T0 that is not finite or out of range; a NULL or misaligned result_dev. */
+int nvbx_search_lattice_poses(const float T0[16], const nvbx_search_lattice* lattice, float* T_out_host);
+int nvbx_relocalize_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float T0[16], const nvbx_search_lattice* lattice,
+                           const nvbx_score_options* score_options, int32_t min_inliers, const nvbx_align_options* align_options,
+                           nvbx_pose_score* scores_dev, nvbx_relocalize_result* result_dev);
+int nvbx_relocalize_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const nvbx_camera* camera, const float T0[16],
+                          const nvbx_search_lattice* lattice, const nvbx_score_options* score_options, int32_t min_inliers,
+                          const nvbx_align_options* align_options, nvbx_pose_score* scores_dev, nvbx_relocalize_result* result_dev);
+
 /* ---- map merging ([U] submap fusion under a rigid transform; SEMANTICS.md "Map merging") ----------------------------------------------
  * Brings the TSDF and colour of `src` into `dst` under p_D = T_D_S p_S: every voxel of every candidate block of dst (the blocks whose voxel
  * centres can fall into the sampling cube of a TSDF block of src; missing ones are allocated) samples src at R_SD p_D + t_SD with the rule of

@@ -24,6 +24,23 @@ def points3(a, dev, what="points"):
     return p
 
 
+def poses16(a, dev, what="poses"):
+    """-> a contiguous (n, 16) float32 tensor on `dev` from (n, 4, 4) or (n, 16) row-major poses.  A tensor is moved and made contiguous, never
+    converted; anything else goes through numpy (converted to float32) and is uploaded."""
+    if not isinstance(a, torch.Tensor):
+        a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 16)))
+    if a.dtype != torch.float32 or a.numel() % 16 or (a.dim() and a.shape[-1] not in (4, 16)):
+        raise ValueError("%s must be (n, 4, 4) float32, got %s %s" % (what, tuple(a.shape), a.dtype))
+    return (a if a.device == dev else a.to(dev)).reshape(-1, 16).contiguous()
+
+
+def score_records(out, n, dev):
+    """The records of score_poses / relocalize_*: `out`, checked, or a new one -- a contiguous int64 [n, 3] tensor on `dev` (24 bytes per pose) --
+    and its two views: -> (records, counts int32 [n, 4]: points, valid, inliers, conflicts; abs_residual_q20 int64 [n])."""
+    rec, = outputs(None if out is None else (out,), (("score records", (n, 3), I64, True, True),), dev)
+    return rec, rec.view(torch.int32).reshape(n, 6)[:, :4], rec[:, 2]
+
+
 def outputs(out, spec, dev):
     """Allocate a call's outputs, or check the caller's.  spec: rows (name, shape, dtypes, required, wanted).
     out=None: -> a tensor of dtypes[0] per wanted row, None for the others.  Otherwise `out` holds one entry per row: a None in a required

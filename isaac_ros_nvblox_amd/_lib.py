@@ -125,6 +125,28 @@ class AlignResult(C.Structure):
                 ("iterations", C.c_int32), ("status", C.c_int32)]
 
 
+class PoseScore(C.Structure):
+    """nvbx_pose_score: one pose's record of nvbx_score_poses_* (24 bytes)"""
+    _fields_ = [("points", C.c_int32), ("valid", C.c_int32), ("inliers", C.c_int32), ("conflicts", C.c_int32), ("abs_residual_q20", C.c_int64)]
+
+
+class ScoreOptions(C.Structure):
+    """nvbx_score_options (20 bytes); nvbx_default_score_options fills it"""
+    _fields_ = [("min_weight", C.c_float), ("inlier_distance_m", C.c_float), ("conflict_distance_m", C.c_float), ("max_depth_m", C.c_float),
+                ("subsampling", C.c_int32)]
+
+
+class SearchLattice(C.Structure):
+    """nvbx_search_lattice (32 bytes): half-extents along x, y, z, half yaw range, steps (nx, ny, nz, nyaw)"""
+    _fields_ = [("half_extent_m", C.c_float * 3), ("half_yaw_rad", C.c_float), ("steps", C.c_int32 * 4)]
+
+
+class RelocalizeResult(C.Structure):
+    """nvbx_relocalize_result: what nvbx_relocalize_* leave in DEVICE memory (832 bytes)"""
+    _fields_ = [("status", C.c_int32), ("best_index", C.c_int32), ("coarse", PoseScore), ("T_coarse", C.c_float * 16), ("refined", PoseScore),
+                ("align", AlignResult)]
+
+
 class MergeOptions(C.Structure):
     """nvbx_merge_options (16 bytes); nvbx_default_merge_options fills it"""
     _fields_ = [("min_weight", C.c_float), ("weight_scale", C.c_float), ("merge_color", C.c_int32), ("pad", C.c_int32)]
@@ -226,6 +248,13 @@ SIGNATURES = {
     "nvbx_align_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp]),
     "nvbx_align_depth": (C.c_int, [_vp, _vp, _i32, _i32, _vp, C.POINTER(Camera), C.POINTER(AlignOptions), _vp]),
     "nvbx_linearize_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp, _vp, _vp, _vp, _vp]),
+    "nvbx_default_score_options": (None, [C.POINTER(ScoreOptions)]),
+    "nvbx_score_poses_points": (C.c_int, [_vp, _vp, _i64, _vp, _i32, C.POINTER(ScoreOptions), _vp]),
+    "nvbx_score_poses_depth": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(Camera), _vp, _i32, C.POINTER(ScoreOptions), _vp]),
+    "nvbx_search_lattice_poses": (C.c_int, [_vp, C.POINTER(SearchLattice), _vp]),
+    "nvbx_relocalize_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(SearchLattice), C.POINTER(ScoreOptions), _i32, C.POINTER(AlignOptions), _vp, _vp]),
+    "nvbx_relocalize_depth": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(Camera), _vp, C.POINTER(SearchLattice), C.POINTER(ScoreOptions), _i32,
+                                        C.POINTER(AlignOptions), _vp, _vp]),
     "nvbx_default_merge_options": (None, [C.POINTER(MergeOptions)]),
     "nvbx_merge_map": (C.c_int, [_vp, _vp, _vp, C.POINTER(MergeOptions), _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),

@@ -13,6 +13,8 @@
 //                       writes the f64 pose state, the status word and the caller's result record.
 // All max_iterations pairs are enqueued up front; the pose of iteration 0 and the options travel as kernel arguments, the pose of the later
 // ones is the state the previous solve left.  Once the status is final the remaining launches read it and return at once.
+// nvbx_relocalize_* (relocalize.hip) enqueues the same launches behind its selection, which leaves iteration 0's pose -- and a status that may
+// already be final -- in the state (AlignArgs::from_state, align_from_state).
 #include <algorithm>
 #include <cmath>
 #include "nvbx_mapper.h"
@@ -26,7 +28,7 @@ constexpr int ALIGN_MAX_WG = 256, ALIGN_TPB = 256;
 enum { ALIGN_RUNNING = 0 };
 enum { MODE_ALIGN = 0, MODE_LINEARIZE = 1 };
 
-struct AlignState { double R[9], t[3]; int32_t status, iterations; };      // 104 bytes, at the front of nvbx_mapper::align_buf
+// (AlignState { double R[9], t[3]; int32_t status, iterations; }: nvbx_mapper.h -- 104 bytes, at the front of nvbx_mapper::align_buf)
 constexpr size_t ALIGN_PARTIAL_OFFSET = 128;
 constexpr size_t ALIGN_BUF_BYTES = ALIGN_PARTIAL_OFFSET + (size_t)ALIGN_MAX_WG * ALIGN_TERMS * sizeof(double);
 
@@ -34,7 +36,8 @@ struct AlignArgs {
   const float* pts;                                             // [n][3], or ...
   const float* depth; int32_t cols, cs, s; float fu, fv, cu, cv, max_d;      // ... the pixels (r s, c s): n = rs x cs of them
   int64_t n;
-  float R0[9], t0[3];                                           // the pose of iteration 0
+  float R0[9], t0[3];                                           // the pose of iteration 0 ...
+  int32_t from_state;                                           // ... unless set: then an earlier launch left it in *st (relocalize.hip), with the status to start from
   int32_t iter, max_iter, mode, min_valid, nblocks;
   float vs, min_weight;
   double huber, damping, min_pivot, stop_t, stop_r;
@@ -46,7 +49,7 @@ template <bool DEPTH>
 __global__ __launch_bounds__(ALIGN_TPB) void k_align_accumulate(DMap m, AlignArgs a) {
   __shared__ double s_part[ALIGN_TPB / 64][ALIGN_TERMS];
   float R[9], t[3];
-  if (a.iter == 0) {
+  if (a.iter == 0 && !a.from_state) {
     for (int k = 0; k < 9; k++) R[k] = a.R0[k];
     for (int k = 0; k < 3; k++) t[k] = a.t0[k];
   } else {
@@ -121,7 +124,7 @@ constexpr int SOLVE_TPB = 256, SOLVE_GROUPS = SOLVE_TPB / 32;
 __global__ __launch_bounds__(SOLVE_TPB) void k_align_solve(AlignArgs a) {
   __shared__ double s_grp[SOLVE_GROUPS][32];
   __shared__ double s_sum[ALIGN_TERMS];
-  if (a.iter > 0 && a.st->status != ALIGN_RUNNING) return;
+  if ((a.iter > 0 || a.from_state) && a.st->status != ALIGN_RUNNING) return;
   // entry j of the partials: group g of 32 lanes takes the slots g, g + 8, .. in order (chains of at most 32 loads instead of one of 256), then the
   // eight groups in order -- a fixed order again
   const int j = threadIdx.x & 31, grp = threadIdx.x >> 5;
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(SOLVE_TPB) void k_align_solve(AlignArgs a) {
   __syncthreads();
   if (threadIdx.x != 0) return;
   double R[9], t[3];
-  if (a.iter == 0) {
+  if (a.iter == 0 && !a.from_state) {
     for (int k = 0; k < 9; k++) R[k] = (double)a.R0[k];
     for (int k = 0; k < 3; k++) t[k] = (double)a.t0[k];
   } else {
@@ -176,14 +179,15 @@ __global__ __launch_bounds__(SOLVE_TPB) void k_align_solve(AlignArgs a) {
   o->iterations = a.iter + 1; o->status = status;
 }
 
-// the checks and the launches of the three entry points.  depth != null: the depth form (pts null), else the point form.
-static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
-              const float T[16], const nvbx_align_options* options, nvbx_align_result* res, int mode, float* out_p, float* out_r, float* out_g,
-              uint8_t* out_v) {
+// the checks of the three entry points, which launch nothing: -> `a` filled but for the buffers.  depth != null: the depth form (pts null), else the
+// point form.  T null (nvbx_relocalize_*): iteration 0 takes its pose and its status from the state record.
+static int align_check(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
+                const float T[16], bool from_state, const nvbx_align_options* options, nvbx_align_result* res, int mode, float* out_p, float* out_r,
+                float* out_g, uint8_t* out_v, AlignArgs& a) {
   if (!m) return NVBX_E_INVALID;
   nvbx_align_options o;
   if (options) o = *options; else nvbx_default_align_options(&o);
-  if (!T || !res) return refuse(who, ": the pose and result_dev are required");
+  if ((!T && !from_state) || !res) return refuse(who, ": the pose and result_dev are required");
   if ((uintptr_t)res & 7) return refuse(who, ": result_dev must be 8-byte aligned");
   if (tsdf_reader_refused(m, who)) return NVBX_E_INVALID;
   if (o.max_iterations < 1 || o.max_iterations > 64) return refuse(who, ": max_iterations must be 1 .. 64");
@@ -193,8 +197,8 @@ static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t 
     return refuse(who, ": damping, min_pivot_ratio and the stop thresholds must be finite and >= 0");
   if (o.min_weight != o.min_weight || o.huber_delta_m != o.huber_delta_m || o.max_depth_m != o.max_depth_m)
     return refuse(who, ": min_weight / huber_delta_m / max_depth_m is not a number");
-  if (!nvbx_pose_in_range(T, m->p.voxel_size * 8.0f, 0.0f)) return refuse(who, ": the pose is not finite or out of range");
-  AlignArgs a{};
+  if (!from_state && !nvbx_pose_in_range(T, m->p.voxel_size * 8.0f, 0.0f)) return refuse(who, ": the pose is not finite or out of range");
+  a = AlignArgs{};
   if (depth || cam) {
     if (!depth || rows <= 0 || cols <= 0 || !nvbx_camera_matches(cam, rows, cols)) return refuse(who, ": the depth image and a camera of its size are required");
     if (o.subsampling < 1) return refuse(who, ": subsampling must be >= 1");
@@ -206,19 +210,32 @@ static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t 
     if (n < 0 || (n > 0 && !pts)) return refuse(who, ": n points need points_xyz_dev");
     a.pts = pts;
   }
-  NVBX_HIP(hipSetDevice(m->device));
-  // reads TSDF voxels and the TSDF flags only: held-back work stays held back, as for the TSDF point query (query.hip)
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
-  if (m->align_buf.ensure(m->stream, ALIGN_BUF_BYTES)) return NVBX_E_DEVICE;
   a.n = n;
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) a.R0[3 * i + j] = T[4 * i + j]; a.t0[i] = T[4 * i + 3]; }
+  a.from_state = from_state ? 1 : 0;
+  if (!from_state)
+    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) a.R0[3 * i + j] = T[4 * i + j]; a.t0[i] = T[4 * i + 3]; }
   a.max_iter = mode == MODE_LINEARIZE ? 1 : o.max_iterations; a.mode = mode; a.min_valid = o.min_valid;
   a.nblocks = (int32_t)std::min<int64_t>((n + ALIGN_TPB - 1) / ALIGN_TPB, ALIGN_MAX_WG);
   a.vs = m->p.voxel_size; a.min_weight = o.min_weight;
   a.huber = (double)o.huber_delta_m; a.damping = o.damping; a.min_pivot = o.min_pivot_ratio; a.stop_t = o.stop_translation_m; a.stop_r = o.stop_rotation_rad;
+  a.res = res; a.out_p = out_p; a.out_r = out_r; a.out_g = out_g; a.out_v = out_v;
+  return NVBX_OK;
+}
+
+// the state record and the partial sums.  (A growth waits for the stream: before the first launch of a call.)
+static int align_buffers(nvbx_mapper* m, AlignArgs& a) {
+  if (m->align_buf.ensure(m->stream, ALIGN_BUF_BYTES)) return NVBX_E_DEVICE;
   a.st = reinterpret_cast<AlignState*>(m->align_buf.as<unsigned char>());
   a.partial = reinterpret_cast<double*>(m->align_buf.as<unsigned char>() + ALIGN_PARTIAL_OFFSET);
-  a.res = res; a.out_p = out_p; a.out_r = out_r; a.out_g = out_g; a.out_v = out_v;
+  return NVBX_OK;
+}
+
+// every launch of a call whose arguments align_check has accepted
+static int align_launch(nvbx_mapper* m, AlignArgs& a) {
+  NVBX_HIP(hipSetDevice(m->device));
+  // reads TSDF voxels and the TSDF flags only: held-back work stays held back, as for the TSDF point query (query.hip)
+  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (align_buffers(m, a)) return NVBX_E_DEVICE;
   for (int32_t it = 0; it < a.max_iter; it++) {
     a.iter = it;
     if (a.nblocks > 0) {
@@ -229,6 +246,28 @@ static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t 
     if (a.nblocks == 0) break;      // (an empty cloud: the first solve says TOO_FEW)
   }
   NVBX_HIP(hipGetLastError());
+  return NVBX_OK;
+}
+
+static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
+              const float T[16], const nvbx_align_options* options, nvbx_align_result* res, int mode, float* out_p, float* out_r, float* out_g,
+              uint8_t* out_v) {
+  AlignArgs a;
+  const int rc = align_check(who, m, pts, n, depth, rows, cols, cam, T, false, options, res, mode, out_p, out_r, out_g, out_v, a);
+  return rc ? rc : align_launch(m, a);
+}
+
+// nvbx_relocalize_* (relocalize.hip): nvbx_align_points / nvbx_align_depth whose iteration 0 reads the pose -- and whether to run at all -- from the
+// state record a launch of the caller's writes.  In steps, so that a refusal comes before the caller's first launch: ALIGN_STEP_CHECK looks at the
+// arguments only, ALIGN_STEP_STATE makes sure of the record and hands it out in *state, ALIGN_STEP_LAUNCH enqueues the iterations.
+int nvbx::align_from_state(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols,
+                           const nvbx_camera* cam, const nvbx_align_options* options, nvbx_align_result* res, AlignStep step, AlignState** state) {
+  AlignArgs a;
+  const int rc = align_check(who, m, pts, n, depth, rows, cols, cam, nullptr, true, options, res, MODE_ALIGN, nullptr, nullptr, nullptr, nullptr, a);
+  if (rc || step == ALIGN_STEP_CHECK) return rc;
+  if (step == ALIGN_STEP_LAUNCH) return align_launch(m, a);
+  if (align_buffers(m, a)) return NVBX_E_DEVICE;
+  *state = a.st;
   return NVBX_OK;
 }
 

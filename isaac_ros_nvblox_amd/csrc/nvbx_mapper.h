@@ -58,6 +58,11 @@ size_t ref_voxel_bytes(uint32_t layer);
 static inline bool layer_writable(uint32_t l) { return l == F_TSDF || l == F_COLOR || l == F_ESDF || l == NVBX_LAYER_OCCUPANCY; }
 static inline bool layer_readable(uint32_t l) { return layer_writable(l) || l == F_FREESPACE; }
 static inline bool layer_listable(uint32_t l) { return layer_readable(l) || l == F_MESH || l == F_FEATURE; }      // (feature blocks are read by nvbx_get_feature_blocks)
+// align.hip.  The pose state of an alignment on the device, and the alignment whose iteration 0 starts from it (for relocalize.hip; described there)
+struct AlignState { double R[9], t[3]; int32_t status, iterations; };      // 104 bytes, at the front of nvbx_mapper::align_buf; status 0 = running
+enum AlignStep { ALIGN_STEP_CHECK, ALIGN_STEP_STATE, ALIGN_STEP_LAUNCH };
+int align_from_state(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
+                     const nvbx_align_options* options, nvbx_align_result* res, AlignStep step, AlignState** state);
 
 }  // namespace nvbx
 
@@ -138,6 +143,8 @@ struct nvbx_mapper {
   nvbx::DevBuf seg_scratch;
   // pose alignment (align.hip): the f64 pose state and the 256 x 29 partial sums of the accumulate launches, about 60 KB
   nvbx::DevBuf align_buf;
+  // relocalisation (relocalize.hip): the lattice tables (4 KB) and, where the caller wants no scores, the lattice's 24-byte records; the tables' host copy
+  nvbx::DevBuf reloc_buf; std::vector<float> reloc_host;
   // map merging (merge.hip), as the destination: a 64-byte head of counters and the key set that counts the distinct candidate blocks
   nvbx::DevBuf merge_buf;
   // frontier scan (frontier.hip), -DNVBX_FRONTIER_TWO_PASS variant only: 128 bytes of voxel classes per slot; the product's single pass needs none

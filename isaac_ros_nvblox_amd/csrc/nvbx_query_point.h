@@ -1,6 +1,6 @@
 // nvbx_query_point.h -- one lane's interpolated point query: the block probes, the eight-corner fetch and the interpolant with its gradient.
-// Device code shared by k_query_points (query.hip) and k_align_accumulate (align.hip), so the two agree bit for bit by construction; the
-// arithmetic itself is the inline code of include/nvblox_hip_device.h.
+// Device code shared by k_query_points (query.hip), k_align_accumulate (align.hip) and k_score_poses (relocalize.hip), so the three agree bit
+// for bit by construction; the arithmetic itself is the inline code of include/nvblox_hip_device.h.
 #pragma once
 #include "nvbx_internal.h"
 #include "../../include/nvblox_hip_device.h"
@@ -48,12 +48,18 @@ __device__ inline uint32_t q_lookup(const DMap& m, bool need, int32_t x, int32_t
   return s;
 }
 
+// DIST_ONLY's memory of the lane's last base block: a lane that walks neighbouring points probes the hash only when the base corner leaves
+// that block (k_view_gain's scheme).  A missing block is remembered as well.  (bx = INT32_MIN: nothing yet -- no block has that index.)
+struct QBlockCache { int32_t bx = INT32_MIN, by = 0, bz = 0; uint32_t slot = SLOT_NONE; };
+
 // The query at p: returns valid; *d = the interpolant or `unknown`, g = its gradient per metre or 0.  `pool` = the layer's voxels (TSDF: m.tsdf as
 // uint2).  Corner (i, j, k) of the lane: block offset o = (i & cx) | (j & cy) << 1 | (k & cz) << 2 from the base block.
 // (DEDUP: every lane of the wavefront must make the call.)
-template <int KIND, bool DEDUP>
+// DIST_ONLY (a further instantiation; the others compile to what they were): the distance alone -- g is not touched and may be null, the gradient's
+// arithmetic is dead code, *d_out has the same bits -- and the base block's slot comes from `cache` while the base corner stays in one block.
+template <int KIND, bool DEDUP, bool DIST_ONLY = false>
 __device__ inline bool q_point(const DMap& m, const uint2* pool, const float p[3], float vs, float min_weight, float unknown, int32_t plane_vz,
-                               float* d_out, float g[3]) {
+                               float* d_out, float g[3], QBlockCache* cache = nullptr) {
   constexpr uint32_t FLAG = KIND == Q_TSDF ? F_TSDF : F_ESDF;
   constexpr int NC = KIND == Q_ESDF2 ? 4 : 8;
   int32_t b[3] = {0, 0, plane_vz}; float t[3] = {0.0f, 0.0f, 0.0f};
@@ -70,6 +76,13 @@ __device__ inline bool q_point(const DMap& m, const uint2* pool, const float p[3
     sl[o] = SLOT_NONE;
     if (KIND == Q_ESDF2 && (o & 4)) continue;
     const bool need = ok && (o & ~cross) == 0;
+    if (DIST_ONLY && o == 0) {
+      if (need) {
+        if (cache->bx != bx || cache->by != by || cache->bz != bz) { cache->slot = q_probe(m, bx, by, bz, FLAG); cache->bx = bx; cache->by = by; cache->bz = bz; }
+        sl[0] = cache->slot;
+      }
+      continue;
+    }
     sl[o] = q_lookup<DEDUP>(m, need, bx + (o & 1), by + ((o >> 1) & 1), bz + (o >> 2), FLAG);
   }
   // corner values; the pair along the layout's fastest axis (TSDF z, ESDF x) is one 16-B load when it stays inside a block
@@ -114,7 +127,8 @@ __device__ inline bool q_point(const DMap& m, const uint2* pool, const float p[3
     }
   }
   float d = unknown;
-  g[0] = g[1] = g[2] = 0.0f;
+  float g_unused[3];
+  if (DIST_ONLY) g = g_unused; else g[0] = g[1] = g[2] = 0.0f;
   if (all) d = KIND == Q_ESDF2 ? nvbx_interp_bilinear(c, t[0], t[1], vs, g) : nvbx_interp_trilinear(c, t[0], t[1], t[2], vs, g);
   *d_out = d;
   return all;

@@ -26,6 +26,12 @@ ALIGN_CONVERGED, ALIGN_MAX_ITERATIONS, ALIGN_TOO_FEW, ALIGN_DEGENERATE, ALIGN_LI
 ALIGN_STATUS_NAMES = {1: "CONVERGED", 2: "MAX_ITERATIONS", 3: "TOO_FEW", 4: "DEGENERATE", 5: "LINEARIZED"}
 ALIGN_RESULT_BYTES = C.sizeof(_lib.AlignResult)
 
+# nvbx_relocalize_result.status (relocalize_points / relocalize_depth); one pose's record of score_poses
+RELOC_OK, RELOC_NO_CANDIDATE = 0, 1
+RELOC_STATUS_NAMES = {0: "OK", 1: "NO_CANDIDATE"}
+RELOC_RESULT_BYTES = C.sizeof(_lib.RelocalizeResult)
+PoseScore = collections.namedtuple("PoseScore", "points valid inliers conflicts abs_residual_q20")
+
 # nvbx_merge_result.status (merge_from)
 MERGE_OK, MERGE_EMPTY_SOURCE, MERGE_NO_OVERLAP = 0, 1, 2
 MERGE_STATUS_NAMES = {0: "OK", 1: "EMPTY_SOURCE", 2: "NO_OVERLAP"}
@@ -186,6 +192,39 @@ class AlignResult:
 
     def __repr__(self):
         return "AlignResult(%s, iterations=%d, n_valid=%d, rmse %.4g -> %.4g)" % (self.status_name, self.iterations, self.n_valid, self.rmse_first, self.rmse_last)
+
+
+class RelocalizeResult:
+    """What relocalize_points / relocalize_depth left behind: `buffer` is the nvbx_relocalize_result record on the device (a uint8 tensor, written
+    by the launches); the first field that is read copies it to the host once.  `align` is an AlignResult over the record's alignment part,
+    `scores` the lattice's records (counts int32 [K, 4], abs_residual_q20 int64 [K]; device tensors) where the call was asked for them."""
+
+    def __init__(self, buffer, scores=None):
+        self.buffer = buffer
+        self.scores = scores
+        self.align = AlignResult(buffer[_lib.RelocalizeResult.align.offset:])
+        self._host = None
+
+    def _r(self):
+        if self._host is None:
+            self._host = _lib.RelocalizeResult.from_buffer_copy(self.buffer.cpu().numpy().tobytes())
+        return self._host
+
+    @staticmethod
+    def _score(s):
+        return PoseScore(int(s.points), int(s.valid), int(s.inliers), int(s.conflicts), int(s.abs_residual_q20))
+
+    status = property(lambda self: int(self._r().status))
+    status_name = property(lambda self: RELOC_STATUS_NAMES.get(int(self._r().status), "?"))
+    best_index = property(lambda self: int(self._r().best_index), doc="h of the selected hypothesis")
+    coarse = property(lambda self: self._score(self._r().coarse), doc="its record")
+    T_coarse = property(lambda self: np.array(self._r().T_coarse, np.float32).reshape(4, 4), doc="its pose")
+    refined = property(lambda self: self._score(self._r().refined), doc="the record of align.T_L_S")
+    T_L_S = property(lambda self: self.align.T_L_S, doc="the refined pose, f32 (T_coarse's refinement; meaningless with NO_CANDIDATE)")
+
+    def __repr__(self):
+        return "RelocalizeResult(%s, hypothesis %d: %d inliers, %d conflicts -> %s, %d inliers)" % (
+            self.status_name, self.best_index, self.coarse.inliers, self.coarse.conflicts, self.align.status_name, self.refined.inliers)
 
 
 class MergeResult:
@@ -846,6 +885,98 @@ class Mapper:
         self._around_torch_stream(lambda: self.lib.nvbx_linearize_points(self._h, ptr(p), n, _np_ptr(T), C.byref(o), ptr(buf), ptr(pl), ptr(r), ptr(g), ptr(v)))
         self._hold("_keep_a", [p])
         return AlignResult(buf), pl, r, g, v
+
+    # -- relocalisation (nvbx_score_poses_* / nvbx_relocalize_*; SEMANTICS.md "Relocalisation")
+    def score_options(self, **kw):
+        """nvbx_score_options: the library's defaults with the given fields replaced (min_weight, inlier_distance_m, conflict_distance_m,
+        max_depth_m, subsampling).  A threshold <= 0 selects its default: one voxel size, half the truncation distance, 1e-4."""
+        return _args.struct_options(_lib.ScoreOptions, self.lib.nvbx_default_score_options, kw, "score")
+
+    def _score_source(self, points_or_depth, cam):
+        """-> (device tensor, Camera | None): cam None: an (n, 3) cloud for the _points entries; else a (rows, cols) depth image for the _depth ones"""
+        if cam is None:
+            p = _args.points3(points_or_depth, self._cuda)
+            return p, None
+        d = self._dev(points_or_depth, self._torch.float32)
+        if d.dim() != 2:
+            raise ValueError("depth must be a (rows, cols) image")
+        return d, self._cam(cam)
+
+    def score_poses(self, points_or_depth, poses, cam=None, out=None, **options):
+        """How well each of K candidate sensor poses ((K, 4, 4) or (K, 16) float32, torch device tensor or numpy array) explains a sensor-frame cloud
+        ((n, 3) float32; cam=None) or a float32 depth image (with `cam`: the pixels (r s, c s) with 0 < depth <= max_depth_m): one launch.
+        -> (counts int32 [K, 4]: points, valid, inliers, conflicts; abs_residual_q20 int64 [K]: sum of |d| in 2^-20 m over the valid points) on the
+        mapper's device, two views of one int64 [K, 3] tensor of 24-byte records.  A pose that is not finite or out of range has points = -1 and
+        zeros.  options: see score_options.  out: that preallocated int64 [K, 3] tensor, nothing is allocated."""
+        src, k = self._score_source(points_or_depth, cam)
+        T = _args.poses16(poses, self._cuda); n = int(T.shape[0])
+        o = self.score_options(**options)
+        rec, counts, residual = _args.score_records(out, n, self._cuda)
+        if k is None:
+            call = lambda: self.lib.nvbx_score_poses_points(self._h, ptr(src), src.shape[0], ptr(T), n, C.byref(o), ptr(rec))
+        else:      # (a non-collapsing pointer: the entry refuses a NULL image before it looks at its size)
+            call = lambda: self.lib.nvbx_score_poses_depth(self._h, C.c_void_p(src.data_ptr()), src.shape[0], src.shape[1], C.byref(k), ptr(T), n,
+                                                           C.byref(o), ptr(rec))
+        self._around_torch_stream(call, order=n > 0)
+        self._hold("_keep_sp", [src, T])      # (the kernel reads the points and the poses: they live until the next call)
+        return counts, residual
+
+    @staticmethod
+    def _lattice(half_extent_m, half_yaw_rad, steps):
+        he = np.broadcast_to(np.asarray(half_extent_m, np.float32), (3,)); st = [int(s) for s in steps]
+        if len(st) != 4:
+            raise ValueError("steps must be (nx, ny, nz, nyaw)")
+        return _lib.SearchLattice((C.c_float * 3)(*he.tolist()), float(half_yaw_rad), (C.c_int32 * 4)(*st))
+
+    def search_lattice(self, T0, half_extent_m, half_yaw_rad, steps):
+        """The poses relocalize_* score around T0: -> (K, 4, 4) float32 numpy array, K = nx ny nz nyaw, hypothesis
+        h = ((ix ny + iy) nz + iz) nyaw + iw at t0 + (dx[ix], dy[iy], dz[iz]) with Rz(yaw[iw]) R0; step i of s covers -half .. +half evenly
+        (0 for s = 1).  half_extent_m: one number or (x, y, z).  Host only."""
+        lat = self._lattice(half_extent_m, half_yaw_rad, steps); T = self._T(T0)
+        K = 1
+        for s in lat.steps:
+            K *= max(int(s), 0)
+        out = np.zeros((max(min(K, 1 << 20), 1), 4, 4), np.float32)
+        K = self._check(self.lib.nvbx_search_lattice_poses(_np_ptr(T), C.byref(lat), _np_ptr(out)))
+        return out[:K]
+
+    def _relocalize(self, src, k, T0, half_extent_m, half_yaw_rad, steps, min_inliers, score, align, scores, out):
+        lat = self._lattice(half_extent_m, half_yaw_rad, steps); T = self._T(T0)
+        so = self.score_options(**(score or {})); ao = self.align_options(**(align or {}))
+        buf = _args.result_buffer(out, RELOC_RESULT_BYTES, self._cuda)
+        views = None
+        rec = None
+        if scores is not None and scores is not False:
+            K = int(np.prod([int(s) for s in lat.steps]))
+            rec, counts, residual = _args.score_records(None if scores is True else scores, K, self._cuda)
+            views = (counts, residual)
+        mi = int(min_inliers) if min_inliers is not None else 0
+        if k is None:
+            call = lambda: self.lib.nvbx_relocalize_points(self._h, ptr(src), src.shape[0], _np_ptr(T), C.byref(lat), C.byref(so), mi, C.byref(ao),
+                                                           ptr(rec), ptr(buf))
+        else:
+            call = lambda: self.lib.nvbx_relocalize_depth(self._h, C.c_void_p(src.data_ptr()), src.shape[0], src.shape[1], C.byref(k), _np_ptr(T),
+                                                          C.byref(lat), C.byref(so), mi, C.byref(ao), ptr(rec), ptr(buf))
+        self._around_torch_stream(call)
+        self._hold("_keep_a", [src])
+        return RelocalizeResult(buf, views)
+
+    def relocalize_points(self, points, T0, half_extent_m, half_yaw_rad, steps, min_inliers=None, score=None, align=None, scores=None, out=None):
+        """Find a sensor-frame cloud's pose in the map from a guess that may be far outside the truncation band: the lattice search_lattice(T0,
+        half_extent_m, half_yaw_rad, steps) is scored as by score_poses, the hypothesis with the most inliers - conflicts (ties: more inliers, then
+        the lower index) is refined with align_points' iterations, and the refined pose is scored once more -- all enqueued at once on the mapper's
+        stream, nothing waits on the host.  -> RelocalizeResult.  With fewer than min_inliers (default 50) inliers at the best hypothesis the
+        status is NO_CANDIDATE and no refinement runs.  score / align: dicts of score_options / align_options fields.  scores: True, or a
+        preallocated int64 [K, 3] tensor: the lattice's records are kept (result.scores).  out: a preallocated result buffer (uint8 tensor of
+        RELOC_RESULT_BYTES bytes)."""
+        src, _ = self._score_source(points, None)
+        return self._relocalize(src, None, T0, half_extent_m, half_yaw_rad, steps, min_inliers, score, align, scores, out)
+
+    def relocalize_depth(self, depth, T0, cam, half_extent_m, half_yaw_rad, steps, min_inliers=None, score=None, align=None, scores=None, out=None):
+        """relocalize_points for a float32 depth image: scoring takes the pixels (r s, c s) of the score options' subsampling and max_depth_m, the
+        refinement those of the align options', both back-projected inside the launches."""
+        src, k = self._score_source(depth, cam)
+        return self._relocalize(src, k, T0, half_extent_m, half_yaw_rad, steps, min_inliers, score, align, scores, out)
 
     # -- map merging (nvbx_merge_map; SEMANTICS.md "Map merging")
     def merge_options(self, **kw):

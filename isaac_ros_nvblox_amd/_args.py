@@ -1,15 +1,70 @@
-"""Argument coercion and output buffers of the mapper's reader calls (mapper.py, from the point queries down to view_gain).
-
+"""Argument coercion and output buffers of the mapper's calls (mapper.py): one coercion per kind of input, one tensor -> pointer conversion (`ptr`),
+ValueError on bad input.  Writers, converters and exporters: `image` / `depth_image` for what a call is fed, `pose` / `pose_block`, `camera` /
+`lidar`, and `frame` for the C argument group of an image with its pose and intrinsics.  Reader calls: `points3` / `poses16` and `outputs`.
 Pure functions: the target torch.device is an argument, nothing here touches the library or a stream, so they run with torch.device("cpu")
-on a machine without a GPU (tests/test_wrapper_args.py).  A reader call declares its outputs as a spec for `outputs` and adds no coercion
-code of its own ("Host language").
+on a machine without a GPU (tests/test_wrapper_args.py).  A call adds no coercion code of its own ("Host language").
 """
 import ctypes as C
 import numpy as np
 import torch
 
+from ._lib import Camera, Lidar
+
 F32, F16, I32, I64, U8 = (torch.float32,), (torch.float16,), (torch.int32,), (torch.int64,), (torch.uint8,)
 FLAG = (torch.bool, torch.uint8)      # what a `valid` / `hit` output may be: the kernels write one byte, 0 or 1
+
+
+def image(a, dev, dtype, what="image", dims=None, channels=None, convert=True):
+    """-> a contiguous tensor of `dtype` on `dev`; with dims (the shape in words: "(rows, cols)" for depth, range and mask images, "(rows, cols, 3)"
+    for colour) of that many dimensions, the last one of `channels` where given.  A tensor is moved and made contiguous, never converted;
+    anything else goes through numpy and is uploaded -- where an array of another dtype IS converted (a float64 depth image, a bool mask:
+    what Mapper._dev always did) unless convert=False."""
+    if not isinstance(a, torch.Tensor):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+        a = a.to(dtype) if convert else a
+    t = (a if a.device == dev else a.to(dev)).contiguous()
+    if t.dtype != dtype or (dims and t.dim() != dims.count(",") + 1) or (channels and t.shape[-1] not in channels):
+        raise ValueError("%s must be a %s%s array, got %s %s" % (what, dims + " " if dims else "", str(dtype)[6:], tuple(t.shape), t.dtype))
+    return t
+
+
+def depth_image(a, dev, what="depth"):
+    """-> ((rows, cols) tensor, "f32" | "u16mm").  THE rule for a depth image in u16 millimetres: a torch.int16 tensor (torch has no uint16
+    arithmetic; the kernels read the bits as uint16) or an array numpy calls uint16, whose bits go into an int16 tensor unchanged.  Anything
+    else is float32 metres."""
+    u16 = a.dtype == torch.int16 if isinstance(a, torch.Tensor) else np.asarray(a).dtype == np.uint16
+    if u16 and not isinstance(a, torch.Tensor):
+        a = torch.from_numpy(np.ascontiguousarray(a).view(np.int16))
+    return image(a, dev, torch.int16 if u16 else torch.float32, what, "(rows, cols)"), "u16mm" if u16 else "f32"
+
+
+def pose(T):      # -> a contiguous float32 (4, 4) numpy array from anything that holds 16 numbers, row-major
+    return np.ascontiguousarray(np.asarray(T, np.float32).reshape(4, 4))
+
+
+def pose_block(poses):      # n poses -> one contiguous float32 (n, 16) numpy array
+    return np.ascontiguousarray(np.stack([pose(T) for T in poses]).reshape(len(poses), 16))
+
+
+def camera(cam):      # a Camera, or (fu, fv, cu, cv, width, height) -> Camera
+    return cam if isinstance(cam, Camera) else Camera(float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]), int(cam[4]), int(cam[5]))
+
+
+def lidar(lidar):      # a Lidar, or (azimuth divisions, elevation divisions, min range, min elevation, max elevation) -> Lidar
+    return lidar if isinstance(lidar, Lidar) else Lidar(int(lidar[0]), int(lidar[1]), float(lidar[2]), float(lidar[3]), float(lidar[4]))
+
+
+def np_ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def frame(img, T, model, collapse=True):
+    """THE C argument group of an image with its pose and intrinsics: -> ((pointer, rows, cols, pose pointer, byref(model)), keep).
+    img: a device tensor (rows, cols[, channels]), or a library-owned frame with .ptr, .rows and .cols (ColorFrame); model: a Camera or a
+    Lidar.  keep = (img, pose array, model): what the pointers point into, to be held for as long as the group is in use."""
+    T = pose(T)
+    p, rows, cols = (ptr(img, collapse), img.shape[0], img.shape[1]) if isinstance(img, torch.Tensor) else (C.c_void_p(img.ptr), img.rows, img.cols)
+    return (p, rows, cols, np_ptr(T), C.byref(model)), (img, T, model)
 
 
 def points3(a, dev, what="points"):
@@ -93,11 +148,12 @@ def sparse_volume(out, dev, count_blocks, scores_required=True, all_queries=None
     return tuple(t), cap, counts
 
 
-def ptr(x):
+def ptr(x, collapse=True):
     """THE tensor -> c_void_p conversion: None and an empty tensor become NULL.  Every entry point the reader calls use takes NULL where
     the count or capacity that sizes the tensor is 0 (its first check reads `n > 0 && !pointer`), and NULL for an optional output means
-    'not wanted', which is what an empty one is."""
-    return C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None
+    'not wanted', which is what an empty one is; the writers' entry points refuse NULL and a zero size in one check, with one text.
+    collapse=False: an empty tensor keeps its address -- for an entry point that refuses NULL before it looks at the size, or takes size 0."""
+    return C.c_void_p(x.data_ptr()) if x is not None and (x.numel() or not collapse) else None
 
 
 def result_buffer(out, nbytes, dev):

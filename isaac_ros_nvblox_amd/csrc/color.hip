@@ -296,16 +296,14 @@ int nvbx_mapper::launch_pending_color_after_trace() {
 
 extern "C" int nvbx_integrate_color(nvbx_mapper* m, const uint8_t* rgb_dev, int32_t rows, int32_t cols, const float T_L_C[16],
                                     const nvbx_camera* camera) {
-  if (!m || !rgb_dev || !T_L_C || !camera || !image_dims_ok(rows, cols)) { set_error("nvbx_integrate_color: invalid argument (image sides 1 .. 32768)"); return NVBX_E_INVALID; }
-  if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_color: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (const int rc = nvbx_camera_frame_refused("nvbx_integrate_color", m && rgb_dev && T_L_C && camera, "", rows, cols, camera)) return rc;
   { int rc = NVBX_OK; const void* im = rgb_dev; if (defer_color(m, ColorEnc::rgb8, 1, &im, rows, cols, T_L_C, camera, &rc)) return rc; }
   const PixRgb8 img{rgb_dev};
   return integrate_colors<PixRgb8, 1>(m, 1, &img, rows, cols, T_L_C, camera);
 }
 extern "C" int nvbx_integrate_color_bgra8(nvbx_mapper* m, const uint8_t* bgra_dev, int32_t rows, int32_t cols, const float T_L_C[16],
                                           const nvbx_camera* camera) {
-  if (!m || !bgra_dev || !T_L_C || !camera || !image_dims_ok(rows, cols) || ((uintptr_t)bgra_dev & 3)) { set_error("nvbx_integrate_color_bgra8: invalid argument"); return NVBX_E_INVALID; }
-  if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_color_bgra8: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (const int rc = nvbx_camera_frame_refused("nvbx_integrate_color_bgra8", m && bgra_dev && T_L_C && camera && !((uintptr_t)bgra_dev & 3), nullptr, rows, cols, camera)) return rc;
   { int rc = NVBX_OK; const void* im = bgra_dev; if (defer_color(m, ColorEnc::bgra8, 1, &im, rows, cols, T_L_C, camera, &rc)) return rc; }
   const PixBgra8 img{reinterpret_cast<const uint32_t*>(bgra_dev)};
   return integrate_colors<PixBgra8, 1>(m, 1, &img, rows, cols, T_L_C, camera);
@@ -329,9 +327,7 @@ extern "C" int nvbx_integrate_color_owned(nvbx_mapper* m, void* frame, int32_t b
 // Up to NVBX_MAX_BATCH colour frames (rgb8, same image size) in ONE launch set: see include/nvblox_hip.h
 extern "C" int nvbx_integrate_color_batch(nvbx_mapper* m, int32_t n, const uint8_t* const* rgb_dev, int32_t rows, int32_t cols, const float* T_L_C,
                                           const nvbx_camera* cameras) {
-  if (!m || n < 1 || n > MAX_BATCH || !rgb_dev || !T_L_C || !cameras || !image_dims_ok(rows, cols)) { set_error("nvbx_integrate_color_batch: invalid argument (1 <= n <= 8, image sides 1 .. 32768)"); return NVBX_E_INVALID; }
-  for (int c = 0; c < n; c++)
-    if (!rgb_dev[c] || !nvbx_camera_matches(cameras + c, rows, cols)) { set_error("nvbx_integrate_color_batch: every camera's width/height must equal the images' cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (const int rc = nvbx_camera_frame_refused("nvbx_integrate_color_batch", m && n >= 1 && n <= MAX_BATCH && rgb_dev && T_L_C && cameras, "1 <= n <= 8, ", rows, cols, cameras, n, reinterpret_cast<const void* const*>(rgb_dev))) return rc;
   if (n == 1) return nvbx_integrate_color(m, rgb_dev[0], rows, cols, T_L_C, cameras);
   { int rc = NVBX_OK; if (defer_color(m, ColorEnc::rgb8, n, reinterpret_cast<const void* const*>(rgb_dev), rows, cols, T_L_C, cameras, &rc)) return rc; }     // (held back: a depth batch carries it out)
   PixRgb8 imgs[MAX_BATCH];

@@ -103,8 +103,7 @@ __global__ __launch_bounds__(512) void k_apply_fuse(DMap m, Frame f, const MeasR
 
 extern "C" int nvbx_measure_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const float T_L_C[16], const nvbx_camera* camera,
                                   nvbx_measurement_block* out_dev, int32_t* count_dev, int64_t capacity_blocks) {
-  if (!m || !depth_dev || !T_L_C || !camera || !out_dev || !count_dev || capacity_blocks <= 0 || !image_dims_ok(rows, cols)) { set_error("nvbx_measure_depth: invalid argument"); return NVBX_E_INVALID; }
-  if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_measure_depth: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (const int rc = nvbx_camera_frame_refused("nvbx_measure_depth", m && depth_dev && T_L_C && camera && out_dev && count_dev && capacity_blocks > 0, nullptr, rows, cols, camera)) return rc;
   if (!nvbx_pose_in_range(T_L_C, m->p.voxel_size * 8.0f, m->p.max_integration_distance_m + 2.0f * m->p.truncation_distance_vox * m->p.voxel_size)) {
     set_error("nvbx_measure_depth: T_L_C is not finite or lies outside the addressable block range"); return NVBX_E_INVALID; }
   // measure + apply is DEFINED as equal to nvbx_integrate_depth_batch; what the batch cannot express either (depth dilation, per-frame

@@ -71,6 +71,16 @@ int align_from_state(const char* who, nvbx_mapper* m, const float* pts, int64_t 
 static inline bool nvbx_camera_matches(const nvbx_camera* c, int32_t rows, int32_t cols) {
   return c && c->width == cols && c->height == rows && c->fu > 0.0f && c->fv > 0.0f;
 }
+// THE two refusals of a camera-frame entry point `who`, in their order; 0 = go on.  args_ok: the entry's own conditions on its pointers and counts; hint: what its first refusal says in
+// parentheses ahead of the image sides (null: no parentheses).  images: a batch's n image pointers, each checked with its camera (a single frame: null, its image pointer is part of args_ok)
+static inline int nvbx_camera_frame_refused(const char* who, bool args_ok, const char* hint, int32_t rows, int32_t cols, const nvbx_camera* cameras, int32_t n = 1, const void* const* images = nullptr) {
+  if (!args_ok || !nvbx::image_dims_ok(rows, cols)) return nvbx::refuse(who, hint ? (std::string(": invalid argument (") + hint + "image sides 1 .. 32768)").c_str() : ": invalid argument");
+  for (int c = 0; c < n; c++)
+    if ((images && !images[c]) || !nvbx_camera_matches(cameras + c, rows, cols))
+      return nvbx::refuse(who, images ? ": every camera's width/height must equal the images' cols/rows, focal lengths > 0"
+                                      : ": camera width/height must equal the image's cols/rows, focal lengths > 0");
+  return 0;
+}
 // ... and one that comes without an image (rendering, view gain, feature frames) must describe an image the C-ABI would accept
 static inline bool nvbx_camera_valid(const nvbx_camera* c) {
   return c && c->fu > 0.0f && c->fv > 0.0f && nvbx::image_dims_ok(c->height, c->width);

@@ -568,24 +568,20 @@ static int integrate_cameras(nvbx_mapper* m, int32_t n, const Img* imgs, int32_t
 
 extern "C" int nvbx_integrate_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const float T_L_C[16],
                                     const nvbx_camera* camera) {
-  if (!m || !depth_dev || !T_L_C || !camera || !image_dims_ok(rows, cols)) { set_error("nvbx_integrate_depth: invalid argument (image sides 1 .. 32768)"); return NVBX_E_INVALID; }
-  if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_depth: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (const int rc = nvbx_camera_frame_refused("nvbx_integrate_depth", m && depth_dev && T_L_C && camera, "", rows, cols, camera)) return rc;
   const DepthF32 img{depth_dev};
   return integrate_cameras<DepthF32, 1>(m, 1, &img, rows, cols, T_L_C, camera);
 }
 extern "C" int nvbx_integrate_depth_u16mm(nvbx_mapper* m, const uint16_t* depth_mm_dev, int32_t rows, int32_t cols, const float T_L_C[16],
                                           const nvbx_camera* camera) {
-  if (!m || !depth_mm_dev || !T_L_C || !camera || !image_dims_ok(rows, cols)) { set_error("nvbx_integrate_depth_u16mm: invalid argument (image sides 1 .. 32768)"); return NVBX_E_INVALID; }
-  if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_depth_u16mm: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (const int rc = nvbx_camera_frame_refused("nvbx_integrate_depth_u16mm", m && depth_mm_dev && T_L_C && camera, "", rows, cols, camera)) return rc;
   const DepthU16mm img{depth_mm_dev};
   return integrate_cameras<DepthU16mm, 1>(m, 1, &img, rows, cols, T_L_C, camera);
 }
 // Up to NVBX_MAX_BATCH camera frames (same image size) in ONE launch set: see include/nvblox_hip.h
 extern "C" int nvbx_integrate_depth_batch(nvbx_mapper* m, int32_t n, const float* const* depth_dev, int32_t rows, int32_t cols, const float* T_L_C,
                                           const nvbx_camera* cameras) {
-  if (!m || n < 1 || n > MAX_BATCH || !depth_dev || !T_L_C || !cameras || !image_dims_ok(rows, cols)) { set_error("nvbx_integrate_depth_batch: invalid argument (1 <= n <= 8, image sides 1 .. 32768)"); return NVBX_E_INVALID; }
-  for (int c = 0; c < n; c++)
-    if (!depth_dev[c] || !nvbx_camera_matches(cameras + c, rows, cols)) { set_error("nvbx_integrate_depth_batch: every camera's width/height must equal the images' cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (const int rc = nvbx_camera_frame_refused("nvbx_integrate_depth_batch", m && n >= 1 && n <= MAX_BATCH && depth_dev && T_L_C && cameras, "1 <= n <= 8, ", rows, cols, cameras, n, reinterpret_cast<const void* const*>(depth_dev))) return rc;
   // what a batch cannot express falls back to the separate calls it is defined by: per-frame freespace time stamps, depth dilation
   if (n == 1 || m->p.projective_layer_type == 2 || (m->p.do_depth_preprocessing && m->p.depth_preprocessing_num_dilations > 0)) {
     for (int c = 0; c < n; c++) { const int rc = nvbx_integrate_depth(m, depth_dev[c], rows, cols, T_L_C + 16 * c, cameras + c); if (rc) return rc; }
@@ -612,8 +608,7 @@ static bool pair_colour_encodings_differ(const nvbx_mapper* ma, const nvbx_mappe
 }
 extern "C" int nvbx_integrate_depth_pair(nvbx_mapper* ma, const float* depth_a_dev, nvbx_mapper* mb, const float* depth_b_dev, int32_t rows, int32_t cols,
                                          const float T_L_C[16], const nvbx_camera* camera) {
-  if (!ma || !mb || ma == mb || !depth_a_dev || !depth_b_dev || !T_L_C || !camera || !image_dims_ok(rows, cols)) { set_error("nvbx_integrate_depth_pair: invalid argument (two different mappers, image sides 1 .. 32768)"); return NVBX_E_INVALID; }
-  if (!nvbx_camera_matches(camera, rows, cols)) { set_error("nvbx_integrate_depth_pair: camera width/height must equal the image's cols/rows, focal lengths > 0"); return NVBX_E_INVALID; }
+  if (const int rc = nvbx_camera_frame_refused("nvbx_integrate_depth_pair", ma && mb && ma != mb && depth_a_dev && depth_b_dev && T_L_C && camera, "two different mappers, ", rows, cols, camera)) return rc;
   static const int pair_on = nvbx_knob_switch(getenv("NVBX_DEPTH_PAIR"));       // (A/B: 0 = always the two separate calls)
   if (!pair_on || ma->device != mb->device || ma->stream != mb->stream || !pair_can_fuse(ma) || !pair_can_fuse(mb) ||
       pair_colour_encodings_differ(ma, mb)) {

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _args, _lib
-from ._args import F16, F32, FLAG, I32, I64, U8, ptr
+from ._args import F16, F32, FLAG, I32, I64, U8, np_ptr as _np_ptr, ptr
 from ._lib import BoundingShape, Camera, Counters, Index3D, Lidar, Params
 
 LAYER_TSDF, LAYER_COLOR, LAYER_ESDF, LAYER_MESH, LAYER_OCCUPANCY, LAYER_FREESPACE = 1, 2, 4, 8, 16, 32
@@ -91,10 +91,6 @@ def frame_pool_stats():
     return tuple(int(v) for v in out)
 
 
-def _np_ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 class ColorFrame:
     """A colour image in a library-owned, reference-counted device frame (nvbx_frame_acquire, include/nvblox_hip.h): what nvblox::Image<Color>
     device memory is in the C++ facade.  A mapper that holds integrate_color back RETAINS the frame instead of copying the image; `write` first makes
@@ -132,7 +128,7 @@ class ColorFrame:
             self.lib.nvbx_frame_release(old)
         if hasattr(src, "data_ptr"):
             assert src.is_contiguous() and src.numel() * src.element_size() == self.nbytes
-            sp = C.c_void_p(src.data_ptr())
+            sp = ptr(src)
         else:
             a = np.ascontiguousarray(src, np.uint8); assert a.nbytes == self.nbytes
             self._host_keep = a; sp = _np_ptr(a)
@@ -353,26 +349,31 @@ class Mapper:
                 cur.wait_stream(ms)
         setattr(self, slot, tensors)
 
+    # -- Argument coercion and output buffers live in _args.py, for every call: a call adds no coercion code of its own and hands tensors to the
+    #    library through `ptr`; a reader call declares its outputs as a spec of (name, shape, dtypes, required, wanted) rows ("Host language")
+    @property
+    def _cuda(self):
+        return self._torch.device("cuda", self.device)
+
     def _dev(self, a, dtype):
-        torch = self._torch
-        if isinstance(a, torch.Tensor):
-            t = a
-            if not t.is_cuda:
-                t = t.cuda(self.device)
-            t = t.contiguous()
-            assert t.dtype == dtype, (t.dtype, dtype)
-            return t
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).cuda(self.device)
+        return _args.image(a, self._cuda, dtype)
 
-    @staticmethod
-    def _T(T):
-        return np.ascontiguousarray(np.asarray(T, np.float32).reshape(4, 4))
+    _T = staticmethod(_args.pose)
+    _cam = staticmethod(_args.camera)
+    _lidar = staticmethod(_args.lidar)
 
-    @staticmethod
-    def _cam(cam):
-        if isinstance(cam, Camera):
-            return cam
-        return Camera(float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]), int(cam[4]), int(cam[5]))
+    def _image(self, a, what="depth", dtype=None):      # a (rows, cols) image: float32 (depth, range) unless dtype says otherwise (uint8: a mask)
+        return _args.image(a, self._cuda, dtype or self._torch.float32, what, "(rows, cols)")
+
+    def _frame(self, fn, img, T, model):
+        """-> the prepared call of an image with its pose and intrinsics: (fn, pointer, rows, cols, pose pointer, byref(model), keep), keep[0] = img"""
+        group, keep = _args.frame(img, T, model)
+        return (fn,) + group + (keep,)
+
+    def _run(self, a, slot):      # a prepared call, now; its device image is kept alive in `slot` until the next call (stream-ordered use)
+        self._check(a[0](self._h, *a[1:6]))
+        if slot:
+            self._hold(slot, [a[6][0]])
 
     def set_params(self, params):
         self._check(self.lib.nvbx_mapper_set_params(self._h, C.byref(params)))
@@ -406,115 +407,76 @@ class Mapper:
 
     # -- integration (async)
     def integrate_depth(self, depth, T_L_C, cam):
-        torch = self._torch
-        if isinstance(depth, torch.Tensor) and depth.dtype == torch.int16 or (
-                not isinstance(depth, torch.Tensor) and np.asarray(depth).dtype == np.uint16):
-            if not isinstance(depth, torch.Tensor):
-                depth = torch.from_numpy(np.ascontiguousarray(depth).view(np.int16))
-            d = self._dev(depth, torch.int16)
-            fn = self.lib.nvbx_integrate_depth_u16mm
-        else:
-            d = self._dev(depth, torch.float32)
-            fn = self.lib.nvbx_integrate_depth
-        T = self._T(T_L_C); k = self._cam(cam)
-        self._check(fn(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k)))
-        self._hold("_keep", [d])   # keep the device image alive until the next call (stream-ordered use)
-
-    @staticmethod
-    def _lidar(lidar):
-        if isinstance(lidar, Lidar):
-            return lidar
-        return Lidar(int(lidar[0]), int(lidar[1]), float(lidar[2]), float(lidar[3]), float(lidar[4]))
+        """depth [rows, cols]: float32 metres, or u16 millimetres (a numpy uint16 array / a torch.int16 tensor holding those bits)"""
+        self._run(self.prepare_depth(depth, T_L_C, cam), "_keep")
 
     def integrate_lidar_depth(self, range_image, T_L_C, lidar):
         """range image [elevation divisions, azimuth divisions] f32 metres; lidar = (cols, rows, min_range, min_el, max_el)."""
-        d = self._dev(range_image, self._torch.float32)
-        T = self._T(T_L_C); k = self._lidar(lidar)
-        self._check(self.lib.nvbx_integrate_lidar_depth(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k)))
-        self._hold("_keep", [d])
+        self._run(self.prepare_lidar(range_image, T_L_C, lidar), "_keep")
 
     def prepare_lidar(self, range_image, T_L_C, lidar):
-        d = self._dev(range_image, self._torch.float32)
-        T = self._T(T_L_C); k = self._lidar(lidar)
-        return (self.lib.nvbx_integrate_lidar_depth, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k), (d, T, k))
+        return self._frame(self.lib.nvbx_integrate_lidar_depth, self._image(range_image, "range_image"), T_L_C, _args.lidar(lidar))
 
     def motion_compensate_pointcloud(self, points, rel_time_ms, T_L_S_start, T_L_S_end, scan_duration_ms):
         """LiDAR motion compensation: points [n, 3] measured at rel_time_ms [n] within the scan -> sensor frame at scan start (device tensor)."""
-        torch = self._torch
-        p = self._dev(np.ascontiguousarray(points, np.float32) if not isinstance(points, torch.Tensor) else points, torch.float32)
-        t = self._dev(np.ascontiguousarray(rel_time_ms, np.float32) if not isinstance(rel_time_ms, torch.Tensor) else rel_time_ms, torch.float32)
-        out = torch.empty_like(p)
-        self._check(self.lib.nvbx_motion_compensate_pointcloud(self._h, C.c_void_p(p.data_ptr()), C.c_void_p(t.data_ptr()), p.shape[0],
-                                                               _np_ptr(self._T(T_L_S_start)), _np_ptr(self._T(T_L_S_end)), float(scan_duration_ms),
-                                                               C.c_void_p(out.data_ptr())))
+        p = _args.points3(points, self._cuda); t = _args.image(rel_time_ms, self._cuda, self._torch.float32, "rel_time_ms")
+        out = self._torch.empty_like(p)
+        self._check(self.lib.nvbx_motion_compensate_pointcloud(self._h, ptr(p), ptr(t), p.shape[0], _np_ptr(self._T(T_L_S_start)),
+                                                               _np_ptr(self._T(T_L_S_end)), float(scan_duration_ms), ptr(out)))
         self.synchronize()
         return out
 
     def depth_image_from_pointcloud(self, points, lidar):
-        torch = self._torch
-        p = self._dev(points, torch.float32)
-        assert p.dim() == 2 and p.shape[1] == 3
-        k = self._lidar(lidar)
-        img = torch.zeros((k.num_elevation_divisions, k.num_azimuth_divisions), dtype=torch.float32, device=p.device)
-        self._check(self.lib.nvbx_depth_image_from_pointcloud(self._h, C.c_void_p(p.data_ptr()), p.shape[0], C.byref(k), C.c_void_p(img.data_ptr())))
+        p = _args.points3(points, self._cuda); k = _args.lidar(lidar)
+        img = self._torch.zeros((k.num_elevation_divisions, k.num_azimuth_divisions), dtype=self._torch.float32, device=p.device)
+        # (a non-collapsing pointer: the entry takes an empty cloud, but not a NULL one)
+        self._check(self.lib.nvbx_depth_image_from_pointcloud(self._h, ptr(p, collapse=False), p.shape[0], C.byref(k), ptr(img)))
         self.synchronize()
         return img
 
     def integrate_color(self, rgb, T_L_C, cam):
         """rgb8 [rows, cols, 3] or bgra8 [rows, cols, 4] (the two encodings image_conversions.cpp:170-176 accepts)."""
-        if isinstance(rgb, ColorFrame):
-            T = self._T(T_L_C); k = self._cam(cam)
-            fn = self.lib.nvbx_integrate_color_bgra8 if rgb.channels == 4 else self.lib.nvbx_integrate_color
-            self._check(fn(self._h, C.c_void_p(rgb.ptr), rgb.rows, rgb.cols, _np_ptr(T), C.byref(k)))
-            return
-        d = self._dev(rgb, self._torch.uint8)
-        assert d.dim() == 3 and d.shape[2] in (3, 4)
-        T = self._T(T_L_C); k = self._cam(cam)
-        if d.shape[2] == 4:
-            self._check(self.lib.nvbx_integrate_color_bgra8(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k)))
-            self._hold("_keep_c", [d])
-            return
-        self._check(self.lib.nvbx_integrate_color(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k)))
-        self._hold("_keep_c", [d])
+        self._run(self._color(rgb, T_L_C, cam, (3, 4)), None if isinstance(rgb, ColorFrame) else "_keep_c")
 
     # -- pre-marshalled calls: the reference hands ready C++ objects to integrateDepth/Color; this keeps Python's per-call
     #    argument marshalling (tensor checks, numpy pose copy, struct construction) out of a measured loop
     def prepare_depth(self, depth, T_L_C, cam):
-        torch = self._torch
-        d = self._dev(depth, torch.float32)
-        T = self._T(T_L_C); k = self._cam(cam)
-        return (self.lib.nvbx_integrate_depth, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k), (d, T, k))
+        d, kind = _args.depth_image(depth, self._cuda)
+        return self._frame(self.lib.nvbx_integrate_depth_u16mm if kind == "u16mm" else self.lib.nvbx_integrate_depth, d, T_L_C, _args.camera(cam))
+
+    def _color(self, rgb, T_L_C, cam, channels):
+        """the prepared call of a colour image (a ColorFrame, or what `image` takes) with one of `channels` channels: 4 = bgra8"""
+        if not isinstance(rgb, ColorFrame):
+            rgb = _args.image(rgb, self._cuda, self._torch.uint8, "rgb", "(rows, cols, %s)" % " or ".join(map(str, channels)), channels)
+        elif rgb.channels not in channels:
+            raise ValueError("the ColorFrame has %d channels, not one of %s" % (rgb.channels, channels))
+        ch = rgb.channels if isinstance(rgb, ColorFrame) else rgb.shape[2]
+        return self._frame(self.lib.nvbx_integrate_color_bgra8 if ch == 4 else self.lib.nvbx_integrate_color, rgb, T_L_C, _args.camera(cam))
 
     def prepare_color(self, rgb, T_L_C, cam):
-        if isinstance(rgb, ColorFrame):
-            assert rgb.channels == 3
-            T = self._T(T_L_C); k = self._cam(cam)
-            return (self.lib.nvbx_integrate_color, C.c_void_p(rgb.ptr), rgb.rows, rgb.cols, _np_ptr(T), C.byref(k), (rgb, T, k))
-        d = self._dev(rgb, self._torch.uint8)
-        assert d.dim() == 3 and d.shape[2] == 3
-        T = self._T(T_L_C); k = self._cam(cam)
-        return (self.lib.nvbx_integrate_color, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k), (d, T, k))
+        return self._color(rgb, T_L_C, cam, (3,))
 
     # -- camera batches (nvbx_integrate_depth_batch / _color_batch): n frames of one image size in ONE launch set
-    def _batch(self, fn, imgs, dtype, poses, cams):
+    def _batch(self, fn, imgs, coerce, poses, cams):
         n = len(imgs)
-        d = [i if isinstance(i, ColorFrame) else self._dev(i, dtype) for i in imgs]
-        ptrs = (C.c_void_p * n)(*[t.ptr if isinstance(t, ColorFrame) else t.data_ptr() for t in d])
-        T = np.ascontiguousarray(np.stack([self._T(p) for p in poses]).reshape(n, 16))
+        d = [i if isinstance(i, ColorFrame) else coerce(i) for i in imgs]
+        ptrs = (C.c_void_p * n)(*[t.ptr if isinstance(t, ColorFrame) else t.data_ptr() for t in d])      # (raw addresses: the elements of an array)
+        T = _args.pose_block(poses)
         if not isinstance(cams, (list, tuple)) or not isinstance(cams[0], (list, tuple, Camera)):
             cams = [cams] * n
-        ks = (Camera * n)(*[self._cam(k) for k in cams])
-        r_, c_ = (d[0].rows, d[0].cols) if isinstance(d[0], ColorFrame) else (d[0].shape[0], d[0].shape[1])
-        return (fn, n, ptrs, r_, c_, _np_ptr(T), ks, (d, T))
+        ks = (Camera * n)(*[_args.camera(k) for k in cams])
+        rows, cols = (d[0].rows, d[0].cols) if isinstance(d[0], ColorFrame) else d[0].shape[:2]
+        return (fn, n, ptrs, rows, cols, _np_ptr(T), ks, (d, T))
 
     def prepare_depth_batch(self, depths, poses, cams):
-        return self._batch(self.lib.nvbx_integrate_depth_batch, depths, self._torch.float32, poses, cams)
+        return self._batch(self.lib.nvbx_integrate_depth_batch, depths, self._image, poses, cams)
 
     def prepare_color_batch(self, rgbs, poses, cams):
         # (nvbx_integrate_color_batch takes rgb8 only: a bgra8 frame would be decoded as rgb8)
         if any(isinstance(i, ColorFrame) and i.channels != 3 for i in rgbs):
             raise ValueError("integrate_color_batch: rgb8 frames only (3 channels)")
-        return self._batch(self.lib.nvbx_integrate_color_batch, rgbs, self._torch.uint8, poses, cams)
+        rgb8 = lambda i: _args.image(i, self._cuda, self._torch.uint8, "rgb", "(rows, cols, 3)", (3,))      # noqa: E731
+        return self._batch(self.lib.nvbx_integrate_color_batch, rgbs, rgb8, poses, cams)
 
     def integrate_prepared_batch(self, a):
         rc = a[0](self._h, a[1], a[2], a[3], a[4], a[5], a[6])
@@ -531,10 +493,11 @@ class Mapper:
         """nvbx_integrate_depth_pair: self.integrate_depth(depth_a) followed by other.integrate_depth(depth_b) -- the background / foreground mappers of a
         MultiMapper's dynamic and human mapping types, fed the two halves of one mask-split depth frame -- in two launches instead of four (both mappers on
         one stream; anything else falls back to the two calls).  Same maps, bit for bit."""
-        da = self._dev(depth_a, self._torch.float32); db = self._dev(depth_b, self._torch.float32)
-        assert da.shape == db.shape
-        self._check(self.lib.nvbx_integrate_depth_pair(self._h, C.c_void_p(da.data_ptr()), other._h, C.c_void_p(db.data_ptr()), da.shape[0], da.shape[1],
-                                                       _np_ptr(self._T(T_L_C)), C.byref(self._cam(cam))))
+        da = self._image(depth_a, "depth_a"); db = self._image(depth_b, "depth_b")
+        if da.shape != db.shape:
+            raise ValueError("depth_a %s and depth_b %s differ in shape" % (tuple(da.shape), tuple(db.shape)))
+        (pa, rows, cols, T, k), keep = _args.frame(da, T_L_C, _args.camera(cam))
+        self._check(self.lib.nvbx_integrate_depth_pair(self._h, pa, other._h, ptr(db), rows, cols, T, k))
         self._hold("_keep", [da, db]); other._hold("_keep", [db])
 
     def integrate_prepared(self, a):
@@ -559,42 +522,41 @@ class Mapper:
 
     def detect_dynamics(self, depth, T_L_C, cam, max_distance_m=0.0):
         """DynamicsDetection::computeDynamics: uint8 device tensor [rows, cols], 1 = the pixel's point lies in high-confidence freespace."""
-        torch = self._torch
-        d = self._dev(depth, torch.float32)
-        mask = torch.empty(d.shape, dtype=torch.uint8, device=d.device)
-        self._check(self.lib.nvbx_detect_dynamics(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(self._T(T_L_C)),
-                                                  C.byref(self._cam(cam)), float(max_distance_m), C.c_void_p(mask.data_ptr())))
+        d = self._image(depth)
+        mask = self._torch.empty(d.shape, dtype=self._torch.uint8, device=d.device)
+        self.detect_dynamics_into(d, T_L_C, cam, max_distance_m, mask)
         self.synchronize()
         return mask
 
     # -- no-sync forms for a stream-ordered caller (outputs pre-allocated on the mapper's device; the caller's tensors must live on
     #    the mapper's stream or be ordered against it)
     def detect_dynamics_into(self, depth_dev, T_L_C, cam, max_distance_m, mask_out):
-        self._check(self.lib.nvbx_detect_dynamics(self._h, C.c_void_p(depth_dev.data_ptr()), depth_dev.shape[0], depth_dev.shape[1], _np_ptr(self._T(T_L_C)),
-                                                  C.byref(self._cam(cam)), float(max_distance_m), C.c_void_p(mask_out.data_ptr())))
+        group, keep = _args.frame(depth_dev, T_L_C, _args.camera(cam))
+        self._check(self.lib.nvbx_detect_dynamics(self._h, *group, float(max_distance_m), ptr(mask_out)))
 
     def remove_small_components_inplace(self, mask_dev, min_size):
         """(asynchronous on the mapper's stream)"""
-        self._check(self.lib.nvbx_remove_small_components(self._h, C.c_void_p(mask_dev.data_ptr()), mask_dev.shape[0], mask_dev.shape[1], int(min_size)))
+        self._check(self.lib.nvbx_remove_small_components(self._h, ptr(mask_dev), mask_dev.shape[0], mask_dev.shape[1], int(min_size)))
 
     def split_depth_by_mask_into(self, depth_dev, mask_dev, T_CM_CD, depth_cam, mask_cam, occlusion_threshold_m, unmasked_out, masked_out):
-        self._check(self.lib.nvbx_split_depth_by_mask(self._h, C.c_void_p(depth_dev.data_ptr()), depth_dev.shape[0], depth_dev.shape[1],
-                                                      C.c_void_p(mask_dev.data_ptr()), mask_dev.shape[0], mask_dev.shape[1], _np_ptr(self._T(T_CM_CD)),
-                                                      C.byref(self._cam(depth_cam)), C.byref(self._cam(mask_cam)), float(occlusion_threshold_m),
-                                                      C.c_void_p(unmasked_out.data_ptr()), C.c_void_p(masked_out.data_ptr()), None))
+        self._split_depth(depth_dev, mask_dev, T_CM_CD, depth_cam, mask_cam, occlusion_threshold_m, unmasked_out, masked_out, None)
+
+    def _split_depth(self, d, mk, T_CM_CD, depth_cam, mask_cam, occlusion_threshold_m, un, ma, ov):
+        (pd, rows, cols, T, dc), keep = _args.frame(d, T_CM_CD, _args.camera(depth_cam))
+        self._check(self.lib.nvbx_split_depth_by_mask(self._h, pd, rows, cols, ptr(mk), mk.shape[0], mk.shape[1], T, dc, C.byref(_args.camera(mask_cam)),
+                                                      float(occlusion_threshold_m), ptr(un), ptr(ma), ptr(ov)))
 
     def dynamic_depth_split_into(self, depth_dev, T_L_C, cam, max_distance_m, min_component_size, occlusion_threshold_m, mask_out, unmasked_out, masked_out, overlay_out=None):
         """The dynamic-mapping frame's front end in one call (three launches): detect_dynamics -> remove_small_components -> split_depth_by_mask."""
-        self._check(self.lib.nvbx_dynamic_depth_split(self._h, C.c_void_p(depth_dev.data_ptr()), depth_dev.shape[0], depth_dev.shape[1], _np_ptr(self._T(T_L_C)),
-                                                      C.byref(self._cam(cam)), float(max_distance_m), int(min_component_size), float(occlusion_threshold_m),
-                                                      C.c_void_p(mask_out.data_ptr()), C.c_void_p(unmasked_out.data_ptr()), C.c_void_p(masked_out.data_ptr()),
-                                                      C.c_void_p(overlay_out.data_ptr()) if overlay_out is not None else None))
+        group, keep = _args.frame(depth_dev, T_L_C, _args.camera(cam))
+        self._check(self.lib.nvbx_dynamic_depth_split(self._h, *group, float(max_distance_m), int(min_component_size), float(occlusion_threshold_m),
+                                                      ptr(mask_out), ptr(unmasked_out), ptr(masked_out), ptr(overlay_out)))
 
     def remove_small_components(self, mask, min_size):
         torch = self._torch
-        mk = self._dev(mask, torch.uint8).clone()
+        mk = self._image(mask, "mask", torch.uint8).clone()
         torch.cuda.current_stream(mk.device).synchronize()      # the clone ran on torch's stream, the library works on the mapper's
-        self._check(self.lib.nvbx_remove_small_components(self._h, C.c_void_p(mk.data_ptr()), mk.shape[0], mk.shape[1], int(min_size)))
+        self.remove_small_components_inplace(mk, min_size)
         self.synchronize()          # (the call is asynchronous on the mapper's stream; the tensor goes back to torch's)
         return mk
 
@@ -659,12 +621,16 @@ class Mapper:
         return out[0] if found[0] else None
 
     def set_block(self, layer, idx, data):
-        data = np.ascontiguousarray(data, _DT[layer]); assert data.size == 512
+        data = np.ascontiguousarray(data, _DT[layer])
+        if data.size != 512:
+            raise ValueError("data must hold the 512 voxels of a block, got %d" % data.size)
         self._check(self.lib.nvbx_set_block(self._h, layer, Index3D(int(idx[0]), int(idx[1]), int(idx[2])), _np_ptr(data)))
 
     def set_blocks(self, layer, indices, data):
         idx = np.ascontiguousarray(np.asarray(indices, np.int32).reshape(-1, 3))
-        data = np.ascontiguousarray(data, _DT[layer]); assert data.size == 512 * idx.shape[0]
+        data = np.ascontiguousarray(data, _DT[layer])
+        if data.size != 512 * idx.shape[0]:
+            raise ValueError("data must hold 512 voxels for each of the %d blocks, got %d" % (idx.shape[0], data.size))
         self._check(self.lib.nvbx_set_blocks(self._h, layer, _np_ptr(idx), idx.shape[0], _np_ptr(data)))
 
     def save_map(self, path):
@@ -706,22 +672,19 @@ class Mapper:
         self._check(self.lib.nvbx_esdf_slice_size(self._h, C.byref(r), C.byref(c), _np_ptr(aabb)))
         img = torch.empty((r.value, c.value), dtype=torch.float32, device="cuda:%d" % self.device)
         if img.numel():
-            self._check(self.lib.nvbx_esdf_slice_to_image(self._h, unknown_value, C.c_void_p(img.data_ptr()), img.numel(), C.byref(r), C.byref(c), _np_ptr(aabb)))
+            self._check(self.lib.nvbx_esdf_slice_to_image(self._h, unknown_value, ptr(img), img.numel(), C.byref(r), C.byref(c), _np_ptr(aabb)))
         return img, aabb
 
     def occupancy_grid_from_slice(self, img_dev, unknown_value=1000.0):
-        torch = self._torch
-        grid = torch.empty(img_dev.shape, dtype=torch.int8, device=img_dev.device)
-        self._check(self.lib.nvbx_occupancy_grid_from_slice(self._h, C.c_void_p(img_dev.data_ptr()), img_dev.shape[0], img_dev.shape[1], unknown_value, C.c_void_p(grid.data_ptr())))
+        grid = self._torch.empty(img_dev.shape, dtype=self._torch.int8, device=img_dev.device)
+        self._check(self.lib.nvbx_occupancy_grid_from_slice(self._h, ptr(img_dev), img_dev.shape[0], img_dev.shape[1], unknown_value, ptr(grid)))
         self.synchronize()
         return grid
 
     def pointcloud_from_slice(self, img_dev, aabb, slice_height, unknown_value=1000.0):
-        torch = self._torch
-        pts = torch.empty((img_dev.numel(), 4), dtype=torch.float32, device=img_dev.device)
-        n = C.c_int32()
-        a = np.ascontiguousarray(aabb, np.float32)
-        self._check(self.lib.nvbx_pointcloud_from_slice(self._h, C.c_void_p(img_dev.data_ptr()), img_dev.shape[0], img_dev.shape[1], _np_ptr(a), float(slice_height), unknown_value, C.c_void_p(pts.data_ptr()), C.byref(n)))
+        pts = self._torch.empty((img_dev.numel(), 4), dtype=self._torch.float32, device=img_dev.device)
+        n = C.c_int32(); a = np.ascontiguousarray(aabb, np.float32)
+        self._check(self.lib.nvbx_pointcloud_from_slice(self._h, ptr(img_dev), img_dev.shape[0], img_dev.shape[1], _np_ptr(a), float(slice_height), unknown_value, ptr(pts), C.byref(n)))
         return pts[:n.value]
 
     def esdf_slice_image_combined(self, other, unknown_value=1000.0):
@@ -732,45 +695,36 @@ class Mapper:
         if r.value == 0:
             return np.zeros((0, 0), np.float32), np.array(list(aabb), np.float32)
         img = torch.empty((r.value, c.value), dtype=torch.float32, device="cuda:%d" % self.device)
-        self._check(self.lib.nvbx_esdf_slice_combined_to_image(self._h, other._h, unknown_value, C.c_void_p(img.data_ptr()), img.numel(),
-                                                               C.byref(r), C.byref(c), aabb))
+        self._check(self.lib.nvbx_esdf_slice_combined_to_image(self._h, other._h, unknown_value, ptr(img), img.numel(), C.byref(r), C.byref(c), aabb))
         self.synchronize()
         return img.cpu().numpy(), np.array(list(aabb), np.float32)
 
     def backproject_depth(self, depth, cam, max_distance_m=0.0, T_L_C=None):
         """DepthImageBackProjector::backProjectOnGPU (+ transformPointcloudOnGPU if T_L_C is given): [n, 3] float32 host array."""
-        import torch
-        d, rows, cols = self._dev(depth, self._torch.float32), depth.shape[0], depth.shape[1]
-        pts = torch.empty((rows * cols, 3), dtype=torch.float32, device=d.device)
-        n = C.c_int64()
-        self._check(self.lib.nvbx_backproject_depth(self._h, C.c_void_p(d.data_ptr()), rows, cols, C.byref(self._cam(cam)), max_distance_m,
-                                                    C.c_void_p(pts.data_ptr()), rows * cols, C.byref(n)))
+        d = self._image(depth); rows, cols = d.shape
+        pts = self._torch.empty((rows * cols, 3), dtype=self._torch.float32, device=d.device); n = C.c_int64()
+        self._check(self.lib.nvbx_backproject_depth(self._h, ptr(d), rows, cols, C.byref(_args.camera(cam)), max_distance_m, ptr(pts), rows * cols, C.byref(n)))
         pts = pts[:n.value]
         if T_L_C is not None and n.value:
-            T = self._T(T_L_C)
-            self._check(self.lib.nvbx_transform_pointcloud(self._h, _np_ptr(T), C.c_void_p(pts.data_ptr()), n.value, C.c_void_p(pts.data_ptr())))
+            self._check(self.lib.nvbx_transform_pointcloud(self._h, _np_ptr(self._T(T_L_C)), ptr(pts), n.value, ptr(pts)))
             self.synchronize()
         return pts.cpu().numpy()
 
     def split_depth_by_mask(self, depth, mask, T_CM_CD, depth_cam, mask_cam, occlusion_threshold_m=0.25, overlay=False):
         """ImageMasker::splitImageOnGPU (MultiMapper::integrateDepth with a mask): device tensors (unmasked, masked[, overlay])."""
         torch = self._torch
-        d = self._dev(depth, torch.float32); mk = self._dev(mask, torch.uint8)
+        d = self._image(depth); mk = self._image(mask, "mask", torch.uint8)
         un = torch.empty_like(d); ma = torch.empty_like(d)
         ov = torch.empty(d.shape + (3,), dtype=torch.uint8, device=d.device) if overlay else None
-        self._check(self.lib.nvbx_split_depth_by_mask(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], C.c_void_p(mk.data_ptr()),
-                                                      mk.shape[0], mk.shape[1], _np_ptr(self._T(T_CM_CD)), C.byref(self._cam(depth_cam)),
-                                                      C.byref(self._cam(mask_cam)), float(occlusion_threshold_m), C.c_void_p(un.data_ptr()),
-                                                      C.c_void_p(ma.data_ptr()), C.c_void_p(ov.data_ptr()) if overlay else None))
+        self._split_depth(d, mk, T_CM_CD, depth_cam, mask_cam, occlusion_threshold_m, un, ma, ov)
         self.synchronize()       # (the outputs are torch tensors: torch's stream is not the mapper's)
         return (un, ma, ov) if overlay else (un, ma)
 
     def split_color_by_mask(self, rgb, mask):
         torch = self._torch
-        c = self._dev(rgb, torch.uint8); mk = self._dev(mask, torch.uint8)
+        c = _args.image(rgb, self._cuda, torch.uint8, "rgb", "(rows, cols, channels)"); mk = self._image(mask, "mask", torch.uint8)
         un = torch.empty_like(c); ma = torch.empty_like(c)
-        self._check(self.lib.nvbx_split_color_by_mask(self._h, C.c_void_p(c.data_ptr()), c.shape[0], c.shape[1], C.c_void_p(mk.data_ptr()),
-                                                      C.c_void_p(un.data_ptr()), C.c_void_p(ma.data_ptr())))
+        self._check(self.lib.nvbx_split_color_by_mask(self._h, ptr(c), c.shape[0], c.shape[1], ptr(mk), ptr(un), ptr(ma)))
         self.synchronize()
         return un, ma
 
@@ -782,19 +736,13 @@ class Mapper:
         return v
 
     def esdf_dense_grid(self, min_vox, size_vox, default_value):
-        torch = self._torch
         mn = np.asarray(min_vox, np.int32); sz = np.asarray(size_vox, np.int32)
-        out = torch.empty(tuple(int(s) for s in sz), dtype=torch.float32, device="cuda:%d" % self.device)
-        self._check(self.lib.nvbx_esdf_dense_grid(self._h, _np_ptr(mn), _np_ptr(sz), default_value, C.c_void_p(out.data_ptr())))
+        out = self._torch.empty(tuple(int(s) for s in sz), dtype=self._torch.float32, device=self._cuda)
+        self._check(self.lib.nvbx_esdf_dense_grid(self._h, _np_ptr(mn), _np_ptr(sz), default_value, ptr(out)))
         self.synchronize()
         return out.cpu().numpy()
 
-    # -- Reader calls, from the point queries down to view_gain.  Their argument coercion and output buffers live in _args.py: a call declares its
-    #    outputs as a spec of (name, shape, dtypes, required, wanted) rows and adds no coercion code of its own ("Host language").
-    @property
-    def _cuda(self):
-        return self._torch.device("cuda", self.device)
-
+    # -- Reader calls, from the point queries down to view_gain: ordered against torch's current stream on both sides, outputs by spec (see "helpers")
     def _around_torch_stream(self, call, order=True):
         """`call` enqueues on the mapper's stream, ordered behind torch's current stream (which produced the inputs) and ahead of it (which reads
         the results): no host synchronisation either way.  order=False: a call that launches nothing."""
@@ -1041,18 +989,13 @@ class Mapper:
         """Average a feature image into the voxels the frame sees.  feat: (rows_f, cols_f, C) torch.float16 device tensor or numpy float16 array;
         `cam` is the full-resolution camera the features were computed from, feature pixel (i, j) is centred on its pixel coordinate
         ((j + 0.5) stride, (i + 0.5) stride)."""
-        torch = self._torch
-        if not isinstance(feat, torch.Tensor):
-            feat = np.asarray(feat)
-        if feat.dtype not in (torch.float16, np.float16) or len(feat.shape) != 3:
-            raise ValueError("feat must be a (rows_f, cols_f, C) float16 array, got %s %s" % (tuple(feat.shape), feat.dtype))
-        f = self._dev(feat, torch.float16)
+        f = _args.image(feat, self._cuda, self._torch.float16, "feat", "(rows_f, cols_f, C)", convert=False)
         ch = getattr(self, "feature_channels", 0)      # (0: not enabled -- the library refuses the call)
         if ch and f.shape[2] != ch:
             raise NvbxError("integrate_features: the image has %d channels, the layer %d (enable_features)" % (f.shape[2], ch))
-        T = self._T(T_L_C); k = self._cam(cam)
-        self._around_torch_stream(lambda: self.lib.nvbx_integrate_features(
-            self._h, C.c_void_p(f.data_ptr()), f.shape[0], f.shape[1], int(stride), _np_ptr(T), C.byref(k)))
+        # (a non-collapsing pointer: nvbx_integrate_features refuses a NULL image before it looks at its size)
+        (pf, rows, cols, T, k), keep = _args.frame(f, T_L_C, _args.camera(cam), collapse=False)
+        self._around_torch_stream(lambda: self.lib.nvbx_integrate_features(self._h, pf, rows, cols, int(stride), T, k))
         self._hold("_keep_f", [f])      # (the kernel reads the image: it, and an uploaded copy, live until the next feature frame)
 
     def query_features(self, points, out=None):
@@ -1310,40 +1253,37 @@ class Mapper:
 
     def measure_depth(self, depth, T_L_C, cam, out_blocks, out_count):
         """This rank's camera -> measurement records into caller-owned device tensors: out_blocks uint8 [capacity, 4112], out_count int32 [1]."""
-        d = self._dev(depth, self._torch.float32)
-        T = self._T(T_L_C); k = self._cam(cam)
-        self._check(self.lib.nvbx_measure_depth(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k),
-                                                C.c_void_p(out_blocks.data_ptr()), C.c_void_p(out_count.data_ptr()), int(out_blocks.shape[0])))
+        d = self._image(depth)
+        group, keep = _args.frame(d, T_L_C, _args.camera(cam))
+        self._check(self.lib.nvbx_measure_depth(self._h, *group, ptr(out_blocks), ptr(out_count), int(out_blocks.shape[0])))
         self._hold("_keep", [d])
 
     def apply_measurements(self, gathered, counts, owner_mod=0, owner_rank=0):
         """gathered uint8 [world, stride, 4112], counts int32 [world] (device): every camera's measurements applied in rank order."""
-        self._check(self.lib.nvbx_apply_measurements(self._h, C.c_void_p(gathered.data_ptr()), C.c_void_p(counts.data_ptr()), int(gathered.shape[0]),
-                                                     int(gathered.shape[1]), int(owner_mod), int(owner_rank)))
+        self._check(self.lib.nvbx_apply_measurements(self._h, ptr(gathered), ptr(counts), int(gathered.shape[0]), int(gathered.shape[1]),
+                                                     int(owner_mod), int(owner_rank)))
 
     # -- multi-GPU hooks (SURVEY.md 8e)
     def esdf_dirty_list(self, idx_out, count_out):
         """Write the Index3D list [cap,3] int32 + count [1] int32 of TSDF blocks dirtied since the last updateEsdf
         into caller-owned device tensors (async)."""
-        self._check(self.lib.nvbx_esdf_dirty_list(self._h, C.c_void_p(idx_out.data_ptr()), C.c_void_p(count_out.data_ptr()), int(idx_out.shape[0])))
+        self._check(self.lib.nvbx_esdf_dirty_list(self._h, ptr(idx_out), ptr(count_out), int(idx_out.shape[0])))
 
     def set_view_export(self, packed_tensor):
         """Register (or, with None, unregister) an int32 device tensor [1 + cap, 3]: every following integrate_depth writes the indices
         of the blocks it updates into it (row 0 = count) from inside its own launch.  The tensor must stay alive while registered."""
-        if packed_tensor is None:
-            self._check(self.lib.nvbx_set_view_export(self._h, None, 0)); self._view_export = None
-        else:
-            self._view_export = packed_tensor
-            self._check(self.lib.nvbx_set_view_export(self._h, C.c_void_p(packed_tensor.data_ptr()), int(packed_tensor.shape[0]) - 1))
+        self._check(self.lib.nvbx_set_view_export(self._h, ptr(packed_tensor), int(packed_tensor.shape[0]) - 1 if packed_tensor is not None else 0))
+        self._view_export = packed_tensor      # (the one it replaces is let go of only now: it stayed registered until the call)
 
     def mark_esdf_dirty(self, idx_tensor, count_tensor, max_count):
-        self._check(self.lib.nvbx_mark_esdf_dirty(self._h, C.c_void_p(idx_tensor.data_ptr()), C.c_void_p(count_tensor.data_ptr()), int(max_count)))
+        # (a non-collapsing pointer: the entry takes max_count 0 with an empty list, but not a NULL one)
+        self._check(self.lib.nvbx_mark_esdf_dirty(self._h, ptr(idx_tensor, collapse=False), ptr(count_tensor), int(max_count)))
 
     def mark_esdf_dirty_gathered(self, gathered, world, self_rank, max_count, deferred=False):
         """gathered: int32 device tensor [world, 1 + max_count, 3] (row 0 = count); one launch for all peers -- or, deferred,
         no launch at all: the next integrate_color carries it (the tensor must stay alive and unchanged until then)."""
         fn = self.lib.nvbx_mark_esdf_dirty_gathered_deferred if deferred else self.lib.nvbx_mark_esdf_dirty_gathered
-        self._check(fn(self._h, C.c_void_p(gathered.data_ptr()), int(world), int(self_rank), int(max_count)))
+        self._check(fn(self._h, ptr(gathered), int(world), int(self_rank), int(max_count)))
 
     # -- instrumentation
     def set_profiling(self, enable):

@@ -1,11 +1,17 @@
-"""The reader calls of mapper.py on one tiny map (a 64 x 48 depth frame of a wall, 8 feature channels, one feature frame): preallocated
-outputs give what the allocating call gives and allocate nothing, an empty input gives empty tensors, and a refused call leaves the error
-text it always left.  What the calls compute is checked by the suites of each call; this one is about the path their arguments take
-(isaac_ros_nvblox_amd/_args.py) and the shared refusals of the C-ABI (nvbx::refuse, tsdf_reader_refused, nvbx_camera_valid, seg_check)."""
+"""The path the mapper's arguments take (isaac_ros_nvblox_amd/_args.py) and the shared refusals of the C-ABI (nvbx::refuse, tsdf_reader_refused,
+nvbx_camera_valid, seg_check, nvbx_camera_frame_refused).  What the calls compute is checked by the suites of each call.
+Reader calls, on one tiny map (a 64 x 48 depth frame of a wall, 8 feature channels, one feature frame): preallocated outputs give what the
+allocating call gives and allocate nothing, an empty input gives empty tensors, and a refused call leaves the error text it always left.
+Writer and converter calls, on one or two 160 x 120 frames of synthetic.Scene: every form an input may take (numpy array, device tensor,
+strided device view, prepared tuple, ColorFrame, bgra8, u16 millimetres) gives the same map or the same result, byte for byte; bad input is
+refused with ValueError and leaves the mapper usable; the camera-frame entry points leave the error texts they always left."""
 import ctypes as C
 
 import numpy as np
 import pytest
+
+import helpers as H
+from isaac_ros_nvblox_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
 
@@ -198,3 +204,253 @@ def test_refusal_texts(wall):
         assert counts.tolist() == [-77, -77]
     finally:
         occ.close(); other.close()
+
+
+# ------------------------------------------------------------------------------------------------ writer and converter calls
+SCAM = H.SMALL_CAM
+ROWS, COLS = SCAM[5], SCAM[4]
+
+
+@pytest.fixture(scope="module")
+def scene_frames():
+    """Two frames of synthetic.Scene: (depth in whole millimetres u16, the same depth f32, rgb with three different channels, pose).
+    Whole millimetres: the u16 image decodes to exactly the float32 one ((float)mm * (1.0f / 1000.0f) in the kernels)."""
+    sc = S.Scene(); out = []
+    for i in (0, 9):
+        T = S.trajectory_pose(i)
+        d, rgb = S.render(sc, T, SCAM)
+        d_mm = np.round(d * 1000.0).astype(np.uint16)
+        d_f32 = d_mm.astype(np.float32) * np.float32(1 / 1000)
+        rgb = rgb.copy(); rgb[..., 1] //= 2; rgb[..., 2] = 255 - rgb[..., 2]      # (the scene is grey: now the channel order matters)
+        out.append((d_mm, d_f32, np.ascontiguousarray(rgb), np.asarray(T, np.float32)))
+    assert out[0][0].max() >= 1000 and (out[0][0] > 0).sum() > ROWS * COLS // 2
+    return out
+
+
+def _fresh(M, stream=None, **params):
+    return M.Mapper(M.default_params(**params), device=0, block_capacity=1 << 13, stream=stream)
+
+
+def _map_bytes(M, m, layers=None):
+    """every block of the TSDF, colour and ESDF layers, in the order of the sorted block indices"""
+    out = []
+    for lay in layers or (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF):
+        idx = m.block_indices(lay)
+        idx = np.ascontiguousarray(idx[np.lexsort((idx[:, 2], idx[:, 1], idx[:, 0]))])
+        blk, found = m.get_blocks(lay, idx)
+        assert found.all()
+        out.append((idx.tobytes(), blk.tobytes()))
+    return out
+
+
+def _mapped(M, torch, *calls, **params):
+    """A fresh mapper, fed by calls(m) in order, then update_esdf: -> its layers.  Torch's current stream is the mapper's for the duration, so
+    an upload or a copy the wrapper makes is ordered ahead of the launches that read it."""
+    m = _fresh(M, **params)
+    try:
+        with torch.cuda.stream(m.torch_stream()):
+            keep = [c(m) for c in calls]      # (a prepared tuple lives until the map has been read)
+            m.update_esdf()
+            got = _map_bytes(M, m)
+        del keep
+        return got
+    finally:
+        m.close()
+
+
+def _strided(torch, t, dim):
+    """a non-contiguous device view that holds t: every second element along `dim` of a tensor twice as long there"""
+    shape = list(t.shape); shape[dim] *= 2
+    wide = torch.zeros(shape, dtype=t.dtype, device=t.device)
+    view = wide[(slice(None),) * dim + (slice(None, None, 2),)]
+    view.copy_(t)
+    assert not view.is_contiguous() and torch.equal(view, t)
+    return view
+
+
+def _prepared(prepare, *args):
+    def call(m):
+        a = getattr(m, prepare)(*args); m.integrate_prepared(a)
+        return a
+    return call
+
+
+def test_input_forms_give_one_map(hip_lib, scene_frames):
+    import torch
+    from isaac_ros_nvblox_amd import mapper as M
+    d_mm, d, rgb, T = scene_frames[0]
+    assert ((d_mm.astype(np.float32) * np.float32(1 / 1000)) == d).all()
+    d_t = torch.from_numpy(d).cuda(); rgb_t = torch.from_numpy(rgb).cuda()
+    bgra = np.ascontiguousarray(np.concatenate([rgb[..., ::-1], np.full((ROWS, COLS, 1), 255, np.uint8)], 2))
+    frame = M.ColorFrame(ROWS, COLS, 3).write(rgb)
+    torch.cuda.synchronize()
+    depth_forms = {
+        "numpy": lambda m: m.integrate_depth(d, T, SCAM),
+        "tensor": lambda m: m.integrate_depth(d_t, T, SCAM),
+        "strided": lambda m: m.integrate_depth(_strided(torch, d_t, 1), T, SCAM),
+        "prepared": _prepared("prepare_depth", d_t, T, SCAM),
+        "u16 numpy": lambda m: m.integrate_depth(d_mm, T, SCAM),
+        "i16 tensor": lambda m: m.integrate_depth(torch.from_numpy(d_mm.view(np.int16)).cuda(), T, SCAM),
+    }
+    color_forms = {
+        "numpy": lambda m: m.integrate_color(rgb, T, SCAM),
+        "tensor": lambda m: m.integrate_color(rgb_t, T, SCAM),
+        "strided": lambda m: m.integrate_color(_strided(torch, rgb_t, 1), T, SCAM),
+        "prepared": _prepared("prepare_color", rgb_t, T, SCAM),
+        "ColorFrame": lambda m: m.integrate_color(frame, T, SCAM),
+        "bgra8": lambda m: m.integrate_color(bgra, T, SCAM),
+    }
+    want = _mapped(M, torch, depth_forms["numpy"], color_forms["numpy"])
+    assert len(want[0][0]) > 12 * 20 and len(want[1][0]) > 0 and len(want[2][0]) > 0          # (all three layers hold blocks)
+    for (dn, df), (cn, cf) in list(zip(depth_forms.items(), color_forms.items()))[1:]:
+        got = _mapped(M, torch, df, cf)
+        for name, w, g in zip(("tsdf", "color", "esdf"), want, got):
+            assert w == g, "depth as %s, colour as %s: the %s layer differs from the numpy forms'" % (dn, cn, name)
+    frame.close()
+
+
+def test_batch_and_pair_forms_give_one_map(hip_lib, scene_frames):
+    import torch
+    from isaac_ros_nvblox_amd import mapper as M
+    ds = [f[1] for f in scene_frames]; Ts = [f[3] for f in scene_frames]
+    want = _mapped(M, torch, lambda m: m.integrate_depth_batch(ds, Ts, SCAM))
+
+    def prepared(m):
+        a = m.prepare_depth_batch(ds, Ts, SCAM); m.integrate_prepared_batch(a)
+        return a
+    assert _mapped(M, torch, prepared) == want
+
+    # the pair: the left half of the frame into one mapper, the right half into the other
+    da = ds[0].copy(); da[:, COLS // 2:] = 0.0
+    db = ds[0].copy(); db[:, :COLS // 2] = 0.0
+
+    stream = torch.cuda.Stream()      # both mappers on it, and torch for the duration: the uploads are ordered ahead of either mapper's launches
+
+    def pair(a_img, b_img):
+        a = _fresh(M, stream.cuda_stream); b = _fresh(M, stream.cuda_stream)
+        try:
+            with torch.cuda.stream(stream):
+                a.integrate_depth_pair(a_img, b, b_img, Ts[0], SCAM)
+                a.update_esdf(); b.update_esdf()
+                return _map_bytes(M, a, (M.LAYER_TSDF, M.LAYER_ESDF)), _map_bytes(M, b, (M.LAYER_TSDF, M.LAYER_ESDF))
+        finally:
+            a.close(); b.close()
+    da_t = torch.from_numpy(da).cuda(); db_t = torch.from_numpy(db).cuda()
+    torch.cuda.synchronize()
+    want_a, want_b = pair(da_t, db_t)
+    assert len(want_a[0][0]) > 0 and len(want_b[0][0]) > 0 and want_a != want_b
+    got_a, got_b = pair(da, db)
+    assert got_a == want_a and got_b == want_b
+
+
+def test_converters_take_numpy_and_device_tensors_alike(hip_lib, scene_frames):
+    import torch
+    from isaac_ros_nvblox_amd import mapper as M
+    _, d, rgb, T = scene_frames[0]
+    rng = np.random.default_rng(11)
+    mask = (rng.random((ROWS, COLS)) < 0.3).astype(np.uint8)
+    lidar = (64, 16, 0.1, -0.4, 0.4)
+    cloud = np.ascontiguousarray((S.lidar_beam_dirs(lidar)[::2, ::3] * rng.uniform(1.0, 5.0, (8, 22, 1))).reshape(-1, 3).astype(np.float32))
+    times = np.linspace(0.0, 100.0, len(cloud)).astype(np.float32)
+    T1 = T.copy(); T1[0, 3] += 0.2
+    cuda = lambda a: torch.from_numpy(a).cuda()      # noqa: E731
+    rows_sorted = lambda p: np.ascontiguousarray(p[np.lexsort((p[:, 2], p[:, 1], p[:, 0]))])      # noqa: E731  (the points come in no particular order)
+    m = _fresh(M, projective_layer_type=2)            # (TSDF + freespace: what detect_dynamics reads)
+    try:
+        with torch.cuda.stream(m.torch_stream()):
+            m.integrate_depth(d, T, SCAM)
+            calls = {
+                "detect_dynamics": lambda dev: (m.detect_dynamics(dev(d), T, SCAM, 4.0),),
+                "split_depth_by_mask": lambda dev: m.split_depth_by_mask(dev(d), dev(mask), np.eye(4, dtype=np.float32), SCAM, SCAM, 0.25, overlay=True),
+                "split_color_by_mask": lambda dev: m.split_color_by_mask(dev(rgb), dev(mask)),
+                "backproject_depth": lambda dev: (torch.from_numpy(rows_sorted(m.backproject_depth(dev(d), SCAM, 4.0, T))),),
+                "depth_image_from_pointcloud": lambda dev: (m.depth_image_from_pointcloud(dev(cloud), lidar),),
+                "motion_compensate_pointcloud": lambda dev: (m.motion_compensate_pointcloud(dev(cloud), dev(times), T, T1, 100.0),),
+            }
+            for what, call in calls.items():
+                host = call(lambda a: a); dev = call(cuda)
+                _same(host, dev, what)
+                assert all(t.numel() > 0 for t in host), what
+            un, ma, ov = calls["split_depth_by_mask"](cuda)
+            assert float(un.max()) > 0.0 and float(ma.max()) > 0.0                          # (the mask splits the frame)
+            assert float(calls["depth_image_from_pointcloud"](cuda)[0].max()) > 1.0         # (the cloud lands in the image)
+    finally:
+        m.close()
+
+
+def test_bad_input_is_refused_with_valueerror_and_the_mapper_goes_on(hip_lib, scene_frames):
+    import torch
+    from isaac_ros_nvblox_amd import mapper as M
+    _, d, rgb, T = scene_frames[0]
+    m = _fresh(M); other = _fresh(M)
+    try:
+        refusals = (
+            lambda: m.integrate_depth(torch.zeros((ROWS, COLS), dtype=torch.uint8, device="cuda"), T, SCAM),      # a uint8 tensor as depth
+            lambda: m.integrate_color(np.zeros((ROWS, COLS, 2), np.uint8), T, SCAM),                              # a 2-channel colour image
+            lambda: m.integrate_depth_pair(d, other, d[:-1], T, SCAM),                                            # two shapes in one pair
+            lambda: m.set_block(M.LAYER_TSDF, (0, 0, 0), np.zeros(511, M.TSDF_DT)),                               # 511 voxels
+        )
+        for k, call in enumerate(refusals):
+            with pytest.raises(ValueError):
+                call()
+            m.integrate_depth(d, T, SCAM); m.integrate_color(rgb, T, SCAM); m.update_esdf()
+            assert m.num_blocks(M.LAYER_TSDF) > 0, k
+            v = m.invariant_violations()
+            assert v is None or not any(v), (k, v)
+    finally:
+        m.close(); other.close()
+
+
+def test_camera_frame_refusal_texts(hip_lib):
+    """The two refusals every camera-frame entry point shares, called at the C-ABI: a NULL image, and a camera one pixel wider than the image."""
+    import torch
+    from isaac_ros_nvblox_amd import mapper as M
+    a = _fresh(M); b = _fresh(M)
+    try:
+        k = M.Camera(80.0, 80.0, 79.5, 59.5, COLS, ROWS); wide = M.Camera(80.0, 80.0, 79.5, 59.5, COLS + 1, ROWS)
+        ks = (M.Camera * 1)(k); wides = (M.Camera * 1)(wide)
+        T = np.eye(4, dtype=np.float32); Tp = T.ctypes.data_as(C.c_void_p)
+        img = torch.zeros((ROWS, COLS, 4), dtype=torch.uint8, device="cuda")      # (as many bytes as any of the images; never read)
+        p = C.c_void_p(img.data_ptr())
+        imgs = (C.c_void_p * 1)(img.data_ptr()); null_imgs = (C.c_void_p * 1)(None)
+        blocks = torch.empty((4, M.Mapper.MEAS_BLOCK_BYTES), dtype=torch.uint8, device="cuda"); count = torch.zeros(1, dtype=torch.int32, device="cuda")
+        pb, pc = C.c_void_p(blocks.data_ptr()), C.c_void_p(count.data_ptr())
+        L = hip_lib
+        cases = (
+            (lambda: L.nvbx_integrate_depth(a._h, None, ROWS, COLS, Tp, C.byref(k)), "nvbx_integrate_depth: invalid argument (image sides 1 .. 32768)"),
+            (lambda: L.nvbx_integrate_depth(a._h, p, ROWS, COLS, Tp, C.byref(wide)),
+             "nvbx_integrate_depth: camera width/height must equal the image's cols/rows, focal lengths > 0"),
+            (lambda: L.nvbx_integrate_depth_u16mm(a._h, None, ROWS, COLS, Tp, C.byref(k)), "nvbx_integrate_depth_u16mm: invalid argument (image sides 1 .. 32768)"),
+            (lambda: L.nvbx_integrate_depth_u16mm(a._h, p, ROWS, COLS, Tp, C.byref(wide)),
+             "nvbx_integrate_depth_u16mm: camera width/height must equal the image's cols/rows, focal lengths > 0"),
+            (lambda: L.nvbx_integrate_depth_batch(a._h, 1, None, ROWS, COLS, Tp, ks), "nvbx_integrate_depth_batch: invalid argument (1 <= n <= 8, image sides 1 .. 32768)"),
+            (lambda: L.nvbx_integrate_depth_batch(a._h, 1, null_imgs, ROWS, COLS, Tp, ks),
+             "nvbx_integrate_depth_batch: every camera's width/height must equal the images' cols/rows, focal lengths > 0"),
+            (lambda: L.nvbx_integrate_depth_batch(a._h, 1, imgs, ROWS, COLS, Tp, wides),
+             "nvbx_integrate_depth_batch: every camera's width/height must equal the images' cols/rows, focal lengths > 0"),
+            (lambda: L.nvbx_integrate_depth_pair(a._h, None, b._h, p, ROWS, COLS, Tp, C.byref(k)),
+             "nvbx_integrate_depth_pair: invalid argument (two different mappers, image sides 1 .. 32768)"),
+            (lambda: L.nvbx_integrate_depth_pair(a._h, p, b._h, p, ROWS, COLS, Tp, C.byref(wide)),
+             "nvbx_integrate_depth_pair: camera width/height must equal the image's cols/rows, focal lengths > 0"),
+            (lambda: L.nvbx_integrate_color(a._h, None, ROWS, COLS, Tp, C.byref(k)), "nvbx_integrate_color: invalid argument (image sides 1 .. 32768)"),
+            (lambda: L.nvbx_integrate_color(a._h, p, ROWS, COLS, Tp, C.byref(wide)),
+             "nvbx_integrate_color: camera width/height must equal the image's cols/rows, focal lengths > 0"),
+            (lambda: L.nvbx_integrate_color_bgra8(a._h, None, ROWS, COLS, Tp, C.byref(k)), "nvbx_integrate_color_bgra8: invalid argument"),
+            (lambda: L.nvbx_integrate_color_bgra8(a._h, C.c_void_p(img.data_ptr() + 1), ROWS, COLS, Tp, C.byref(k)), "nvbx_integrate_color_bgra8: invalid argument"),
+            (lambda: L.nvbx_integrate_color_bgra8(a._h, p, ROWS, COLS, Tp, C.byref(wide)),
+             "nvbx_integrate_color_bgra8: camera width/height must equal the image's cols/rows, focal lengths > 0"),
+            (lambda: L.nvbx_integrate_color_batch(a._h, 1, None, ROWS, COLS, Tp, ks), "nvbx_integrate_color_batch: invalid argument (1 <= n <= 8, image sides 1 .. 32768)"),
+            (lambda: L.nvbx_integrate_color_batch(a._h, 1, null_imgs, ROWS, COLS, Tp, ks),
+             "nvbx_integrate_color_batch: every camera's width/height must equal the images' cols/rows, focal lengths > 0"),
+            (lambda: L.nvbx_integrate_color_batch(a._h, 1, imgs, ROWS, COLS, Tp, wides),
+             "nvbx_integrate_color_batch: every camera's width/height must equal the images' cols/rows, focal lengths > 0"),
+            (lambda: L.nvbx_measure_depth(a._h, None, ROWS, COLS, Tp, C.byref(k), pb, pc, 4), "nvbx_measure_depth: invalid argument"),
+            (lambda: L.nvbx_measure_depth(a._h, p, ROWS, COLS, Tp, C.byref(wide), pb, pc, 4),
+             "nvbx_measure_depth: camera width/height must equal the image's cols/rows, focal lengths > 0"),
+        )
+        for k_, (call, text) in enumerate(cases):
+            assert call() == -1, (k_, text)
+            assert L.nvbx_last_error().decode() == text, k_
+        assert a.num_blocks(M.LAYER_TSDF) == 0 and b.num_blocks(M.LAYER_TSDF) == 0          # (nothing was integrated)
+    finally:
+        a.close(); b.close()

@@ -1,4 +1,4 @@
-"""isaac_ros_nvblox_amd/_args.py: the argument coercion and the output-buffer path of the mapper's reader calls, on the CPU.
+"""isaac_ros_nvblox_amd/_args.py: the argument coercion of all the mapper's calls and the output-buffer path of its reader calls, on the CPU.
 The functions take the target device as an argument and touch neither the library nor a stream."""
 import ctypes as C
 
@@ -42,6 +42,132 @@ def test_points3_refuses_wrong_dtype_and_shape():
         A.points3(torch.zeros((4, 2), dtype=torch.float32), CPU)
     with pytest.raises(ValueError, match="origins"):                   # the message names the argument
         A.points3(torch.zeros(3, dtype=torch.float32), CPU, "origins")
+
+
+# ------------------------------------------------------------------------------------------------ image, depth_image
+DEPTH = dict(dtype=torch.float32, what="depth", dims="(rows, cols)")
+COLOR = dict(dtype=torch.uint8, what="rgb", dims="(rows, cols, 3 or 4)", channels=(3, 4))
+
+
+def test_image_accepts_list_array_strided_empty_and_device_tensor():
+    t = A.image([[1, 2], [3, 4]], CPU, **DEPTH)
+    assert t.dtype == torch.float32 and t.tolist() == [[1.0, 2.0], [3.0, 4.0]] and t.is_contiguous()
+
+    a = np.arange(12 * 16, dtype=np.float32).reshape(12, 16)
+    assert np.array_equal(A.image(a, CPU, **DEPTH).numpy(), a)
+    view = a[:, ::2]                                                    # every second column
+    assert not view.flags.c_contiguous
+    t = A.image(view, CPU, **DEPTH)
+    assert t.is_contiguous() and tuple(t.shape) == (12, 8) and np.array_equal(t.numpy(), view)
+    tv = torch.from_numpy(a)[:, ::2]
+    t = A.image(tv, CPU, **DEPTH)
+    assert t.is_contiguous() and torch.equal(t, tv)
+
+    for empty in (np.zeros((0, 16), np.float32), np.zeros((0, 0), np.float32), torch.zeros((0, 16), dtype=torch.float32)):
+        t = A.image(empty, CPU, **DEPTH)
+        assert t.dtype == torch.float32 and tuple(t.shape) == tuple(empty.shape)
+    assert tuple(A.image(np.zeros((0, 4, 3), np.uint8), CPU, **COLOR).shape) == (0, 4, 3)
+
+    same = torch.zeros((12, 16), dtype=torch.float32)
+    assert A.image(same, CPU, **DEPTH).data_ptr() == same.data_ptr()     # already right: no copy
+    rgb = torch.zeros((4, 5, 3), dtype=torch.uint8)
+    assert A.image(rgb, CPU, **COLOR).data_ptr() == rgb.data_ptr()
+    assert tuple(A.image(np.zeros((4, 5, 4), np.uint8), CPU, **COLOR).shape) == (4, 5, 4)
+
+
+def test_image_converts_arrays_but_never_tensors():
+    t = A.image(np.array([[1.5, 2.5]], np.float64), CPU, **DEPTH)        # an array of another dtype is converted, as Mapper._dev always did
+    assert t.dtype == torch.float32 and t.tolist() == [[1.5, 2.5]]
+    assert A.image(np.array([[True, False]]), CPU, torch.uint8, "mask", "(rows, cols)").tolist() == [[1, 0]]
+    with pytest.raises(ValueError, match=r"depth must be a \(rows, cols\) float32 array, got \(1, 2\) torch.float64"):
+        A.image(torch.zeros((1, 2), dtype=torch.float64), CPU, **DEPTH)
+    with pytest.raises(ValueError, match="depth"):
+        A.image(torch.zeros((4, 4), dtype=torch.uint8), CPU, **DEPTH)   # a uint8 image is no depth image
+    with pytest.raises(ValueError, match="feat must be a"):             # convert=False: nor is an array converted
+        A.image(np.zeros((2, 2, 8), np.float32), CPU, torch.float16, "feat", "(rows_f, cols_f, C)", convert=False)
+    assert A.image(np.zeros((2, 2, 8), np.float16), CPU, torch.float16, "feat", "(rows_f, cols_f, C)", convert=False).dtype == torch.float16
+
+
+def test_image_refuses_wrong_rank_and_channel_count():
+    with pytest.raises(ValueError, match=r"depth must be a \(rows, cols\) float32 array, got \(5,\)"):
+        A.image(np.zeros(5, np.float32), CPU, **DEPTH)                  # 1-D where 2-D is needed
+    with pytest.raises(ValueError, match="depth"):
+        A.image(torch.zeros((2, 3, 1), dtype=torch.float32), CPU, **DEPTH)
+    for ch in (2, 5):
+        with pytest.raises(ValueError, match=r"rgb must be a \(rows, cols, 3 or 4\) uint8 array, got \(4, 5, %d\)" % ch):
+            A.image(np.zeros((4, 5, ch), np.uint8), CPU, **COLOR)
+        with pytest.raises(ValueError, match="rgb"):
+            A.image(torch.zeros((4, 5, ch), dtype=torch.uint8), CPU, **COLOR)
+    with pytest.raises(ValueError, match="rgb"):
+        A.image(np.zeros((4, 5), np.uint8), CPU, **COLOR)
+    assert A.image(torch.zeros(7, dtype=torch.int32), CPU, torch.int32).dim() == 1      # no dims given: any rank (Mapper._dev)
+
+
+def test_depth_image_kinds():
+    mm = np.array([[0, 1000, 32768, 65535]], np.uint16)
+    t, kind = A.depth_image(mm, CPU)
+    assert kind == "u16mm" and t.dtype == torch.int16 and tuple(t.shape) == (1, 4)
+    assert t.numpy().view(np.uint16).tolist() == [[0, 1000, 32768, 65535]]          # the bits of a value >= 32768 are kept
+    assert t.tolist() == [[0, 1000, -32768, -1]]
+    i16 = torch.from_numpy(mm.view(np.int16))
+    t, kind = A.depth_image(i16, CPU)
+    assert kind == "u16mm" and t.data_ptr() == i16.data_ptr()
+    f = torch.full((3, 4), 1.5)
+    t, kind = A.depth_image(f, CPU)
+    assert kind == "f32" and t.data_ptr() == f.data_ptr()
+    for other in (np.full((3, 4), 1.5, np.float32), np.full((3, 4), 1.5), [[1.5, 2.0]], np.array([[1, 2]], np.int16)):      # numpy's int16 is no u16 image
+        t, kind = A.depth_image(other, CPU)
+        assert kind == "f32" and t.dtype == torch.float32
+    for bad in (torch.zeros((3, 4), dtype=torch.uint8), torch.zeros((3, 4), dtype=torch.float64), np.zeros(4, np.uint16), torch.zeros(4, dtype=torch.int16)):
+        with pytest.raises(ValueError, match="depth"):
+            A.depth_image(bad, CPU)
+
+
+# ------------------------------------------------------------------------------------------------ pose, pose_block, camera, lidar, frame
+def test_pose_and_pose_block():
+    T = (np.arange(16, dtype=np.float64) * 0.25 - 1.0).reshape(4, 4)
+    forms = [A.pose(T.tolist()), A.pose(T.reshape(16)), A.pose(T), A.pose(torch.from_numpy(T))]
+    for p in forms:
+        assert p.dtype == np.float32 and p.shape == (4, 4) and p.flags.c_contiguous and p.tobytes() == T.astype(np.float32).tobytes()
+    assert A.pose(T.T).flags.c_contiguous and np.array_equal(A.pose(T.T), T.T.astype(np.float32))
+    with pytest.raises(ValueError):
+        A.pose(np.zeros(12))
+    block = A.pose_block([T, T.tolist(), T.reshape(16) + 1.0])
+    assert block.dtype == np.float32 and block.shape == (3, 16) and block.flags.c_contiguous
+    assert block[0].tobytes() == forms[0].tobytes() and block[1].tobytes() == forms[0].tobytes()
+    assert np.array_equal(block[2], (T.reshape(16) + 1.0).astype(np.float32))
+
+
+def test_camera_and_lidar_from_tuple_or_struct():
+    from isaac_ros_nvblox_amd._lib import Camera, Lidar
+    k = A.camera((80, 81.5, 79.5, 59.5, 160.0, 120))
+    assert isinstance(k, Camera) and (k.fu, k.fv, k.cu, k.cv, k.width, k.height) == (80.0, 81.5, 79.5, 59.5, 160, 120)
+    assert A.camera(k) is k
+    k2 = A.camera(Camera(80.0, 81.5, 79.5, 59.5, 160, 120))
+    assert all(getattr(k, f) == getattr(k2, f) for f, _ in Camera._fields_)
+    ld = A.lidar((1024.0, 64, 0.1, -0.4, 0.4))
+    assert isinstance(ld, Lidar) and A.lidar(ld) is ld
+    ld2 = Lidar(1024, 64, 0.1, -0.4, 0.4)
+    assert all(getattr(ld, f) == getattr(ld2, f) for f, _ in Lidar._fields_)
+    assert (ld.num_azimuth_divisions, ld.num_elevation_divisions) == (1024, 64)
+
+
+def test_frame_argument_group():
+    img = torch.zeros((12, 16, 3), dtype=torch.uint8)
+    k = A.camera((8.0, 8.0, 7.5, 5.5, 16, 12))
+    T = np.eye(4, dtype=np.float64)
+    (p, rows, cols, Tp, kref), keep = A.frame(img, T, k)
+    assert p.value == img.data_ptr() and (rows, cols) == (12, 16)
+    assert keep[0] is img and keep[2] is k and keep[1].dtype == np.float32 and Tp.value == keep[1].ctypes.data
+    assert kref._obj is k
+    empty = torch.zeros((12, 16), dtype=torch.float32)[:0]               # an empty view of memory that exists
+    assert A.frame(empty, T, k)[0][:3] == (None, 0, 16)
+    assert A.frame(empty, T, k, collapse=False)[0][0].value == C.c_void_p(empty.data_ptr()).value      # (the address torch reports for it)
+
+    class Owned:                                                        # what a ColorFrame looks like: an address and its sides
+        ptr, rows, cols = 4096, 12, 16
+    (p, rows, cols, _, _), keep = A.frame(Owned, T, A.lidar((16, 12, 0.1, -0.4, 0.4)))
+    assert (p.value, rows, cols) == (4096, 12, 16) and keep[0] is Owned
 
 
 # ------------------------------------------------------------------------------------------------ outputs
@@ -150,6 +276,8 @@ def test_ptr_null_for_none_and_empty():
     t = torch.zeros(4, dtype=torch.float32)
     p = A.ptr(t)
     assert isinstance(p, C.c_void_p) and p.value == t.data_ptr()
+    # collapse=False: whatever address torch reports for the empty tensor (recent versions report 0 themselves)
+    assert A.ptr(t[3:3], collapse=False).value == C.c_void_p(t[3:3].data_ptr()).value and A.ptr(None, collapse=False) is None
 
 
 def test_result_buffer():

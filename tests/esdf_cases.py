@@ -3,6 +3,7 @@ case is put through the CPU checker and read back."""
 import numpy as np
 
 import esdf_independent as EI
+import helpers as H
 
 VOXEL = 0.05
 # r = esdf_max_distance_m / voxel_size, as a caller writes it (float32(r * voxel_size); the float32 quotient is what comes out of that: "57" at
@@ -34,7 +35,6 @@ def params(M, r, voxel_size=VOXEL, **kw):
 
 
 def oracle_map(oracle_mod, pg, idx, data):
-    import helpers as H
     o = oracle_mod.OracleMap(H.copy_params(pg, oracle_mod.OrcParams))
     oracle_set(oracle_mod, o, idx, data)
     return o
@@ -50,19 +50,14 @@ def oracle_esdf(oracle_mod, o):
     return idx, [o.get_block(oracle_mod.L_ESDF, i) for i in idx]
 
 
-ESDF_FIELDS = ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site")
-
-
 def assert_same_blocks(tag, idx_a, blocks_a, idx_b, blocks_b):
-    """Two read-backs of the ESDF layer hold the same blocks with the same voxels, every field of every voxel (all eight planes of a block)."""
-    a = {tuple(i): np.asarray(blocks_a[k]).reshape(512) for k, i in enumerate(np.asarray(idx_a).reshape(-1, 3).tolist())}
-    b = {tuple(i): np.asarray(blocks_b[k]).reshape(512) for k, i in enumerate(np.asarray(idx_b).reshape(-1, 3).tolist())}
-    assert set(a) == set(b), (tag, "block sets differ", sorted(set(a) ^ set(b))[:5])
-    for i in a:
-        for f in ESDF_FIELDS:
-            if not np.array_equal(a[i][f], b[i][f]):
-                v = np.argwhere(a[i][f].reshape(512, -1) != b[i][f].reshape(512, -1))[0, 0]
-                raise AssertionError((tag, "block", i, f, "voxel z + 8y + 64x =", int(v), a[i][f][v].tolist(), b[i][f][v].tolist()))
+    """Two read-backs of the ESDF layer hold the same blocks with the same voxels, every field of every voxel (all eight planes of a block), in
+    whichever order each lists its blocks."""
+    def state(idx, blocks):
+        idx = np.asarray(idx, np.int32).reshape(-1, 3)
+        order = np.lexsort(idx.T[::-1])
+        return {"layers": {H.M.LAYER_ESDF: (idx[order], np.asarray(blocks).reshape(-1, 512)[order])}}
+    H.assert_same_map(state(idx_a, blocks_a), state(idx_b, blocks_b), tag, fields={H.M.LAYER_ESDF: H.ESDF_FIELDS})
 
 
 def assert_field(tag, f, sites, where, r, dims):

@@ -75,8 +75,8 @@ SWITCHES = [dict(tsdf_set_free_distance_on_decayed=1, tsdf_decayed_free_distance
 @pytest.mark.gpu
 @pytest.mark.parametrize("sw", SWITCHES, ids=["set_free", "keep_blocks", "keep_blocks+set_free"])
 def test_tsdf_decay_switches_parity(oracle_mod, hip_lib, sw):
-    from test_gpu_parity import make_pair, compare_layer, TOL
-    from test_gpu_sequences import check_all
+    from helpers import make_pair, compare_layer, TOL
+    from helpers import check_all
     M, g, o = make_pair(oracle_mod, tsdf_decay_factor=0.3, tsdf_decayed_weight_threshold=0.2, max_integration_distance_m=5.0, invalid_depth_decay_factor=0.8, **sw)
     sc = S.Scene()
     fr = H.frames(8, CAM, stride=11)
@@ -104,7 +104,7 @@ def test_tsdf_decay_switches_parity(oracle_mod, hip_lib, sw):
 @pytest.mark.parametrize("sw", [dict(occupancy_decay_to_free=1), dict(decay_deallocate_decayed_blocks=0), dict(occupancy_decay_to_free=1, decay_deallocate_decayed_blocks=0)],
                          ids=["to_free", "keep_blocks", "to_free+keep_blocks"])
 def test_occupancy_decay_switches_parity(oracle_mod, hip_lib, sw):
-    from test_gpu_parity import make_pair, compare_occupancy, TOL
+    from helpers import make_pair, compare_occupancy, TOL
     occ = dict(projective_layer_type=1, free_region_occupancy_probability=0.3, occupied_region_occupancy_probability=0.9, max_integration_distance_m=5.0,
                free_region_decay_probability=0.6, occupied_region_decay_probability=0.2)
     M, g, o = make_pair(oracle_mod, **occ, **sw)

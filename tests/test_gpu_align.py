@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import align_independent as A
+import helpers as H
 
 pytestmark = pytest.mark.gpu
 VS = 0.05
@@ -273,7 +274,6 @@ def test_early_stop_and_failures(room, frames):
 def test_alignment_leaves_the_map_and_held_back_work_alone(frames):
     """under colour deferral a colour frame and an updateEsdf are held back when the alignment runs between two depth frames: the final layers are
     bit-identical to the same sequence without it"""
-    from isaac_ros_nvblox_amd import mapper as M
     _, _, x, st = frames[10]
 
     def sequence(align):
@@ -288,15 +288,8 @@ def test_alignment_leaves_the_map_and_held_back_work_alone(frames):
             if align and k >= 1:
                 results.append(m.align_points(x, st[0]) if k == 1 else m.align_depth(frames[10][0], st[0], A.SMALL_CAM))
         m.flush(); m.synchronize()
-        out = {}
-        for layer in (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF):
-            idx = m.block_indices(layer)
-            idx = idx[np.lexsort(idx.T[::-1])]
-            out[layer] = (idx, m.get_blocks(layer, idx)[0])
-        return out, results
+        return H.map_state(m), results
     plain, _ = sequence(False)
     with_align, results = sequence(True)
     assert len(results) == 3 and all(r.n_valid > 100 for r in results)
-    for layer in plain:
-        assert np.array_equal(plain[layer][0], with_align[layer][0]), layer
-        assert plain[layer][1].tobytes() == with_align[layer][1].tobytes(), layer
+    H.assert_same_map(plain, with_align, "without and with the alignment calls")

@@ -8,13 +8,10 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import ESDF_FIELDS, compare_layer
 from isaac_ros_nvblox_amd import synthetic as S
-from test_gpu_parity import TOL, compare_layer, make_pair
 
 pytestmark = pytest.mark.gpu
-
-ESDF_FIELDS = ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site")
-
 
 def rig_frames(n_cams, k, cam=H.SMALL_CAM, noise=0.0):
     """Frame k of n cameras on the same rig circle at 45 degree yaw offsets (BASELINE.json configs[3]): heavily overlapping views."""
@@ -25,15 +22,6 @@ def rig_frames(n_cams, k, cam=H.SMALL_CAM, noise=0.0):
         d, rgb = S.render(sc, T, cam, color=True, noise_sigma=noise, rng=rng)
         out.append((d, rgb, T))
     return out
-
-
-def layers_equal(M, a, b, layer, fields):
-    ia, ib = a.block_indices(layer), b.block_indices(layer)
-    assert np.array_equal(ia, ib)
-    ba, _ = a.get_blocks(layer, ia); bb, _ = b.get_blocks(layer, ib)
-    for f in fields:
-        assert np.array_equal(ba[f], bb[f]), (layer, f)
-    return len(ia)
 
 
 @pytest.mark.parametrize("n_cams", [2, 4, 8])
@@ -60,10 +48,7 @@ def test_batch_equals_separate_calls(oracle_mod, hip_lib, n_cams, kw):
         assert H.idx_set(gb.last_color_view()) == H.idx_set(gs.last_color_view()) == H.idx_set(o.last_color_view())
         assert np.array_equal(gb.synthetic_depth(), gs.synthetic_depth())
         gb.update_esdf(); gs.update_esdf(); o.update_esdf()
-    n = layers_equal(M, gb, gs, M.LAYER_TSDF, ("distance", "weight"))
-    assert n > 150
-    layers_equal(M, gb, gs, M.LAYER_COLOR, ("r", "g", "b", "weight"))
-    layers_equal(M, gb, gs, M.LAYER_ESDF, ESDF_FIELDS)
+    H.assert_same_map(gb, gs, "batch vs separate calls", min_blocks={M.LAYER_TSDF: 151})
     compare_layer(M, gb, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
     compare_layer(M, gb, o, M.LAYER_COLOR, oracle_mod.L_COLOR, fields_tol=("weight",), lsb_fields=("r", "g", "b"))
     compare_layer(M, gb, o, M.LAYER_ESDF, oracle_mod.L_ESDF, fields_exact=ESDF_FIELDS)
@@ -73,10 +58,7 @@ def test_batch_equals_separate_calls(oracle_mod, hip_lib, n_cams, kw):
         assert (b["weight"] > 3.5).sum() > 1000
     # mesh of the batched map == mesh of the sequential map
     gb.update_color_mesh(); gs.update_color_mesh()
-    ma, mb = gb.mesh(), gs.mesh()
-    assert set(ma) == set(mb)
-    for key in ma:
-        assert np.array_equal(ma[key]["triangles"], mb[key]["triangles"]) and np.array_equal(ma[key]["vertices"], mb[key]["vertices"])
+    H.assert_same_map(gb, gs, "batch vs separate calls, after the mesh update", mesh=True)
     assert gb.counters()["capacity_overflow"] == 0
 
 
@@ -91,7 +73,7 @@ def test_decay_after_a_batch_spares_the_last_cameras_view(oracle_mod, hip_lib):
     for d, _, T in fr:
         gs.integrate_depth(d, T, cam); o.integrate_depth(d, T, cam)
     gb.decay_tsdf(True); gs.decay_tsdf(True); o.decay_tsdf(True)
-    layers_equal(M, gb, gs, M.LAYER_TSDF, ("distance", "weight"))
+    H.assert_same_map(gb, gs, "decay after a batch", layers=(M.LAYER_TSDF,))
     compare_layer(M, gb, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
     b, _ = gb.get_blocks(M.LAYER_TSDF, gb.block_indices(M.LAYER_TSDF))
     w = np.unique(b["weight"])
@@ -110,7 +92,7 @@ def test_batch_of_one_and_fallbacks(oracle_mod, hip_lib):
         gb.integrate_depth_batch([d for d, _, _ in fr[:nb]], [T for _, _, T in fr[:nb]], cam)
         for d, _, T in fr[:nb]:
             gs.integrate_depth(d, T, cam)
-        assert layers_equal(M, gb, gs, M.LAYER_TSDF, ("distance", "weight")) > 50
+        H.assert_same_map(gb, gs, kw, layers=(M.LAYER_TSDF,), min_blocks=51)
 
 
 def test_batch_argument_checks(hip_lib):
@@ -147,6 +129,6 @@ def test_batches_and_measurement_exchange_across_pool_growth(oracle_mod, hip_lib
         gm.apply_measurements(all_buf, all_cnt); gm.synchronize()
     assert gb.capacity > 1024 and gm.capacity > 1024
     assert gb.counters()["capacity_overflow"] == 0 and gm.counters()["capacity_overflow"] == 0
-    n = layers_equal(M, gb, gs, M.LAYER_TSDF, ("distance", "weight"))
-    layers_equal(M, gm, gs, M.LAYER_TSDF, ("distance", "weight"))
-    assert n > 1100
+    gs_state = H.map_state(gs, layers=(M.LAYER_TSDF,))
+    H.assert_same_map(gb, gs_state, "batch across pool growth", min_blocks=1101)
+    H.assert_same_map(gm, gs_state, "measurement exchange across pool growth")

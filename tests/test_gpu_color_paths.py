@@ -16,7 +16,6 @@ import pytest
 import color_independent as CI
 import helpers as H
 from isaac_ros_nvblox_amd import synthetic as S
-from test_gpu_round6 import _same, _short
 
 pytestmark = pytest.mark.gpu
 
@@ -71,7 +70,7 @@ class Feeder:
 def _kernel_counts(m):
     names = {}
     for k_, v in m.profile().items():
-        names[_short(k_)] = names.get(_short(k_), 0) + v["count"]
+        names[H.short(k_)] = names.get(H.short(k_), 0) + v["count"]
     return names
 
 
@@ -165,8 +164,8 @@ def test_colour_layer_against_the_model_pair_b_640x480(hip_lib):
 # ------------------------------------------------------------------------------------------------ the pair against the two calls, both mappers with colour
 def _layers_of(M, p):
     if p.projective_layer_type == 1:
-        return [("occupancy", M.LAYER_OCCUPANCY), ("esdf", M.LAYER_ESDF)]
-    return [("tsdf", M.LAYER_TSDF), ("color", M.LAYER_COLOR), ("esdf", M.LAYER_ESDF)]
+        return (M.LAYER_OCCUPANCY, M.LAYER_ESDF)
+    return (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF)
 
 
 def _pair_vs_two_calls(hip_lib, pa, pb, schedule, seed, cam=H.SMALL_CAM, disrupt=True, model_check=False):
@@ -233,10 +232,10 @@ def _pair_vs_two_calls(hip_lib, pa, pb, schedule, seed, cam=H.SMALL_CAM, disrupt
                     if e != "none":
                         _model_step(M, x, models[id(x)], CI.decode(bgra if KIND[e] else rgb), T, cam, p_, ("pair", "a" if x is A else "b", e, step))
             if rng.random() < 0.15:
-                _same(M, A, RA, la, ("a", seed, step)); _same(M, B, RB, lb, ("b", seed, step))
+                H.assert_same_map(A, RA, ("a", seed, step), layers=la); H.assert_same_map(B, RB, ("b", seed, step), layers=lb)
         for m_ in (A, B, RA, RB):
             m_.synchronize()
-        _same(M, A, RA, la, ("a, end", seed)); _same(M, B, RB, lb, ("b, end", seed))
+        H.assert_same_map(A, RA, ("a, end", seed), layers=la); H.assert_same_map(B, RB, ("b, end", seed), layers=lb)
         names = _kernel_counts(A)
         for m_ in (A, B, RA, RB):
             m_.close()
@@ -320,5 +319,5 @@ def test_colour_batch_refuses_a_bgra8_frame(hip_lib):
     with pytest.raises(ValueError):
         g.integrate_color_batch([f, f], [T, T], cam)
     g.synchronize()
-    assert not [k for k in g.profile() if _short(k).startswith("k_")], g.profile()
+    assert not [k for k in g.profile() if H.short(k).startswith("k_")], g.profile()
     f.close(); g.close()

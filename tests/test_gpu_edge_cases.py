@@ -86,11 +86,11 @@ def test_pools_grow_on_demand_without_data_loss(oracle_mod, hip_lib):
         caps.append(g.capacity)
     assert caps[-1] >= 4096 and caps[0] == 1024 and sorted(caps) == caps
     assert g.counters()["capacity_overflow"] == 0
-    from test_gpu_parity import compare_layer
+    from helpers import compare_layer
     n, _ = compare_layer(M, g, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
     assert n > 1200
     compare_layer(M, g, o, M.LAYER_COLOR, oracle_mod.L_COLOR, fields_tol=("weight",), lsb_fields=("r", "g", "b"))
-    compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF, fields_exact=("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"))
+    compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF, fields_exact=H.ESDF_FIELDS)
     g.update_color_mesh(full=True); o.update_mesh(full=True)
     mg = g.mesh()
     for idx in o.block_indices(oracle_mod.L_TSDF):
@@ -192,16 +192,14 @@ def test_esdf_layer_changes_only_in_update_esdf(oracle_mod, hip_lib):
         g.integrate_depth(d, T, H.SMALL_CAM); g.integrate_color(rgb, T, H.SMALL_CAM)
         o.integrate_depth(d, T, H.SMALL_CAM); o.integrate_color(rgb, T, H.SMALL_CAM)
     g.update_esdf(); o.update_esdf()
-    idx0 = g.block_indices(M.LAYER_ESDF); blk0, _ = g.get_blocks(M.LAYER_ESDF, idx0); img0, aabb0 = g.esdf_slice_image()
+    before = H.map_state(g, layers=(M.LAYER_ESDF,), slice=True)
+    idx0 = before["layers"][M.LAYER_ESDF][0]
     assert np.array_equal(idx0, o.block_indices(oracle_mod.L_ESDF))
     # new depth + colour: marking happens inside the colour launch, but nothing observable may change
     for d, rgb, T in fr[2:]:
         g.integrate_depth(d, T, H.SMALL_CAM); g.integrate_color(rgb, T, H.SMALL_CAM)
         o.integrate_depth(d, T, H.SMALL_CAM); o.integrate_color(rgb, T, H.SMALL_CAM)
-        idx1 = g.block_indices(M.LAYER_ESDF); blk1, _ = g.get_blocks(M.LAYER_ESDF, idx1); img1, aabb1 = g.esdf_slice_image()
-        assert np.array_equal(idx0, idx1) and np.array_equal(aabb0, aabb1) and np.array_equal(img0, img1)
-        for f_ in ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"):
-            assert np.array_equal(blk0[f_], blk1[f_]), f_
+        H.assert_same_map(before, g, "the ESDF between two updates")
     # ... until updateEsdf, after which every query path sees the completed update (held-back EDT included)
     g.update_esdf(); o.update_esdf()
     img2, _ = g.esdf_slice_image(); ref, _ = o.esdf_slice_image()
@@ -212,7 +210,7 @@ def test_esdf_layer_changes_only_in_update_esdf(oracle_mod, hip_lib):
     blk2, _ = g.get_blocks(M.LAYER_ESDF, idx2)
     for k, i in enumerate(idx2):
         bo = o.get_block(oracle_mod.L_ESDF, i)
-        for f_ in ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"):
+        for f_ in H.ESDF_FIELDS:
             assert np.array_equal(blk2[k][f_], bo[f_]), (f_, i)
 
 
@@ -231,28 +229,17 @@ def test_save_and_load_map_round_trip(oracle_mod, hip_lib, tmp_path):
     d0, rgb0, T0 = H.frames(1, H.SMALL_CAM, start=100)[0]
     b.integrate_depth(d0, T0, H.SMALL_CAM)                       # content that the load must replace
     b.load_map(path)
-    for layer in (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF):
-        ia, ib = a.block_indices(layer), b.block_indices(layer)
-        assert len(ia) > 10 and np.array_equal(ia, ib)
-        va, _ = a.get_blocks(layer, ia); vb, fb = b.get_blocks(layer, ib)
-        assert fb.all() and va.tobytes() == vb.tobytes()
-    sa, aa = a.esdf_slice_image(); sb, ab = b.esdf_slice_image()
-    assert np.array_equal(sa, sb) and np.allclose(aa, ab)
+    saved = H.map_state(a, slice=True, mesh=True)
+    H.assert_same_map(saved, H.map_state(b, slice=True), "the loaded map", min_blocks=11)
     # loaded TSDF blocks are dirty: the ESDF / mesh recomputed from them equal the saved mapper's
     b.update_esdf(); b.update_color_mesh()
-    sb2, _ = b.esdf_slice_image()
-    assert np.array_equal(sa, sb2)
+    H.assert_same_map(saved, b, "ESDF and mesh recomputed from the loaded map", layers=(M.LAYER_TSDF, M.LAYER_COLOR))
     ma, mb = a.mesh(), b.mesh()
-    assert set(ma.keys()) == set(mb.keys()) and len(ma) > 10
-    for k in ma:
-        assert np.array_equal(ma[k]["triangles"], mb[k]["triangles"]) and np.array_equal(ma[k]["vertices"], mb[k]["vertices"])
-        assert np.array_equal(ma[k]["colors"], mb[k]["colors"])
+    assert len(ma) > 10 and all(np.array_equal(ma[k]["colors"], mb[k]["colors"]) for k in ma)
     # both mappers keep integrating identically
     d1, rgb1, T1 = H.frames(1, H.SMALL_CAM, start=60)[0]
     a.integrate_depth(d1, T1, H.SMALL_CAM); b.integrate_depth(d1, T1, H.SMALL_CAM)
-    ia = a.block_indices(M.LAYER_TSDF)
-    assert np.array_equal(ia, b.block_indices(M.LAYER_TSDF))
-    assert a.get_blocks(M.LAYER_TSDF, ia)[0].tobytes() == b.get_blocks(M.LAYER_TSDF, ia)[0].tobytes()
+    H.assert_same_map(a, b, "one further frame", layers=(M.LAYER_TSDF,))
     # error behaviour: missing file, garbage file, wrong voxel size -> error, map untouched
     n_before = b.num_blocks(M.LAYER_TSDF)
     bad = tmp_path / "bad.nvbxmap"; bad.write_bytes(b"not a map file at all" * 10)

@@ -44,12 +44,8 @@ def _capacity(n_blocks):
     return cap
 
 
-def _read(M, g, layer=None):
-    layer = M.LAYER_ESDF if layer is None else layer
-    idx = g.block_indices(layer)
-    b, found = g.get_blocks(layer, idx)
-    assert found.all()
-    return idx, b
+def _read(M, g):
+    return H.map_state(g, layers=(M.LAYER_ESDF,))["layers"][M.LAYER_ESDF]
 
 
 def _kernels(g):
@@ -345,16 +341,14 @@ def test_radius_limit(oracle_mod, hip_lib, mode, r_bad):
     changed = np.array([not np.array_equal(d2[k], data[k]) for k in range(len(i2))], bool)
     assert np.array_equal(i2, idx) and changed.any()
     g.set_blocks(M.LAYER_TSDF, i2[changed], d2[changed])
-    before = (_read(M, g, M.LAYER_TSDF), _read(M, g))
+    before = H.map_state(g, layers=(M.LAYER_TSDF, M.LAYER_ESDF))
     bad_m = EI.distance_at_least_radius(64, EC.VOXEL) if r_bad == 64 else EI.distance_for_radius(r_bad, EC.VOXEL)
     assert EI.radius_of(bad_m, EC.VOXEL)[0] >= 64
     g.set_params(M.default_params(voxel_size=EC.VOXEL, esdf_max_distance_m=bad_m, esdf_mode=mode))
     for _ in range(2):
         with pytest.raises(M.NvbxError, match="esdf_max_distance_m / voxel_size must be < 64 voxels"):
             g.update_esdf()
-    after = (_read(M, g, M.LAYER_TSDF), _read(M, g))
-    for (ia, ba), (ib, bb) in zip(before, after):
-        assert np.array_equal(ia, ib) and ba.tobytes() == bb.tobytes(), (mode, r_bad, "the refused update changed the map")
+    H.assert_same_map(before, g, (mode, r_bad, "the refused update changed the map"))
     g.set_params(pg)
     g.update_esdf()
     EC.assert_field((mode, "after"), fields(*_read(M, g)), sites2, where, q, dims)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import feature_match_independent as FM
+import helpers as H
 
 pytestmark = pytest.mark.gpu
 
@@ -309,28 +310,14 @@ def test_matching_leaves_the_map_bit_identical(room_frames):
         m.integrate_depth(d, T, CAM); m.integrate_color(rgb, T, CAM)
         m.integrate_features(_feature_image(rng, Cn), T, CAM, STRIDE)
 
-    def snapshot():
-        out = {}
-        for name, layer in (("tsdf", M.LAYER_TSDF), ("color", M.LAYER_COLOR), ("esdf", M.LAYER_ESDF), ("mesh", M.LAYER_MESH), ("feature", M.LAYER_FEATURE)):
-            idx = m.block_indices(layer)
-            out[name + "_idx"] = idx
-            if name in ("tsdf", "color") and len(idx):
-                out[name] = m.get_blocks(layer, idx)[0].view(np.uint8)
-        f, w, found = m.feature_blocks(out["tsdf_idx"])
-        out["feat"] = f.view(np.uint16); out["feat_w"] = w.view(np.uint32); out["feat_found"] = found
-        c = m.counters()
-        out["counters"] = np.array([c[k] for k in sorted(c)])
-        return out
-    a = snapshot()
-    assert len(a["tsdf_idx"]) > 100 and len(a["color_idx"]) > 50 and len(a["feature_idx"]) > 50
+    layers = (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF, M.LAYER_FEATURE)
+    before = H.map_state(m, layers), m.block_indices(M.LAYER_MESH), m.counters()
     q = _queries(Cn, 33)
     for metric in ("dot", "cosine"):
         m.match_features(q, metric, 1.0, all_scores=True)
         m.match_points(rng.uniform(-3, 3, (500, 3)).astype(np.float32), q, metric)
-    b = snapshot()
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
+    H.assert_same_map(before[0], m, "before and after the calls", min_blocks={M.LAYER_TSDF: 101, M.LAYER_COLOR: 51, M.LAYER_FEATURE: 51})
+    assert np.array_equal(before[1], m.block_indices(M.LAYER_MESH)) and before[2] == m.counters()
     m.close()
 
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import feature_independent as FI
+import helpers as H
 
 pytestmark = pytest.mark.gpu
 
@@ -298,14 +299,9 @@ def test_pool_growth_carries_the_layer():
 
 
 # ---- 7. nothing else moves
-def _snapshot(M, m):
+def _other_outputs(M, m):
+    """what the map comparison does not hold: the synthetic depth image, the last colour view, the mesh's sizes and the counters"""
     out = {}
-    for name, layer in (("tsdf", M.LAYER_TSDF), ("color", M.LAYER_COLOR), ("esdf", M.LAYER_ESDF)):
-        idx = m.block_indices(layer)
-        out[name + "_idx"] = idx
-        out[name] = m.get_blocks(layer, idx)[0].view(np.uint8) if len(idx) else np.zeros(0, np.uint8)
-    img, aabb = m.esdf_slice_image()
-    out["slice"] = np.asarray(img).view(np.uint32); out["slice_aabb"] = np.asarray(aabb)
     out["synth"] = m.synthetic_depth().view(np.uint32)
     out["color_view"] = m.last_color_view()
     mesh = m.mesh()
@@ -353,10 +349,11 @@ def test_a_mapper_with_features_computes_everything_else_as_one_without(deferral
             assert m.num_blocks(M.LAYER_FEATURE) > 0 and "_feature_pool_bytes" in m.profile()
         else:
             assert "_feature_pool_bytes" not in m.profile() and m.num_blocks(M.LAYER_FEATURE) == 0      # nothing was ever allocated for features
-        snaps.append(_snapshot(M, m))
+        snaps.append((H.map_state(m, slice=True), _other_outputs(M, m)))
         m.close()
-    a, b = snaps
-    assert len(a["tsdf_idx"]) > 100 and len(a["color_idx"]) > 50 and len(a["esdf_idx"]) > 10 and a["mesh"][2] > 1000
+    (sa, a), (sb, b) = snaps
+    H.assert_same_map(sa, sb, "without and with features", min_blocks={M.LAYER_TSDF: 101, M.LAYER_COLOR: 51, M.LAYER_ESDF: 11})
+    assert a["mesh"][2] > 1000
     for k in a:
         assert np.array_equal(a[k], b[k]), k
 

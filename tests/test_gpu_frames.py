@@ -13,11 +13,6 @@ from isaac_ros_nvblox_amd import synthetic as S
 pytestmark = pytest.mark.gpu
 
 
-def _bit_equal(M, a, b, tag=""):
-    from test_gpu_pipeline import _equal_maps
-    _equal_maps(M, a, b, tag)
-
-
 def _count(prof, name):
     return sum(v["count"] for k_, v in prof.items() if name in k_)
 
@@ -58,7 +53,7 @@ def test_recycled_image_in_a_library_frame_is_not_copied_and_not_lost(oracle_mod
             assert not img.shared()
             owned.update_esdf()
         classic.synchronize(); owned.synchronize()
-    _bit_equal(M, classic, owned, "frames / %s" % writer)
+    H.assert_same_map(classic, owned, "frames / %s" % writer, slice=True)
     prof = owned.profile()
     assert _count(prof, "k_stage_color") == 0, {k_: v["count"] for k_, v in prof.items()}
     assert _count(prof, "k_integrate_tsdf_color") >= 10           # two launches per frame all along
@@ -124,7 +119,7 @@ def test_frame_api_contract(oracle_mod, hip_lib):
     assert lib.nvbx_frame_refcount(q) == 1                    # the mapper's (held back)
     g.synchronize()
     assert lib.nvbx_frame_refcount(q) == 0                    # carried out: back in the pool
-    _bit_equal(M, ref, g, "owned")
+    H.assert_same_map(ref, g, "owned", slice=True)
     # deferral off: the frame is read by launches enqueued at once and let go of behind them
     g.set_color_deferral(False)
     q2 = C.c_void_p(); assert lib.nvbx_color_image_acquire(g._h, cam[5], cam[4], 3, C.byref(q2)) == 0
@@ -132,7 +127,7 @@ def test_frame_api_contract(oracle_mod, hip_lib):
     assert lib.nvbx_integrate_color_owned(g._h, q2, 3, cam[5], cam[4], Tm.ctypes.data_as(C.c_void_p), C.byref(k)) == 0
     assert lib.nvbx_frame_refcount(q2) == 0
     ref.integrate_color(rgb, T, cam)
-    _bit_equal(M, ref, g, "owned, classic order")
+    H.assert_same_map(ref, g, "owned, classic order", slice=True)
     assert lib.nvbx_frame_release(p) == 0
     g.close(); ref.close()
     torch.cuda.synchronize()
@@ -174,7 +169,7 @@ def test_pool_backpressure_when_the_host_runs_far_ahead(oracle_mod, hip_lib, mon
         aux.synchronize()
         owned.integrate_color(img, T, cam); owned.update_esdf()
     owned.synchronize()
-    _bit_equal(M, classic, owned, "back-pressure")
+    H.assert_same_map(classic, owned, "back-pressure", slice=True)
     held, free, nbytes, created, waits, syncs = M.frame_pool_stats()
     assert held == 1 and free <= 2 and created - stats0[3] <= 3 and waits > stats0[4], (held, free, created - stats0[3], waits - stats0[4], syncs - stats0[5])
     img.close(); classic.close(); owned.close()

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import frontier_independent as FI
+import helpers as H
 import segment_independent as SI
 
 pytestmark = pytest.mark.gpu
@@ -304,16 +305,6 @@ def test_view_gain_wall_and_empty_map(hip_lib):
 
 
 # ---- 8. nothing is written to the map, held-back work stays held back
-def _map_state(m):
-    M, _ = _mods()
-    out = {}
-    for layer in (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF):
-        idx = m.block_indices(layer)
-        idx = idx[np.lexsort(idx.T[::-1])]
-        out[layer] = (idx, m.get_blocks(layer, idx)[0])
-    return out
-
-
 def test_map_unchanged_and_held_back_work_stays_held_back(hip_lib):
     """Two mappers with colour deferral on get the same frames; one of them runs the three calls between pipelined frames.  Its map is byte for
     byte the other's and, apart from the calls' own kernels, it has launched exactly the same kernels as often: the held-back colour frame and
@@ -344,13 +335,10 @@ def test_map_unchanged_and_held_back_work_stays_held_back(hip_lib):
     pb = {k: v["count"] for k, v in B.profile().items() if not k.startswith("_")}
     assert pa == pb, (pa, pb)
     assert any("k_integrate_tsdf_color" in k for k in pa), list(pa)[:20]     # the pipelined path has run: colour frames were carried, not flushed
-    before = _map_state(A)
+    before = H.map_state(A)
     A.find_frontiers(); A.frontier_clusters(); A.view_gain(np.stack([f[2] for f in frames]), CAM, subsampling=4, max_range_m=3.0)
-    after = _map_state(A)
-    sb = _map_state(B)
-    for layer in before:
-        assert np.array_equal(before[layer][0], after[layer][0]) and before[layer][1].tobytes() == after[layer][1].tobytes(), layer
-        assert np.array_equal(before[layer][0], sb[layer][0]) and before[layer][1].tobytes() == sb[layer][1].tobytes(), layer
+    H.assert_same_map(before, A, "before and after the three calls")
+    H.assert_same_map(before, B, "against the mapper that never made them")
     A.close(); B.close()
 
 

@@ -6,12 +6,10 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import ESDF_FIELDS, TOL, compare_layer, make_pair
 from isaac_ros_nvblox_amd import synthetic as S
-from test_gpu_parity import TOL, compare_layer, make_pair
 
 pytestmark = pytest.mark.gpu
-
-ESDF_FIELDS = ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site")
 
 
 def world_rotation(yaw_deg=17.0, roll_deg=9.0, shift=(0.013, -0.027, 0.041)):

@@ -16,6 +16,7 @@ import time
 import numpy as np
 import pytest
 
+import helpers as H
 import launch_geometry_child as LG
 
 pytestmark = pytest.mark.gpu
@@ -93,31 +94,7 @@ def run(tmp_path_factory):
         print("  %6.1f s  %s" % (s, tag))
 
 
-def _dtypes():
-    from isaac_ros_nvblox_amd import mapper as M
-    return dict(tsdf=M.TSDF_DT, color=M.COLOR_DT, esdf=M.ESDF_DT, occupancy=M.OCCUPANCY_DT)
-
-
-def _first_difference(key, a, b):
-    """Where two snapshot arrays first differ: mapper, phase, layer, block, field and a few voxel values."""
-    parts = key.split("/")
-    if a.shape != b.shape:
-        return "%s: shapes differ %s vs %s" % (key, a.shape, b.shape)
-    if len(parts) == 4 and parts[3] == "bytes":
-        dt = _dtypes()[parts[2]]
-        va = a.view(dt).reshape(-1, 512); vb = b.view(dt).reshape(-1, 512)
-        for k in range(len(va)):
-            if va[k].tobytes() != vb[k].tobytes():
-                for f in dt.names:
-                    fa, fb = va[k][f], vb[k][f]
-                    bad = np.nonzero((fa != fb).reshape(512, -1).any(1))[0]
-                    if len(bad):
-                        return "phase %s, mapper %s, layer %s, block #%d (sorted index order), field %s, voxels %s: %s vs %s" % (
-                            parts[0], parts[1], parts[2], k, f, bad[:4].tolist(), fa[bad[:4]].tolist(), fb[bad[:4]].tolist())
-    flat_a, flat_b = a.reshape(-1), b.reshape(-1)
-    bad = np.nonzero(flat_a.view(np.uint8) != flat_b.view(np.uint8))[0] if a.dtype == b.dtype else []
-    i = int(bad[0]) // a.dtype.itemsize if len(bad) else 0
-    return "%s: first difference at flat element %d: %s vs %s" % (key, i, flat_a[i:i + 4].tolist(), flat_b[i:i + 4].tolist())
+LAYER_OF = {name: layer for layer, name in H.LAYER_NAMES.items()}
 
 
 def _assert_same_maps(base, other, tag):
@@ -126,7 +103,13 @@ def _assert_same_maps(base, other, tag):
     for k in keys:
         a, b = base[k], other[k]
         if a.shape != b.shape or a.dtype != b.dtype or a.tobytes() != b.tobytes():
-            pytest.fail("%s differs from the default run: %s" % (tag, _first_difference(k, a, b)))
+            phase, mapper, what = k.split("/", 2)
+            if what.endswith("/bytes"):                                  # the blocks of a layer, in the order of its "/idx" array
+                dt = H.LAYER_FIELDS[LAYER_OF[what.split("/")[0]]]
+                diff = H.block_difference(base[k[:-len("bytes")] + "idx"], a.view(dt), b.view(dt))
+            else:
+                diff = H.array_difference(a, b)
+            pytest.fail("%s differs from the default run: phase %s, mapper %s, %s: %s" % (tag, phase, mapper, what, diff))
 
 
 def _launch_counts(out, mapper):
@@ -159,7 +142,6 @@ class Checker:
         self.m, self.cleared, self.out, self.queries = {}, {}, {}, {}
 
     def new(self, name):
-        import helpers as H
         kw, _, _ = LG.MAPPERS[name]
         self.m[name] = self.O.OracleMap(H.copy_params(self.M.default_params(**kw), self.O.OrcParams))
         self.cleared[name] = []
@@ -263,12 +245,11 @@ class Checker:
 def _compare_with_checker(g, o, key_prefix, name):
     M = LG
     layers = M.MAPPERS[name][2]
-    dts = _dtypes()
     for lay in layers:
         ig, io = g[key_prefix + lay + "/idx"], o[key_prefix + lay + "/idx"]
         assert np.array_equal(ig, io), (key_prefix + lay, "block index sets differ", len(ig), len(io),
                                         sorted(set(map(tuple, ig.tolist())) ^ set(map(tuple, io.tolist())))[:5])
-        bg = g[key_prefix + lay + "/bytes"].view(dts[lay]).reshape(-1, 512)
+        bg = g[key_prefix + lay + "/bytes"].view(H.LAYER_FIELDS[LAYER_OF[lay]]).reshape(-1, 512)
         for k, bo in enumerate(o[key_prefix + lay + "/blocks"]):
             b = bg[k]; where = (key_prefix + lay, tuple(io[k].tolist()))
             if lay == "tsdf":
@@ -281,7 +262,7 @@ def _compare_with_checker(g, o, key_prefix, name):
                 for f in ("r", "g", "b"):
                     assert np.abs(b[f].astype(np.int32) - bo[f].astype(np.int32)).max() <= 1, where + (f,)
             else:
-                for f in ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"):
+                for f in H.ESDF_FIELDS:
                     assert np.array_equal(b[f], bo[f]), where + (f,)
     assert np.array_equal(g[key_prefix + "cleared"], o[key_prefix + "cleared"]), (key_prefix, "cleared blocks differ",
                                                                                    len(g[key_prefix + "cleared"]), len(o[key_prefix + "cleared"]))

@@ -4,6 +4,7 @@
 import numpy as np
 import pytest
 
+import helpers as H
 import merge_independent as MI
 
 pytestmark = pytest.mark.gpu
@@ -43,25 +44,25 @@ def _integrate(m, frames, color=True):
             m.integrate_color(rgb, T, CAM)
 
 
-def _layers(m):
+def _blocks_of(m):
+    """({block: tsdf[512]}, {block: color[512]}): the form the merge model takes"""
     M, _ = _mods()
     return MI.read_layers(m, M)
 
 
-def _same_layers(a, b, what=""):
-    for la, lb, name in zip(a, b, ("tsdf", "color")):
-        assert set(la) == set(lb), "%s: %s block sets differ" % (what, name)
-        for k in la:
-            assert la[k].tobytes() == lb[k].tobytes(), "%s: %s block %r differs" % (what, name, k)
+def _tsdf_color_state(m):
+    M, _ = _mods()
+    return H.map_state(m, layers=(M.LAYER_TSDF, M.LAYER_COLOR))
 
 
 def _merge_and_check(dst, src, T, what="", **options):
     """merge on the GPU, the model on the layers read before it; everything compared exactly.  -> (model result, GPU result, layers after)"""
-    dt, dc = _layers(dst); st, sc = _layers(src)
+    dt, dc = _blocks_of(dst); st, sc = _blocks_of(src)
+    src_before = _tsdf_color_state(src)
     p = dst.params
     r = MI.merge(dt, dc, st, sc, T, p.voxel_size, _trunc(p), p.max_weight, **{**{k: MI.DEFAULTS[k] for k in MI.DEFAULTS}, **options})
     res = dst.merge_from(src, T, **options)
-    at, ac = _layers(dst)
+    at, ac = _blocks_of(dst)
     assert set(at) == set(r["tsdf"]) == set(dt) | set(r["candidates"]), what
     assert (res.source_blocks, res.candidate_blocks, res.blocks_allocated, res.voxels_fused, res.color_voxels_fused, res.status) == \
         (r["source_blocks"], r["candidate_blocks"], r["blocks_allocated"], r["voxels_fused"], r["color_voxels_fused"], r["status"]), (what, res)
@@ -73,8 +74,7 @@ def _merge_and_check(dst, src, T, what="", **options):
     assert set(ac) == set(r["color"]), what
     for k, v in r["color"].items():
         assert ac[k].tobytes() == v.tobytes(), "%s: colour block %r differs from the model" % (what, k)
-    s2t, s2c = _layers(src)
-    _same_layers((st, sc), (s2t, s2c), what + " (src is not modified)")
+    H.assert_same_map(src_before, src, what + " (src is not modified)")
     return r, res, (at, ac)
 
 
@@ -196,7 +196,7 @@ def test_two_blocks_adjacent_across_a_face_and_the_options(hip_lib):
             assert (w <= F32(5.0)).all() and (w == F32(5.0)).any()        # the clamp was reached
             if opts.get("merge_color", 1) == 0:
                 assert res.color_voxels_fused == 0
-                _same_layers((dc,), (ac,), "merge_color = 0 leaves dst's colour layer alone")
+                assert set(ac) == set(dc) and all(ac[k].tobytes() == dc[k].tobytes() for k in dc), "merge_color = 0 leaves dst's colour layer alone"
             else:
                 assert res.color_voxels_fused > 0
             src.close(); dst.close()
@@ -236,7 +236,7 @@ def test_a_plane_stays_the_plane(hip_lib):
     T = TRANSFORMS["general_30"]
     res = dst.merge_from(src, T)
     assert res.status_name == "OK"
-    at, _ = _layers(dst)
+    at, _ = _blocks_of(dst)
     T64 = T.astype(np.float64)
     n2 = T64[:3, :3] @ n; c2 = c0 - n2 @ T64[:3, 3]
     Tinv = np.linalg.inv(T64)
@@ -267,13 +267,14 @@ def test_the_mapper_afterwards_behaves_as_after_set_blocks(src_room, room_frames
     _integrate(dst, room_frames[3:5])
     res = dst.merge_from(src_room, TRANSFORMS["general_30"])
     assert res.status_name == "OK"
-    at, ac = _layers(dst)
+    at, ac = _blocks_of(dst)
+    merged = _tsdf_color_state(dst)
     twin = _mapper()
     _upload(twin, at, ac)
-    _same_layers((at, ac), _layers(twin), "the twin holds the merged layers")
+    H.assert_same_map(merged, twin, "the twin holds the merged layers")
     dst.save_map(str(tmp_path / "merged.nvblx"))
     loaded = _mapper(); loaded.load_map(str(tmp_path / "merged.nvblx"))
-    _same_layers((at, ac), _layers(loaded), "save_map / load_map")
+    H.assert_same_map(merged, loaded, "save_map / load_map")
     loaded.close()
     for m in (dst, twin):
         m.update_esdf(); m.update_color_mesh()
@@ -289,16 +290,16 @@ def test_the_mapper_afterwards_behaves_as_after_set_blocks(src_room, room_frames
     d, rgb, T = room_frames[5]
     for m in (dst, twin):
         m.integrate_depth(d, T, CAM); m.integrate_color(rgb, T, CAM); m.update_esdf()
-    _same_layers(_layers(dst), _layers(twin), "one further depth + colour frame")
+    H.assert_same_map(_tsdf_color_state(dst), twin, "one further depth + colour frame")
     assert np.array_equal(dst.esdf_slice_image()[0], twin.esdf_slice_image()[0])
     # and the flags agree with in_band over the voxels: a colour frame over a map whose flags were recomputed from scratch (set_params does so
     # when the truncation distance changes -- here it is uploaded afresh) gives the same colours
     fresh = _mapper()
-    t2, c2 = _layers(dst)
+    t2, c2 = _blocks_of(dst)
     _upload(fresh, t2, c2)
     for m in (dst, fresh):
         m.integrate_color(room_frames[4][1], room_frames[4][2], CAM)
-    _same_layers(_layers(dst), _layers(fresh), "colour frame over the merged map's band flags")
+    H.assert_same_map(_tsdf_color_state(dst), fresh, "colour frame over the merged map's band flags")
     dst.close(); twin.close(); fresh.close()
 
 
@@ -318,7 +319,7 @@ def _pipelined_pair(room_frames, deferral, sync):
     src.integrate_depth(room_frames[2][0], room_frames[2][2], CAM)
     if sync:
         src.synchronize(); dst.synchronize()
-    out = (_layers(dst), _layers(src), (res.candidate_blocks, res.voxels_fused, res.color_voxels_fused, res.status))
+    out = (_tsdf_color_state(dst), _tsdf_color_state(src), (res.candidate_blocks, res.voxels_fused, res.color_voxels_fused, res.status))
     src.close(); dst.close()
     return out
 
@@ -330,7 +331,7 @@ def test_held_back_work_and_a_following_source_frame(hip_lib, room_frames):
         got = _pipelined_pair(room_frames, deferral, sync)
         what = "deferral %r, synchronised %r" % (deferral, sync)
         assert got[2] == ref[2], what
-        _same_layers(got[0], ref[0], what + ": dst"); _same_layers(got[1], ref[1], what + ": src")
+        H.assert_same_map(got[0], ref[0], what + ": dst"); H.assert_same_map(got[1], ref[1], what + ": src")
 
 
 # ---- 6. growth and capacity
@@ -348,11 +349,11 @@ def test_capacity_error_leaves_the_destination_unchanged(src_room):
     dst.set_max_capacity(64)
     t, c = _blocks(rng, _cube((0, 0, 0), 2), color=True)
     _upload(dst, t, c)
-    before = _layers(dst)
+    before = _tsdf_color_state(dst)
     with pytest.raises(M.NvbxError, match=r"error -3: nvbx_merge_map"):
         dst.merge_from(src_room, TRANSFORMS["identity"])
     assert dst.capacity == 64
-    _same_layers(_layers(dst), before, "after the capacity error")
+    H.assert_same_map(before, dst, "after the capacity error")
     # and the mapper is usable: a merge that fits goes through
     small = _mapper(1 << 8)
     _upload(small, *_blocks(rng, [(0, 0, 0)]))
@@ -368,7 +369,7 @@ def test_refusals_name_the_call_and_change_nothing(hip_lib):
     t, c = _blocks(rng, _cube((0, 0, 0), 2), color=True)
     src = _mapper(1 << 8); dst = _mapper(1 << 8)
     _upload(src, t, c); _upload(dst, *_blocks(rng, [(0, 0, 1), (5, 5, 5)], color=True))
-    before = _layers(dst)
+    before = _tsdf_color_state(dst)
     I = TRANSFORMS["identity"]
     other_vs = _mapper(1 << 8, voxel_size=0.1)
     occ = _mapper(1 << 8, projective_layer_type=1)
@@ -390,7 +391,7 @@ def test_refusals_name_the_call_and_change_nothing(hip_lib):
     for what, d, s, T, opts in cases:
         with pytest.raises(M.NvbxError, match=r"error -1: nvbx_merge_map: "):
             d.merge_from(s, T, **opts)
-        _same_layers(_layers(dst), before, what)
+        H.assert_same_map(before, dst, what)
     buf = torch.empty(M.MERGE_RESULT_BYTES + 8, dtype=torch.uint8, device="cuda")
     with pytest.raises(ValueError):
         dst.merge_from(src, I, out=buf[4:4 + M.MERGE_RESULT_BYTES])

@@ -66,7 +66,6 @@ def test_measurement_exchange_equals_one_mapper_batch(oracle_mod, hip_lib):
     all-gather): every rank's map == ONE mapper integrating the three cameras as a batch (bit for bit) == the oracle fed sequentially."""
     import torch
     from isaac_ros_nvblox_amd import mapper as M
-    from test_gpu_parity import compare_layer
     world, stride = 3, 1024
     cam = H.SMALL_CAM
     pg = M.default_params(weighting_mode=4, invalid_depth_decay_factor=0.8)
@@ -92,13 +91,10 @@ def test_measurement_exchange_equals_one_mapper_batch(oracle_mod, hip_lib):
         single.integrate_depth_batch([d for d, _ in fr], [T for _, T in fr], cam)
         for d, T in fr:
             o.integrate_depth(d, T, cam)
-    idx = single.block_indices(M.LAYER_TSDF)
-    bs, _ = single.get_blocks(M.LAYER_TSDF, idx)
+    batch = H.map_state(single, layers=(M.LAYER_TSDF,))
     for r in range(world):
-        assert np.array_equal(ranks[r].block_indices(M.LAYER_TSDF), idx)
-        br, _ = ranks[r].get_blocks(M.LAYER_TSDF, idx)
-        assert np.array_equal(br["distance"], bs["distance"]) and np.array_equal(br["weight"], bs["weight"])
-    n, _ = compare_layer(M, ranks[1], o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
+        H.assert_same_map(ranks[r], batch, "rank %d vs the one-mapper batch" % r)
+    n, _ = H.compare_layer(M, ranks[1], o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
     assert n > 300
     # the fused replicas run the rest of the path like any map: ESDF slices agree
     for m_ in ranks + [single]:
@@ -123,7 +119,6 @@ def test_pipelined_measurement_fusion_on_the_hip_mapper(oracle_mod, hip_lib):
     import torch
     from isaac_ros_nvblox_amd import mapper as M
     from isaac_ros_nvblox_amd.dist import PipelinedMeasurementFusion
-    from test_gpu_parity import compare_layer
     cam = H.SMALL_CAM
     pg = M.default_params(invalid_depth_decay_factor=0.8)
     stream = torch.cuda.Stream()
@@ -145,15 +140,6 @@ def test_pipelined_measurement_fusion_on_the_hip_mapper(oracle_mod, hip_lib):
         assert mf.drain(fused) == 1
         fused.integrate_color(prev[1], prev[2], cam); fused.update_esdf()
         assert mf.f.sent_bytes_total <= 1.25 * mf.f.used_bytes_total + 64 * 4112
-    idx = plain.block_indices(M.LAYER_TSDF)
-    assert np.array_equal(fused.block_indices(M.LAYER_TSDF), idx) and len(idx) > 300
-    for layer, fields in ((M.LAYER_TSDF, ("distance", "weight")), (M.LAYER_COLOR, ("r", "g", "b", "weight"))):
-        ia = plain.block_indices(layer)
-        assert np.array_equal(fused.block_indices(layer), ia)
-        a, _ = plain.get_blocks(layer, ia); b, _ = fused.get_blocks(layer, ia)
-        for f in fields:
-            assert np.array_equal(a[f], b[f]), (layer, f)
-    sa, aa = plain.esdf_slice_image(); sb, ab = fused.esdf_slice_image()
-    assert sa.shape == sb.shape and np.array_equal(sa, sb) and np.array_equal(aa, ab)
-    n, _ = compare_layer(M, fused, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
+    H.assert_same_map(plain, fused, "plain vs fused", layers=(M.LAYER_TSDF, M.LAYER_COLOR), min_blocks={M.LAYER_TSDF: 301}, slice=True)
+    n, _ = H.compare_layer(M, fused, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
     assert n > 300

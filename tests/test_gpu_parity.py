@@ -7,41 +7,10 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import TOL, compare_layer, compare_occupancy, make_pair
 from isaac_ros_nvblox_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-4
-
-
-def make_pair(oracle_mod, **kw):
-    from isaac_ros_nvblox_amd import mapper as M
-    pg = M.default_params(**kw)
-    po = H.copy_params(pg, oracle_mod.OrcParams)
-    return M, M.Mapper(pg, block_capacity=1 << 14), oracle_mod.OracleMap(po)
-
-
-def compare_layer(M, g, o, layer_g, layer_o, fields_exact=(), fields_tol=(), lsb_fields=()):
-    ig = g.block_indices(layer_g); io = o.block_indices(layer_o)
-    assert H.idx_set(ig) == H.idx_set(io), "block index sets differ: only-gpu %s only-oracle %s" % (
-        sorted(H.idx_set(ig) - H.idx_set(io))[:5], sorted(H.idx_set(io) - H.idx_set(ig))[:5])
-    assert np.array_equal(ig, io)            # both sorted lexicographically
-    bg, found = g.get_blocks(layer_g, ig)
-    assert found.all()
-    worst = 0.0
-    for k, idx in enumerate(io):
-        bo = o.get_block(layer_o, idx)
-        for f in fields_exact:
-            assert np.array_equal(bg[k][f], bo[f]), (f, idx)
-        for f in fields_tol:
-            d = np.abs(bg[k][f].astype(np.float64) - bo[f].astype(np.float64)).max()
-            worst = max(worst, d)
-            assert d <= TOL, (f, idx, d)
-        for f in lsb_fields:
-            d = np.abs(bg[k][f].astype(np.int32) - bo[f].astype(np.int32)).max()
-            assert d <= 1, (f, idx, d)
-    return len(io), worst
-
 
 @pytest.mark.parametrize("weighting_mode", [0, 1, 2, 3, 4, 5])     # all six WeightingFunctionType values (mapper_initialization.cpp:31-42)
 def test_tsdf_parity_small(oracle_mod, hip_lib, weighting_mode):
@@ -164,8 +133,7 @@ def test_esdf_parity(oracle_mod, hip_lib):
             ig, ag = g.esdf_slice_image(1000.0); io, ao = o.esdf_slice_image(1000.0)
             assert ig.shape == io.shape and np.array_equal(ag, ao)
             assert np.abs(ig - io).max() <= TOL
-    n, worst = compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF,
-                             fields_exact=("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"))
+    n, worst = compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF, fields_exact=H.ESDF_FIELDS)
     assert n > 10
     c = g.counters()
     assert c["esdf_blocks_swept"] > 0 and c["capacity_overflow"] == 0
@@ -289,16 +257,6 @@ def test_decay_and_clear_parity(oracle_mod, hip_lib):
     compare_layer(M, g, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
 
 
-def compare_occupancy(M, g, o, oracle_mod):
-    ig = g.block_indices(M.LAYER_OCCUPANCY); io = o.block_indices(oracle_mod.L_TSDF)
-    assert np.array_equal(ig, io), (len(ig), len(io))
-    bg, found = g.get_blocks(M.LAYER_OCCUPANCY, ig)
-    assert found.all()
-    for k, idx in enumerate(io):
-        assert np.array_equal(bg[k]["log_odds"], o.get_block(oracle_mod.L_TSDF, idx)["distance"]), idx     # adds and compares only: bit-exact
-    return len(io), bg
-
-
 def test_occupancy_mapper_parity(oracle_mod, hip_lib):
     """Mapper(voxel_size, memory_type, ProjectiveLayerType::kOccupancy): mapping_type static_occupancy (nvblox_base.yaml:9) and the
     dynamic mapper of the segmentation configuration (specializations/nvblox_segmentation.yaml:9-22): log-odds integration,
@@ -350,9 +308,7 @@ def test_occupancy_map_file_round_trip(hip_lib, tmp_path):
     a.update_esdf()
     p = tmp_path / "occ.nvbxmap"; a.save_map(p)
     b = M.Mapper(M.default_params(projective_layer_type=1), block_capacity=1 << 12); b.load_map(p)
-    ia = a.block_indices(M.LAYER_OCCUPANCY)
-    assert len(ia) > 50 and np.array_equal(ia, b.block_indices(M.LAYER_OCCUPANCY))
-    assert a.get_blocks(M.LAYER_OCCUPANCY, ia)[0].tobytes() == b.get_blocks(M.LAYER_OCCUPANCY, ia)[0].tobytes()
+    H.assert_same_map(a, b, "the loaded occupancy map", layers=(M.LAYER_OCCUPANCY,), min_blocks=51)
     t = M.Mapper(M.default_params(), block_capacity=1 << 12)
     with pytest.raises(RuntimeError):
         t.load_map(p)                                                            # a TSDF mapper cannot hold an occupancy layer
@@ -407,8 +363,7 @@ def test_mask_split_and_human_mapping_parity(oracle_mod, hip_lib):
 
 
 def compare_esdf3(M, g, o, oracle_mod):
-    n, _ = compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF,
-                         fields_exact=("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"))
+    n, _ = compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF, fields_exact=H.ESDF_FIELDS)
     return n
 
 

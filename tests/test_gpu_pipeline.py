@@ -10,27 +10,13 @@ from isaac_ros_nvblox_amd import synthetic as S
 pytestmark = pytest.mark.gpu
 
 
-def _equal_maps(M, a, b, tag=""):
-    for layer, fields in ((M.LAYER_TSDF, ("distance", "weight")), (M.LAYER_COLOR, ("r", "g", "b", "weight")),
-                          (M.LAYER_ESDF, ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"))):
-        ia = a.block_indices(layer); ib = b.block_indices(layer)
-        assert np.array_equal(ia, ib), (tag, layer, len(ia), len(ib))
-        if len(ia) == 0:
-            continue
-        ba, _ = a.get_blocks(layer, ia); bb, _ = b.get_blocks(layer, ia)
-        for f in fields:
-            assert np.array_equal(ba[f], bb[f]), (tag, layer, f)
-    sa, aa = a.esdf_slice_image(); sb, ab = b.esdf_slice_image()
-    assert sa.shape == sb.shape and np.array_equal(sa, sb) and np.array_equal(aa, ab)
-
-
 @pytest.mark.parametrize("staged", [True, False], ids=["staged", "zero_copy"])
 @pytest.mark.parametrize("cam", [H.SMALL_CAM, S.REPLICA_LIKE_CAM], ids=["160x120", "640x480"])
 def test_steady_state_pipeline_equals_classic_and_oracle(oracle_mod, hip_lib, cam, staged):
     """The bench's loop -- depth, colour, updateEsdf per frame -- for 12 frames: every frame but the first takes the pipelined path.  Both forms of
     the deferral: staged (the shipped default: a raw-pointer image is copied first) and zero-copy (opt-in) -- ADVICE r04."""
     from isaac_ros_nvblox_amd import mapper as M
-    from test_gpu_parity import compare_layer, TOL
+    from helpers import compare_layer, TOL
     pg = M.default_params(); po = H.copy_params(pg, oracle_mod.OrcParams)
     classic = M.Mapper(pg, block_capacity=1 << 14); piped = M.Mapper(pg, block_capacity=1 << 14); o = oracle_mod.OracleMap(po)
     classic.set_color_deferral(False)          # (a new mapper defers in the staged form: the reference order is asked for)
@@ -40,15 +26,14 @@ def test_steady_state_pipeline_equals_classic_and_oracle(oracle_mod, hip_lib, ca
             m_.integrate_depth(d, T, cam); m_.integrate_color(rgb, T, cam); m_.update_esdf()
         assert H.idx_set(piped.last_view()) == H.idx_set(o.last_view())
         if k in (0, 5, 11):                  # (a query flushes the pipeline: the frames in between run pipelined, undisturbed)
-            _equal_maps(M, classic, piped)
+            H.assert_same_map(classic, piped, slice=True)
             assert H.idx_set(piped.last_color_view()) == H.idx_set(o.last_color_view())
     compare_layer(M, piped, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
     compare_layer(M, piped, o, M.LAYER_COLOR, oracle_mod.L_COLOR, fields_tol=("weight",), lsb_fields=("r", "g", "b"))
     sg, _ = piped.esdf_slice_image(); so, _ = o.esdf_slice_image()
     assert sg.shape == so.shape and np.abs(sg - so).max() <= TOL
     piped.update_color_mesh(); classic.update_color_mesh()
-    ma, mb = piped.mesh(), classic.mesh()
-    assert ma.keys() == mb.keys() and all(np.array_equal(ma[k_]["triangles"], mb[k_]["triangles"]) and np.array_equal(ma[k_]["vertices"], mb[k_]["vertices"]) for k_ in ma)
+    H.assert_same_map(piped, classic, "after the mesh update", mesh=True)
     assert piped.counters()["capacity_overflow"] == 0
 
 
@@ -92,9 +77,9 @@ def test_deferred_calls_are_replayed_by_every_other_entry_point(oracle_mod, hip_
         if k == 12:
             b.set_color_deferral(True)
         if k % 4 == 1 or k == 15:
-            _equal_maps(M, a, b, "frame %d" % k)
+            H.assert_same_map(a, b, "frame %d" % k, slice=True)
     both(lambda m: m.update_esdf())
-    _equal_maps(M, a, b)
+    H.assert_same_map(a, b, slice=True)
     assert len(a.block_indices(M.LAYER_COLOR)) > 50
     # clear() with a frame held back: the frame is dropped with the map
     d, rgb, T = fr[0]
@@ -102,7 +87,7 @@ def test_deferred_calls_are_replayed_by_every_other_entry_point(oracle_mod, hip_
     both(lambda m: m.clear())
     assert b.num_blocks(M.LAYER_TSDF) == 0
     both(lambda m: m.integrate_depth(d, T, cam)); both(lambda m: m.integrate_color(rgb, T, cam)); both(lambda m: m.update_esdf())
-    _equal_maps(M, a, b)
+    H.assert_same_map(a, b, slice=True)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
@@ -144,9 +129,9 @@ def test_fused_colour_tsdf_launch_under_irregular_calls(oracle_mod, hip_lib, see
             sa, _ = a.esdf_slice_image(); sb, _ = b.esdf_slice_image()      # a query: flushes the pipeline
             assert np.array_equal(sa, sb), k
         if k % 9 == 8:
-            _equal_maps(M, a, b, "seed %d frame %d" % (seed, k))
+            H.assert_same_map(a, b, "seed %d frame %d" % (seed, k), slice=True)
     both(lambda m: m.update_esdf())
-    _equal_maps(M, a, b, "seed %d end" % seed)
+    H.assert_same_map(a, b, "seed %d end" % seed, slice=True)
     prof = b.profile()
     names = " ".join(prof.keys())
     assert "k_integrate_tsdf_color<Img, PixRgb8" in names and "k_integrate_tsdf_color<Img, PixBgra8" in names, names[:600]      # the fused launch has run, both encodings
@@ -183,13 +168,12 @@ def test_camera_batches_take_the_pipeline_too(oracle_mod, hip_lib, ncam):
         if k == 10:
             both(lambda m: m.decay_tsdf(True))
         if k in (2, 7, 13):
-            _equal_maps(M, a, b, "%d cameras step %d" % (ncam, k))
+            H.assert_same_map(a, b, "%d cameras step %d" % (ncam, k), slice=True)
             assert H.idx_set(a.last_view()) == H.idx_set(b.last_view()) and H.idx_set(a.last_color_view()) == H.idx_set(b.last_color_view())
     both(lambda m: m.update_esdf())
-    _equal_maps(M, a, b, "%d cameras end" % ncam)
+    H.assert_same_map(a, b, "%d cameras end" % ncam, slice=True)
     both(lambda m: m.update_color_mesh())
-    ma, mb = a.mesh(), b.mesh()
-    assert ma.keys() == mb.keys() and all(np.array_equal(ma[k_]["triangles"], mb[k_]["triangles"]) and np.array_equal(ma[k_]["vertices"], mb[k_]["vertices"]) for k_ in ma)
+    H.assert_same_map(a, b, "%d cameras, after the mesh update" % ncam, mesh=True)
     prof = b.profile()
     fused = sum(v["count"] for k_, v in prof.items() if "k_integrate_tsdf_color" in k_)
     assert fused >= 7, {k_: v["count"] for k_, v in prof.items()}          # (of 15 depth launches: the ones that followed a colour batch directly)
@@ -248,17 +232,9 @@ def test_dynamic_mapping_frame_keeps_the_pipeline(oracle_mod, hip_lib, cam):
                         assert torch.equal(x, y), i
                 kept = kept[-1:]
         n_dyn = int(kept[-1][0][0][1].sum().item())
-        _equal_maps(M, gs_a, gs_b, "static mapper")
-        ia, ib = gs_a.block_indices(M.LAYER_FREESPACE), gs_b.block_indices(M.LAYER_FREESPACE)
-        assert np.array_equal(ia, ib) and len(ia) > 50
-        fa, _ = gs_a.get_blocks(M.LAYER_FREESPACE, ia); fb, _ = gs_b.get_blocks(M.LAYER_FREESPACE, ia)
-        for f in ("last_occupied_timestamp_ms", "consecutive_occupancy_duration_ms", "is_high_confidence_freespace", "initialized"):
-            assert np.array_equal(fa[f], fb[f]), f
-        oa, ob = gd_a.block_indices(M.LAYER_OCCUPANCY), gd_b.block_indices(M.LAYER_OCCUPANCY)
-        assert np.array_equal(oa, ob)
-        if len(oa):
-            ba, _ = gd_a.get_blocks(M.LAYER_OCCUPANCY, oa); bb, _ = gd_b.get_blocks(M.LAYER_OCCUPANCY, oa)
-            assert np.array_equal(ba["log_odds"], bb["log_odds"])
+        H.assert_same_map(gs_a, gs_b, "static mapper", layers=(M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF, M.LAYER_FREESPACE),
+                          min_blocks={M.LAYER_FREESPACE: 51}, slice=True)
+        H.assert_same_map(gd_a, gd_b, "dynamic mapper", layers=(M.LAYER_OCCUPANCY,))
         prof = gs_b.profile()
         n_trace = sum(v["count"] for k_, v in prof.items() if "k_sphere_trace" in k_)
         n_mark = sum(v["count"] for k_, v in prof.items() if "k_mark_view" in k_)

@@ -10,6 +10,7 @@ import textwrap
 import numpy as np
 import pytest
 
+import helpers as H
 import query_independent as Q
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,16 +173,6 @@ def _frames(n, start=0):
     return list(S.sequence(n, start=start, n_frames_in_loop=200))
 
 
-def _map_state(m):
-    from isaac_ros_nvblox_amd import mapper as M
-    out = {}
-    for layer in (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF):
-        idx = m.block_indices(layer)
-        idx = idx[np.lexsort(idx.T[::-1])]
-        out[layer] = (idx, m.get_blocks(layer, idx)[0])
-    return out
-
-
 @pytest.mark.gpu
 def test_call_order_under_colour_deferral(hip_lib):
     import torch
@@ -214,9 +205,7 @@ def test_call_order_under_colour_deferral(hip_lib):
     for a, b in zip(qa, qb):
         assert np.array_equal(a, b)
     assert qa[2].sum() > 1000
-    sa, sc = _map_state(A), _map_state(C_)
-    for layer in sa:
-        assert np.array_equal(sa[layer][0], sc[layer][0]) and sa[layer][1].tobytes() == sc[layer][1].tobytes(), layer
+    H.assert_same_map(A, C_, "a query between pipelined frames")
     pa = {k: v["count"] for k, v in A.profile().items() if not k.startswith("_") and "query" not in k}
     pc = {k: v["count"] for k, v in C_.profile().items() if not k.startswith("_")}
     assert pa == pc, (pa, pc)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import align_independent as A
+import helpers as H
 import relocalize_independent as RI
 
 pytestmark = pytest.mark.gpu
@@ -389,7 +390,6 @@ def test_refusals_launch_nothing_and_leave_the_mapper_usable(room, frames):
 def test_relocalisation_leaves_the_map_and_held_back_work_alone(frames):
     """under colour deferral a colour frame and an updateEsdf are held back when the four calls run between two depth frames: the final layers are
     bit-identical to the same sequence without them"""
-    from isaac_ros_nvblox_amd import mapper as M
     d10, T_true, x, T0 = frames[10]
     poses = RI.lattice_poses(T0, **dict(RI.LATTICE, steps=(3, 3, 1, 3)))
 
@@ -409,15 +409,8 @@ def test_relocalisation_leaves_the_map_and_held_back_work_alone(frames):
                 results.append(_np(m.score_poses(d10, poses, cam=A.SMALL_CAM)[0])[:, 1].max())
                 results.append(m.relocalize_depth(d10, T0, A.SMALL_CAM, **RI.LATTICE).coarse.valid)
         m.flush(); m.synchronize()
-        out = {}
-        for layer in (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF):
-            idx = m.block_indices(layer)
-            idx = idx[np.lexsort(idx.T[::-1])]
-            out[layer] = (idx, m.get_blocks(layer, idx)[0])
-        return out, results
+        return H.map_state(m), results
     plain, _ = sequence(False)
     with_calls, results = sequence(True)
     assert len(results) == 6 and all(r > 100 for r in results), results
-    for layer in plain:
-        assert np.array_equal(plain[layer][0], with_calls[layer][0]), layer
-        assert plain[layer][1].tobytes() == with_calls[layer][1].tobytes(), layer
+    H.assert_same_map(plain, with_calls, "without and with the relocalisation calls")

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import helpers as H
 import render_cases as RC
 import render_independent as R
 
@@ -245,21 +246,6 @@ def test_wall_normals_agree_with_the_analytic_scene(hip_lib):
 
 
 # ---- 8
-def _state(m):
-    from isaac_ros_nvblox_amd import mapper as M
-    out = {}
-    for layer in (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF):
-        idx = m.block_indices(layer)
-        idx = idx[np.lexsort(idx.T[::-1])]
-        out[layer] = (idx, m.get_blocks(layer, idx)[0])
-    return out
-
-
-def _same_state(a, b):
-    for layer in a:
-        assert np.array_equal(a[layer][0], b[layer][0]) and a[layer][1].tobytes() == b[layer][1].tobytes(), layer
-
-
 @pytest.mark.gpu
 def test_held_back_work(hip_lib):
     from isaac_ros_nvblox_amd import mapper as M
@@ -289,8 +275,8 @@ def test_held_back_work(hip_lib):
     for m in (A, B, N):
         m.synchronize()
     assert np.array_equal(mid[0], mid[1]) and (mid[0] > 0).any()
-    sa, sb, sn = _state(A), _state(B), _state(N)
-    _same_state(sa, sn); _same_state(sb, sn)
+    never = H.map_state(N)
+    H.assert_same_map(A, never, "rendered without colour"); H.assert_same_map(B, never, "rendered with colour")
     launches = lambda m: {k: v["count"] for k, v in m.profile().items() if not k.startswith("_") and "k_render" not in k}      # noqa: E731
     assert launches(A) == launches(N), (launches(A), launches(N))
     assert sum(v["count"] for k, v in A.profile().items() if "k_render" in k) == 1

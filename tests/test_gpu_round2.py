@@ -5,12 +5,10 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import ESDF_FIELDS, TOL, compare_layer, make_pair
 from isaac_ros_nvblox_amd import synthetic as S
-from test_gpu_parity import TOL, compare_layer, make_pair
 
 pytestmark = pytest.mark.gpu
-
-ESDF_FIELDS = ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site")
 
 
 def test_two_esdf_updates_back_to_back(oracle_mod, hip_lib):
@@ -151,12 +149,7 @@ def test_nvblx_layer_cake_is_an_sqlite_database(oracle_mod, hip_lib, tmp_path):
     db.close()
     g2 = M.Mapper(M.default_params(), block_capacity=1 << 12)
     g2.load_map(path)
-    for layer, fields in ((M.LAYER_TSDF, ("distance", "weight")), (M.LAYER_COLOR, ("r", "g", "b", "weight")), (M.LAYER_ESDF, ESDF_FIELDS)):
-        ia, ib = g.block_indices(layer), g2.block_indices(layer)
-        assert np.array_equal(ia, ib)
-        ba, _ = g.get_blocks(layer, ia); bb, _ = g2.get_blocks(layer, ib)
-        for f in fields:
-            assert np.array_equal(ba[f], bb[f]), (layer, f)
+    H.assert_same_map(g, g2, "the loaded layer cake")
     # the loaded map keeps working: a further ESDF update gives the slice of the original
     g.update_esdf(); g2.update_esdf()
     sa, _ = g.esdf_slice_image(); sb, _ = g2.esdf_slice_image()

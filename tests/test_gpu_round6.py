@@ -13,28 +13,6 @@ from isaac_ros_nvblox_amd import synthetic as S
 pytestmark = pytest.mark.gpu
 
 
-def _layers(M, m, layers):
-    out = {}
-    for name, lay in layers:
-        idx = m.block_indices(lay)
-        blk, _ = m.get_blocks(lay, idx)
-        out[name] = (idx, blk)
-    return out
-
-
-def _same(M, a, b, layers, tag):
-    la, lb = _layers(M, a, layers), _layers(M, b, layers)
-    for name in la:
-        ia, ba = la[name]; ib, bb = lb[name]
-        assert np.array_equal(ia, ib), (tag, name, len(ia), len(ib))
-        assert ba.tobytes() == bb.tobytes(), (tag, name)
-
-
-def _short(name):
-    import bench
-    return bench.short(name)
-
-
 @pytest.mark.parametrize("cam", [H.SMALL_CAM, S.REPLICA_LIKE_CAM], ids=["160x120", "640x480"])
 def test_depth_pair_equals_the_two_calls_and_the_checker(oracle_mod, hip_lib, cam):
     """The dynamic-mapping frame as bench.py --workload decay drives it: front end, static mapper (TSDF + freespace, colour, ESDF), dynamic mapper
@@ -91,10 +69,10 @@ def test_depth_pair_equals_the_two_calls_and_the_checker(oracle_mod, hip_lib, ca
                 assert img_a.shape == img_b.shape and np.array_equal(img_a, img_b), i
         for m_ in (sa, sb, da, db):
             m_.synchronize()
-        static_layers = [("tsdf", M.LAYER_TSDF), ("color", M.LAYER_COLOR), ("esdf", M.LAYER_ESDF), ("freespace", M.LAYER_FREESPACE)]
-        dyn_layers = [("occupancy", M.LAYER_OCCUPANCY), ("esdf", M.LAYER_ESDF)]
-        _same(M, sa, sb, static_layers, "static mapper, pair vs two calls")
-        _same(M, da, db, dyn_layers, "dynamic mapper, pair vs two calls")
+        static_layers = (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF, M.LAYER_FREESPACE)
+        dyn_layers = (M.LAYER_OCCUPANCY, M.LAYER_ESDF)
+        H.assert_same_map(sa, sb, "static mapper, pair vs two calls", layers=static_layers)
+        H.assert_same_map(da, db, "dynamic mapper, pair vs two calls", layers=dyn_layers)
         # ... and the checker: block sets equal, TSDF / occupancy values within the contract (observed: 0)
         for g, o, lay_g, lay_o in ((sa, os_, M.LAYER_TSDF, oracle_mod.L_TSDF), (da, od, M.LAYER_OCCUPANCY, oracle_mod.L_TSDF)):
             ig = g.block_indices(lay_g); io = o.block_indices(lay_o)
@@ -108,10 +86,10 @@ def test_depth_pair_equals_the_two_calls_and_the_checker(oracle_mod, hip_lib, ca
         # the pair really shared launches: pair kernels in the first mapper's profile, no view-marking launch of its own on most frames
         names = {}
         for k_, v in sa.profile().items():
-            names[_short(k_)] = names.get(_short(k_), 0) + v["count"]
+            names[H.short(k_)] = names.get(H.short(k_), 0) + v["count"]
         assert names.get("k_mark_view_pair", 0) >= n_frames - 1 and names.get("k_integrate_tsdf_color_pair", 0) >= n_frames - 1, names
         assert names.get("k_mark_view", 0) <= 1, names
-        dn = {_short(k_) for k_ in da.profile()}
+        dn = {H.short(k_) for k_ in da.profile()}
         assert "k_mark_view" not in dn and "k_integrate_tsdf" not in dn, dn
         for m_ in (sa, sb, da, db):
             m_.close()
@@ -136,9 +114,9 @@ def test_depth_pair_falls_back_to_the_two_calls(oracle_mod, hip_lib):
         b.update_esdf(); rb.update_esdf()
     for m_ in (a, b, ra, rb):
         m_.synchronize()
-    lay = [("tsdf", M.LAYER_TSDF), ("color", M.LAYER_COLOR), ("esdf", M.LAYER_ESDF)]
-    _same(M, a, ra, lay, "fallback a"); _same(M, b, rb, lay, "fallback b")
-    assert not ({"k_mark_view_pair", "k_integrate_tsdf_color_pair"} & {_short(k_) for k_ in a.profile()}), list(a.profile())
+    lay = (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF)
+    H.assert_same_map(a, ra, "fallback a", layers=lay); H.assert_same_map(b, rb, "fallback b", layers=lay)
+    assert not ({"k_mark_view_pair", "k_integrate_tsdf_color_pair"} & {H.short(k_) for k_ in a.profile()}), list(a.profile())
     d_dev = torch.from_numpy(fr[0][0]).cuda(); Tm = np.ascontiguousarray(np.asarray(fr[0][2], np.float32).reshape(4, 4))
     k = M.Camera(*[float(v) for v in cam[:4]], int(cam[4]), int(cam[5]))
     assert hip_lib.nvbx_integrate_depth_pair(a._h, C.c_void_p(d_dev.data_ptr()), a._h, C.c_void_p(d_dev.data_ptr()), cam[5], cam[4], Tm.ctypes.data_as(C.c_void_p), C.byref(k)) < 0
@@ -160,8 +138,8 @@ def test_depth_pair_in_randomised_call_sequences(oracle_mod, hip_lib, seed):
     rng = np.random.default_rng(100 + seed)
     ps = M.default_params(tsdf_decay_factor=0.8, tsdf_decayed_weight_threshold=0.3)
     pd = M.default_params(projective_layer_type=1, free_region_decay_probability=0.6, occupied_region_decay_probability=0.35)
-    lay_s = [("tsdf", M.LAYER_TSDF), ("color", M.LAYER_COLOR), ("esdf", M.LAYER_ESDF)]
-    lay_d = [("occupancy", M.LAYER_OCCUPANCY), ("esdf", M.LAYER_ESDF)]
+    lay_s = (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF)
+    lay_d = (M.LAYER_OCCUPANCY, M.LAYER_ESDF)
     with torch.cuda.stream(stream):
         sa = M.Mapper(ps, block_capacity=1 << 13, stream=stream.cuda_stream); da = M.Mapper(pd, block_capacity=1 << 12, stream=stream.cuda_stream)
         sb = M.Mapper(ps, block_capacity=1 << 13, stream=stream.cuda_stream); db = M.Mapper(pd, block_capacity=1 << 12, stream=stream.cuda_stream)
@@ -201,10 +179,10 @@ def test_depth_pair_in_randomised_call_sequences(oracle_mod, hip_lib, seed):
                 on = bool(rng.integers(2))
                 sa.set_color_deferral(on, staged=True); sb.set_color_deferral(on, staged=True)
             if rng.random() < 0.15:
-                _same(M, sa, sb, lay_s, ("static", seed, step)); _same(M, da, db, lay_d, ("dynamic", seed, step))
+                H.assert_same_map(sa, sb, ("static", seed, step), layers=lay_s); H.assert_same_map(da, db, ("dynamic", seed, step), layers=lay_d)
         for m_ in (sa, sb, da, db):
             m_.synchronize()
-        _same(M, sa, sb, lay_s, ("static, end", seed)); _same(M, da, db, lay_d, ("dynamic, end", seed))
+        H.assert_same_map(sa, sb, ("static, end", seed), layers=lay_s); H.assert_same_map(da, db, ("dynamic, end", seed), layers=lay_d)
         assert n_pair > 20 and sa.counters()["capacity_overflow"] == 0
         for m_ in (sa, sb, da, db):
             m_.close()
@@ -216,8 +194,6 @@ def test_a_view_of_two_thousand_blocks_takes_the_pipeline_like_the_room(oracle_m
     on the way (4 096 -> 16 384 blocks) with work held back.  Eight frames of depth + colour + updateEsdf on a default mapper (two launches per frame) and on one in
     classic order: the same map bit for bit, and the checker's."""
     from isaac_ros_nvblox_amd import mapper as M
-    from test_gpu_parity import compare_layer, TOL
-    from test_gpu_sequences import check_all
     cam = S.REPLICA_LIKE_CAM
     hall = S.Scene(room_min=(-7.0, -6.0, 0.0), room_max=(7.0, 6.0, 3.0))
     pg = M.default_params(); po = H.copy_params(pg, oracle_mod.OrcParams)
@@ -232,12 +208,7 @@ def test_a_view_of_two_thousand_blocks_takes_the_pipeline_like_the_room(oracle_m
         n_view.append(len(np.asarray(o.last_view()).reshape(-1, 3)))
         assert H.idx_set(piped.last_view()) == H.idx_set(o.last_view())
     assert min(n_view) > 1500, n_view
-    for layer, fields in ((M.LAYER_TSDF, ("distance", "weight")), (M.LAYER_COLOR, ("r", "g", "b", "weight"))):
-        ia = classic.block_indices(layer); ib = piped.block_indices(layer)
-        assert np.array_equal(ia, ib)
-        ba, _ = classic.get_blocks(layer, ia); bb, _ = piped.get_blocks(layer, ia)
-        for f in fields:
-            assert np.array_equal(ba[f], bb[f]), (layer, f)
+    H.assert_same_map(classic, piped, "classic vs pipelined", layers=(M.LAYER_TSDF, M.LAYER_COLOR))
     piped.update_color_mesh(full=True); o.update_mesh(full=True)
-    n_tri = check_all(M, oracle_mod, piped, o)
+    n_tri = H.check_all(M, oracle_mod, piped, o)
     assert n_tri > 50000 and piped.counters()["capacity_overflow"] == 0 and piped.capacity >= 1 << 13

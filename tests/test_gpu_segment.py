@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import feature_match_independent as FM
+import helpers as H
 import segment_independent as SI
 
 pytestmark = pytest.mark.gpu
@@ -300,29 +301,15 @@ def test_both_calls_leave_the_map_bit_identical(feature_map, noise27):
     M, _ = _mods()
     m, Cn = feature_map
 
-    def snapshot():
-        out = {}
-        for name, layer in (("tsdf", M.LAYER_TSDF), ("color", M.LAYER_COLOR), ("esdf", M.LAYER_ESDF), ("mesh", M.LAYER_MESH), ("feature", M.LAYER_FEATURE)):
-            idx = m.block_indices(layer)
-            out[name + "_idx"] = idx
-            if name in ("tsdf", "color") and len(idx):
-                out[name] = m.get_blocks(layer, idx)[0].view(np.uint8)
-        f, w, found = m.feature_blocks(out["tsdf_idx"])
-        out["feat"] = f.view(np.uint16); out["feat_w"] = w.view(np.uint32); out["feat_found"] = found
-        c = m.counters()
-        out["counters"] = np.array([c[k] for k in sorted(c)])
-        return out
-    a = snapshot()
-    assert len(a["tsdf_idx"]) > 100 and len(a["color_idx"]) > 50 and len(a["feature_idx"]) > 50
+    layers = (M.LAYER_TSDF, M.LAYER_COLOR, M.LAYER_ESDF, M.LAYER_FEATURE)
+    before = H.map_state(m, layers), m.block_indices(M.LAYER_MESH), m.counters()
     bidx, lab, sc, _ = noise27
     for conn in (6, 26):
         m.label_components(bidx, lab, sc, conn, 2)
         for metric in ("dot", "cosine"):
             m.segment_features(_queries(Cn, 5), metric, 1.0, 0.0, conn, 2)
-    b = snapshot()
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
+    H.assert_same_map(before[0], m, "before and after the calls", min_blocks={M.LAYER_TSDF: 101, M.LAYER_COLOR: 51, M.LAYER_FEATURE: 51})
+    assert np.array_equal(before[1], m.block_indices(M.LAYER_MESH)) and before[2] == m.counters()
 
 
 def _thresholds(best, lab, bound, Q):

@@ -7,34 +7,10 @@ import pytest
 
 import helpers as H
 from isaac_ros_nvblox_amd import synthetic as S
-from test_gpu_parity import make_pair, compare_layer, TOL
+from helpers import TOL, check_all, compare_layer, make_pair
 
 pytestmark = pytest.mark.gpu
 CAM = H.SMALL_CAM
-
-
-def check_all(M, oracle_mod, g, o, mesh=True):
-    compare_layer(M, g, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
-    compare_layer(M, g, o, M.LAYER_COLOR, oracle_mod.L_COLOR, fields_tol=("weight",), lsb_fields=("r", "g", "b"))
-    assert H.idx_set(g.block_indices(M.LAYER_ESDF)) == H.idx_set(o.block_indices(oracle_mod.L_ESDF))
-    if len(o.block_indices(oracle_mod.L_ESDF)):
-        sg, ag = g.esdf_slice_image(); so, ao = o.esdf_slice_image()
-        assert sg.shape == so.shape and np.abs(sg - so).max() <= TOL and np.allclose(ag, ao, atol=1e-6)
-    if mesh:
-        mg = g.mesh()
-        n_tri = 0
-        for idx in o.block_indices(oracle_mod.L_TSDF):
-            mo = o.mesh_block(idx)
-            a = mg.get(tuple(idx))
-            if a is None:
-                assert mo is None or len(mo["triangles"]) == 0, idx
-                continue
-            assert np.array_equal(a["triangles"], mo["triangles"]), idx
-            if len(mo["vertices"]):
-                assert np.abs(a["vertices"] - mo["vertices"]).max() <= TOL
-            n_tri += len(mo["triangles"])
-        return n_tri
-    return 0
 
 
 @pytest.mark.parametrize("deferral", [False, True], ids=["classic", "colour-deferral"])

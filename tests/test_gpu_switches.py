@@ -10,16 +10,15 @@ import pytest
 
 import helpers as H
 from esdf_independent import numpy_propagation
+from helpers import ESDF_FIELDS, TOL, compare_layer, make_pair
 from isaac_ros_nvblox_amd import synthetic as S
-from test_gpu_parity import TOL, compare_layer, make_pair
 
 pytestmark = pytest.mark.gpu
 
 
 def tsdf_map(g, M):
-    idx = g.block_indices(M.LAYER_TSDF)
-    b, found = g.get_blocks(M.LAYER_TSDF, idx)
-    return {tuple(i): b[k].copy() for k, i in enumerate(idx.tolist())}
+    idx, b = H.map_state(g, layers=(M.LAYER_TSDF,))["layers"][M.LAYER_TSDF]
+    return {tuple(i): b[k] for k, i in enumerate(idx.tolist())}
 
 
 def maps_differ(a, b, field="weight"):
@@ -129,8 +128,7 @@ def test_esdf_exact_transform_vs_iterative_propagation(oracle_mod, hip_lib, prop
             g.update_esdf(); o.update_esdf()
             ig, ag = g.esdf_slice_image(1000.0); io, ao = o.esdf_slice_image(1000.0)
             assert ig.shape == io.shape and np.array_equal(ag, ao) and np.abs(ig - io).max() <= TOL
-    n, worst = compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF,
-                             fields_exact=("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"))
+    n, worst = compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF, fields_exact=ESDF_FIELDS)
     assert n > 10
     # independent check of the definition itself (numpy): dense site / domain images from the GPU's own ESDF layer
     idx = g.block_indices(M.LAYER_ESDF)
@@ -220,8 +218,7 @@ def test_depth_sampling_and_site_rule_switches(oracle_mod, hip_lib, kw):
         g.integrate_depth(d, T, H.SMALL_CAM); o.integrate_depth(d, T, H.SMALL_CAM)
     g.update_esdf(); o.update_esdf()
     compare_layer(M, g, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
-    n, _ = compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF,
-                         fields_exact=("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site"))
+    n, _ = compare_layer(M, g, o, M.LAYER_ESDF, oracle_mod.L_ESDF, fields_exact=ESDF_FIELDS)
     assert n > 10
 
 
@@ -235,8 +232,7 @@ def test_plain_instantiation_equals_the_general_kernel(oracle_mod, hip_lib):
     for k, (d, rgb, T) in enumerate(H.frames(4, H.SMALL_CAM, color=False, stride=9)):
         d = d.copy(); d[10 + 5 * k:30 + 5 * k, 20:60] = 0.0
         gp.integrate_depth(d, T, H.SMALL_CAM); gg.integrate_depth(d, T, H.SMALL_CAM)
-    a, b = tsdf_map(gp, M), tsdf_map(gg, M)
-    assert len(a) > 100 and not maps_differ(a, b)
+    H.assert_same_map(gp, gg, "camera: plain vs general kernel", layers=(M.LAYER_TSDF,), min_blocks=101)
     lidar = (256, 16, 0.1, -np.deg2rad(15.0), np.deg2rad(15.0))
     kw = dict(voxel_size=0.1, lidar_max_integration_distance_m=30.0, raycast_subsampling_factor=2)
     gp = M.Mapper(M.default_params(**kw), block_capacity=1 << 16)
@@ -246,5 +242,4 @@ def test_plain_instantiation_equals_the_general_kernel(oracle_mod, hip_lib):
         T = S.lidar_pose(i * 7)
         img = S.render_lidar(sc, T, lidar, max_range=40.0)
         gp.integrate_lidar_depth(img, T, lidar); gg.integrate_lidar_depth(img, T, lidar)
-    a, b = tsdf_map(gp, M), tsdf_map(gg, M)
-    assert len(a) > 1000 and not maps_differ(a, b)
+    H.assert_same_map(gp, gg, "LiDAR: plain vs general kernel", layers=(M.LAYER_TSDF,), min_blocks=1001)

@@ -64,7 +64,7 @@ def test_oracle_ground_candidates_and_plane_on_the_analytic_floor(oracle_mod):
 
 @pytest.mark.gpu
 def test_ground_plane_parity(oracle_mod, hip_lib):
-    from test_gpu_parity import make_pair
+    from helpers import make_pair
     M, g, o = make_pair(oracle_mod, max_integration_distance_m=5.0)
     _feed(g); _feed(o)
     for band in ((-0.15, 0.15), (-10.0, 10.0), (0.3, 1.2)):
@@ -96,10 +96,10 @@ def test_esdf_slice_follows_the_ground_plane(oracle_mod, hip_lib):
     [esdf_slice_min_height, esdf_slice_max_height] of the same heights -- identical ESDF layer; (2) over a tilted plane every column looks at its own
     band: HIP == checker on every ESDF voxel over incremental updates with a decay in between, and the layer differs from the fixed-height one."""
     from isaac_ros_nvblox_amd import mapper as M
-    from test_gpu_parity import compare_layer
+    from helpers import compare_layer
     cam = H.SMALL_CAM
     fr = H.frames(10, cam, stride=9, color=False)
-    fields = ("squared_distance_vox", "parent_direction", "is_inside", "observed", "is_site")
+    fields = H.ESDF_FIELDS
     fixed = M.Mapper(M.default_params(esdf_slice_min_height=0.09, esdf_slice_max_height=0.65), block_capacity=1 << 13)
     flat = M.Mapper(_plane_params(M, (0.0, 0.0, 1.0, 0.0), 0.09, 0.56), block_capacity=1 << 13)
     tilt = (0.06, -0.04, 1.0, -0.12)

@@ -330,7 +330,7 @@ def test_lidar_depth_then_camera_colour_parity(oracle_mod, hip_lib):
     colour integrator's per-block band flags stale and the colour launch repairs them from the TSDF -- same colour layer as the
     oracle; a second colour frame (flags repaired) and a camera depth frame in between (flags kept exact) as well."""
     from isaac_ros_nvblox_amd import mapper as M
-    from test_gpu_parity import make_pair, compare_layer
+    from helpers import make_pair, compare_layer
     lidar = (256, 32, 0.1, -np.deg2rad(30.0), np.deg2rad(30.0))
     Mm, g, o = make_pair(oracle_mod, lidar_max_integration_distance_m=8.0, raycast_subsampling_factor=2)
     sc = S.Scene()

@@ -188,6 +188,7 @@ static bool defer_color(nvbx_mapper* m, ColorEnc enc, int32_t n, const void* con
   }
   if (n_copy) {
     const int32_t wgi = (int32_t)std::min<int64_t>(256, std::max<int64_t>(1, (int64_t)(bytes >> 4) / 256 + 1));      // 640x480 rgb8: 226 workgroups, one 16-B access per thread
+    (void)hipGetLastError();      // (what an earlier call of this thread left behind is not this launch's; a device fault is sticky and still shows below)
     NVBX_LAUNCH(m, k_stage_color, dim3((unsigned)(wgi * n_copy)), dim3(256), sp, (int64_t)bytes, wgi);
     if (hipGetLastError() != hipSuccess) { undo(); set_error("colour staging copy"); *rc_out = NVBX_E_DEVICE; return true; }
   }

@@ -70,12 +70,20 @@ static int pool_max() { const char* e = getenv("NVBX_FRAME_POOL_MAX"); return e 
 // caller holds g_mu (a dead owner's words are not read)
 static bool fence_reached(const FrameFence& f) { return f.st->dead || (int32_t)(__atomic_load_n(f.progress, __ATOMIC_ACQUIRE) - f.seq) >= 0; }
 static void recycle_event(int device, hipEvent_t ev) { g_event_pool[device].push_back(ev); }
+// Whatever hipEventQuery answers is dealt with here ("not yet": pending; any other answer: reached, or an error we cannot wait out).  The runtime
+// keeps an error answer as the calling thread's last error until somebody reads it (some releases keep hipErrorNotReady too), and the next
+// hipGetLastError() behind a launch would report a launch that went well as failed -- so it is taken back here, as everywhere in this file.
+static bool event_pending(hipEvent_t ev) {
+  const hipError_t e = hipEventQuery(ev);
+  if (e != hipSuccess) (void)hipGetLastError();
+  return e == hipErrorNotReady;
+}
 // drop the fences and events that have been reached; true = none left (any writer may have the frame).  Caller holds g_mu.
 static bool cooled(PoolFrame* f) {
   f->fences.erase(std::remove_if(f->fences.begin(), f->fences.end(), [](const FrameFence& x) { return fence_reached(x); }), f->fences.end());
   if (!f->events.empty()) {
     f->events.erase(std::remove_if(f->events.begin(), f->events.end(), [f](const EventFence& x) {
-                      if (hipEventQuery(x.ev) == hipErrorNotReady) return false;        // (any other answer: reached, or an error we cannot wait out)
+                      if (event_pending(x.ev)) return false;
                       recycle_event(f->device, x.ev); return true; }), f->events.end());
   }
   return f->fences.empty() && f->events.empty();
@@ -218,7 +226,7 @@ extern "C" int nvbx_frame_acquire(int device, size_t bytes, void* writer_stream,
       for (;;) {
         { std::lock_guard<std::mutex> lk(g_mu);
           bool pending = false;
-          for (PoolFrame* f : g_frames) if (f == wait_frame && f->refs == 0) for (const EventFence& x : f->events) pending = pending || hipEventQuery(x.ev) == hipErrorNotReady;
+          for (PoolFrame* f : g_frames) if (f == wait_frame && f->refs == 0) for (const EventFence& x : f->events) pending = pending || event_pending(x.ev);
           if (!pending) break; }
         std::this_thread::yield();
       }

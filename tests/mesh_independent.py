@@ -1,4 +1,5 @@
-"""Table-free model of the mesh integrator's rules, for tests/test_independent_checks.py (numpy; shares no code with the checker or the product).
+"""Table-free model of the mesh integrator's rules, for tests/test_independent_checks.py and the drawn-field suites (tests/mesh_cases.py,
+tests/test_mesh_model.py, tests/test_gpu_mesh_drawn.py); numpy, shares no code with the checker or the product.
 
 What a marching-cubes mesh of one block must be, whatever the triangle table: one vertex on every lattice edge whose end voxels differ in sign and that
 borders a cube of the block with eight observed corners; the vertex sits at the linear zero crossing; vertices in ascending edge order; every triangle
@@ -69,6 +70,75 @@ def expected_block(i, lo, d, w, has, col, cw, vs, min_weight):
         return np.zeros(0, np.int64), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8), active
     eids = np.concatenate(eids); order = np.argsort(eids)
     return eids[order], np.concatenate(pos)[order], np.concatenate(cols)[order], active
+
+
+def lattice(i, lo, a):
+    """the 9^3 corner lattice of block i (own voxels + the first plane of the +x/+y/+z neighbours) out of a dense array of dense_layers"""
+    o = (np.asarray(i) - lo) * 8
+    return a[tuple(slice(int(q), int(q) + 9) for q in o)]
+
+
+def edge_cubes(eids):
+    """-> (cubes int64 [..., 4, 3], inside bool [..., 4]): the up to four cubes of the block around each lattice edge id -- the edge (l, axis) borders
+    the cubes l - {0, 1} in the two other axes -- and which of them lie in 0 .. 7"""
+    eids = np.asarray(eids, np.int64)
+    axis = eids % 3; li = eids // 3
+    l = np.stack([li // 81, (li // 9) % 9, li % 9], -1)                          # [..., 3]
+    step = np.array([[[0, 0, 0], [0, 1, 0], [0, 0, 1], [0, 1, 1]],               # axis 0: back off in y, z
+                     [[0, 0, 0], [1, 0, 0], [0, 0, 1], [1, 0, 1]],               # axis 1: in x, z
+                     [[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0]]], np.int64)    # axis 2: in x, y
+    c = l[..., None, :] - step[axis]
+    return c, ((c >= 0) & (c <= 7)).all(-1)
+
+
+def triangle_edge_cubes(eids, triangles, active):
+    """Where a triangle lives, from topology alone (its vertices may sit on lattice corners, or the whole triangle in a cube face, where a
+    centroid says nothing): the three lattice edges of its vertices have at least one ACTIVE cube of the block in common.
+    eids: the model's ascending edge ids (vertex id -> edge id); -> (per triangle: has such a cube [nt], the union of those cubes bool [8,8,8])."""
+    tri = np.asarray(triangles, np.int64).reshape(-1, 3)
+    seen = np.zeros((8, 8, 8), bool)
+    if len(tri) == 0:
+        return np.zeros(0, bool), seen
+    c, inside = edge_cubes(np.asarray(eids, np.int64)[tri])                      # [nt, 3 edges, 4, 3], [nt, 3, 4]
+    key = np.where(inside, (c[..., 0] * 8 + c[..., 1]) * 8 + c[..., 2], -1)      # [nt, 3, 4]
+    k0 = key[:, 0, :]                                                            # the candidates: the first edge's cubes
+    common = (k0 >= 0) & (k0[:, :, None] == key[:, 1, None, :]).any(-1) & (k0[:, :, None] == key[:, 2, None, :]).any(-1)
+    common &= active.reshape(-1)[np.maximum(k0, 0)]
+    seen.reshape(-1)[k0[common]] = True
+    return common.any(1), seen
+
+
+def expected_normals(vertices, triangles, rule, voxel_size):
+    """float64 normals of welded vertices from the mesh's own float32 vertices.  Rule 0: the first triangle that references the vertex; rule 1: the
+    sum of the unnormalised normals of the block's triangles that reference it.  -> (unit normals [n, 3] (0 where the sum is 0), mask [n]: the
+    unnormalised length is at least 1e-3 voxel_size^2 -- below that the direction is rounding noise of the float32 positions)."""
+    v = np.asarray(vertices, np.float64); tri = np.asarray(triangles, np.int64).reshape(-1, 3)
+    nv, nt = len(v), len(tri)
+    fn = np.cross(v[tri[:, 1]] - v[tri[:, 0]], v[tri[:, 2]] - v[tri[:, 0]]) if nt else np.zeros((0, 3))
+    if rule == 0:
+        first = np.full(nv, nt, np.int64)
+        np.minimum.at(first, tri.reshape(-1), np.repeat(np.arange(nt), 3))
+        assert (first < nt).all(), "a vertex no triangle references"
+        acc = fn[first]
+    else:
+        acc = np.zeros((nv, 3))
+        for q in range(3):                       # (a triangle's three vertices lie on three different edges: none is named twice)
+            np.add.at(acc, tri[:, q], fn)
+    ln = np.linalg.norm(acc, axis=1)
+    unit = np.divide(acc, ln[:, None], out=np.zeros_like(acc), where=ln[:, None] > 0)
+    return unit, ln >= 1e-3 * float(voxel_size) ** 2
+
+
+CORNERS = ((0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1))
+
+
+def cube_cases(neg, active):
+    """histogram [256] of the sign patterns (bit c = corner c negative, the usual marching-cubes corner order) of the active cubes; neg: bool
+    [9,9,9] over the block's corner lattice"""
+    case = np.zeros((8, 8, 8), np.int64)
+    for c, (dx, dy, dz) in enumerate(CORNERS):
+        case |= neg[dx:dx + 8, dy:dy + 8, dz:dz + 8].astype(np.int64) << c
+    return np.bincount(case[active], minlength=256)
 
 
 def triangle_cubes(i, v, tri, vs):

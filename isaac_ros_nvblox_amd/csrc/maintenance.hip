@@ -199,7 +199,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 // `srec`: window record of the next ESDF update.  An ESDF block that is dropped takes its sites with it: the distances of
 // every voxel within the search radius of those sites are stale, so the block joins the next update's window (the
 // distance transform is exact on any window that contains every change of the site set).
-__global__ __launch_bounds__(512) void k_clear_outside(DMap m, float cx, float cy, float cz, float r2, float bs, int32_t srec, int32_t esdf3d, int32_t* cleared_idx) {
+// A dropped projective block of the ESDF z band [bz_lo, bz_hi] whose column's ESDF block (bx, by, bz_out) STAYS takes that column's sites with
+// it: the ESDF block is flagged for a re-mark and put on the ESDF work list, as k_decay's dead-block branch does (2-D ESDF only: in 3-D mode the
+// ESDF voxels live in the dropped slot itself).  Whether the ESDF block stays is this thread's own centre test of it, not that slot's flags --
+// another workgroup may be freeing the slot in this launch, and a freed slot must end up neither flagged nor listed.  The lookup reads the
+// table as it was before the launch: the rebuild follows it.
+__global__ __launch_bounds__(512) void k_clear_outside(DMap m, float cx, float cy, float cz, float r2, float bs, int32_t srec, int32_t esdf3d, int32_t* cleared_idx,
+                                                       int32_t bz_lo, int32_t bz_hi, int32_t bz_out) {
   // Two steps per 512 slots: every thread tests ONE slot (coalesced flag / index loads: on a large map almost every block stays, and a
   // workgroup per slot spent two dependent round trips on each -- 92 us for 146 k blocks), the few slots outside are collected in LDS,
   // then the workgroup clears those one after the other with all its threads.
@@ -236,6 +242,17 @@ __global__ __launch_bounds__(512) void k_clear_outside(DMap m, float cx, float c
       if (flags & F_TSDF) {                              // Mapper::getClearedBlocks (layer_publishing.cpp:716)
         const int32_t p = atomicAdd(&m.counters[C_CLEARED], 1);
         if (p < (int32_t)m.capacity) { cleared_idx[3 * p] = m.slot_index[3 * slot]; cleared_idx[3 * p + 1] = m.slot_index[3 * slot + 1]; cleared_idx[3 * p + 2] = m.slot_index[3 * slot + 2]; }
+        const int32_t bx = m.slot_index[3 * slot], by = m.slot_index[3 * slot + 1], bz = m.slot_index[3 * slot + 2];
+        if (!esdf3d && bz >= bz_lo && bz <= bz_hi) {
+          const float ex = ((float)bx * bs + bs * 0.5f) - cx, ey = ((float)by * bs + bs * 0.5f) - cy, ez = ((float)bz_out * bs + bs * 0.5f) - cz;
+          if (!(((ex * ex + ey * ey) + ez * ez) > r2)) {       // the column's ESDF block, if there is one, stays
+            const uint32_t es = any_slot(m, bx, by, bz_out);
+            if (slot_ok(es) && (m.slot_flags[es] & F_ESDF)) {
+              const uint32_t eold = atomicOr(&m.slot_flags[es], F_ESDF_REMARK | F_DIRTY_ESDF);
+              if (!(eold & F_DIRTY_ESDF)) list_append(m, S_LIST_ESDF_DIRTY, (int32_t)es);
+            }
+          }
+        }
       }
       if ((flags & F_ESDF) && esdf3d) {                  // 3-D ESDF: the dropped block joins the next update's 3-D window
         const int32_t bx = m.slot_index[3 * slot], by = m.slot_index[3 * slot + 1], bz = m.slot_index[3 * slot + 2];
@@ -428,9 +445,12 @@ extern "C" int nvbx_clear_outside_radius(nvbx_mapper* m, const float center[3], 
   NVBX_HIP(hipSetDevice(m->device));
   if (m->join_side()) return NVBX_E_DEVICE;
   if (m->undo_marks()) return NVBX_E_DEVICE;          // deallocates: unresolved marking passes are taken back first
+  if (m->begin_dirtying()) return NVBX_E_DEVICE;      // (a surviving ESDF block whose column lost a projective block joins the ESDF work list)
   const int grid = (int)std::min<int64_t>((m->capacity + 511) / 512, 2048);          // 512 slots per workgroup iteration
+  EsdfArgs ea = m->make_esdf_args();
+  if (ea.plane_on) { ea.bz_lo = INT32_MIN + 1; ea.bz_hi = INT32_MAX; }      // ground-plane mode: a dropped block of ANY height has its column re-marked, as decay does
   NVBX_LAUNCH(m, k_clear_outside, dim3(grid), dim3(512), m->d, center[0], center[1], center[2], radius * radius, m->p.voxel_size * 8.0f,
-              (int32_t)(S_ESDF_REC + (int)(m->esdf_epoch & 1)), (int32_t)(m->p.esdf_mode == 1), m->cleared_idx);
+              (int32_t)(S_ESDF_REC + (int)(m->esdf_epoch & 1)), (int32_t)(m->p.esdf_mode == 1), m->cleared_idx, ea.bz_lo, ea.bz_hi, ea.bz_out);
   return rebuild_table(m);
 }
 

@@ -1748,15 +1748,32 @@ int64_t orc_decay_occupancy(OrcMap* m) {
   if (removed) map_rebuild(m);
   return removed;
 }
-/* Mapper::clearOutsideRadius restated (nvblox_node.cpp:1566-1583): drop blocks whose centre is farther than r from c. */
+/* Mapper::clearOutsideRadius restated (nvblox_node.cpp:1566-1583): drop blocks whose centre is farther than r from c.  A dropped projective
+ * block of the ESDF z band whose column's ESDF block stays has that column re-marked by the next update, as decay does it (2-D ESDF). */
+static int outside_radius(Idx3 i, float bs, const float* c, float r) {
+  const float dx = ((float)i.x * bs + bs * 0.5f) - c[0], dy = ((float)i.y * bs + bs * 0.5f) - c[1], dz = ((float)i.z * bs + bs * 0.5f) - c[2];
+  const float d2 = (dx * dx + dy * dy) + dz * dz;
+  return d2 > r * r;
+}
 int64_t orc_clear_outside_radius(OrcMap* m, const float* c, float r) {
-  const float bs = m->p.voxel_size * 8.0f;
+  const OrcParams* p = &m->p;
+  const float bs = p->voxel_size * 8.0f;
+  if (p->esdf_mode != 1) {                         /* (before anything is freed: the table still finds every block) */
+    const EsdfCfg ec = esdf_cfg(p);
+    for (int64_t q = 0; q < m->count; q++) {
+      Block* b = m->order[q];
+      if (!(b->flags & L_TSDF) || !outside_radius(b->idx, bs, c, r)) continue;
+      if (!(ec.plane_on || (b->idx.z >= floor_div8(ec.kz_min) && b->idx.z <= floor_div8(ec.kz_max)))) continue;      /* (ground-plane mode: a block of any height) */
+      Idx3 ei = {b->idx.x, b->idx.y, floor_div8(ec.kz_out)};
+      if (outside_radius(ei, bs, c, r)) continue;
+      Block* eb = map_find(m, ei);
+      if (eb && (eb->flags & L_ESDF)) eb->remark_esdf = 1;
+    }
+  }
   int64_t removed = 0, keep = 0;
   for (int64_t q = 0; q < m->count; q++) {
     Block* b = m->order[q];
-    float dx = ((float)b->idx.x * bs + bs * 0.5f) - c[0], dy = ((float)b->idx.y * bs + bs * 0.5f) - c[1], dz = ((float)b->idx.z * bs + bs * 0.5f) - c[2];
-    float d2 = (dx * dx + dy * dy) + dz * dz;
-    if (d2 > r * r) { if (b->flags & L_TSDF) cleared_push(m, b->idx); block_free(b); removed++; } else m->order[keep++] = b;
+    if (outside_radius(b->idx, bs, c, r)) { if (b->flags & L_TSDF) cleared_push(m, b->idx); block_free(b); removed++; } else m->order[keep++] = b;
   }
   m->count = keep;
   if (removed) map_rebuild(m);

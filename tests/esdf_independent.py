@@ -205,6 +205,50 @@ def tsdf_blocks_3d(sites, alloc, params, origin=(0, 0, 0)):
     return np.asarray(idx, np.int32).reshape(-1, 3), np.asarray(data, TSDF_DT).reshape(-1, 512)
 
 
+def voxel_marks(blocks, params):
+    """(site, observed, inside) of TSDF voxels, each by itself (SEMANTICS.md "ESDF 2-D"): observed = weight >= esdf_min_weight; inside = observed
+    and distance <= 0; site = observed and |distance| <= esdf_max_site_distance_vox voxels (and, site rule 0, distance <= 0)."""
+    d = np.asarray(blocks["distance"], np.float32); w = np.asarray(blocks["weight"], np.float32)
+    obs = w >= np.float32(params.esdf_min_weight)
+    ins = obs & (d <= 0)
+    site = obs & (np.abs(d) <= np.float32(params.esdf_max_site_distance_vox) * np.float32(params.voxel_size))
+    if int(params.esdf_site_rule) == 0:
+        site &= d <= 0
+    return site, obs, ins
+
+
+def column_marks_2d(tsdf_idx, tsdf_blocks, params, origin, shape_blocks):
+    """Dense [y, x] (site, observed, inside) over the box origin (bx, by) + shape_blocks (nby, nbx): the column rule applied to a TSDF read-back --
+    a column is marked by ANY voxel of it within the z band [esdf_slice_min_height, esdf_slice_max_height] (voxel rows, not block rows)."""
+    vs = np.float32(params.voxel_size)
+    kz_lo, kz_hi = (int(np.floor(np.float32(h) / vs)) for h in (params.esdf_slice_min_height, params.esdf_slice_max_height))
+    Hh, W = shape_blocks[0] * 8, shape_blocks[1] * 8
+    out = [np.zeros((Hh, W), bool) for _ in range(3)]
+    for i, b in zip(np.asarray(tsdf_idx, np.int64).reshape(-1, 3).tolist(), tsdf_blocks):
+        x0, y0 = (i[0] - origin[0]) * 8, (i[1] - origin[1]) * 8
+        kz = i[2] * 8 + np.arange(8)
+        zsel = (kz >= kz_lo) & (kz <= kz_hi)
+        if not (0 <= x0 < W and 0 <= y0 < Hh) or not zsel.any():
+            continue
+        for o, m in zip(out, voxel_marks(np.asarray(b).reshape(8, 8, 8), params)):
+            o[y0:y0 + 8, x0:x0 + 8] |= m[:, :, zsel].any(2).T
+    return tuple(out)
+
+
+def volume_marks_3d(tsdf_idx, tsdf_blocks, params, origin, shape_blocks):
+    """Dense [x, y, z] (site, observed, inside) over the box: 3-D ESDF, every voxel marked by its own TSDF voxel."""
+    dims = tuple(8 * s for s in shape_blocks)
+    out = [np.zeros(dims, bool) for _ in range(3)]
+    for i, b in zip(np.asarray(tsdf_idx, np.int64).reshape(-1, 3).tolist(), tsdf_blocks):
+        s = [(i[a] - origin[a]) * 8 for a in range(3)]
+        if not all(0 <= s[a] < dims[a] for a in range(3)):
+            continue
+        sl = tuple(slice(s[a], s[a] + 8) for a in range(3))
+        for o, m in zip(out, voxel_marks(np.asarray(b).reshape(8, 8, 8), params)):
+            o[sl] = m
+    return tuple(out)
+
+
 Fields = collections.namedtuple("Fields", "dom sq parent site observed inside")
 
 

@@ -479,6 +479,8 @@ def test_tsdf_decay_rule_against_a_numpy_model(oracle_mod, exclude, kw):
     OBSERVED voxel that falls below the threshold becomes free instead (distance = tsdf_decayed_free_distance_vox voxels, weight = the threshold); the last
     camera view's blocks are spared on request.  Four calls in a row, block sets and every voxel compared exactly after each."""
     import helpers as H
+    import maintenance_cases as MC
+    import maintenance_independent as MM
     from isaac_ros_nvblox_amd import mapper as M
     cam = H.SMALL_CAM
     pg = M.default_params(tsdf_decay_factor=0.45, tsdf_decayed_weight_threshold=0.3, **kw)
@@ -487,31 +489,20 @@ def test_tsdf_decay_rule_against_a_numpy_model(oracle_mod, exclude, kw):
     for d, _, T in H.frames(3, cam, stride=13, color=False):
         o.integrate_depth(d, T, cam)
     spared = {tuple(int(v) for v in r) for r in np.asarray(o.last_view())} if exclude else set()
-    model = {tuple(int(v) for v in i): (o.get_block(oracle_mod.L_TSDF, i)["distance"].astype(np.float32).copy(), o.get_block(oracle_mod.L_TSDF, i)["weight"].astype(np.float32).copy())
-             for i in o.block_indices(oracle_mod.L_TSDF)}
-    f = np.float32(p.tsdf_decay_factor); thr = np.float32(p.tsdf_decayed_weight_threshold); free_d = np.float32(p.tsdf_decayed_free_distance_vox) * np.float32(p.voxel_size)
+    ti = o.block_indices(oracle_mod.L_TSDF)
+    model = MC.state_from_read({"tsdf": (ti, [o.get_block(oracle_mod.L_TSDF, i) for i in ti])})
     n_dropped = 0; n_freed_vox = 0
     for call in range(4):
         o.decay_tsdf(exclude)
-        for key in list(model):
-            if key in spared:
-                continue
-            d, w0 = model[key]
-            w = (w0 * f).astype(np.float32)
-            below = w < thr
-            alive = bool((~below).any()) or not int(p.decay_deallocate_decayed_blocks)
-            if int(p.tsdf_set_free_distance_on_decayed):
-                to_free = below & (w0 > 0)
-                d = np.where(to_free, free_d, d).astype(np.float32); w = np.where(to_free, thr, w).astype(np.float32); n_freed_vox += int(to_free.sum())
-            if alive:
-                model[key] = (d, w)
-            else:
-                del model[key]; n_dropped += 1
+        before = model
+        model, cleared = MM.decay_tsdf(before, sorted(spared), p)
+        n_dropped += len(cleared)
+        n_freed_vox += sum(int((MM.bits(b["tsdf"]["distance"]) != MM.bits(before[key]["tsdf"]["distance"])).sum()) for key, b in model.items())      # (only a voxel set free changes its distance)
         got = {tuple(int(v) for v in i) for i in o.block_indices(oracle_mod.L_TSDF)}
         assert got == set(model), (call, len(got), len(model))
-        for key, (d, w) in model.items():
+        for key, blk in model.items():
             b = o.get_block(oracle_mod.L_TSDF, np.array(key, np.int32))
-            assert np.array_equal(b["weight"], w) and np.array_equal(b["distance"], d), (call, key)
+            assert np.array_equal(b["weight"], blk["tsdf"]["weight"]) and np.array_equal(b["distance"], blk["tsdf"]["distance"]), (call, key)
     if kw.get("decay_deallocate_decayed_blocks", 1) and not kw.get("tsdf_set_free_distance_on_decayed"):
         assert n_dropped > 20, n_dropped                  # (weights <= 3 after three frames: 3 * 0.45^3 < 0.3 -- whole blocks go)
     if kw.get("tsdf_set_free_distance_on_decayed"):
@@ -576,6 +567,7 @@ def test_radius_clearing_against_a_numpy_model(oracle_mod):
     """clearOutsideRadius: a block goes iff the centre of its cube lies farther than the radius from the centre point -- numpy float32 on the block index list;
     the cleared-block list names exactly the projective blocks that went."""
     import helpers as H
+    import maintenance_independent as MM
     from isaac_ros_nvblox_amd import mapper as M
     cam = H.SMALL_CAM
     p = H.copy_params(M.default_params(), oracle_mod.OrcParams)
@@ -584,16 +576,16 @@ def test_radius_clearing_against_a_numpy_model(oracle_mod):
         o.integrate_depth(d, T, cam)
     o.update_esdf()
     before = o.block_indices(oracle_mod.L_TSDF)
-    c = np.array([0.3, -0.2, 1.1], np.float32); r = np.float32(1.9); bs = np.float32(8) * np.float32(p.voxel_size)
-    ctr = (before.astype(np.float32) * bs + bs * np.float32(0.5)) - c
-    d2 = (ctr[:, 0] * ctr[:, 0] + ctr[:, 1] * ctr[:, 1]) + ctr[:, 2] * ctr[:, 2]
-    keep = ~(d2 > r * r)
+    c = np.array([0.3, -0.2, 1.1], np.float32); r = np.float32(1.9)
+    state = {tuple(int(v) for v in i): MM.make_block(tsdf=o.get_block(oracle_mod.L_TSDF, i)) for i in before}
+    kept, cleared = MM.clear_outside_radius(state, c, r, p.voxel_size)
+    keep = np.array([tuple(int(v) for v in i) in kept for i in before], bool)
     o.take_cleared_blocks()
     o.clear_outside_radius(tuple(float(v) for v in c), float(r))
     after = {tuple(int(v) for v in i) for i in o.block_indices(oracle_mod.L_TSDF)}
     assert after == {tuple(int(v) for v in i) for i in before[keep]} and 20 < keep.sum() < len(before) - 20
     gone = {tuple(int(v) for v in i) for i in np.asarray(o.take_cleared_blocks()).reshape(-1, 3)}
-    assert gone == {tuple(int(v) for v in i) for i in before[~keep]}
+    assert gone == {tuple(int(v) for v in i) for i in before[~keep]} == {tuple(k) for k in cleared.tolist()}
 
 
 def test_mesh_rules_against_a_table_free_numpy_model(oracle_mod):
@@ -726,6 +718,7 @@ def test_shape_clearing_against_a_numpy_model(oracle_mod):
     """clearTsdfInsideShapes: a voxel is reset (distance 0, weight 0) iff its centre lies inside one of the spheres / boxes; every other voxel is untouched --
     numpy float32 over the dense layer."""
     import helpers as H
+    import maintenance_independent as MM
     from isaac_ros_nvblox_amd import mapper as M
     cam = H.SMALL_CAM
     p = H.copy_params(M.default_params(), oracle_mod.OrcParams)
@@ -736,18 +729,10 @@ def test_shape_clearing_against_a_numpy_model(oracle_mod):
     before = {tuple(int(v) for v in i): o.get_block(oracle_mod.L_TSDF, i).copy() for i in ti}
     shapes = np.array([[0, 1.5, 1.0, 0.6, 0.8, 0, 0], [1, -3.1, -2.6, -0.1, -1.0, 0.0, 1.0], [0, 9.0, 9.0, 9.0, 0.2, 0, 0]], np.float32)
     n_reported = o.clear_tsdf_inside_shapes([("sphere", tuple(s[1:4]), s[4]) if s[0] == 0 else ("aabb", tuple(s[1:4]), tuple(s[4:7])) for s in shapes])
-    vs = np.float32(p.voxel_size); bs = np.float32(8) * vs
-    lin = np.arange(512); v3 = np.stack([lin // 64, (lin // 8) % 8, lin % 8], 1).astype(np.float32)
+    model_shapes = [("sphere", tuple(s[1:4]), s[4]) if s[0] == 0 else ("aabb", tuple(s[1:4]), tuple(s[4:7])) for s in shapes]
     n = 0
     for key, b0 in before.items():
-        c = (np.asarray(key, np.float32) * bs)[None, :] + v3 * vs + vs * np.float32(0.5)
-        inside = np.zeros(512, bool)
-        for s in shapes:
-            if s[0] == 0:
-                dd = c - s[1:4]
-                inside |= ((dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]) <= s[4] * s[4]
-            else:
-                inside |= (c >= s[1:4]).all(1) & (c <= s[4:7]).all(1)
+        inside = MM.shape_mask(key, model_shapes, p.voxel_size)
         b1 = o.get_block(oracle_mod.L_TSDF, np.asarray(key, np.int32))
         assert (b1["distance"][inside] == 0).all() and (b1["weight"][inside] == 0).all(), key
         assert np.array_equal(b1["distance"][~inside], b0["distance"][~inside]) and np.array_equal(b1["weight"][~inside], b0["weight"][~inside]), key

@@ -233,6 +233,12 @@ int nvbx_flush(nvbx_mapper* m);
  * enable = 0: the classic order, every call launches its own kernels (four launches per frame).  NVBX_COLOR_DEFERRAL=0|1|2 in the environment sets the
  * default of mappers created afterwards. */
 int nvbx_mapper_set_color_deferral(nvbx_mapper* m, int32_t enable);
+/* The NVBX_* environment variables of the library (launch geometry and A/B switches; none changes a result) are read when a mapper is
+ * created and kept per mapper.  nvbx_mapper_reload_knobs reads them again for this mapper: held-back work is carried out first, under the old
+ * settings; the calls that follow use the new ones.  Four variables shape a mapper at creation and are NOT re-applied to a live one: NVBX_MAX_BLOCKS
+ * (nvbx_mapper_set_max_capacity keeps what it last set), NVBX_COLOR_DEFERRAL (likewise nvbx_mapper_set_color_deferral), NVBX_SIDE_STREAM (streams and
+ * events) and NVBX_DEFER_EDT.  NVBX_FRAME_POOL_MAX belongs to the process-wide frame pool, not to a mapper, and is read whenever the pool would grow. */
+int nvbx_mapper_reload_knobs(nvbx_mapper* m);
 /* ---- Library-owned device frames: OWNERSHIP TRANSFER of input images (csrc/frames.hip).
  * Replaces the node-owned, re-used device image buffers of the reference (nvblox_node.hpp:484-488: color_image_, filled by the conversion on the
  * mapper's stream right before integrateColor, nvblox_node.cpp:1237-1263, conversions/image_conversions_thrust.cu:68-84) for a library that may hold a

@@ -60,10 +60,9 @@ __global__ __launch_bounds__(512) void k_integrate_color(DMap m, FrameSetC<Pix, 
   color_integrate_worker<Pix, NB>(m, fs, synth_all, srows, scols, mesh_list, (int32_t)blockIdx.x - n_mark_wg - n_edt_wg, (int32_t)gridDim.x - n_mark_wg - n_edt_wg);
 }
 
-// lanes per ray of the sphere-tracing launch for a batch of n cameras (1, 2, 4 or 8)
-static int sphere_trace_lanes(int n) {
-  static const int forced = nvbx_knob_st_lanes(getenv("NVBX_ST_LANES"));       // (sweeps)
-  if (forced) return forced;
+// lanes per ray of the sphere-tracing launch for a batch of n cameras (1, 2, 4 or 8); knobs.st_lanes forces a value (NVBX_ST_LANES: sweeps)
+static int sphere_trace_lanes(const nvbx_mapper* m, int n) {
+  if (m->knobs.st_lanes) return m->knobs.st_lanes;
   // measured (tools/st_lanes_sweep.sh, profiles/r03d_st_lanes.txt; us per launch at 8 / 4 / 2 / 1 lanes): 8 cameras 30.6 / 23.6 / 21.8 / 26.3,
   // 4 cameras 20.0 / 16.7 / 18.2 / 24.4, 2 cameras 13.1 / 13.5 / 16.1 / 21.4
   return n >= 6 ? 2 : (n >= 3 ? 4 : 8);
@@ -95,7 +94,7 @@ static int color_setup(nvbx_mapper* m, int32_t n, const Pix* imgs, int32_t rows,
 }
 template <int NB>
 static int color_launch_trace(nvbx_mapper* m, const PoseSet<NB>& ps, int32_t n, int32_t srows, int32_t scols, int32_t mark_wg = 0, const EsdfArgs& ea = EsdfArgs{}) {
-  const int rl = sphere_trace_lanes(n);
+  const int rl = sphere_trace_lanes(m, n);
   const int32_t n_trace = trace_patch_workgroups(rl, srows, scols) * n;
   const dim3 st_grid((unsigned)(n_trace + mark_wg));
 #define NVBX_ST_LAUNCH(RL) NVBX_LAUNCH(m, (k_sphere_trace<NB, RL>), st_grid, dim3(256), m->d, ps, m->synth.as<float>(), srows, scols, m->p.sphere_tracing_max_steps, \
@@ -223,8 +222,8 @@ template <int NB> int nvbx_mapper::pending_color_trace_rider(TraceRiderT<NB>* tr
   if (rc) return rc;
   tr->synth = synth.as<float>(); tr->srows = srows; tr->scols = scols; tr->max_steps = p.sphere_tracing_max_steps;
   tr->max_len = p.sphere_tracing_max_ray_length_m; tr->eps_m = p.sphere_tracing_surface_eps_vox * p.voxel_size;
-  static const int fused_lanes = nvbx_knob_fused_trace_lanes(getenv("NVBX_FUSED_TRACE_LANES"));       // (A/B, one frame: 4 or 8 lanes per ray)
-  tr->lanes = NB == 1 ? fused_lanes : std::max(2, sphere_trace_lanes(c.n));
+  // (knobs.fused_trace_lanes -- A/B, one frame: 4 or 8 lanes per ray)
+  tr->lanes = NB == 1 ? knobs.fused_trace_lanes : std::max(2, sphere_trace_lanes(this, c.n));
   tr->n_wg = trace_patch_workgroups(tr->lanes, srows, scols) * c.n;
   return NVBX_OK;
 }
@@ -243,7 +242,7 @@ void nvbx_mapper::pending_marking_args(int32_t* mark_wg, EsdfArgs* ea_out, bool 
     // longest part of the view-marking launch (18.6 us against the tiles' 16.1; tools/wg_timeline.py --scene hall: k_mark_view 17.7 -> 16.6 us, tools/mark_riders_ab.sh).
     // A BATCH keeps 256: its view-marking launch is residency-bound and more riders in front keep the tiles waiting (8 cameras: 27.0 -> 27.9 us).
     // NVBX_MARK_RIDERS=n: fixed (A/B).
-    static const int fixed = nvbx_knob_mark_riders(getenv("NVBX_MARK_RIDERS"));
+    const int fixed = knobs.mark_riders;
     const int64_t n_hint = std::max<int64_t>(0, __atomic_load_n(&h_mirror[2], __ATOMIC_RELAXED));
     *mark_wg = fixed > 0 ? fixed : (!single_frame ? 256 : (int32_t)std::min<int64_t>(1024, std::max<int64_t>(256, ((n_hint + n_hint / 4 + 3) / 4 + 7) / 8 * 8)));
   }
@@ -279,8 +278,8 @@ static int replay_pair_t(nvbx_mapper* m, const nvbx_mapper::ColorPending& c) {
   return color_launch_integrate<Pix, NB>(m, fs, srows, scols, true);
 }
 bool nvbx_mapper::replay_pair_applies() const {
-  static const int on = getenv("NVBX_REPLAY_PAIR") ? atoi(getenv("NVBX_REPLAY_PAIR")) : 1;      // (A/B: 0 = three classic launches)
-  return on && held.color_pending.on && held.esdf_update_pending && p.projective_layer_type != 1 && p.esdf_mode == 0 && p.esdf_propagation == 0 && !use_side && defer_edt && !held.import_pending;
+  // (knobs.replay_pair -- A/B: 0 = three classic launches)
+  return knobs.replay_pair && held.color_pending.on && held.esdf_update_pending && p.projective_layer_type != 1 && p.esdf_mode == 0 && p.esdf_propagation == 0 && !use_side && defer_edt && !held.import_pending;
 }
 int nvbx_mapper::replay_pair() {
   const ColorPending c = take_pending(); held.esdf_update_pending = false;

@@ -171,7 +171,7 @@ extern "C" int nvbx_update_esdf(nvbx_mapper* m) {
   // comes first (join_side -> replay_deferred, in call order)
   // (... or, with the switch on and no colour frame around, behind nothing: the next camera depth frame carries it alone -- depth-only hosts,
   //  occupancy mappers; nvbx_mapper::esdf_only_carry)
-  static const int esdf_only = getenv("NVBX_ESDF_ONLY_CARRY") ? atoi(getenv("NVBX_ESDF_ONLY_CARRY")) : 1;      // (A/B: 0 = an updateEsdf is held back behind a colour frame only)
+  const int esdf_only = m->knobs.esdf_only_carry;      // (NVBX_ESDF_ONLY_CARRY -- A/B: 0 = an updateEsdf is held back behind a colour frame only)
   if ((m->held.color_pending.on || (esdf_only && m->color_deferral && !m->pipelined_order && !m->held.import_pending)) && !m->replaying && m->p.esdf_propagation == 0 && !m->use_side && m->defer_edt) {
     // (an update already held back is carried out first: two updates in a row stay two updates -- epochs and the "last update" counters as in
     //  the undeferred sequence)

@@ -66,7 +66,7 @@ struct DeviceGuard {
   ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
 };
 
-static int pool_max() { const char* e = getenv("NVBX_FRAME_POOL_MAX"); return e ? std::max(2, atoi(e)) : 8; }      // (read where a frame would be created: rare)
+static int pool_max() { return nvbx_knob_frame_pool_max(getenv("NVBX_FRAME_POOL_MAX")); }      // (the pool is process-wide, no mapper's: read where a frame would be created -- rare)
 // caller holds g_mu (a dead owner's words are not read)
 static bool fence_reached(const FrameFence& f) { return f.st->dead || (int32_t)(__atomic_load_n(f.progress, __ATOMIC_ACQUIRE) - f.seq) >= 0; }
 static void recycle_event(int device, hipEvent_t ev) { g_event_pool[device].push_back(ev); }

@@ -543,16 +543,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NVBX_SPARSE
 // the beam-centric far-field launch; view_class = nullptr: everything goes to the dense launch
 int launch_lidar_sparse(nvbx_mapper* m, const FrameSet<DepthF32, 1>& fs, const LidarSensor& sensor, bool plain, uint8_t** view_class, int32_t** dense_list) {
   *view_class = nullptr; *dense_list = nullptr;
-  static const int enabled = nvbx_knob_switch(getenv("NVBX_LIDAR_SPARSE"));       // (A/B: 0 = dense launch only)
-  if (!enabled || !plain || !(m->p.lidar_nearest_interpolation_max_allowable_dist_to_ray_vox <= 0.55f)) return NVBX_OK;
+  // (knobs.lidar_sparse -- A/B: 0 = dense launch only)
+  if (!m->knobs.lidar_sparse || !plain || !(m->p.lidar_nearest_interpolation_max_allowable_dist_to_ray_vox <= 0.55f)) return NVBX_OK;
   // [capacity class bytes][NSH x capacity view-list indices: the dense launch's work list, one region per shard]
   const size_t class_bytes = ((size_t)m->capacity + 15) & ~(size_t)15;
   if (m->view_class.ensure(m->stream, class_bytes + (size_t)NSH * (size_t)m->capacity * 4)) return NVBX_E_DEVICE;
   uint8_t* vc = m->view_class.as<uint8_t>();
-  static const int sparse_grid = nvbx_knob_lidar_sparse_grid(getenv("NVBX_LIDAR_SPARSE_GRID"));    // (six resident wavefronts per SIMD = 1536 workgroups; 1536 / 2048 / 2560 / 3072 / 3584 / 4096 / 8192 workgroups: 111.1 / 109.5 / 110.5 / 111.0 / 114.8 / 115.3 / 114.3 us with strided passes and the work list)
+  const int sparse_grid = m->knobs.lidar_sparse_grid;    // (NVBX_LIDAR_SPARSE_GRID; six resident wavefronts per SIMD = 1536 workgroups; 1536 / 2048 / 2560 / 3072 / 3584 / 4096 / 8192 workgroups: 111.1 / 109.5 / 110.5 / 111.0 / 114.8 / 115.3 / 114.3 us with strided passes and the work list)
   // (with an exchange buffer registered -- nvbx_set_view_export -- the dense launch walks the whole view list, as it writes every record's index there)
-  static const int use_list = nvbx_knob_switch(getenv("NVBX_LIDAR_DENSE_LIST"));       // (A/B: 0 = the dense launch skips the taken records of the whole list)
-  int32_t* dense = (use_list && !m->view_export) ? reinterpret_cast<int32_t*>(vc + class_bytes) : nullptr;
+  // (knobs.lidar_dense_list -- A/B: 0 = the dense launch skips the taken records of the whole list)
+  int32_t* dense = (m->knobs.lidar_dense_list && !m->view_export) ? reinterpret_cast<int32_t*>(vc + class_bytes) : nullptr;
   NVBX_LAUNCH(m, (k_lidar_sparse<DepthF32>), dim3(sparse_grid), dim3(256), m->d, fs, sensor, (const int4*)m->view_list, (int32_t)m->capacity, m->mesh_list_live(), vc, dense);
   *dense_list = dense;
   *view_class = vc;
@@ -563,9 +563,9 @@ int launch_lidar_sparse(nvbx_mapper* m, const FrameSet<DepthF32, 1>& fs, const L
 // launches k_mark_view (a scan without a range limit or with a box beyond the grid's addressing / memory cap; NVBX_LIDAR_VIEW_GRID=0)
 int launch_view_grid(nvbx_mapper* m, const FrameSet<DepthF32, 1>& fs, const LidarSensor& sensor, int tiles, int32_t fence_report, bool* used) {
   *used = false;
-  static const int enabled = getenv("NVBX_LIDAR_VIEW_GRID") ? atoi(getenv("NVBX_LIDAR_VIEW_GRID")) : 1;       // (A/B: 0 = k_mark_view<Lidar>)
   const Frame& f = fs.f[0];
-  if (!enabled || !(f.max_dist > 0.0f) || m->capacity > (1ll << 24)) return NVBX_OK;
+  // (knobs.lidar_view_grid -- A/B: 0 = k_mark_view<Lidar>)
+  if (!m->knobs.lidar_view_grid || !(f.max_dist > 0.0f) || m->capacity > (1ll << 24)) return NVBX_OK;
   // the box: every ray ends within max_dist of the sensor; along z the beams' elevation range bounds it (|world z of a unit beam| <=
   // hypot(R20, R21) cos(el) + |R22 sin(el)|, elevation table rows on the host: ensure_lidar_tables)
   const double reach = (double)f.max_dist / (double)f.block_size;
@@ -574,11 +574,11 @@ int launch_view_grid(nvbx_mapper* m, const FrameSet<DepthF32, 1>& fs, const Lida
   for (int k = 0; k < sensor.l.rows; k++) wz = std::max(wz, hxy * std::fabs((double)m->lidar_host[2 * (size_t)k + 1]) + std::fabs((double)f.R_LC[8] * (double)m->lidar_host[2 * (size_t)k]));
   int64_t H = (int64_t)std::ceil(reach) + 2, Hz = std::min<int64_t>(H, (int64_t)std::ceil(reach * std::min(1.0, wz)) + 2);
   // (tests: a box SMALLER than the sensor's range -- the blocks beyond it take the hash path, block by block; tests/test_gpu_round5.py)
-  static const int64_t reach_cap = getenv("NVBX_VIEW_GRID_REACH") ? atoll(getenv("NVBX_VIEW_GRID_REACH")) : 0;
+  const int64_t reach_cap = m->knobs.view_grid_reach;      // (NVBX_VIEW_GRID_REACH; 0 = no cap)
   if (reach_cap > 0) { H = std::min(H, reach_cap); Hz = std::min(Hz, reach_cap); }
   const int64_t ncx = (2 * H + 1 + 3) / 4, ncz = (2 * Hz + 1 + 3) / 4;
   const int64_t cells = ncx * ncx * ncz;
-  static const int64_t cap_mb = getenv("NVBX_VIEW_GRID_MAX_MB") ? atoll(getenv("NVBX_VIEW_GRID_MAX_MB")) : 128;
+  const int64_t cap_mb = m->knobs.view_grid_max_mb;      // (NVBX_VIEW_GRID_MAX_MB: 1 .. 2^20, default 128)
   if (ncx > 256 || ncz > 256 || cells * 64 > (cap_mb << 20)) return NVBX_OK;
   const size_t coarse_bytes = ((size_t)cells + 3) & ~(size_t)3;
   bool grew = false;

@@ -421,7 +421,7 @@ extern "C" int nvbx_decay_tsdf(nvbx_mapper* m, int32_t exclude_last_view) {
   if (m->join_side()) return NVBX_E_DEVICE;
   if (m->undo_marks()) return NVBX_E_DEVICE;          // decay deallocates: unresolved marking passes are taken back first
   if (m->begin_dirtying()) return NVBX_E_DEVICE;
-  static const int decay_grid = nvbx_knob_decay_grid(getenv("NVBX_DECAY_GRID"));      // (env: tools/decay_grid_sweep.sh)
+  const int decay_grid = m->knobs.decay_grid;      // (NVBX_DECAY_GRID: tools/decay_grid_sweep.sh)
   // eight slots per workgroup iteration: a room-sized map needs a few hundred workgroups, and launching 4096 costs it ~1.5 us
   const int64_t hw_seen = std::max<int64_t>(1, __atomic_load_n(&m->h_mirror[1], __ATOMIC_RELAXED));       // (high-water mark as last reported: a hint, the kernel grid-strides)
   const int grid = (int)std::min<int64_t>(std::min<int64_t>(m->capacity, decay_grid), std::max<int64_t>(512, (hw_seen + 7) / 8));

@@ -208,6 +208,15 @@ static const char* params_problem(const nvbx_mapper_params* p) {
 }
 
 // ------------------------------------------------------------------------------------------------ C-ABI: lifetime
+// THE read of the mapper's NVBX_* environment variables, all through nvbx_knobs.h (the frame pool's own is process-wide: frames.hip)
+static void read_knobs(nvbx_mapper* m) { nvbx_knobs_read(&m->knobs, [](const char* name) -> const char* { return getenv(name); }); }
+extern "C" int nvbx_mapper_reload_knobs(nvbx_mapper* m) {
+  if (!m) return NVBX_E_INVALID;
+  NVBX_HIP(hipSetDevice(m->device));
+  if (m->join_side()) return NVBX_E_DEVICE;          // (anything held back under the old settings is carried out)
+  read_knobs(m);
+  return NVBX_OK;
+}
 extern "C" int nvbx_mapper_create(int device, void* hip_stream, const nvbx_mapper_params* params, int64_t block_capacity, nvbx_mapper** out) {
   if (!params || !out || (block_capacity != 0 && (block_capacity < 64 || block_capacity > (1ll << 24)))) {
     set_error("nvbx_mapper_create: invalid argument (null pointer, or block_capacity outside 64 .. 2^24 and not 0 = automatic)"); return NVBX_E_INVALID;
@@ -222,18 +231,19 @@ extern "C" int nvbx_mapper_create(int device, void* hip_stream, const nvbx_mappe
   }
   nvbx_mapper* m = new nvbx_mapper();
   m->device = device; m->p = *params; m->capacity = block_capacity;
+  read_knobs(m);
   // the pools double on demand up to this many blocks (nvbx_mapper_set_max_capacity; NVBX_MAX_BLOCKS in the environment)
   m->max_capacity = std::max<int64_t>(block_capacity, 1ll << 22);
-  { const char* e = getenv("NVBX_MAX_BLOCKS"); if (e && atoll(e) > 0) m->max_capacity = std::max<int64_t>(block_capacity, std::min<int64_t>(atoll(e), 1ll << 24)); }
+  if (m->knobs.max_blocks > 0) m->max_capacity = std::max<int64_t>(block_capacity, std::min<int64_t>(m->knobs.max_blocks, 1ll << 24));
   if (hip_stream) { m->stream = (hipStream_t)hip_stream; m->own_stream = false; }
   else { hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking); if (e != hipSuccess) { set_error("hipStreamCreate", e); delete m; return NVBX_E_DEVICE; } m->own_stream = true; }
   nvbx::frames_register_stream(device, m->stream); m->stream_registered = true;      // (frames let go of without a fence wait for this stream too, frames.hip)
   // ESDF on a side stream beside colour integration: off by default, NVBX_SIDE_STREAM=1 enables (the
   // cross-stream hand-off costs ~10 us each way on this runtime, which eats most of the overlap)
-  { const char* e = getenv("NVBX_SIDE_STREAM"); m->use_side = (e && e[0] == '1'); }
-  m->defer_edt = nvbx_knob_switch(getenv("NVBX_DEFER_EDT")) != 0;
+  m->use_side = m->knobs.side_stream != 0;
+  m->defer_edt = m->knobs.defer_edt != 0;
   // colour deferral of a new mapper (nvbx_mapper_set_color_deferral overrides): NVBX_COLOR_DEFERRAL = 0 / 1 / 2 in the environment
-  { const int cd = nvbx_knob_color_deferral(getenv("NVBX_COLOR_DEFERRAL")); if (cd >= 0) { m->color_deferral = cd != 0; m->color_staging = cd == 2; } }
+  { const int cd = m->knobs.color_deferral; if (cd >= 0) { m->color_deferral = cd != 0; m->color_staging = cd == 2; } }
   if (m->use_side) {
     if (hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&m->ev_main, hipEventDisableTiming) != hipSuccess ||

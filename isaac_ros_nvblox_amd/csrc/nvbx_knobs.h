@@ -1,15 +1,18 @@
 /* nvbx_knobs.h -- the environment knobs of the launch geometry and the A/B switches, parsed in one place (plain C: the host code includes it, and
- * tests/test_knobs.py compiles THIS file with gcc and checks the mapping on the CPU).  Each function takes the variable's value (getenv's result, NULL
- * when unset) and returns what the library uses.  A missing, malformed or out-of-range value gives the default, so no setting can size a launch at zero
- * or drop work; rider counts are rounded up to a multiple of 8.  No knob changes a result, only which workgroup does what. */
+ * tests/test_knobs.py compiles THIS file with gcc and checks the mapping on the CPU).  Each nvbx_knob_* function takes the variable's value (NULL when
+ * unset) and returns what the library uses.  A missing, malformed or out-of-range value gives the default, so no setting can size a launch at zero
+ * or drop work; rider counts are rounded up to a multiple of 8.  No knob changes a result, only which workgroup does what.
+ * struct nvbx_knobs holds one mapper's settings; nvbx_knobs_read fills it, and names every variable there and nowhere else. */
 #ifndef NVBX_KNOBS_H_
 #define NVBX_KNOBS_H_
 #include <errno.h>
+#include <limits.h>
 #include <stdlib.h>
 #include <string.h>
 
 #define NVBX_KNOB_GRID_MAX (1 << 20)      /* workgroups of one part of a launch */
 #define NVBX_KNOB_RIDERS_MAX (1 << 16)    /* rider workgroups of one held-back pass */
+#define NVBX_KNOB_SCORE_CHUNKS_MAX 1024   /* point chunks of a pose (relocalize.hip: SCORE_MAX_CHUNKS) */
 
 /* s as a whole decimal integer in [lo, hi]; anything else: def */
 static inline int nvbx_knob_int(const char* s, int def, int lo, int hi) {
@@ -27,6 +30,8 @@ static inline int nvbx_knob_riders(const char* s, int def) {
 }
 /* an A/B switch: 0 or 1, default on */
 static inline int nvbx_knob_switch(const char* s) { return nvbx_knob_int(s, 1, 0, 1); }
+/* ... and one that is off unless asked for: 0 or 1, default off */
+static inline int nvbx_knob_opt_in(const char* s) { return nvbx_knob_int(s, 0, 0, 1); }
 
 /* NVBX_INTEG_GRID: cap on the TSDF update's workgroups; 0 = the built-in cap (1024 for one camera, 512 for a batch) */
 static inline int nvbx_knob_integ_grid(const char* s) { return nvbx_knob_int(s, 0, 1, NVBX_KNOB_GRID_MAX); }
@@ -68,5 +73,59 @@ static inline int nvbx_knob_fused_trace_lanes(const char* s) { return nvbx_knob_
 static inline int nvbx_knob_lidar_sparse_grid(const char* s) { return nvbx_knob_int(s, 2048, 1, NVBX_KNOB_GRID_MAX); }
 /* NVBX_COLOR_DEFERRAL: a new mapper's colour deferral, 0 off / 1 zero-copy / 2 staged; -1 = unset (the library's default, staged) */
 static inline int nvbx_knob_color_deferral(const char* s) { return nvbx_knob_int(s, -1, 0, 2); }
-/* NVBX_FUSE_COLC, NVBX_DEPTH_PAIR, NVBX_LIDAR_SPARSE, NVBX_LIDAR_DENSE_LIST, NVBX_DEFER_EDT: nvbx_knob_switch */
+/* NVBX_SCORE_CHUNKS: point chunks per pose of k_score_poses, 1 = one workgroup per pose; 0 = the launch's own choice */
+static inline int nvbx_knob_score_chunks(const char* s) { return nvbx_knob_int(s, 0, 1, NVBX_KNOB_SCORE_CHUNKS_MAX); }
+/* NVBX_VIEW_GRID_REACH: cap, in blocks, on the half side of the LiDAR view grid's box; 0 = no cap */
+static inline int nvbx_knob_view_grid_reach(const char* s) { return nvbx_knob_int(s, 0, 1, 1 << 20); }
+/* NVBX_VIEW_GRID_MAX_MB: the largest LiDAR view grid, in MiB, that is allocated */
+static inline int nvbx_knob_view_grid_max_mb(const char* s) { return nvbx_knob_int(s, 128, 1, 1 << 20); }
+/* NVBX_MAX_BLOCKS: bound of the pools' growth (the mapper clamps it to [initial capacity, 2^24]); 0 = the built-in bound */
+static inline int nvbx_knob_max_blocks(const char* s) { return nvbx_knob_int(s, 0, 1, INT_MAX); }
+/* NVBX_FRAME_POOL_MAX: frames per image size in the library's pool (process-wide, frames.hip); an integer below 2 gives 2 */
+static inline int nvbx_knob_frame_pool_max(const char* s) { const int v = nvbx_knob_int(s, 8, INT_MIN, 1 << 16); return v < 2 ? 2 : v; }
+
+/* One mapper's knobs: filled at nvbx_mapper_create and again by nvbx_mapper_reload_knobs.  Four of them shape the mapper at creation and are
+ * not applied to a live one: max_blocks, side_stream, color_deferral, defer_edt (include/nvblox_hip.h). */
+struct nvbx_knobs {
+  /* A/B switches */
+  int fuse_colc, depth_pair, lidar_sparse, lidar_dense_list, lidar_view_grid, defer_edt, replay_pair, esdf_only_carry;      /* default on */
+  int side_stream, query_dedup;                                                                                            /* default off */
+  int color_deferral, mark_tiles_first;                                                                                    /* -1 = unset */
+  /* launch geometry */
+  int integ_grid, color_grid, decay_grid, lidar_sparse_grid, grid_margin_pct, grid_margin_blocks;
+  int edt_riders, pair_b_edt_riders, mark_riders;
+  int st_lanes, fused_trace_lanes, render_lanes, score_chunks;
+  /* sizes */
+  int view_grid_reach, view_grid_max_mb, max_blocks;
+};
+/* lookup(name): the variable's value, or NULL when it is unset (the library hands in the environment's, the test a table) */
+static inline void nvbx_knobs_read(struct nvbx_knobs* k, const char* (*lookup)(const char* name)) {
+  k->fuse_colc = nvbx_knob_switch(lookup("NVBX_FUSE_COLC"));
+  k->depth_pair = nvbx_knob_switch(lookup("NVBX_DEPTH_PAIR"));
+  k->lidar_sparse = nvbx_knob_switch(lookup("NVBX_LIDAR_SPARSE"));
+  k->lidar_dense_list = nvbx_knob_switch(lookup("NVBX_LIDAR_DENSE_LIST"));
+  k->lidar_view_grid = nvbx_knob_switch(lookup("NVBX_LIDAR_VIEW_GRID"));
+  k->defer_edt = nvbx_knob_switch(lookup("NVBX_DEFER_EDT"));
+  k->replay_pair = nvbx_knob_switch(lookup("NVBX_REPLAY_PAIR"));
+  k->esdf_only_carry = nvbx_knob_switch(lookup("NVBX_ESDF_ONLY_CARRY"));
+  k->side_stream = nvbx_knob_opt_in(lookup("NVBX_SIDE_STREAM"));
+  k->query_dedup = nvbx_knob_opt_in(lookup("NVBX_QUERY_DEDUP"));
+  k->color_deferral = nvbx_knob_color_deferral(lookup("NVBX_COLOR_DEFERRAL"));
+  k->mark_tiles_first = nvbx_knob_mark_tiles_first(lookup("NVBX_MARK_TILES_FIRST"));
+  k->integ_grid = nvbx_knob_integ_grid(lookup("NVBX_INTEG_GRID"));
+  k->color_grid = nvbx_knob_color_grid(lookup("NVBX_COLOR_GRID"));
+  k->decay_grid = nvbx_knob_decay_grid(lookup("NVBX_DECAY_GRID"));
+  k->lidar_sparse_grid = nvbx_knob_lidar_sparse_grid(lookup("NVBX_LIDAR_SPARSE_GRID"));
+  nvbx_knob_grid_margin(lookup("NVBX_GRID_MARGIN"), &k->grid_margin_pct, &k->grid_margin_blocks);
+  k->edt_riders = nvbx_knob_edt_riders(lookup("NVBX_EDT_RIDERS"));
+  k->pair_b_edt_riders = nvbx_knob_pair_b_edt_riders(lookup("NVBX_PAIR_B_EDT_RIDERS"));
+  k->mark_riders = nvbx_knob_mark_riders(lookup("NVBX_MARK_RIDERS"));
+  k->st_lanes = nvbx_knob_st_lanes(lookup("NVBX_ST_LANES"));
+  k->fused_trace_lanes = nvbx_knob_fused_trace_lanes(lookup("NVBX_FUSED_TRACE_LANES"));
+  k->render_lanes = nvbx_knob_render_lanes(lookup("NVBX_RENDER_LANES"));
+  k->score_chunks = nvbx_knob_score_chunks(lookup("NVBX_SCORE_CHUNKS"));
+  k->view_grid_reach = nvbx_knob_view_grid_reach(lookup("NVBX_VIEW_GRID_REACH"));
+  k->view_grid_max_mb = nvbx_knob_view_grid_max_mb(lookup("NVBX_VIEW_GRID_MAX_MB"));
+  k->max_blocks = nvbx_knob_max_blocks(lookup("NVBX_MAX_BLOCKS"));
+}
 #endif

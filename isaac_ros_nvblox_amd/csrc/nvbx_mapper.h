@@ -110,7 +110,10 @@ struct nvbx_mapper {
   hipStream_t side = nullptr;
   hipEvent_t ev_main = nullptr, ev_side = nullptr;
   hipEvent_t ev_order = nullptr;     // nvbx_mapper_wait_for: this mapper's stream as the producer
-  bool use_side = false;        // NVBX_SIDE_STREAM=0 disables
+  // The NVBX_* environment knobs (nvbx_knobs.h), read at nvbx_mapper_create and again by nvbx_mapper_reload_knobs: every launch-geometry and A/B
+  // decision of this mapper reads them here.  max_capacity, use_side, color_deferral / color_staging and defer_edt take their value at creation only.
+  nvbx_knobs knobs{};
+  bool use_side = false;        // knobs.side_stream at creation (NVBX_SIDE_STREAM=1 enables)
   bool side_pending = false;    // ESDF work enqueued on `side` that `stream` has not waited for yet
   bool main_dirty = true;       // non-colour work enqueued on `stream` since ev_main was recorded
   int join_side(bool carry_out_held = true);      // first call of every entry point (held.hip): held-back work is carried out, `stream` waits for the side stream (no host sync)

@@ -31,10 +31,9 @@ __global__ __launch_bounds__(256) void k_query_points(DMap m, const float* __res
 
 template <int KIND>
 int launch_query(nvbx_mapper* m, const float* pts, int64_t n, float min_weight, float unknown, int32_t plane_vz, float* dist, float* grad, uint8_t* valid) {
-  // (A/B, tools/query_bench.py: 1 = the wave-level de-duplication; measured slower on coherent and uniform batches alike)
-  static const int dedup = getenv("NVBX_QUERY_DEDUP") ? atoi(getenv("NVBX_QUERY_DEDUP")) : 0;
+  // (NVBX_QUERY_DEDUP -- A/B, tools/query_bench.py: 1 = the wave-level de-duplication; measured slower on coherent and uniform batches alike)
   const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), block(256);
-  if (dedup) NVBX_LAUNCH(m, (k_query_points<KIND, true>), grid, block, m->d, pts, n, m->p.voxel_size, min_weight, unknown, plane_vz, dist, grad, valid);
+  if (m->knobs.query_dedup) NVBX_LAUNCH(m, (k_query_points<KIND, true>), grid, block, m->d, pts, n, m->p.voxel_size, min_weight, unknown, plane_vz, dist, grad, valid);
   else NVBX_LAUNCH(m, (k_query_points<KIND, false>), grid, block, m->d, pts, n, m->p.voxel_size, min_weight, unknown, plane_vz, dist, grad, valid);
   NVBX_HIP(hipGetLastError());
   return NVBX_OK;

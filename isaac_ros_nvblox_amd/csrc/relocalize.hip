@@ -30,7 +30,7 @@
 using namespace nvbx;
 
 constexpr int SCORE_TPB = 256, SCORE_WAVES = SCORE_TPB / 64;
-constexpr int64_t SCORE_MAX_CHUNKS = 1024;   // point chunks of a pose (gridDim.y): 262 144 points at one per lane
+constexpr int64_t SCORE_MAX_CHUNKS = NVBX_KNOB_SCORE_CHUNKS_MAX;   // 1024 point chunks of a pose (gridDim.y): 262 144 points at one per lane
 constexpr float Q20 = 1048576.0f;
 enum { POSE_LIST = 0, POSE_LATTICE = 1, POSE_REFINED = 2 };
 
@@ -229,9 +229,9 @@ int score_points_check(const char* who, const float* pts, int64_t n, const float
 // One launch over n_poses poses; the arguments have been checked, the mapper's stream is ready.  Chunks: a workgroup per 256 points, one point per
 // lane, for every pose count -- measured faster than one workgroup per pose even where the poses alone fill the device (DESIGN.md 2.20,
 // EXPERIMENTS.md); beyond SCORE_MAX_CHUNKS x 256 points the lanes take runs of consecutive points.  (A/B, tools/relocalize_bench.py:
-// NVBX_SCORE_CHUNKS = c forces c chunks where the points allow, 1 = one workgroup per pose; read at every call, so that one process can measure both.)
+// NVBX_SCORE_CHUNKS = c forces c chunks where the points allow, 1 = one workgroup per pose; nvbx_mapper_reload_knobs lets one process measure both.)
 int score_launch(nvbx_mapper* m, ScoreArgs a, const ScoreOptions& o, int64_t n_poses, bool records_are_zero) {
-  const int forced = nvbx_knob_int(getenv("NVBX_SCORE_CHUNKS"), 0, 1, (int)SCORE_MAX_CHUNKS);      // (0: unset, malformed or out of range)
+  const int forced = m->knobs.score_chunks;      // (0: unset, malformed or out of range)
   const int64_t full = std::max<int64_t>((a.n + SCORE_TPB - 1) / SCORE_TPB, 1);
   const int64_t chunks_wanted = forced > 0 ? forced : SCORE_MAX_CHUNKS;
   int64_t chunks = std::min(std::min(chunks_wanted, full), SCORE_MAX_CHUNKS);

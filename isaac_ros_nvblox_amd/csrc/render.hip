@@ -191,10 +191,9 @@ __global__ __launch_bounds__(256) void k_render(DMap m, RenderArgs a) {
 
 // Lanes per ray (8, 4, 2 or 1) by ray count, as sphere_trace_lanes() chooses for a batch of cameras (color.hip: 19 200 rays per camera there):
 // a few ten thousand rays leave the chip idle and want the latency trick, hundreds of thousands fill it on their own and want fewer
-// speculative samples.  NVBX_RENDER_LANES forces a value (tools/render_bench.py's A/B).
-int render_lanes(int64_t rays) {
-  static const int forced = nvbx_knob_render_lanes(getenv("NVBX_RENDER_LANES"));
-  if (forced) return forced;
+// speculative samples.  NVBX_RENDER_LANES (knobs.render_lanes) forces a value (tools/render_bench.py's A/B).
+int render_lanes(const nvbx_mapper* m, int64_t rays) {
+  if (m->knobs.render_lanes) return m->knobs.render_lanes;
   return rays >= 6 * 19200 ? 2 : (rays >= 3 * 19200 ? 4 : 8);
 }
 
@@ -253,7 +252,7 @@ extern "C" int nvbx_render_view_with(nvbx_mapper* m, const nvbx_render_options* 
   a.fu = camera->fu; a.fv = camera->fv; a.cu = camera->cu; a.cv = camera->cv;
   a.subsample = ss.s; a.srows = ss.rows; a.scols = ss.cols;
   a.depth = depth_dev; a.color = color_rgb_dev; a.normal = normal_xyz_dev;
-  const int rl = render_lanes((int64_t)ss.rows * ss.cols);
+  const int rl = render_lanes(m, (int64_t)ss.rows * ss.cols);
   return launch_render<SRC_VIEW>(m, rl, dim3((unsigned)trace_patch_workgroups(rl, ss.rows, ss.cols)), a);
 }
 
@@ -273,7 +272,7 @@ extern "C" int nvbx_cast_rays_with(nvbx_mapper* m, const nvbx_render_options* op
   a.origin_lim = nvbx_pose_limit(m->p.voxel_size * 8.0f, a.max_len);        // (nvbx_pose_in_range's bound, per ray)
   if (!(a.origin_lim > 0.0f)) { set_error("nvbx_cast_rays: max_ray_length_m reaches beyond the addressable block range (+-2^20 blocks)"); return NVBX_E_INVALID; }
   a.depth = t_dev; a.hit = hit_dev; a.color = color_rgb_dev; a.normal = normal_xyz_dev;
-  const int rl = render_lanes(n);
+  const int rl = render_lanes(m, n);
   const int64_t rpw = 256 / rl;
   return launch_render<SRC_RAYS>(m, rl, dim3((unsigned)std::min<int64_t>((n + rpw - 1) / rpw, RAYS_GRID_MAX)), a);
 }

@@ -272,8 +272,8 @@ static_assert(sizeof(DMap) + sizeof(FrameSet<DepthF32, MAX_BATCH>) + sizeof(Fram
 // steps of TWO mappers around two shared launches (k_mark_view_pair, k_integrate_tsdf_color_pair).  The steps are the former body of integrate_depth_impl, cut
 // where it launches; what each step does to the mapper's host state, and in which order, is unchanged.
 static bool fused_colour_applies(const nvbx_mapper* m) {
-  static const int fuse_on = nvbx_knob_switch(getenv("NVBX_FUSE_COLC"));      // (A/B: 0 = three launches per frame)
-  return fuse_on && m->p.projective_layer_type != 1 && m->p.esdf_mode == 0 && m->p.esdf_propagation == 0 && !m->lidar_integrated && m->capacity <= (1ll << 24);
+  // (knobs.fuse_colc -- A/B: 0 = three launches per frame)
+  return m->knobs.fuse_colc && m->p.projective_layer_type != 1 && m->p.esdf_mode == 0 && m->p.esdf_propagation == 0 && !m->lidar_integrated && m->capacity <= (1ll << 24);
 }
 template <int NB> struct DepthSteps {
   int tiles = 0, edt_wg = 0; EsdfArgs ea{}; TraceRiderT<NB> tr{};                 // launch 1
@@ -323,8 +323,7 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
     // riders before or after the tiles (A/B: NVBX_MARK_TILES_FIRST = 0 / 1).  One frame: tiles first (15.2 vs 15.8 us).  A batch of 8: riders first
     // (32.4 vs 42.0 us) -- its 2 688 single-wavefront tile workgroups, each holding its LDS key set, take most of the workgroup slots, and
     // sphere-tracing workgroups dispatched behind them start when the tiles are done: the launch took the SUM of its parts.
-    static const int tiles_first_env = nvbx_knob_mark_tiles_first(getenv("NVBX_MARK_TILES_FIRST"));
-    const bool tiles_first = tiles_first_env >= 0 ? tiles_first_env != 0 : NB == 1;
+    const bool tiles_first = m->knobs.mark_tiles_first >= 0 ? m->knobs.mark_tiles_first != 0 : NB == 1;
     if (tiles_first) st.tr.n_tile_wg = st.tiles;
     if (st.fused && !st.has_color) m->pending_marking_args(&st.tr.n_mark_wg, &st.ea, NB == 1);
     if (st.fused && st.has_color) {
@@ -342,11 +341,7 @@ static int depth_step_before_mark_view(nvbx_mapper* m, FrameSet<Img, NB>& fs, De
 }
 // a launch grid sized from the count the GPU last reported keeps a margin over it: 25 % + 64 is what a view that grows while exploring needs
 // (NVBX_GRID_MARGIN="percent,blocks": A/B only -- tools/env_ab.sh)
-static int64_t with_grid_margin(int64_t n) {
-  struct Margin { int pct, blocks; Margin() { nvbx_knob_grid_margin(getenv("NVBX_GRID_MARGIN"), &pct, &blocks); } };
-  static const Margin mg;
-  return n + n * mg.pct / 100 + mg.blocks;
-}
+static int64_t with_grid_margin(const nvbx_mapper* m, int64_t n) { return n + n * m->knobs.grid_margin_pct / 100 + m->knobs.grid_margin_blocks; }
 // step 2: between the two launches -- the host-side steps of the held-back calls, then the sizes of the TSDF-update part
 template <typename Sensor, int NB>
 static int depth_step_between(nvbx_mapper* m, DepthSteps<NB>& st) {
@@ -365,14 +360,13 @@ static int depth_step_between(nvbx_mapper* m, DepthSteps<NB>& st) {
   // grid-stride over the view list: exactly the 1024 workgroups that are resident together (4 per CU)
   // (a camera BATCH: 512 -- its fused launch is residency-bound, 1 024 eight-wavefront workgroups resident, and 1 024 TSDF workgroups in front kept the colour
   //  part waiting: 4 / 8 cameras 0.0382 / 0.0560 -> 0.0365 / 0.0547 ms per step, tools/fused_grid_sweep.sh)
-  static const int grid_cap_env = nvbx_knob_integ_grid(getenv("NVBX_INTEG_GRID"));    // (env: tools/integ_grid_sweep.sh, tools/fused_grid_sweep.sh)
-  const int grid_cap = grid_cap_env > 0 ? grid_cap_env : (NB > 1 ? 512 : 1024);
+  const int grid_cap = m->knobs.integ_grid > 0 ? m->knobs.integ_grid : (NB > 1 ? 512 : 1024);    // (NVBX_INTEG_GRID: tools/integ_grid_sweep.sh, tools/fused_grid_sweep.sh)
   // ... or fewer when the view is smaller: sized from the view count of the last launch the GPU has finished (pinned host memory, not
   // waited for) + 25 % + 64; a hint only -- the kernel grid-strides over whatever the count turns out to be
   // (no launch finished yet -- a new or just cleared map: the full grid; sized for 64 blocks, the first scans of a LiDAR map, enqueued faster
   //  than the first finishes, took 1.7 ms each for their 112 k blocks: the whole of round 4's first "exploring" LiDAR figure)
   const int64_t n_hint = std::max<int64_t>(0, __atomic_load_n(&m->h_mirror[2], __ATOMIC_RELAXED));
-  const int64_t n_want = with_grid_margin(n_hint);
+  const int64_t n_want = with_grid_margin(m, n_hint);
   const int64_t want = n_hint == 0 ? (int64_t)grid_cap : ((n_want + 7) / 8) * 8;
   st.grid = (int)std::max<int64_t>(8, std::min<int64_t>(std::min<int64_t>(m->capacity, grid_cap), want));
   st.spec_lanes = (int32_t)std::min<int64_t>(64, (n_want + st.grid - 1) / st.grid);
@@ -383,14 +377,13 @@ static int depth_step_between(nvbx_mapper* m, DepthSteps<NB>& st) {
 template <int NB>
 static void depth_step_fused_riders(nvbx_mapper* m, DepthSteps<NB>& st) {
   st.n_edt = 0; st.ea_edt = m->held.edt_args;
-  static const int edt_riders = nvbx_knob_edt_riders(getenv("NVBX_EDT_RIDERS"));      // (A/B; a multiple of 8, at least 8)
-  if (m->held.edt_pending) { st.n_edt = edt_riders; m->held.edt_pending = false; }
+  if (m->held.edt_pending) { st.n_edt = m->knobs.edt_riders; m->held.edt_pending = false; }      // (NVBX_EDT_RIDERS -- A/B; a multiple of 8, at least 8)
   st.cand = st.tr.cand;
   st.cand_idx = st.tr.cand_cnt_idx;
   const int64_t c_hint = std::max<int64_t>(0, __atomic_load_n(&m->h_mirror[3], __ATOMIC_RELAXED));         // candidates of the last colour frame the GPU has finished
   // (no colour frame: update + distance transform only; no colour launch finished yet -- a new or just cleared map: as many as the TSDF part)
-  static const int color_cap = nvbx_knob_color_grid(getenv("NVBX_COLOR_GRID"));      // (A/B: workgroups of the colour part, tools/fused_grid_sweep.sh)
-  st.cgrid = !st.has_color ? 0 : (int)std::max<int64_t>(8, std::min<int64_t>(std::min<int64_t>(m->capacity, color_cap), c_hint == 0 ? (int64_t)st.grid : ((with_grid_margin(c_hint) + 7) / 8) * 8));
+  const int color_cap = m->knobs.color_grid;      // (NVBX_COLOR_GRID -- A/B: workgroups of the colour part, tools/fused_grid_sweep.sh)
+  st.cgrid = !st.has_color ? 0 : (int)std::max<int64_t>(8, std::min<int64_t>(std::min<int64_t>(m->capacity, color_cap), c_hint == 0 ? (int64_t)st.grid : ((with_grid_margin(m, c_hint) + 7) / 8) * 8));
   // a held-back union step of the multi-GPU exchange (nvbx_mark_esdf_dirty_gathered_deferred) rides here in eight workgroups: the peers'
   // blocks become ESDF-dirty for the NEXT marking pass (its own marking launch, or a ride in the colour launch, would be a third launch;
   // beside this frame's view marking it would meet blocks that launch is just allocating -- DESIGN.md 6.1)
@@ -473,8 +466,7 @@ static int integrate_depth_pair_impl(nvbx_mapper* ma, FrameSet<Img, 1> fa, nvbx_
   if (sb.fused) depth_step_fused_riders<1>(mb, sb);
   // (the second mapper of a pair is the foreground mapper: a few blocks.  Its distance transform gets 64 workers instead of 256 -- they grid-stride, and the
   //  launch is residency-bound: every idle 8-wavefront workgroup holds a slot for ~1.5 us)
-  static const int pair_b_edt = nvbx_knob_pair_b_edt_riders(getenv("NVBX_PAIR_B_EDT_RIDERS"));
-  if (sb.n_edt > pair_b_edt) sb.n_edt = pair_b_edt;
+  if (sb.n_edt > mb->knobs.pair_b_edt_riders) sb.n_edt = mb->knobs.pair_b_edt_riders;      // (NVBX_PAIR_B_EDT_RIDERS, the second mapper's)
   // ONE pixel type for the pair: whichever mapper holds a colour frame, else rgb8; a mapper that holds none passes an empty set of that type
   if (sa.has_color && sb.has_color && sa.col.fs.index() != sb.col.fs.index()) { set_error("nvbx_integrate_depth_pair: colour frames of two encodings"); return NVBX_E_INVALID; }
   auto fused_args = [&](nvbx_mapper* m, const FrameSet<Img, 1>& f, const DepthSteps<1>& st, const auto& lead_fs) {
@@ -609,7 +601,7 @@ static bool pair_colour_encodings_differ(const nvbx_mapper* ma, const nvbx_mappe
 extern "C" int nvbx_integrate_depth_pair(nvbx_mapper* ma, const float* depth_a_dev, nvbx_mapper* mb, const float* depth_b_dev, int32_t rows, int32_t cols,
                                          const float T_L_C[16], const nvbx_camera* camera) {
   if (const int rc = nvbx_camera_frame_refused("nvbx_integrate_depth_pair", ma && mb && ma != mb && depth_a_dev && depth_b_dev && T_L_C && camera, "two different mappers, ", rows, cols, camera)) return rc;
-  static const int pair_on = nvbx_knob_switch(getenv("NVBX_DEPTH_PAIR"));       // (A/B: 0 = always the two separate calls)
+  const bool pair_on = ma->knobs.depth_pair && mb->knobs.depth_pair;       // (NVBX_DEPTH_PAIR -- A/B: 0 in either mapper = always the two separate calls)
   if (!pair_on || ma->device != mb->device || ma->stream != mb->stream || !pair_can_fuse(ma) || !pair_can_fuse(mb) ||
       pair_colour_encodings_differ(ma, mb)) {
     const int rc = nvbx_integrate_depth(ma, depth_a_dev, rows, cols, T_L_C, camera); if (rc) return rc;

@@ -284,6 +284,12 @@ class Mapper:
         (staged=True is the default here as in C and C++ -- ADVICE r04.)  An image in a ColorFrame is never copied, in either form."""
         self._check(self.lib.nvbx_mapper_set_color_deferral(self._h, (2 if staged else 1) if enable else 0))
 
+    def reload_knobs(self):
+        """Read the library's NVBX_* environment variables again for this mapper (they are read at creation and kept per mapper).
+        Held-back work is carried out first, under the old settings.  NVBX_MAX_BLOCKS, NVBX_COLOR_DEFERRAL, NVBX_SIDE_STREAM and NVBX_DEFER_EDT
+        apply at creation only."""
+        self._check(self.lib.nvbx_mapper_reload_knobs(self._h))
+
     # -- ground plane (MultiMapper::ground_plane_estimator())
     def tsdf_zero_crossings(self, min_z_m, max_z_m):
         """xyz [N, 3] float32 of the TSDF's upward zero crossings with height in [min_z_m, max_z_m], sorted by (x, y, z)."""

@@ -1,5 +1,5 @@
-"""The scripted workload of tests/test_gpu_launch_geometry.py, in a process of its own (the NVBX_* knobs are read once per process, so every setting
-needs a fresh one):  python tests/launch_geometry_child.py INPUTS.npz OUT.npz
+"""The scripted workload of tests/test_gpu_launch_geometry.py, in a process of its own (a mapper reads the NVBX_* knobs when it is created, so one process
+could hold every setting; a process per setting also keeps a fault of one from the others):  python tests/launch_geometry_child.py INPUTS.npz OUT.npz
 
 `schedule` drives five kinds of mapper through one fixed sequence of calls and takes a snapshot of every mapper after every phase (a later decay or
 clear could hide an earlier error):

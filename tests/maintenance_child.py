@@ -1,6 +1,6 @@
-"""The part of tests/test_gpu_maintenance_drawn.py that needs a process of its own: at the default grid every wavefront of k_decay holds ONE block
+"""The part of tests/test_gpu_maintenance_drawn.py that runs in a process of its own: at the default grid every wavefront of k_decay holds ONE block
 until a map exceeds 32768 blocks, so the bookkeeping that keeps 64 blocks per wavefront in lanes never runs on a small map.  NVBX_DECAY_GRID is
-read once per process; with NVBX_DECAY_GRID=1 in the environment the decay launch is one workgroup, whose eight wavefronts take 64 blocks each per
+read when a mapper is created (the process of its own keeps a fault away from the rest of the file); with NVBX_DECAY_GRID=1 in the environment the decay launch is one workgroup, whose eight wavefronts take 64 blocks each per
 round.  Run as  python tests/maintenance_child.py : case A (the weight ladder, all four variants) and the five-round conservation sequence against
 the model, then the marker on stdout."""
 import os

@@ -1,5 +1,5 @@
-"""Child process of tests/test_gpu_render_lanes.py: NVBX_RENDER_LANES is read once per process, so every lanes-per-ray setting renders the
-same cases in a process of its own and saves what it got.  Usage: python render_lanes_child.py OUT.npz"""
+"""Child process of tests/test_gpu_render_lanes.py: NVBX_RENDER_LANES is read when a mapper is created; every lanes-per-ray setting renders the
+same cases in a process of its own (a fault under one setting stays there) and saves what it got.  Usage: python render_lanes_child.py OUT.npz"""
 import os
 import sys
 

@@ -3,7 +3,7 @@ order-free"; 5.1: no result depends on a knob).  Most launches size their grid f
 waited for -- and grid-stride over the real count, so whether the paths a short grid takes (the late record fetch past `spec_lanes`, many blocks per
 workgroup, k_decay's rounds of 64 blocks per wave with one workgroup, the marking pass's two-level reset with few workers) run in a test is left to
 timing.  Here every NVBX_* knob that moves a grid, a rider count or the launch structure is set to small and odd values, one child process per
-setting (tests/launch_geometry_child.py: the knobs are read once per process), and every snapshot of the scripted schedule must equal the
+setting (tests/launch_geometry_child.py: a mapper reads the knobs at creation; a child also keeps a fault to itself), and every snapshot of the scripted schedule must equal the
 default run's byte for byte.  The default run is itself run twice (a difference there is a race) and checked against the CPU checker: every
 layer, cleared list, slice and mesh (vertices, normals, colours, triangles) of every snapshot, and the point queries against the float64 query model
 (tests/query_independent.py) evaluated on the checker's blocks."""

@@ -148,10 +148,15 @@ def test_scores_on_the_other_launch_shapes(room, frames, monkeypatch):
     x = mixed_cloud(1200, cloud, T_true)
     poses, kinds = mixed_poses(2049, T_true, seed=1)
     c0, r0 = check_against_model(room, x, poses, kinds)
-    for chunks in ("1", "3"):
-        monkeypatch.setenv("NVBX_SCORE_CHUNKS", chunks)
-        c, r = _gpu_records(*room.score_poses(x, poses))
-        assert np.array_equal(c, c0) and np.array_equal(r, r0), chunks
+    try:         # (`room` is shared: a mapper keeps the knobs it last read)
+        for chunks in ("1", "3"):
+            monkeypatch.setenv("NVBX_SCORE_CHUNKS", chunks)
+            room.reload_knobs()
+            c, r = _gpu_records(*room.score_poses(x, poses))
+            assert np.array_equal(c, c0) and np.array_equal(r, r0), chunks
+    finally:
+        monkeypatch.undo()
+        room.reload_knobs()
 
 
 def test_options_replace_the_thresholds(room, frames):

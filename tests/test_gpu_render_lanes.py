@@ -1,6 +1,6 @@
 """Every lanes-per-ray instantiation of the render / ray-cast kernel (render.hip: 8, 4, 2 or 1 lanes march one ray and share its epilogue).
-The library picks by ray count -- 8 below 57 600 rays, 4 below 115 200, 2 above -- and NVBX_RENDER_LANES forces a value, read once per
-process: tests/render_lanes_child.py renders the same cases under each setting in a process of its own.  Each setting's results are held
+The library picks by ray count -- 8 below 57 600 rays, 4 below 115 200, 2 above -- and NVBX_RENDER_LANES forces a value, read when a mapper is
+created: tests/render_lanes_child.py renders the same cases under each setting in a process of its own.  Each setting's results are held
 against the colour frame's synthetic depth, the independent model, the colour layer and the point query's gradient, and all settings
 against each other bit for bit.  The unforced child covers the by-count choice on a 320 x 240 view (4 lanes) and 134 400 rays (2 lanes);
 the 1-lane child also casts more rays than the capped grid holds, so the ray list's grid-stride loop repeats."""

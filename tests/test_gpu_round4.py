@@ -115,8 +115,8 @@ def test_bench_line_carries_parity_and_mode():
 @pytest.mark.parametrize("knobs", [dict(), dict(NVBX_REPLAY_PAIR="0"), dict(NVBX_ESDF_ONLY_CARRY="0"), dict(NVBX_REPLAY_PAIR="0", NVBX_ESDF_ONLY_CARRY="0")],
                          ids=["default", "no_replay_pair", "no_esdf_only_carry", "neither"])
 def test_fused_launches_stress_repeated_runs(knobs):
-    """The randomised call patterns of tests/test_gpu_pipeline.py (three seeds), twenty repetitions each in ONE process per knob setting (the knobs
-    are read once per process), bit-identity with the classic mapper asserted in every repetition: an intermittent race between the riders of
+    """The randomised call patterns of tests/test_gpu_pipeline.py (three seeds), twenty repetitions each in ONE process per knob setting (every mapper
+    of the process reads the knobs as it is created), bit-identity with the classic mapper asserted in every repetition: an intermittent race between the riders of
     the fused launches shows as a failure in SOME repetition (65a453c: 5 of 8)."""
     code = (
         "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"

@@ -3,7 +3,7 @@
 * `k_mark_view_grid` / `k_scan_view_grid` / `k_resolve_view` are the default and every LiDAR test runs through them; here the same
   parity tests run once more (a) with the hash path (`NVBX_LIDAR_VIEW_GRID=0`: `k_mark_view<Lidar>`) and (b) with a box of 12 blocks reach
   (`NVBX_VIEW_GRID_REACH=12`: most of a 25-40 m scan lies OUTSIDE the box and takes `mark_block`, block by block, beside the grid) -- the switches are
-  read once per process, hence subprocesses;
+  read when a mapper is created; the subprocesses set them for a whole run of tests/test_lidar.py;
 * `nvbx_esdf_slice_to_host` (size + image written into pinned host memory by the slicing launch itself) against the two-step device slice, through
   growth of the layer, the capacity error and an empty layer."""
 import ctypes as C

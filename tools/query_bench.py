@@ -1,7 +1,7 @@
 """Throughput of the interpolated point queries (nvbx_query_points).
 
 The room map of the 640x480 200-pose loop (synthetic.sequence) is built once, for a 3-D ESDF mapper and a default 2-D one, and saved;
-then child processes -- one per setting of NVBX_QUERY_DEDUP (read once per process), alternating, each under its own time limit --
+then child processes -- one per setting of NVBX_QUERY_DEDUP (read when the child's mappers are created), alternating, each under its own time limit --
 load the maps and time the queries with device events over >= --seconds of back-to-back calls after warm-up:
   layers: TSDF (3-D mapper), ESDF 3-D, ESDF 2-D;  distributions: coherent (4 096 clusters of points in 0.5 m boxes in the observed
   free space, cluster after cluster) and uniform (over the map's block AABB);  n = 2^20 and 2^24.

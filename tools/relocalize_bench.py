@@ -108,13 +108,16 @@ def main():
         err_t = float(np.linalg.norm(res.align.T64[:3, 3] - T_true[:3, 3].astype(np.float64)))
         score = lambda: m.score_poses(depth, poses, cam=cam, out=rec_out, **kw)
         # (the span is the kernel's; the call by events also holds the memset that zeroes the records of a split launch)
-        os.environ.pop("NVBX_SCORE_CHUNKS", None)
+        # (a mapper keeps the knobs it last read: reload_knobs after each change of the environment)
+        os.environ.pop("NVBX_SCORE_CHUNKS", None); m.reload_knobs()
         span_us, spans = score_span_us(m, score, a.calls); score_call_us = event_us(torch, score, a.calls)
-        os.environ["NVBX_SCORE_CHUNKS"] = "1"
-        whole_us, _ = score_span_us(m, score, a.calls); whole_call_us = event_us(torch, score, a.calls)
-        os.environ["NVBX_SCORE_CHUNKS"] = "1024"
-        split_us, _ = score_span_us(m, score, a.calls); split_call_us = event_us(torch, score, a.calls)
-        os.environ.pop("NVBX_SCORE_CHUNKS", None)
+        try:
+            os.environ["NVBX_SCORE_CHUNKS"] = "1"; m.reload_knobs()
+            whole_us, _ = score_span_us(m, score, a.calls); whole_call_us = event_us(torch, score, a.calls)
+            os.environ["NVBX_SCORE_CHUNKS"] = "1024"; m.reload_knobs()
+            split_us, _ = score_span_us(m, score, a.calls); split_call_us = event_us(torch, score, a.calls)
+        finally:
+            os.environ.pop("NVBX_SCORE_CHUNKS", None); m.reload_knobs()
         # the blocks the launch must read at least: the base corners' blocks of every transformed point, a pose chunk at a time
         keys = []
         for lo in range(0, K, 1024):

@@ -1,7 +1,7 @@
 """Time of rendering and ray casts (nvbx_render_view / nvbx_cast_rays) on the bench's room map.
 
 The room map of the 640x480 200-pose loop (synthetic.sequence) is built once and saved; then child processes -- one per setting of
-NVBX_RENDER_LANES (read once per process; 0 = the library's choice by ray count), alternating, each under its own time limit -- load the map
+NVBX_RENDER_LANES (read when the child's mapper is created; 0 = the library's choice by ray count), alternating, each under its own time limit -- load the map
 and time, after warm-up and over >= --seconds of back-to-back calls each:
   view_160x120_depth       640 x 480 at subsampling 4, depth only -- next to its yardstick `k_sphere_trace`, the stand-alone sphere tracing of
                            integrate_color at the same pose on the same mapper in classic order (set_color_deferral(0)): the same march over

@@ -622,6 +622,52 @@ int nvbx_frontier_clusters(nvbx_mapper* m, float min_weight, float free_distance
 int nvbx_view_gain(nvbx_mapper* m, const float* T_L_C_dev, int32_t n_views, const nvbx_camera* camera, int32_t subsampling,
                    float max_range_m, float min_weight, float free_distance_m, nvbx_gain* gains_dev);
 
+/* ---- cost field and paths (which goal can be reached, and how far is the drive; SEMANTICS.md "Cost field and paths") -----------------
+ * Over a distance image image_dev[rows][cols] (DEVICE memory, f32, row = y, col = x) as nvbx_esdf_slice_to_image and
+ * nvbx_esdf_slice_combined_to_image write it, with their unknown_value -- or any image of that form.  `options` is host memory.  A pixel with
+ * stored value v is UNKNOWN iff fabsf(v - unknown_value) < 1e-2f (nvbx_occupancy_grid_from_slice's test), TRAVERSABLE iff it is not unknown,
+ * v > 0 and v >= robot_radius_m (a NaN v is not), and with allow_unknown != 0 an unknown pixel is traversable too.  A traversable pixel's
+ * penalty: t = inflation_radius_m - v; 0 if !(t > 0); else u = penalty_per_m * t and max_penalty if !(u < (float)max_penalty), else
+ * (int32_t)u; a traversable unknown pixel's is unknown_penalty.  A move goes from a traversable pixel p to a traversable 8-neighbour q inside
+ * the image, diagonally only if both pixels that share an edge with p and q are traversable, and costs B + pen(p) + pen(q), B = 10 along an
+ * axis, 14 diagonally.  Both calls read the image only and write their outputs only: the map is untouched, held-back work stays held back.
+ * On a refusal (NVBX_E_INVALID, nvbx_last_error set) nothing is launched and the mapper stays usable.  Refused by both: a NULL mapper, image,
+ * options or field; rows or cols <= 0 or rows x cols > 2^22; a NaN or negative robot_radius_m, inflation_radius_m or penalty_per_m; a NaN
+ * unknown_value; max_penalty or unknown_penalty outside 0 .. 200 (a step then costs at most 414, and 414 x 2^22 < 2^31: no sum overflows).
+ * nvbx_cost_field: cost_dev[rows][cols] = the least total cost of a move sequence from any accepted source to the pixel: 0 at a source,
+ *   NVBX_COST_UNREACHED where there is none and at every pixel that is not traversable.  sources_rc_dev[n_sources][2] = (row, col), DEVICE
+ *   memory; one outside the image or on a pixel that is not traversable is ignored, duplicates are harmless, none accepted: all UNREACHED.
+ *   *accepted_dev (NULL: not wanted) = the number of accepted entries.  The field is the unique fixed point of an integer relaxation and
+ *   bit-specified.  The call enqueues relaxation rounds in batches on the mapper's stream and WAITS for the device after each batch to read
+ *   one counter: it returns with the field complete (everything enqueued on the stream before it has then run as well).  NVBX_E_DEVICE with
+ *   a message if rows x cols rounds did not reach the fixed point, which the algorithm excludes.  Also refused: n_sources < 0; a NULL
+ *   sources_rc_dev with n_sources > 0.
+ * nvbx_trace_paths: for each of n_starts pixels starts_rc_dev[i] = (row, col) the path that descends cost_dev, a field of this image and
+ *   these options: it begins at the start; at p with 0 < G(p) < UNREACHED the next pixel is the FIRST allowed neighbour q in the order (drow,
+ *   dcol) = (0,1) (1,0) (0,-1) (-1,0) (1,1) (1,-1) (-1,-1) (-1,1) with G(q) + c(p, q) == G(p); it ends at the first pixel with G = 0, which
+ *   is included.  path_rc_dev[i][capacity][2] receives the pixels, length_dev[i] their number -- also when it exceeds `capacity`; pixels from
+ *   the capacity on are written nowhere -- 0 for a start outside the image or UNREACHED, -1 if no neighbour satisfies the equation (the field
+ *   is not one of this image and these options; never an error code).  One lane per start, at most rows x cols steps, asynchronous on the
+ *   mapper's stream.  Also refused: n_starts < 0; capacity < 0; a NULL starts_rc_dev, path_rc_dev or length_dev with n_starts > 0.
+ *   n_starts == 0 launches nothing. */
+#define NVBX_COST_UNREACHED 0x7fffffff
+typedef struct {
+  float robot_radius_m;        /* 0.25 */
+  float inflation_radius_m;    /* 0.75 */
+  float penalty_per_m;         /* 100 */
+  float unknown_value;         /* 1000: what the slice call was given */
+  int32_t max_penalty;         /* 200 */
+  int32_t unknown_penalty;     /* 50 */
+  int32_t allow_unknown;       /* 0 */
+  int32_t pad;
+} nvbx_cost_options;            /* 32 bytes; offsets 0 4 8 12 16 20 24 28 */
+void nvbx_default_cost_options(nvbx_cost_options* options);
+int nvbx_cost_field(nvbx_mapper* m, const float* image_dev, int32_t rows, int32_t cols, const nvbx_cost_options* options,
+                    const int32_t* sources_rc_dev, int32_t n_sources, int32_t* cost_dev, int32_t* accepted_dev);
+int nvbx_trace_paths(nvbx_mapper* m, const float* image_dev, int32_t rows, int32_t cols, const nvbx_cost_options* options,
+                     const int32_t* cost_dev, const int32_t* starts_rc_dev, int32_t n_starts, int32_t* path_rc_dev, int32_t capacity,
+                     int32_t* length_dev);
+
 /* ---- map file (Mapper::saveLayerCake(path) -> bool, loadMap(path) -> bool: nvblox_node.cpp:1663-1668,1698-1703) -----------------
  * A path ending in .nvblx is written as an SQLITE database, like the reference's layer cake: table layers(layer_type, voxel_size,
  * block_size, voxel_bytes, num_blocks) + one table <layer_type>_blocks(index_x, index_y, index_z, data BLOB) per layer (tsdf_layer,

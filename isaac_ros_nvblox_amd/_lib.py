@@ -107,6 +107,12 @@ class Gain(C.Structure):
     _fields_ = [("rays", C.c_int32), ("unknown_samples", C.c_int32), ("free_samples", C.c_int32), ("rays_hit", C.c_int32)]
 
 
+class CostOptions(C.Structure):
+    """nvbx_cost_options (32 bytes); nvbx_default_cost_options fills it"""
+    _fields_ = [("robot_radius_m", C.c_float), ("inflation_radius_m", C.c_float), ("penalty_per_m", C.c_float), ("unknown_value", C.c_float),
+                ("max_penalty", C.c_int32), ("unknown_penalty", C.c_int32), ("allow_unknown", C.c_int32), ("pad", C.c_int32)]
+
+
 class AlignOptions(C.Structure):
     """nvbx_align_options (56 bytes); nvbx_default_align_options fills it"""
     _fields_ = [("max_iterations", C.c_int32), ("subsampling", C.c_int32), ("min_weight", C.c_float), ("huber_delta_m", C.c_float),
@@ -245,6 +251,9 @@ SIGNATURES = {
     "nvbx_find_frontiers": (C.c_int, [_vp, _f, _f, _i32, _pi32, _vp, _vp, _vp, _i64, _vp]),
     "nvbx_frontier_clusters": (C.c_int, [_vp, _f, _f, _i32, _pi32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "nvbx_view_gain": (C.c_int, [_vp, _vp, _i32, C.POINTER(Camera), _i32, _f, _f, _f, _vp]),
+    "nvbx_default_cost_options": (None, [C.POINTER(CostOptions)]),
+    "nvbx_cost_field": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(CostOptions), _vp, _i32, _vp, _vp]),
+    "nvbx_trace_paths": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(CostOptions), _vp, _vp, _i32, _vp, _i32, _vp]),
     "nvbx_default_align_options": (None, [C.POINTER(AlignOptions)]),
     "nvbx_align_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp]),
     "nvbx_align_depth": (C.c_int, [_vp, _vp, _i32, _i32, _vp, C.POINTER(Camera), C.POINTER(AlignOptions), _vp]),

@@ -2,7 +2,8 @@
  * tests/test_knobs.py compiles THIS file with gcc and checks the mapping on the CPU).  Each nvbx_knob_* function takes the variable's value (NULL when
  * unset) and returns what the library uses.  A missing, malformed or out-of-range value gives the default, so no setting can size a launch at zero
  * or drop work; rider counts are rounded up to a multiple of 8.  No knob changes a result, only which workgroup does what.
- * struct nvbx_knobs holds one mapper's settings; nvbx_knobs_read fills it, and names every variable there and nowhere else. */
+ * struct nvbx_knobs holds one mapper's settings; nvbx_knobs_read fills it, and names every variable there and nowhere else.  The cost field's two
+ * knobs have a struct and a read of their own in front of it (nvbx_plan_knobs). */
 #ifndef NVBX_KNOBS_H_
 #define NVBX_KNOBS_H_
 #include <errno.h>
@@ -83,6 +84,17 @@ static inline int nvbx_knob_view_grid_max_mb(const char* s) { return nvbx_knob_i
 static inline int nvbx_knob_max_blocks(const char* s) { return nvbx_knob_int(s, 0, 1, INT_MAX); }
 /* NVBX_FRAME_POOL_MAX: frames per image size in the library's pool (process-wide, frames.hip); an integer below 2 gives 2 */
 static inline int nvbx_knob_frame_pool_max(const char* s) { const int v = nvbx_knob_int(s, 8, INT_MIN, 1 << 16); return v < 2 ? 2 : v; }
+
+/* The cost field's knobs (plan.hip), a struct and a read of their own beside the mapper's: filled where nvbx_knobs is, through the
+ * same lookup.  NVBX_PLAN_ROUNDS_PER_WAIT: relaxation rounds enqueued between two reads of the changed counter; NVBX_PLAN_TILE_SWEEPS: sweeps a
+ * workgroup makes over its tile before it stores it and asks for another round.  No result depends on either. */
+static inline int nvbx_knob_plan_rounds_per_wait(const char* s) { return nvbx_knob_int(s, 16, 1, 1024); }
+static inline int nvbx_knob_plan_tile_sweeps(const char* s) { return nvbx_knob_int(s, 64, 1, 4096); }
+struct nvbx_plan_knobs { int rounds_per_wait, tile_sweeps; };
+static inline void nvbx_plan_knobs_read(struct nvbx_plan_knobs* k, const char* (*lookup)(const char* name)) {
+  k->rounds_per_wait = nvbx_knob_plan_rounds_per_wait(lookup("NVBX_PLAN_ROUNDS_PER_WAIT"));
+  k->tile_sweeps = nvbx_knob_plan_tile_sweeps(lookup("NVBX_PLAN_TILE_SWEEPS"));
+}
 
 /* One mapper's knobs: filled at nvbx_mapper_create and again by nvbx_mapper_reload_knobs.  Four of them shape the mapper at creation and are
  * not applied to a live one: max_blocks, side_stream, color_deferral, defer_edt (include/nvblox_hip.h). */

@@ -113,6 +113,7 @@ struct nvbx_mapper {
   // The NVBX_* environment knobs (nvbx_knobs.h), read at nvbx_mapper_create and again by nvbx_mapper_reload_knobs: every launch-geometry and A/B
   // decision of this mapper reads them here.  max_capacity, use_side, color_deferral / color_staging and defer_edt take their value at creation only.
   nvbx_knobs knobs{};
+  nvbx_plan_knobs plan_knobs{}; // ... and the cost field's two (plan.hip), read with them
   bool use_side = false;        // knobs.side_stream at creation (NVBX_SIDE_STREAM=1 enables)
   bool side_pending = false;    // ESDF work enqueued on `side` that `stream` has not waited for yet
   bool main_dirty = true;       // non-colour work enqueued on `stream` since ev_main was recorded
@@ -162,6 +163,8 @@ struct nvbx_mapper {
   nvbx::DevBuf merge_buf;
   // frontier scan (frontier.hip), -DNVBX_FRONTIER_TWO_PASS variant only: 128 bytes of voxel classes per slot; the product's single pass needs none
   nvbx::DevBuf frontier_scratch;
+  // cost field (plan.hip): a 64-byte head of counters, the class word of every pixel and the two sets of active-tile flags of the largest image so far
+  nvbx::DevBuf plan_scratch;
   // mesh arena
   float* mesh_vert = nullptr; float* mesh_nrm = nullptr; uint8_t* mesh_col = nullptr; int32_t* mesh_tri = nullptr;
   nvbx::MeshRecord* mesh_rec = nullptr;

@@ -36,6 +36,7 @@ PoseScore = collections.namedtuple("PoseScore", "points valid inliers conflicts 
 MERGE_OK, MERGE_EMPTY_SOURCE, MERGE_NO_OVERLAP = 0, 1, 2
 MERGE_STATUS_NAMES = {0: "OK", 1: "EMPTY_SOURCE", 2: "NO_OVERLAP"}
 MERGE_RESULT_BYTES = C.sizeof(_lib.MergeResult)
+COST_UNREACHED = 0x7fffffff      # NVBX_COST_UNREACHED: cost_field's value where no move sequence leads
 
 TSDF_DT = np.dtype([("distance", "<f4"), ("weight", "<f4")])
 COLOR_DT = np.dtype([("r", "u1"), ("g", "u1"), ("b", "u1"), ("pad", "u1"), ("weight", "<f4")])
@@ -1238,6 +1239,71 @@ class Mapper:
             self._h, ptr(p), n, C.byref(k), s, float(max_range_m) if max_range_m is not None else 0.0, mw, fd, ptr(g)), order=n > 0)
         self._hold("_keep_vg", [p])      # (the kernel reads the poses: they, and an uploaded copy, live until the next call)
         return g
+
+    # -- cost field and paths (nvbx_cost_field / nvbx_trace_paths; SEMANTICS.md "Cost field and paths")
+    def cost_options(self, **kw):
+        """nvbx_cost_options: the library's defaults with the given fields replaced (robot_radius_m, inflation_radius_m, penalty_per_m,
+        unknown_value, max_penalty, unknown_penalty, allow_unknown)."""
+        return _args.struct_options(_lib.CostOptions, self.lib.nvbx_default_cost_options, kw, "cost")
+
+    def cost_field(self, image_dev, sources_rc, out=None, accepted=None, **options):
+        """The integer cost-to-go field over a distance image (esdf_slice_image_device, esdf_slice_image_combined, or any (rows, cols) float32
+        image of that form) from the source pixels sources_rc ((n, 2) int32 (row, col), torch device tensor or numpy array; slice_pixels makes
+        them from metres): -> int32 [rows, cols] on the mapper's device, 0 at an accepted source, COST_UNREACHED where no move sequence leads
+        and on every pixel that is not traversable.  A source outside the image or on such a pixel is ignored.  options: see cost_options --
+        unknown_value must be the one the image was sliced with.  The call waits for the device (between batches of relaxation rounds) and
+        returns with the field complete; it reads the image only.  out: a preallocated int32 [rows, cols] tensor; accepted: an int32 [1]
+        device tensor that receives the number of accepted sources."""
+        torch = self._torch
+        img = self._image(image_dev, "image")
+        rows, cols = int(img.shape[0]), int(img.shape[1])
+        o = self.cost_options(**options)
+        src = _args.pixels2(sources_rc, self._cuda, "sources_rc")
+        cost, acc = _args.outputs((out, accepted) if out is not None or accepted is not None else None,
+                                  (("cost", (rows, cols), I32, False, True), ("accepted", (1,), I32, False, False)), self._cuda)
+        if cost is None:
+            cost = torch.empty((rows, cols), dtype=torch.int32, device=self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_cost_field(self._h, ptr(img, collapse=False), rows, cols, C.byref(o), ptr(src), int(src.shape[0]),
+                                                                   ptr(cost, collapse=False), ptr(acc)))
+        return cost
+
+    def trace_paths(self, image_dev, field, starts_rc, capacity, out=None, **options):
+        """The paths that descend `field` (cost_field of this image and these options) from the pixels starts_rc ((n, 2) int32 (row, col)):
+        -> (paths int32 [n, capacity, 2] of (row, col), lengths int32 [n]) on the mapper's device.  A path runs from its start to the first
+        pixel of cost 0, both included; lengths[i] is its number of pixels, also beyond `capacity` (pixels from the capacity on are not
+        written; rows past a path's end are left as they were), 0 for a start outside the image or unreached, -1 where the field does not
+        belong to the image.  Asynchronous.  out=(paths, lengths): preallocated tensors, nothing is allocated."""
+        torch = self._torch
+        img = self._image(image_dev, "image")
+        rows, cols = int(img.shape[0]), int(img.shape[1])
+        o = self.cost_options(**options)
+        f = _args.image(field, self._cuda, torch.int32, "field", "(rows, cols)", convert=False)
+        if tuple(f.shape) != (rows, cols):
+            raise ValueError("field must have the image's shape %s, got %s" % ((rows, cols), tuple(f.shape)))
+        st = _args.pixels2(starts_rc, self._cuda, "starts_rc")
+        n, cap = int(st.shape[0]), int(capacity)
+        if cap < 0:
+            raise ValueError("capacity must be >= 0")
+        paths, lengths = _args.outputs(out, (("paths", (n, cap, 2), I32, True, True), ("lengths", (n,), I32, True, True)), self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_trace_paths(self._h, ptr(img, collapse=False), rows, cols, C.byref(o), ptr(f, collapse=False), ptr(st), n,
+                                                                    ptr(paths, collapse=False), cap, ptr(lengths)), order=n > 0)
+        self._hold("_keep_tp", [img, f, st])      # (the kernel reads them: they, and uploaded copies, live until the next call)
+        return paths, lengths
+
+    def slice_pixels(self, points_xy, aabb):
+        """Metres -> pixels of the ESDF slice image that came with `aabb` (esdf_slice_image_device / esdf_slice_image / ..._combined):
+        points_xy (n, 2) or (n, 3) (z ignored) -> int32 numpy [n, 2] of (row, col); col = floor(x / voxel_size) - lrint(aabb[0] / voxel_size),
+        row likewise with y and aabb[1], in float32 (the slice's AABB starts at a block's min corner, so the second term is a whole number of
+        voxels).  A point outside the image gives a pixel outside it, which cost_field and trace_paths ignore.  No kernel, host only."""
+        p = np.asarray(points_xy, np.float32)
+        p = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 2)
+        if p.shape[1] not in (2, 3):
+            raise ValueError("points_xy must be (n, 2) or (n, 3), got %s" % (p.shape,))
+        vs = np.float32(self.params.voxel_size)
+        a = np.asarray(aabb, np.float32).reshape(-1)
+        col = np.floor(p[:, 0] / vs).astype(np.int64) - np.int64(np.rint(a[0] / vs))
+        row = np.floor(p[:, 1] / vs).astype(np.int64) - np.int64(np.rint(a[1] / vs))
+        return np.stack([row, col], 1).astype(np.int32)
 
     def mesh(self):
         """Mesh of the last update_color_mesh: dict block index tuple -> dict(vertices, normals, colors, triangles)."""

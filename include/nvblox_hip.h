@@ -668,6 +668,60 @@ int nvbx_trace_paths(nvbx_mapper* m, const float* image_dev, int32_t rows, int32
                      const int32_t* cost_dev, const int32_t* starts_rc_dev, int32_t n_starts, int32_t* path_rc_dev, int32_t capacity,
                      int32_t* length_dev);
 
+/* ---- elevation and traversability (how high is the ground here, can the robot stand here, how far is the next place where it cannot;
+ *      SEMANTICS.md "Elevation and traversability") -------------------------------------------------------------------------------------
+ * Per-column products of the TSDF layer, pixel-aligned with the slice image: pixel (r, c) is the voxel column gx = x0 + c, gy = y0 + r in
+ * global voxel coordinates g = 8 block + v (row = y, col = x), the band is gz in [z_lo, z_hi], both included.  All image pointers are
+ * DEVICE memory, row-major [rows][cols]; `options` is host memory.  Both calls are for TSDF mappers, read only, asynchronous on the
+ * mapper's stream with no host wait inside, and leave held-back work held back.  On a refusal (NVBX_E_INVALID, nvbx_last_error set)
+ * nothing is launched and the mapper stays usable.
+ * nvbx_elevation_map: a voxel with stored {d, w} is OBSERVED iff its block is allocated and carries the TSDF layer, w >= min_weight and
+ *   d == d (a NaN weight or distance is not observed), SOLID iff observed and d <= 0, FREE iff observed and d > 0, all in f32.  With zt =
+ *   the largest gz of the band whose voxel is solid, status_dev = NVBX_ELEV_UNKNOWN: no observed voxel in the band; NVBX_ELEV_SURFACE: zt
+ *   exists, zt + 1 <= z_hi and voxel zt + 1 is observed (then free); NVBX_ELEV_BLOCKED: zt exists without that (the solid reaches the
+ *   band's top, or what lies above it is unobserved); NVBX_ELEV_VOID: observed voxels, none solid.  height_dev of a SURFACE pixel, with
+ *   d0 = d(zt), d1 = d(zt + 1) and vs the voxel size: (((float)bz * (8 vs) + (float)vz * vs) + vs * 0.5f) + vs * (-d0 / (d1 - d0)), bz =
+ *   zt >> 3, vz = zt & 7, in f32 in this order without contraction (nvbx_tsdf_zero_crossings' expression); of every other pixel:
+ *   unknown_value.  Both images are fully written and bit-specified; an empty map gives all UNKNOWN.  Refused: a NULL mapper or output;
+ *   an occupancy mapper; rows or cols <= 0 or rows x cols > 2^22; z_hi < z_lo or z_hi - z_lo >= 1024; a box that leaves [-2^23, 2^23)
+ *   voxels on an axis (the addressable blocks times 8); a NaN min_weight or unknown_value.
+ * nvbx_traversability: over such a pair of images (of this call or drawn by the caller; the map is not read).  A pixel is KNOWN iff its
+ *   status is SURFACE -- the status decides, no test on the height.  All arithmetic f32 in the order written, vs = the mapper's voxel
+ *   size.  n_known(p) = the known pixels among the 3 x 3 around p inside the image, p included.  step(p), p known = the largest
+ *   fabsf(h(p) - h(q)) over the known 8-neighbours q (none: 0).  gx(p), p known = (h(r, c+1) - h(r, c-1)) / (2.0f * vs) if both are
+ *   known, else (h(r, c+1) - h(p)) / vs if the right one is, else (h(p) - h(r, c-1)) / vs if the left one is, else 0; gy(p) likewise
+ *   along rows; slope2 = gx * gx + gy * gy.  step and slope2 of a pixel that is not known are 0.  class_dev = NVBX_TERRAIN_UNKNOWN:
+ *   status UNKNOWN, and VOID with void_is_hazard == 0; NVBX_TERRAIN_HAZARD: status BLOCKED, VOID with void_is_hazard != 0, a known pixel
+ *   with !(step <= max_step_m) or !(slope2 <= max_slope_tan * max_slope_tan) or n_known < min_known; NVBX_TERRAIN_OK: every other known
+ *   pixel.  distance_dev, R = distance_radius_px: unknown_value on an UNKNOWN pixel, 0 on a HAZARD pixel; an OK pixel takes m = the least
+ *   dr * dr + dc * dc over the HAZARD pixels inside the image with dr * dr + dc * dc <= R * R and gets vs * sqrtf((float)m), or
+ *   vs * (float)(R + 1) if there is none (m is an integer minimum and the root correctly rounded: bit-specified whatever the order of
+ *   the search).  The distance image has the form nvbx_cost_field reads.  (With a distance image the first call, and any with more
+ *   rows x ceil(cols / 64) than every earlier one, grows a mapper-owned scratch buffer and waits for the stream once while it does.)  step_dev, slope2_dev and distance_dev may be NULL: not
+ *   wanted.  Refused: a NULL mapper, height_dev, status_dev, options or class_dev; rows / cols as above; a NaN or negative max_step_m
+ *   or max_slope_tan; a NaN unknown_value; min_known outside 1 .. 9; distance_radius_px outside 0 .. 32. */
+#define NVBX_ELEV_UNKNOWN 0
+#define NVBX_ELEV_SURFACE 1
+#define NVBX_ELEV_BLOCKED 2
+#define NVBX_ELEV_VOID 3
+#define NVBX_TERRAIN_UNKNOWN 0
+#define NVBX_TERRAIN_OK 1
+#define NVBX_TERRAIN_HAZARD 2
+typedef struct {
+  float max_step_m;            /* 0.10 */
+  float max_slope_tan;         /* 0.5 */
+  float unknown_value;         /* 1000: what nvbx_cost_field will be told */
+  int32_t min_known;           /* 5 */
+  int32_t void_is_hazard;      /* 0 */
+  int32_t distance_radius_px;  /* 15 */
+  int32_t pad[2];
+} nvbx_terrain_options;         /* 32 bytes; offsets 0 4 8 12 16 20 24 */
+void nvbx_default_terrain_options(nvbx_terrain_options* options);
+int nvbx_elevation_map(nvbx_mapper* m, int32_t x0, int32_t y0, int32_t rows, int32_t cols, int32_t z_lo, int32_t z_hi, float min_weight,
+                       float unknown_value, float* height_dev, uint8_t* status_dev);
+int nvbx_traversability(nvbx_mapper* m, const float* height_dev, const uint8_t* status_dev, int32_t rows, int32_t cols,
+                        const nvbx_terrain_options* options, uint8_t* class_dev, float* step_dev, float* slope2_dev, float* distance_dev);
+
 /* ---- map file (Mapper::saveLayerCake(path) -> bool, loadMap(path) -> bool: nvblox_node.cpp:1663-1668,1698-1703) -----------------
  * A path ending in .nvblx is written as an SQLITE database, like the reference's layer cake: table layers(layer_type, voxel_size,
  * block_size, voxel_bytes, num_blocks) + one table <layer_type>_blocks(index_x, index_y, index_z, data BLOB) per layer (tsdf_layer,

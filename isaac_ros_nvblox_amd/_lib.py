@@ -113,6 +113,12 @@ class CostOptions(C.Structure):
                 ("max_penalty", C.c_int32), ("unknown_penalty", C.c_int32), ("allow_unknown", C.c_int32), ("pad", C.c_int32)]
 
 
+class TerrainOptions(C.Structure):
+    """nvbx_terrain_options (32 bytes); nvbx_default_terrain_options fills it"""
+    _fields_ = [("max_step_m", C.c_float), ("max_slope_tan", C.c_float), ("unknown_value", C.c_float),
+                ("min_known", C.c_int32), ("void_is_hazard", C.c_int32), ("distance_radius_px", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
 class AlignOptions(C.Structure):
     """nvbx_align_options (56 bytes); nvbx_default_align_options fills it"""
     _fields_ = [("max_iterations", C.c_int32), ("subsampling", C.c_int32), ("min_weight", C.c_float), ("huber_delta_m", C.c_float),
@@ -254,6 +260,9 @@ SIGNATURES = {
     "nvbx_default_cost_options": (None, [C.POINTER(CostOptions)]),
     "nvbx_cost_field": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(CostOptions), _vp, _i32, _vp, _vp]),
     "nvbx_trace_paths": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(CostOptions), _vp, _vp, _i32, _vp, _i32, _vp]),
+    "nvbx_default_terrain_options": (None, [C.POINTER(TerrainOptions)]),
+    "nvbx_elevation_map": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp]),
+    "nvbx_traversability": (C.c_int, [_vp, _vp, _vp, _i32, _i32, C.POINTER(TerrainOptions), _vp, _vp, _vp, _vp]),
     "nvbx_default_align_options": (None, [C.POINTER(AlignOptions)]),
     "nvbx_align_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp]),
     "nvbx_align_depth": (C.c_int, [_vp, _vp, _i32, _i32, _vp, C.POINTER(Camera), C.POINTER(AlignOptions), _vp]),

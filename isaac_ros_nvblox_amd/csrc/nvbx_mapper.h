@@ -165,6 +165,8 @@ struct nvbx_mapper {
   nvbx::DevBuf frontier_scratch;
   // cost field (plan.hip): a 64-byte head of counters, the class word of every pixel and the two sets of active-tile flags of the largest image so far
   nvbx::DevBuf plan_scratch;
+  // traversability (elevation.hip): one bit row of HAZARD flags, ceil(cols / 64) 64-bit words, per row of the largest image so far
+  nvbx::DevBuf terrain_scratch;
   // mesh arena
   float* mesh_vert = nullptr; float* mesh_nrm = nullptr; uint8_t* mesh_col = nullptr; int32_t* mesh_tri = nullptr;
   nvbx::MeshRecord* mesh_rec = nullptr;

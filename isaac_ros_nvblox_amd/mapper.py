@@ -37,6 +37,8 @@ MERGE_OK, MERGE_EMPTY_SOURCE, MERGE_NO_OVERLAP = 0, 1, 2
 MERGE_STATUS_NAMES = {0: "OK", 1: "EMPTY_SOURCE", 2: "NO_OVERLAP"}
 MERGE_RESULT_BYTES = C.sizeof(_lib.MergeResult)
 COST_UNREACHED = 0x7fffffff      # NVBX_COST_UNREACHED: cost_field's value where no move sequence leads
+ELEV_UNKNOWN, ELEV_SURFACE, ELEV_BLOCKED, ELEV_VOID = 0, 1, 2, 3      # NVBX_ELEV_*: elevation_map's status
+TERRAIN_UNKNOWN, TERRAIN_OK, TERRAIN_HAZARD = 0, 1, 2                 # NVBX_TERRAIN_*: traversability's class
 
 TSDF_DT = np.dtype([("distance", "<f4"), ("weight", "<f4")])
 COLOR_DT = np.dtype([("r", "u1"), ("g", "u1"), ("b", "u1"), ("pad", "u1"), ("weight", "<f4")])
@@ -1304,6 +1306,64 @@ class Mapper:
         col = np.floor(p[:, 0] / vs).astype(np.int64) - np.int64(np.rint(a[0] / vs))
         row = np.floor(p[:, 1] / vs).astype(np.int64) - np.int64(np.rint(a[1] / vs))
         return np.stack([row, col], 1).astype(np.int32)
+
+    # -- elevation and traversability (nvbx_elevation_map / nvbx_traversability; SEMANTICS.md "Elevation and traversability")
+    def terrain_options(self, **kw):
+        """nvbx_terrain_options: the library's defaults with the given fields replaced (max_step_m, max_slope_tan, unknown_value, min_known,
+        void_is_hazard, distance_radius_px)."""
+        return _args.struct_options(_lib.TerrainOptions, self.lib.nvbx_default_terrain_options, kw, "terrain")
+
+    def elevation_box(self, aabb, z_min_m, z_max_m, rows=None, cols=None):
+        """The voxel box of an elevation image over `aabb` ((min x, y, z, max x, y, z) metres, as the slice calls return it) and the band
+        z_min_m .. z_max_m: -> (x0, y0, rows, cols, z_lo, z_hi) for elevation_map, x0 = lrint(aabb[0] / voxel_size), y0 likewise with
+        aabb[1], rows = lrint(aabb[4] / voxel_size) - y0 and cols = lrint(aabb[3] / voxel_size) - x0 unless given, z = floor(z_m /
+        voxel_size), all in float32.  Over a slice's AABB the image lies pixel for pixel on the slice image's grid (the AABB runs from a
+        block's min corner to a block's max corner), and slice_pixels serves both.  No kernel, host only."""
+        vs = np.float32(self.params.voxel_size)
+        a = np.asarray(aabb, np.float32).reshape(-1)
+        if a.size != 6:
+            raise ValueError("aabb must hold (min x, y, z, max x, y, z), got %d numbers" % a.size)
+        x0, y0 = int(np.rint(a[0] / vs)), int(np.rint(a[1] / vs))
+        rows = int(np.rint(a[4] / vs)) - y0 if rows is None else int(rows)
+        cols = int(np.rint(a[3] / vs)) - x0 if cols is None else int(cols)
+        z_lo, z_hi = (int(np.floor(np.float32(z) / vs)) for z in (z_min_m, z_max_m))
+        return x0, y0, rows, cols, z_lo, z_hi
+
+    def elevation_map(self, x0, y0, rows, cols, z_lo, z_hi, min_weight=1e-4, unknown_value=1000.0, out=None):
+        """Per-column ground height and status of the TSDF layer over the voxel columns gx = x0 + col, gy = y0 + row and the band
+        z_lo <= gz <= z_hi (global voxel coordinates; elevation_box makes them from metres): -> (height float32 [rows, cols], status uint8
+        [rows, cols]) on the mapper's device.  status: ELEV_UNKNOWN (nothing observed in the band), ELEV_SURFACE (the topmost solid voxel
+        has an observed, free voxel above it inside the band: height = the interpolated zero crossing in metres), ELEV_BLOCKED (solid up to
+        the band's top or with unobserved space above), ELEV_VOID (observed, nothing solid); height is unknown_value wherever the status is
+        not SURFACE.  Asynchronous, reads TSDF voxels only, held-back work stays held back.  out=(height, status): preallocated tensors,
+        nothing is allocated."""
+        rows, cols = int(rows), int(cols)
+        h, s = _args.outputs(out, (("height", (max(rows, 0), max(cols, 0)), F32, True, True), ("status", (max(rows, 0), max(cols, 0)), U8, True, True)), self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_elevation_map(self._h, int(x0), int(y0), rows, cols, int(z_lo), int(z_hi), float(min_weight),
+                                                                      float(unknown_value), ptr(h, collapse=False), ptr(s, collapse=False)))
+        return h, s
+
+    def traversability(self, height, status, step=False, slope=False, distance=True, out=None, **options):
+        """Classes and the distance to the nearest hazard from a height / status image pair (elevation_map's, or any float32 / uint8 pair of
+        one shape): -> dict of tensors [rows, cols] on the mapper's device: "class" uint8 (TERRAIN_UNKNOWN / TERRAIN_OK / TERRAIN_HAZARD),
+        and where asked for "step" float32 (the largest height difference to a known 8-neighbour, metres), "slope2" float32 (the squared
+        gradient, tan^2) and "distance" float32 (metres to the nearest HAZARD pixel within distance_radius_px; voxel_size x (radius + 1)
+        if there is none, 0 on a hazard, unknown_value on an UNKNOWN pixel: the image cost_field takes).  options: see terrain_options.
+        Asynchronous; the map is not read.  out=(class, step | None, slope2 | None, distance | None): preallocated tensors decide what is
+        written (the three flags are not looked at), nothing is allocated."""
+        torch = self._torch
+        h = self._image(height, "height")
+        s = self._image(status, "status", torch.uint8)
+        rows, cols = int(h.shape[0]), int(h.shape[1])
+        if tuple(s.shape) != (rows, cols):
+            raise ValueError("status must have the height image's shape %s, got %s" % ((rows, cols), tuple(s.shape)))
+        o = self.terrain_options(**options)
+        cl, st, sl, di = _args.outputs(out, (("class", (rows, cols), U8, True, True), ("step", (rows, cols), F32, False, bool(step)),
+                                             ("slope2", (rows, cols), F32, False, bool(slope)), ("distance", (rows, cols), F32, False, bool(distance))), self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_traversability(self._h, ptr(h, collapse=False), ptr(s, collapse=False), rows, cols, C.byref(o),
+                                                                       ptr(cl, collapse=False), ptr(st), ptr(sl), ptr(di)))
+        self._hold("_keep_tr", [h, s])      # (the kernels read them: they, and uploaded copies, live until the next call)
+        return {k: v for k, v in (("class", cl), ("step", st), ("slope2", sl), ("distance", di)) if v is not None}
 
     def mesh(self):
         """Mesh of the last update_color_mesh: dict block index tuple -> dict(vertices, normals, colors, triangles)."""

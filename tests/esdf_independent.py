@@ -7,6 +7,11 @@ max_sq = float32(r * r), ri = max(1, floor(r)).  A site at integer offset d from
 |d_axis| <= ri; the voxel's value is the minimum |d|^2 over the sites that count, as float32, or max_sq if none does.  For r < 1 only the
 sites themselves have a distance (0): ri is 1 but max_sq is below 1.
 
+THE MARKING RULE (SEMANTICS.md "ESDF 2-D", "Ground-plane-relative slice"), by which a TSDF or occupancy read-back says what the site set is:
+voxel_marks (each voxel by itself), column_bands / column_marks_2d (the column rule over the z band, fixed or per column over a ground plane),
+volume_marks_3d, block_band / esdf_blocks_expected (which ESDF blocks an update creates); tests/test_esdf_mark_model.py validates these against
+the checker on the drawn cases of tests/esdf_mark_cases.py.
+
 ARRAYS.  2-D fields are [y, x] (row = y, like the slice image), 3-D fields [x, y, z] (like a block's voxels); parents are stored in the
 ARRAY's axis order ((dy, dx) resp. (dx, dy, dz)), so that position + parent indexes the same array.
 """
@@ -207,7 +212,13 @@ def tsdf_blocks_3d(sites, alloc, params, origin=(0, 0, 0)):
 
 def voxel_marks(blocks, params):
     """(site, observed, inside) of TSDF voxels, each by itself (SEMANTICS.md "ESDF 2-D"): observed = weight >= esdf_min_weight; inside = observed
-    and distance <= 0; site = observed and |distance| <= esdf_max_site_distance_vox voxels (and, site rule 0, distance <= 0)."""
+    and distance <= 0; site = observed and |distance| <= esdf_max_site_distance_vox voxels (and, site rule 0, distance <= 0).  The site limit is
+    the float32 product of the two parameters.  An occupancy mapper (projective_layer_type 1) holds log-odds -- a plain float array, or voxels with
+    a field log_odds: observed = v != 0, inside = site = v > 0 (a -0.0 is unknown like 0.0)."""
+    if int(params.projective_layer_type) == 1:
+        blocks = np.asarray(blocks)
+        v = np.asarray(blocks["log_odds"] if blocks.dtype.names else blocks, np.float32)
+        return v > 0, v != 0, v > 0
     d = np.asarray(blocks["distance"], np.float32); w = np.asarray(blocks["weight"], np.float32)
     obs = w >= np.float32(params.esdf_min_weight)
     ins = obs & (d <= 0)
@@ -219,20 +230,101 @@ def voxel_marks(blocks, params):
 
 def column_marks_2d(tsdf_idx, tsdf_blocks, params, origin, shape_blocks):
     """Dense [y, x] (site, observed, inside) over the box origin (bx, by) + shape_blocks (nby, nbx): the column rule applied to a TSDF read-back --
-    a column is marked by ANY voxel of it within the z band [esdf_slice_min_height, esdf_slice_max_height] (voxel rows, not block rows)."""
-    vs = np.float32(params.voxel_size)
-    kz_lo, kz_hi = (int(np.floor(np.float32(h) / vs)) for h in (params.esdf_slice_min_height, params.esdf_slice_max_height))
+    a column is marked by ANY voxel of it within the z band (voxel rows, not block rows; each voxel judged by itself, so two voxels that each
+    meet half of a rule do not add up).  The band is [esdf_slice_min_height, esdf_slice_max_height], or, over a ground plane, the column's own
+    (column_bands)."""
+    kz_lo, kz_hi = column_bands(params, origin, shape_blocks)
     Hh, W = shape_blocks[0] * 8, shape_blocks[1] * 8
     out = [np.zeros((Hh, W), bool) for _ in range(3)]
     for i, b in zip(np.asarray(tsdf_idx, np.int64).reshape(-1, 3).tolist(), tsdf_blocks):
         x0, y0 = (i[0] - origin[0]) * 8, (i[1] - origin[1]) * 8
+        if not (0 <= x0 < W and 0 <= y0 < Hh):
+            continue
         kz = i[2] * 8 + np.arange(8)
-        zsel = (kz >= kz_lo) & (kz <= kz_hi)
-        if not (0 <= x0 < W and 0 <= y0 < Hh) or not zsel.any():
+        lo = kz_lo[y0:y0 + 8, x0:x0 + 8].T[:, :, None]; hi = kz_hi[y0:y0 + 8, x0:x0 + 8].T[:, :, None]       # [x, y, 1]
+        zsel = (kz >= lo) & (kz <= hi)                                                                       # [x, y, z]
+        if not zsel.any():
             continue
         for o, m in zip(out, voxel_marks(np.asarray(b).reshape(8, 8, 8), params)):
-            o[y0:y0 + 8, x0:x0 + 8] |= m[:, :, zsel].any(2).T
+            o[y0:y0 + 8, x0:x0 + 8] |= (m & zsel).any(2).T
     return tuple(out)
+
+
+def plane_on(params):
+    """The z band follows the ground plane (SEMANTICS.md "Ground-plane-relative slice"): the switch, a plane that points up (n_z > 1e-3) and a
+    positive thickness; otherwise the fixed heights apply."""
+    return bool(int(params.esdf_use_ground_plane)) and bool(np.float32(params.esdf_ground_plane[2]) > np.float32(1e-3)) \
+        and bool(np.float32(params.slice_height_thickness_m) > 0)
+
+
+def plane_quotients(params, x, y):
+    """(lower, upper) edge of the plane-relative band at (x, y) metres, in voxels: (h + above) / vs and (h + above + thickness) / vs with
+    h = -(n_x x + n_y y + d) / n_z -- in float64, from the plane coefficients, heights and voxel size as float32 holds them."""
+    n = [float(np.float32(v)) for v in params.esdf_ground_plane]
+    vs = float(np.float32(params.voxel_size))
+    above = float(np.float32(params.slice_height_above_plane_m)); thick = float(np.float32(params.slice_height_thickness_m))
+    h = -(n[0] * np.asarray(x, np.float64) + n[1] * np.asarray(y, np.float64) + n[3]) / n[2]
+    return (h + above) / vs, (h + above + thick) / vs
+
+
+def _column_centres(params, origin, shape_blocks):
+    vs = float(np.float32(params.voxel_size))
+    x = (origin[0] * 8 + np.arange(shape_blocks[1] * 8) + 0.5) * vs
+    y = (origin[1] * 8 + np.arange(shape_blocks[0] * 8) + 0.5) * vs
+    return np.meshgrid(x, y)                                                                               # [y, x] each
+
+
+def column_bands(params, origin, shape_blocks):
+    """(kz_lo, kz_hi) [y, x] int64: the voxel rows of every column's z band over the box origin (bx, by) + shape_blocks (nby, nbx).  Fixed
+    heights: floor(height / voxel_size) of the float32 quotient, the same for all columns.  Over a ground plane: floor of plane_quotients at the
+    column's centre ((b * 8 + v + 0.5) * voxel_size)."""
+    shape = (shape_blocks[0] * 8, shape_blocks[1] * 8)
+    if not plane_on(params):
+        vs = np.float32(params.voxel_size)
+        lo, hi = (int(np.floor(np.float32(h) / vs)) for h in (params.esdf_slice_min_height, params.esdf_slice_max_height))
+        return np.full(shape, lo, np.int64), np.full(shape, hi, np.int64)
+    qlo, qhi = plane_quotients(params, *_column_centres(params, origin, shape_blocks))
+    return np.floor(qlo).astype(np.int64), np.floor(qhi).astype(np.int64)
+
+
+def block_band(params, bx, by):
+    """(bz_lo, bz_hi): the TSDF block rows the band of block column (bx, by) can touch.  Fixed heights: those of slice_geometry.  Over a ground
+    plane: from the lowest and the highest of the plane's heights at the block's four corners (a plane is extremal there)."""
+    if not plane_on(params):
+        return slice_geometry(params)[:2]
+    bs = 8 * float(np.float32(params.voxel_size))
+    xs, ys = np.meshgrid([bx * bs, (bx + 1) * bs], [by * bs, (by + 1) * bs])
+    qlo, qhi = plane_quotients(params, xs, ys)
+    lo, hi = int(np.floor(qlo.min())) >> 3, int(np.floor(qhi.max())) >> 3
+    assert hi - lo <= 61, "a plane-relative band of more than 62 blocks (the product cuts it off there) is not modelled"
+    return lo, hi
+
+
+def band_margin(params, origin, shape_blocks):
+    """How far (in voxels) the nearest band quotient of the box lies from an integer, over every column centre and every block corner: drawn
+    planes keep this at 1e-3 or more, so that floor() is the same in float32 as in exact arithmetic.  inf without a plane."""
+    if not plane_on(params):
+        return np.inf
+    bs = 8 * float(np.float32(params.voxel_size))
+    cx, cy = np.meshgrid((origin[0] + np.arange(shape_blocks[1] + 1)) * bs, (origin[1] + np.arange(shape_blocks[0] + 1)) * bs)
+    q = np.concatenate([np.ravel(v) for v in plane_quotients(params, *_column_centres(params, origin, shape_blocks)) + plane_quotients(params, cx, cy)])
+    return float(np.abs(q - np.rint(q)).min())
+
+
+def esdf_blocks_expected(dirty_idx, params):
+    """The ESDF blocks that an update creates (or keeps) for the dirty TSDF (or occupancy) blocks `dirty_idx`, as a set of (bx, by, bz).  2-D: a
+    dirty block (bx, by, bz) within the band's block rows of its column (block_band) stands for ESDF block (bx, by, bz_out); one outside the band
+    for nothing.  3-D: every dirty block for the ESDF block of its own index."""
+    idx = [tuple(int(v) for v in i) for i in np.asarray(dirty_idx, np.int64).reshape(-1, 3)]
+    if int(params.esdf_mode) == 1:
+        return set(idx)
+    bz_out = slice_geometry(params)[2]
+    out = set()
+    for bx, by, bz in idx:
+        lo, hi = block_band(params, bx, by)
+        if lo <= bz <= hi:
+            out.add((bx, by, bz_out))
+    return out
 
 
 def volume_marks_3d(tsdf_idx, tsdf_blocks, params, origin, shape_blocks):

@@ -413,7 +413,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NVBX_SPARSE
       if (!(x0 < 0 || y0 < 0 || x0 + 1 > cols - 1 || y0 + 1 > rows - 1)) {
         const int32_t i00 = pix(y0, x0, cols);
         const float f00 = img(i00), f10 = img(i00 + 1), f01 = img(i00 + cols), f11 = img(i00 + cols + 1);
-        if (f00 > 0.0f && f10 > 0.0f && f01 > 0.0f && f11 > 0.0f) {
+        if (depth_valid4(f00, f10, f01, f11)) {
           const float mx = fmaxf(fmaxf(f00, f10), fmaxf(f01, f11)), mn = fminf(fminf(f00, f10), fminf(f01, f11));
           if (mx - mn <= sensor.max_diff_m) anyq = true;
         }
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NVBX_SPARSE
     float ob[3] = {0.0f, 0.0f, 0.0f}, db[3] = {1.0f, 0.0f, 0.0f};
     const float dir[3] = {te.y * ta.y, te.y * ta.x, te.x};                   // == LidarSensor::beam_dir(brr, bc)
     bool crossing = false; int axis = 0;
-    if (in_img && bd > 0.0f) {
+    if (in_img && depth_valid(bd)) {
       float t3[3];
       rotate(f.R_LC, org[0], org[1], org[2], t3);
       const float ivs = 1.0f / vs;

@@ -402,14 +402,22 @@ struct DepthF32 { const float* p; __device__ float operator()(int32_t i) const {
 struct DepthU16mm {   // conversions/image_conversions_thrust.cu:39-45 fused into the read
   const uint16_t* p; __device__ float operator()(int32_t i) const { return (float)p[i] * (1.0f / 1000.0f); } };
 
-// returns 1 = value, 0 = no sample (outside the image), -1 = a depth tap is invalid (<= 0)
+// A depth or range tap is valid iff 0 < d < +inf: NaN, <= 0 and both infinities are invalid (SEMANTICS.md 3).  One v_cmp_class (positive
+// subnormal | positive normal), the cost of the `d > 0.0f` it replaces.  An infinite tap must not reach the blend: 0 * inf and inf * (1 / inf^2)
+// are NaN, which passes `sdf < -trunc` and leaves the clamp as -trunc.
+__device__ inline bool positive_finite(float d) { return __builtin_amdgcn_classf(d, 0x080 | 0x100); }
+__device__ inline bool depth_valid(float d) { return positive_finite(d); }
+// the four taps of a bilinear sample (no short circuit: four compares and three scalar ands, no branch)
+__device__ inline bool depth_valid4(float a, float b, float c, float d) { return (int)depth_valid(a) & (int)depth_valid(b) & (int)depth_valid(c) & (int)depth_valid(d); }
+
+// returns 1 = value, 0 = no sample (outside the image), -1 = a depth tap is invalid (not in (0, +inf))
 template <typename Img>
 __device__ inline int interp_depth(const Img& img, int rows, int cols, float u, float v, int nearest, float* out) {
   if (nearest) {
     const int c = (int)floorf(u), r = (int)floorf(v);
     if (c < 0 || r < 0 || c >= cols || r >= rows) return 0;
     const float d = img(pix(r, c, cols));
-    if (!(d > 0.0f)) return -1;
+    if (!depth_valid(d)) return -1;
     *out = d; return 1;
   }
   const float uc = u - 0.5f, vc = v - 0.5f;
@@ -420,7 +428,7 @@ __device__ inline int interp_depth(const Img& img, int rows, int cols, float u, 
   const int32_t i00 = pix(y0, x0, cols);
   const float f00 = img(i00), f10 = img(i00 + 1), f01 = img(i00 + cols), f11 = img(i00 + cols + 1);
   __builtin_amdgcn_sched_barrier(0);        // both rows' loads in flight before the first tap is looked at (else: two serial round trips)
-  if (!(f00 > 0.0f) || !(f10 > 0.0f) || !(f01 > 0.0f) || !(f11 > 0.0f)) return -1;
+  if (!depth_valid4(f00, f10, f01, f11)) return -1;
   const float top = (1.0f - ax) * f00 + ax * f10;
   const float bot = (1.0f - ax) * f01 + ax * f11;
   *out = (1.0f - ay) * top + ay * bot;
@@ -476,7 +484,7 @@ __device__ inline bool tsdf_fuse(const Frame& f, float2* v, float ds, float vd) 
   if (f.skip_at_neg_trunc ? (sdf <= -f.trunc) : (sdf < -f.trunc)) return false;
   const float wm = weight_fn(f.weighting_mode, f.weighting_variant, ds, vd, f.trunc, f.voxel_size, f.max_dist);
   const float wsum = wm + cur.y;
-  if (!(wsum > 0.0f)) return false;
+  if (!positive_finite(wsum)) return false;      // (+inf: 1 / d^2 of a depth whose square underflows -- the blend would be a NaN that the clamp turns into -trunc)
   float fused, wnew = fminf(wsum, f.max_weight);
   if (!f.clamp_before_blend) fused = NVBX_DIV(sdf * wm + cur.x * cur.y, wsum);
   else { float wp = wnew - wm; if (wp < 0.0f) wp = 0.0f; fused = NVBX_DIV(sdf * wm + cur.x * wp, wm + wp); }

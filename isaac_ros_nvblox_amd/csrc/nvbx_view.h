@@ -137,7 +137,7 @@ struct LidarSensor {
       const int32_t i00 = pix(y0, x0, f.cols);
       const float f00 = img(i00), f10 = img(i00 + 1), f01 = img(i00 + f.cols), f11 = img(i00 + f.cols + 1);
       __builtin_amdgcn_sched_barrier(0);      // both rows' loads in flight before the first tap is looked at (else: two serial round trips)
-      if (f00 > 0.0f && f10 > 0.0f && f01 > 0.0f && f11 > 0.0f) {
+      if (depth_valid4(f00, f10, f01, f11)) {
         const float mx = fmaxf(fmaxf(f00, f10), fmaxf(f01, f11)), mn = fminf(fminf(f00, f10), fminf(f01, f11));
         if (mx - mn <= max_diff_m) {
           const float ax = uc - fx, ay = vc - fy;
@@ -151,7 +151,7 @@ struct LidarSensor {
     const int c = (int)floorf(u), rr = (int)floorf(v);
     if (c < 0 || rr < 0 || c >= f.cols || rr >= f.rows) return 0;
     const float d = img(pix(rr, c, f.cols));
-    if (!(d > 0.0f)) return 0;
+    if (!depth_valid(d)) return 0;
     float dir[3]; beam_dir(rr, c, dir);
     const float dot = __builtin_fmaf(pc[2], dir[2], __builtin_fmaf(pc[1], dir[1], pc[0] * dir[0]));
     const float ex = __builtin_fmaf(-dot, dir[0], pc[0]), ey = __builtin_fmaf(-dot, dir[1], pc[1]), ez = __builtin_fmaf(-dot, dir[2], pc[2]);

@@ -321,13 +321,15 @@ static inline int cam_project(const Cam* k, const float* p, float* u, float* v) 
 
 /* interpolate2DLinear with FloatPixelGreaterThanZero ([U] nvblox interpolation_2d): u,v corner-referenced;
  * subtract 0.5 to get centre-referenced; low pixel = floor; needs low+1 in bounds; all four > 0. */
-/* returns 1 = value, 0 = no sample (outside the image), -1 = a depth tap is invalid (<= 0) */
+/* a depth or range tap is valid iff 0 < d < +inf: NaN, <= 0 and both infinities are invalid (an infinite tap would turn the blend into a NaN) */
+static inline int depth_valid(float d) { return d > 0.0f && d < INFINITY; }
+/* returns 1 = value, 0 = no sample (outside the image), -1 = a depth tap is invalid (not in (0, +inf)) */
 static inline int interp_depth(const float* img, int rows, int cols, float u, float v, int nearest, float* out) {
   if (nearest) {
     int c = (int)floorf(u), r = (int)floorf(v);
     if (c < 0 || r < 0 || c >= cols || r >= rows) return 0;
     float d = img[(int64_t)r * cols + c];
-    if (!(d > 0.0f)) return -1;
+    if (!depth_valid(d)) return -1;
     *out = d; return 1;
   }
   float uc = u - 0.5f, vc = v - 0.5f;
@@ -337,7 +339,7 @@ static inline int interp_depth(const float* img, int rows, int cols, float u, fl
   float ax = uc - fx, ay = vc - fy;
   float f00 = img[(int64_t)y0 * cols + x0], f10 = img[(int64_t)y0 * cols + x0 + 1];
   float f01 = img[(int64_t)(y0 + 1) * cols + x0], f11 = img[(int64_t)(y0 + 1) * cols + x0 + 1];
-  if (!(f00 > 0.0f) || !(f10 > 0.0f) || !(f01 > 0.0f) || !(f11 > 0.0f)) return -1;
+  if (!depth_valid(f00) || !depth_valid(f10) || !depth_valid(f01) || !depth_valid(f11)) return -1;
   float top = (1.0f - ax) * f00 + ax * f10;
   float bot = (1.0f - ax) * f01 + ax * f11;
   *out = (1.0f - ay) * top + ay * bot;
@@ -381,7 +383,7 @@ static inline int tsdf_fuse(const OrcParams* p, TsdfVoxel* vx, float ds, float v
   if (p->tsdf_skip_at_negative_truncation ? (sdf <= -trunc) : (sdf < -trunc)) return 0;
   const float wm = weight_fn(p->weighting_mode, p->tsdf_weighting_variant, ds, vd, trunc, p->voxel_size, max_dist);
   const float wsum = wm + vx->weight;
-  if (!(wsum > 0.0f)) return 0;
+  if (!(wsum > 0.0f && wsum < INFINITY)) return 0;      /* (+inf: 1 / d^2 of a depth whose square underflows; the blend would be a NaN) */
   float fused; const float wnew = fminf(wsum, p->max_weight);
   if (!p->tsdf_weight_clamp_before_blend) fused = (sdf * wm + vx->distance * vx->weight) / wsum;
   else { float wp = wnew - wm; if (wp < 0.0f) wp = 0.0f; fused = (sdf * wm + vx->distance * wp) / (wm + wp); }
@@ -758,7 +760,7 @@ static int lidar_sample(const OrcParams* p, const LidarTab* t, const float* img,
   if (!(x0 < 0 || y0 < 0 || x0 + 1 > cols - 1 || y0 + 1 > rows - 1)) {
     const float f00 = img[(int64_t)y0 * cols + x0], f10 = img[(int64_t)y0 * cols + x0 + 1];
     const float f01 = img[(int64_t)(y0 + 1) * cols + x0], f11 = img[(int64_t)(y0 + 1) * cols + x0 + 1];
-    if (f00 > 0.0f && f10 > 0.0f && f01 > 0.0f && f11 > 0.0f) {
+    if (depth_valid(f00) && depth_valid(f10) && depth_valid(f01) && depth_valid(f11)) {
       const float mx = fmaxf(fmaxf(f00, f10), fmaxf(f01, f11)), mn = fminf(fminf(f00, f10), fminf(f01, f11));
       if (mx - mn <= max_diff) {
         const float ax = uc - fx, ay = vc - fy;
@@ -772,7 +774,7 @@ static int lidar_sample(const OrcParams* p, const LidarTab* t, const float* img,
   const int c = (int)floorf(u), rr = (int)floorf(v);
   if (c < 0 || rr < 0 || c >= cols || rr >= rows) return 0;
   const float d = img[(int64_t)rr * cols + c];
-  if (!(d > 0.0f)) return 0;
+  if (!depth_valid(d)) return 0;
   float dir[3]; lidar_dir(t, rr, c, dir);
   const float dot = fmaf(pc[2], dir[2], fmaf(pc[1], dir[1], pc[0] * dir[0]));
   const float ex = fmaf(-dot, dir[0], pc[0]), ey = fmaf(-dot, dir[1], pc[1]), ez = fmaf(-dot, dir[2], pc[2]);
@@ -858,7 +860,7 @@ void orc_lidar_sample_points(const OrcParams* p, const float* lidar5, const floa
     int bil = 0;
     if (!(x0 < 0 || y0 < 0 || x0 + 1 > cols - 1 || y0 + 1 > rows - 1)) {
       const float f00 = range[(int64_t)y0 * cols + x0], f10 = range[(int64_t)y0 * cols + x0 + 1], f01 = range[(int64_t)(y0 + 1) * cols + x0], f11 = range[(int64_t)(y0 + 1) * cols + x0 + 1];
-      if (f00 > 0.0f && f10 > 0.0f && f01 > 0.0f && f11 > 0.0f) {
+      if (depth_valid(f00) && depth_valid(f10) && depth_valid(f01) && depth_valid(f11)) {
         const float mx = fmaxf(fmaxf(f00, f10), fmaxf(f01, f11)), mn = fminf(fminf(f00, f10), fminf(f01, f11));
         bil = (mx - mn <= max_diff);
       }

@@ -87,8 +87,9 @@ def test_whole_path_parity_on_hard_inputs(oracle_mod, hip_lib, case):
 
 def test_non_finite_and_negative_depth_pixels(oracle_mod, hip_lib):
     """A depth image with NaN, +-inf, negative and absurdly large pixels (a driver hiccup): the view and the TSDF of the HIP path equal the
-    oracle's (NaN and non-positive pixels are invalid depth; an infinite range is cut at the integration distance), nothing non-finite is
-    written into the map, and the next clean frame integrates normally."""
+    oracle's (a depth tap is valid iff 0 < d < +inf: NaN, non-positive and infinite pixels are invalid depth for the voxel update; for the view an
+    infinite range is a ray cut at the integration distance), nothing non-finite is written into the map, and the next clean frame integrates
+    normally.  Product and oracle agreeing proves no rule: tests/test_gpu_depth_drawn.py holds both against an independent model."""
     M, g, o = make_pair(oracle_mod)
     rng = np.random.default_rng(5)
     fr = H.frames(3, H.SMALL_CAM, color=False, stride=9)

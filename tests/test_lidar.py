@@ -462,3 +462,75 @@ def test_lidar_hip_map_against_the_independent_model(hip_lib):
     assert np.abs(d[k] - np.clip(sdf[k], -trunc, trunc)).max() < 2e-4
     far = np.hypot(ps[:, 0], ps[:, 1]) > 120.0
     assert (k & far).sum() > 1000 and (k & (ref["branch"] == 1)).sum() > 20000 and (k & (ref["branch"] == 2)).sum() > 5000
+
+
+# ---- an infinite range is no measurement (a tap is valid iff 0 < r < +inf): a patch of +inf in a scan whose voxels were observed free before
+def _infinite_patch_scans():
+    clean = np.full((SMALL_LIDAR[1], SMALL_LIDAR[0]), 8.0, np.float32)
+    holed = clean.copy(); holed[3:13, 96:160] = np.inf
+    zeroed = holed.copy(); zeroed[np.isinf(holed)] = 0.0
+    return clean, holed, zeroed, S.lidar_pose(0)
+
+
+def _infinite_patch_params(module, mode):
+    return module.default_params(voxel_size=0.1, lidar_max_integration_distance_m=12.0, raycast_subsampling_factor=1, weighting_mode=mode)
+
+
+def _check_infinite_patch(before, holed, zeroed, tag):
+    """before / holed / zeroed: {block: voxels [512]} after the clean scan, after the scan with the +inf patch on top, after the scan with the patch set to 0
+    on top.  No voxel observed free turns negative; the two second scans leave the same map (an infinite range still casts a ray, cut at the integration
+    distance, so the holed map may hold more blocks: those are untouched)."""
+    free = flipped = 0
+    for k, b in before.items():
+        was = (b["weight"] > 0) & (b["distance"] > 0)
+        free += int(was.sum()); flipped += int((was & (holed[k]["distance"] < 0)).sum())
+    assert free > 100000 and flipped == 0, (tag, free, flipped)
+    assert set(zeroed) <= set(holed) and len(zeroed) > 1000, tag
+    for k, b in holed.items():
+        assert np.isfinite(b["distance"]).all() and np.isfinite(b["weight"]).all(), (tag, k)
+        if k in zeroed:
+            assert H.block_difference(np.asarray([k]), b, zeroed[k]) is None, (tag, H.block_difference(np.asarray([k]), b, zeroed[k]))
+        else:
+            assert not b["weight"].any() and not b["distance"].any(), (tag, k)
+
+
+def _oracle_map(oracle_mod, o):
+    return {tuple(int(v) for v in i): o.get_block(oracle_mod.L_TSDF, i).copy() for i in o.block_indices(oracle_mod.L_TSDF)}
+
+
+@pytest.mark.parametrize("mode", [0, 2])
+def test_lidar_infinite_range_patch_is_no_measurement(oracle_mod, mode):
+    """The checker: under inverse-square weighting 1 / inf^2 = 0 and inf * 0 = NaN, which the clamp used to turn into -truncation (29 156 voxels of this
+    scan went from free to -0.4); under constant weighting the voxels behind the patch were fused as free space."""
+    clean, holed, zeroed, T = _infinite_patch_scans()
+    maps = []
+    for second in (holed, zeroed):
+        o = oracle_mod.OracleMap(_infinite_patch_params(oracle_mod, mode))
+        o.integrate_lidar_depth(clean, T, SMALL_LIDAR)
+        before = _oracle_map(oracle_mod, o)
+        o.integrate_lidar_depth(second, T, SMALL_LIDAR)
+        maps.append(_oracle_map(oracle_mod, o))
+    _check_infinite_patch(before, maps[0], maps[1], mode)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [0, 2])
+def test_lidar_hip_infinite_range_patch_is_no_measurement(oracle_mod, hip_lib, mode):
+    """The product on the same scans: equal to the checker after each scan (view and voxels), and the same two properties."""
+    from isaac_ros_nvblox_amd import mapper as M
+    clean, holed, zeroed, T = _infinite_patch_scans()
+    maps = []
+    for second in (holed, zeroed):
+        pg = _infinite_patch_params(M, mode)
+        g = M.Mapper(pg, block_capacity=1 << 14); o = oracle_mod.OracleMap(H.copy_params(pg, oracle_mod.OrcParams))
+        for k, img in enumerate((clean, second)):
+            g.integrate_lidar_depth(img, T, SMALL_LIDAR); o.integrate_lidar_depth(img, T, SMALL_LIDAR)
+            assert H.idx_set(g.last_view()) == H.idx_set(o.last_view())
+            n, _ = H.compare_layer(M, g, o, M.LAYER_TSDF, oracle_mod.L_TSDF, fields_tol=("distance", "weight"))
+            assert n > 1000
+            idx, vox = H.map_state(g, layers=(M.LAYER_TSDF,))["layers"][M.LAYER_TSDF]
+            if k == 0:
+                before = {tuple(i): b for i, b in zip(idx.tolist(), vox)}
+        maps.append({tuple(i): b for i, b in zip(idx.tolist(), vox)})
+        assert g.counters()["capacity_overflow"] == 0
+    _check_infinite_patch(before, maps[0], maps[1], mode)

@@ -668,6 +668,44 @@ int nvbx_trace_paths(nvbx_mapper* m, const float* image_dev, int32_t rows, int32
                      const int32_t* cost_dev, const int32_t* starts_rc_dev, int32_t n_starts, int32_t* path_rc_dev, int32_t capacity,
                      int32_t* length_dev);
 
+/* ---- cost volume and 3-D paths (which goal can be reached through free space, and what does the flight cost; SEMANTICS.md "Cost volume
+ *      and 3-D paths") ----------------------------------------------------------------------------------------------------------------------
+ * The cost field over a distance VOLUME volume_dev[nx][ny][nz] (DEVICE memory, f32, element (x, y, z) at (x * ny + y) * nz + z): exactly
+ * what nvbx_esdf_dense_grid writes for size_vox = {nx, ny, nz} with default_value = the options' unknown_value -- or any volume of that
+ * form.  `options` is host memory; the voxel classes and penalties are those of the cost field above, unchanged (UNKNOWN iff fabsf(v -
+ * unknown_value) < 1e-2f; TRAVERSABLE iff not unknown, v > 0 and v >= robot_radius_m; a negative v and a NaN are not; allow_unknown makes
+ * unknown voxels traversable with unknown_penalty).  There are 26 moves d = (dx, dy, dz), components in {-1, 0, 1}, not all 0.  With k =
+ * the number of nonzero components, a move from a traversable p to a traversable q = p + d inside the volume costs B_k + pen(p) + pen(q),
+ * B_1 = 10, B_2 = 14, B_3 = 17, and is allowed iff every voxel p + e is traversable, for each e with e_i in {0, d_i}, e != 0, e != d: the
+ * two voxels beside a face diagonal, the six around a space diagonal; a voxel outside the volume is not traversable.  Nothing squeezes
+ * between two blocked voxels that touch along an edge or at a corner.  ORDER of the moves: by k, then lexicographically by (dx, dy, dz)
+ * with each component ordered +1, 0, -1 -- (1,0,0) (0,1,0) (0,0,1) (0,0,-1) (0,-1,0) (-1,0,0), then (1,1,0) (1,0,1) (1,0,-1) (1,-1,0)
+ * (0,1,1) (0,1,-1) (0,-1,1) (0,-1,-1) (-1,1,0) (-1,0,1) (-1,0,-1) (-1,-1,0), then (1,1,1) (1,1,-1) (1,-1,1) (1,-1,-1) (-1,1,1) (-1,1,-1)
+ * (-1,-1,1) (-1,-1,-1).  Both calls read the volume only and write their outputs only: the map is untouched, held-back work stays held
+ * back.  On a refusal (NVBX_E_INVALID, nvbx_last_error set) nothing is launched and the mapper stays usable.  Refused by both: a NULL mapper,
+ * volume, options or field; nx, ny or nz <= 0 or nx x ny x nz > 2^22 (a step costs at most 17 + 2 x 200 = 417, and 417 x 2^22 < 2^31: no
+ * sum overflows); the options the cost field refuses.
+ * nvbx_cost_volume: cost_dev[nx][ny][nz], int32 in the volume's layout = the least total cost of a move sequence from any accepted source
+ *   to the voxel: 0 at a source, NVBX_COST_UNREACHED where there is none and at every voxel that is not traversable.
+ *   sources_xyz_dev[n_sources][3] = (x, y, z) offsets in the box, DEVICE memory; one outside the box or on a voxel that is not traversable
+ *   is ignored, duplicates are harmless, none accepted: all UNREACHED.  *accepted_dev (NULL: not wanted) = the number of accepted entries.
+ *   The field is the unique fixed point of an integer relaxation and bit-specified.  The call enqueues relaxation rounds in batches on the
+ *   mapper's stream and WAITS for the device after each batch to read one counter: it returns with the field complete.  NVBX_E_DEVICE with
+ *   a message if nx x ny x nz rounds plus one batch did not reach the fixed point, which the algorithm excludes.  Also refused:
+ *   n_sources < 0; a NULL sources_xyz_dev with n_sources > 0.
+ * nvbx_trace_paths_3d: for each of n_starts voxels starts_xyz_dev[i] = (x, y, z) the path that descends cost_dev, a field of this volume
+ *   and these options: it begins at the start; at p with 0 < G(p) < UNREACHED the next voxel is the FIRST allowed neighbour q in the order
+ *   above with G(q) + c(p, q) == G(p); it ends at the first voxel with G = 0, which is included.  path_xyz_dev[i][capacity][3] receives
+ *   the voxels, length_dev[i] their number -- also when it exceeds `capacity`; voxels from the capacity on are written nowhere -- 0 for a
+ *   start outside the box or UNREACHED, -1 if no neighbour satisfies the equation (the field is not one of this volume and these options;
+ *   never an error code).  One lane per start, at most nx x ny x nz steps, asynchronous on the mapper's stream.  Also refused:
+ *   n_starts < 0; capacity < 0; a NULL starts_xyz_dev, path_xyz_dev or length_dev with n_starts > 0.  n_starts == 0 launches nothing. */
+int nvbx_cost_volume(nvbx_mapper* m, const float* volume_dev, int32_t nx, int32_t ny, int32_t nz, const nvbx_cost_options* options,
+                     const int32_t* sources_xyz_dev, int32_t n_sources, int32_t* cost_dev, int32_t* accepted_dev);
+int nvbx_trace_paths_3d(nvbx_mapper* m, const float* volume_dev, int32_t nx, int32_t ny, int32_t nz, const nvbx_cost_options* options,
+                        const int32_t* cost_dev, const int32_t* starts_xyz_dev, int32_t n_starts, int32_t* path_xyz_dev,
+                        int32_t capacity, int32_t* length_dev);
+
 /* ---- elevation and traversability (how high is the ground here, can the robot stand here, how far is the next place where it cannot;
  *      SEMANTICS.md "Elevation and traversability") -------------------------------------------------------------------------------------
  * Per-column products of the TSDF layer, pixel-aligned with the slice image: pixel (r, c) is the voxel column gx = x0 + c, gy = y0 + r in

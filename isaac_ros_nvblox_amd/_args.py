@@ -1,6 +1,6 @@
 """Argument coercion and output buffers of the mapper's calls (mapper.py): one coercion per kind of input, one tensor -> pointer conversion (`ptr`),
 ValueError on bad input.  Writers, converters and exporters: `image` / `depth_image` for what a call is fed, `pose` / `pose_block`, `camera` /
-`lidar`, and `frame` for the C argument group of an image with its pose and intrinsics.  Reader calls: `points3` / `poses16` / `pixels2` and `outputs`.
+`lidar`, and `frame` for the C argument group of an image with its pose and intrinsics.  Reader calls: `points3` / `poses16` / `pixels2` / `voxels3` and `outputs`.
 Pure functions: the target torch.device is an argument, nothing here touches the library or a stream, so they run with torch.device("cpu")
 on a machine without a GPU (tests/test_wrapper_args.py).  A call adds no coercion code of its own ("Host language").
 """
@@ -88,6 +88,18 @@ def pixels2(a, dev, what="pixels"):
         p = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1, 2))).to(dev)
     if p.dtype != torch.int32 or p.dim() != 2 or p.shape[1] != 2:
         raise ValueError("%s must be an (n, 2) int32 array of (row, col), got %s %s" % (what, tuple(p.shape), p.dtype))
+    return p
+
+
+def voxels3(a, dev, what="voxels"):
+    """-> a contiguous (n, 3) int32 tensor of (x, y, z) on `dev`.  A tensor is moved and made contiguous, never converted or reshaped; anything
+    else goes through numpy (converted to int32, reshaped to (-1, 3)) and is uploaded."""
+    if isinstance(a, torch.Tensor):
+        p = (a if a.device == dev else a.to(dev)).contiguous()
+    else:
+        p = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1, 3))).to(dev)
+    if p.dtype != torch.int32 or p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError("%s must be an (n, 3) int32 array of (x, y, z), got %s %s" % (what, tuple(p.shape), p.dtype))
     return p
 
 

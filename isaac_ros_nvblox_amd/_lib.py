@@ -260,6 +260,8 @@ SIGNATURES = {
     "nvbx_default_cost_options": (None, [C.POINTER(CostOptions)]),
     "nvbx_cost_field": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(CostOptions), _vp, _i32, _vp, _vp]),
     "nvbx_trace_paths": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(CostOptions), _vp, _vp, _i32, _vp, _i32, _vp]),
+    "nvbx_cost_volume": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(CostOptions), _vp, _i32, _vp, _vp]),
+    "nvbx_trace_paths_3d": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(CostOptions), _vp, _vp, _i32, _vp, _i32, _vp]),
     "nvbx_default_terrain_options": (None, [C.POINTER(TerrainOptions)]),
     "nvbx_elevation_map": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp]),
     "nvbx_traversability": (C.c_int, [_vp, _vp, _vp, _i32, _i32, C.POINTER(TerrainOptions), _vp, _vp, _vp, _vp]),

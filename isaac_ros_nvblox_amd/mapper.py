@@ -1307,6 +1307,75 @@ class Mapper:
         row = np.floor(p[:, 1] / vs).astype(np.int64) - np.int64(np.rint(a[1] / vs))
         return np.stack([row, col], 1).astype(np.int32)
 
+    # -- cost volume and 3-D paths (nvbx_cost_volume / nvbx_trace_paths_3d; SEMANTICS.md "Cost volume and 3-D paths")
+    def esdf_dense_grid_device(self, min_vox, size_vox, default_value, out=None):
+        """The device-tensor form of esdf_dense_grid: the ESDF distances of the voxel box min_vox .. min_vox + size_vox (global voxel
+        coordinates) -> float32 [nx, ny, nz] on the mapper's device, default_value where nothing is stored: the volume cost_volume takes, with
+        default_value = its unknown_value.  No host copy and no synchronise: ordered on the streams like the other reader calls.
+        out: a preallocated float32 [nx, ny, nz] tensor, nothing is allocated."""
+        mn = np.ascontiguousarray(np.asarray(min_vox, np.int32).reshape(3)); sz = np.ascontiguousarray(np.asarray(size_vox, np.int32).reshape(3))
+        if (sz <= 0).any():
+            raise ValueError("size_vox must be > 0 on every axis, got %s" % (sz.tolist(),))
+        grid, = _args.outputs(None if out is None else (out,), (("grid", tuple(int(v) for v in sz), F32, True, True),), self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_esdf_dense_grid(self._h, _np_ptr(mn), _np_ptr(sz), float(default_value), ptr(grid)))
+        return grid
+
+    def _dense_volume(self, volume_dev):
+        return _args.image(volume_dev, self._cuda, self._torch.float32, "volume", "(nx, ny, nz)")
+
+    def cost_volume(self, volume_dev, sources_xyz, out=None, accepted=None, **options):
+        """The integer cost-to-go field over a distance volume (esdf_dense_grid_device with default_value = unknown_value, or any (nx, ny, nz)
+        float32 volume of that form) over 26-connected moves from the source voxels sources_xyz ((n, 3) int32 (x, y, z) offsets in the box,
+        torch device tensor or numpy array; volume_voxels makes them from metres): -> int32 [nx, ny, nz] on the mapper's device, 0 at an
+        accepted source, COST_UNREACHED where no move sequence leads and on every voxel that is not traversable.  A source outside the box or
+        on such a voxel is ignored.  options: see cost_options.  The call waits for the device (between batches of relaxation rounds) and
+        returns with the field complete; it reads the volume only.  out: a preallocated int32 [nx, ny, nz] tensor; accepted: an int32 [1]
+        device tensor that receives the number of accepted sources."""
+        torch = self._torch
+        vol = self._dense_volume(volume_dev)
+        shape = tuple(int(v) for v in vol.shape)
+        o = self.cost_options(**options)
+        src = _args.voxels3(sources_xyz, self._cuda, "sources_xyz")
+        cost, acc = _args.outputs((out, accepted) if out is not None or accepted is not None else None,
+                                  (("cost", shape, I32, False, True), ("accepted", (1,), I32, False, False)), self._cuda)
+        if cost is None:
+            cost = torch.empty(shape, dtype=torch.int32, device=self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_cost_volume(self._h, ptr(vol, collapse=False), shape[0], shape[1], shape[2], C.byref(o), ptr(src),
+                                                                    int(src.shape[0]), ptr(cost, collapse=False), ptr(acc)))
+        return cost
+
+    def trace_paths_3d(self, volume_dev, field, starts_xyz, capacity, out=None, **options):
+        """The paths that descend `field` (cost_volume of this volume and these options) from the voxels starts_xyz ((n, 3) int32 (x, y, z)):
+        -> (paths int32 [n, capacity, 3] of (x, y, z), lengths int32 [n]) on the mapper's device.  A path runs from its start to the first
+        voxel of cost 0, both included; lengths[i] is its number of voxels, also beyond `capacity` (voxels from the capacity on are not
+        written; rows past a path's end are left as they were), 0 for a start outside the box or unreached, -1 where the field does not
+        belong to the volume.  Asynchronous.  out=(paths, lengths): preallocated tensors, nothing is allocated."""
+        torch = self._torch
+        vol = self._dense_volume(volume_dev)
+        shape = tuple(int(v) for v in vol.shape)
+        o = self.cost_options(**options)
+        f = _args.image(field, self._cuda, torch.int32, "field", "(nx, ny, nz)", convert=False)
+        if tuple(f.shape) != shape:
+            raise ValueError("field must have the volume's shape %s, got %s" % (shape, tuple(f.shape)))
+        st = _args.voxels3(starts_xyz, self._cuda, "starts_xyz")
+        n, cap = int(st.shape[0]), int(capacity)
+        if cap < 0:
+            raise ValueError("capacity must be >= 0")
+        paths, lengths = _args.outputs(out, (("paths", (n, cap, 3), I32, True, True), ("lengths", (n,), I32, True, True)), self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_trace_paths_3d(self._h, ptr(vol, collapse=False), shape[0], shape[1], shape[2], C.byref(o),
+                                                                       ptr(f, collapse=False), ptr(st), n, ptr(paths, collapse=False), cap, ptr(lengths)),
+                                  order=n > 0)
+        self._hold("_keep_tp3", [vol, f, st])      # (the kernel reads them: they, and uploaded copies, live until the next call)
+        return paths, lengths
+
+    def volume_voxels(self, points_xyz, min_vox):
+        """Metres -> voxels of the box that starts at min_vox (esdf_dense_grid_device's): points_xyz (n, 3) -> int32 numpy [n, 3] of (x, y, z)
+        offsets; per axis floor(p / voxel_size) - min_vox, in float32.  A point outside the box gives a voxel outside it, which cost_volume and
+        trace_paths_3d ignore.  No kernel, host only."""
+        p = np.asarray(points_xyz, np.float32).reshape(-1, 3)
+        vs = np.float32(self.params.voxel_size)
+        return (np.floor(p / vs).astype(np.int64) - np.asarray(min_vox, np.int64).reshape(1, 3)).astype(np.int32)
+
     # -- elevation and traversability (nvbx_elevation_map / nvbx_traversability; SEMANTICS.md "Elevation and traversability")
     def terrain_options(self, **kw):
         """nvbx_terrain_options: the library's defaults with the given fields replaced (max_step_m, max_slope_tan, unknown_value, min_known,

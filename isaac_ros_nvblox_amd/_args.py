@@ -67,40 +67,31 @@ def frame(img, T, model, collapse=True):
     return (p, rows, cols, np_ptr(T), C.byref(model)), (img, T, model)
 
 
-def points3(a, dev, what="points"):
-    """-> a contiguous (n, 3) float32 tensor on `dev`.  A tensor is moved and made contiguous, never converted or reshaped; anything else
-    goes through numpy (converted to float32, reshaped to (-1, 3)) and is uploaded."""
+def _rows(a, dev, w, dtype, of, what):
+    """-> a contiguous (n, w) tensor of `dtype` on `dev`; `of`: what a row holds, for the message.  A tensor is moved and made contiguous, never
+    converted or reshaped; anything else goes through numpy (converted to `dtype`, reshaped to (-1, w)) and is uploaded."""
     if isinstance(a, torch.Tensor):
         p = (a if a.device == dev else a.to(dev)).contiguous()
     else:
-        p = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 3))).to(dev)
-    if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
-        raise ValueError("%s must be an (n, 3) float32 array, got %s %s" % (what, tuple(p.shape), p.dtype))
+        p = torch.from_numpy(np.ascontiguousarray(np.asarray(a, getattr(np, str(dtype)[6:])).reshape(-1, w))).to(dev)
+    if p.dtype != dtype or p.dim() != 2 or p.shape[1] != w:
+        raise ValueError("%s must be an (n, %d) %s array%s, got %s %s" % (what, w, str(dtype)[6:], of, tuple(p.shape), p.dtype))
     return p
+
+
+def points3(a, dev, what="points"):
+    """-> a contiguous (n, 3) float32 tensor on `dev`; moved, converted and reshaped as _rows says."""
+    return _rows(a, dev, 3, torch.float32, "", what)
 
 
 def pixels2(a, dev, what="pixels"):
-    """-> a contiguous (n, 2) int32 tensor of (row, col) on `dev`.  A tensor is moved and made contiguous, never converted or reshaped; anything
-    else goes through numpy (converted to int32, reshaped to (-1, 2)) and is uploaded."""
-    if isinstance(a, torch.Tensor):
-        p = (a if a.device == dev else a.to(dev)).contiguous()
-    else:
-        p = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1, 2))).to(dev)
-    if p.dtype != torch.int32 or p.dim() != 2 or p.shape[1] != 2:
-        raise ValueError("%s must be an (n, 2) int32 array of (row, col), got %s %s" % (what, tuple(p.shape), p.dtype))
-    return p
+    """-> a contiguous (n, 2) int32 tensor of (row, col) on `dev`; moved, converted and reshaped as _rows says."""
+    return _rows(a, dev, 2, torch.int32, " of (row, col)", what)
 
 
 def voxels3(a, dev, what="voxels"):
-    """-> a contiguous (n, 3) int32 tensor of (x, y, z) on `dev`.  A tensor is moved and made contiguous, never converted or reshaped; anything
-    else goes through numpy (converted to int32, reshaped to (-1, 3)) and is uploaded."""
-    if isinstance(a, torch.Tensor):
-        p = (a if a.device == dev else a.to(dev)).contiguous()
-    else:
-        p = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1, 3))).to(dev)
-    if p.dtype != torch.int32 or p.dim() != 2 or p.shape[1] != 3:
-        raise ValueError("%s must be an (n, 3) int32 array of (x, y, z), got %s %s" % (what, tuple(p.shape), p.dtype))
-    return p
+    """-> a contiguous (n, 3) int32 tensor of (x, y, z) on `dev`; moved, converted and reshaped as _rows says."""
+    return _rows(a, dev, 3, torch.int32, " of (x, y, z)", what)
 
 
 def poses16(a, dev, what="poses"):

@@ -163,7 +163,7 @@ struct nvbx_mapper {
   nvbx::DevBuf merge_buf;
   // frontier scan (frontier.hip), -DNVBX_FRONTIER_TWO_PASS variant only: 128 bytes of voxel classes per slot; the product's single pass needs none
   nvbx::DevBuf frontier_scratch;
-  // cost field (plan.hip) and cost volume (plan3d.hip): a 64-byte head of counters, the class word of every pixel or voxel and the two sets of active-tile flags of the largest input so far
+  // cost field (plan.hip) and cost volume (plan3d.hip), sized and carved up by nvbx_plan_grid.h's plan_grid_setup alone: a 64-byte head of counters, the class word of every cell and the two sets of active-tile flags of the largest input so far
   nvbx::DevBuf plan_scratch;
   // traversability (elevation.hip): one bit row of HAZARD flags, ceil(cols / 64) 64-bit words, per row of the largest image so far
   nvbx::DevBuf terrain_scratch;

@@ -6,7 +6,7 @@
 // The field is the fixed point of a relaxation over 8 x 8 x 8 voxel tiles; no workgroup ever waits for another, every loop is bounded.
 // k_plan3d_classify: a workgroup per tile writes the class word of its voxels (NVBX_PLAN_BLOCKED or the penalty), fills its part of the field with
 //   UNREACHED, then goes through the source list, sets the accepted sources that lie in its tile to 0 and writes both of its active flags (active:
-//   an accepted source in the tile or in its halo).
+//   an accepted source in the tile or in its halo; nvbx_plan_grid.h's plan_grid_seed, shared with plan.hip).
 // k_plan3d_relax: one round.  A workgroup whose tile is not active ends after one byte load.  An active one stages ONE word per voxel of the tile
 //   and its one-voxel halo in LDS: -1 for a voxel that is not traversable (or outside the volume), UNREACHED for an unreached one, else
 //   H = G + pen -- so that a pull over a move with k nonzero components is H(q) + B_k + pen(p), one LDS read.  Each thread owns two voxels and
@@ -18,11 +18,11 @@
 //   once per batch of rounds.
 //   Every stored value is the cost of a real move sequence and values only fall, so a halo read before or after a neighbour's store of the same
 //   round is a valid bound either way, and that store re-activates the reader (DESIGN.md 2.23 has the argument in full).
-// k_plan3d_trace: a lane per start, the path rule of the header; classes are recomputed from the volume.
+// k_plan3d_trace: a lane per start, the path rule of the header: nvbx_plan_grid.h's walk over PvGrid's 26 moves; classes are recomputed from the volume.
+// The scratch layout, the host's loop over batches of rounds and the argument checks are nvbx_plan_grid.h's too.
 #include <algorithm>
 #include <cmath>
-#include "nvbx_mapper.h"
-#include "nvbx_plan3d_math.h"
+#include "nvbx_plan_grid.h"
 
 using namespace nvbx;
 
@@ -35,18 +35,13 @@ constexpr int PV_CELLS = PV_HX * PV_HY * PV_HZ;                        // 1 000 
 constexpr int PV_TPB = 256;                                            // two voxels per thread
 constexpr int PV_VOX = PV_TX * PV_TY * PV_TZ;
 constexpr int PV_PPT = PV_VOX / PV_TPB;
-constexpr size_t PV_HEAD = 64;            // bytes in front of the scratch: [0] workgroups that changed something in this batch, [1] accepted sources
 static_assert(PV_PLANE >= PV_HY * PV_HZ && PV_PLANE % 32 == 8 && PV_TZ == 8 && PV_TX % 4 == 0 && PV_VOX % PV_TPB == 0, "the LDS layout of pv_local");
+
+constexpr PlanWords PV_WORDS{"volume", "nx, ny and nz", "nx x ny x nz", "xyz"};
 
 struct Plan3Args {
   const float* vol; int32_t nx, ny, nz, ntx, nty, ntz;
-  nvbx_cost_options o;
-  int32_t* cls;                           // [nx][ny][nz] class words
-  int32_t* cost;                          // [nx][ny][nz] the field
-  uint8_t* active;                        // [2][ntx * nty * ntz]
-  uint32_t* head;
-  const int32_t* src; int32_t n_src;
-  int32_t sweeps;
+  PlanGridArgs g;                         // cls and cost are [nx][ny][nz], active [2][ntx * nty * ntz]
 };
 
 // Voxel i of a tile, 0 .. 511: z runs fastest, then x, then y.  The 32 lanes that one ds_read_b32 cycle serves hold 8 z of four neighbouring x:
@@ -69,27 +64,13 @@ __global__ __launch_bounds__(PV_TPB) void k_plan3d_classify(Plan3Args a) {
       const int32_t x = tx * PV_TX + lx, y = ty * PV_TY + ly, z = tz * PV_TZ + lz;
       if (x < a.nx && y < a.ny && z < a.nz) {
         const int64_t g = pv_at(a, x, y, z);
-        a.cls[g] = nvbx_plan_class(a.vol[g], &a.o);
-        a.cost[g] = NVBX_COST_UNREACHED;
+        a.g.cls[g] = nvbx_plan_class(a.vol[g], &a.g.o);
+        a.g.cost[g] = NVBX_COST_UNREACHED;
       }
     }
     __syncthreads();                      // (the fill is behind us: a source's 0 lands on top of it)
-    // A source wakes its own tile and every tile that holds it in its halo: the 0 is a value no relaxation stores, so nobody else would mark them.
-    int found = 0;
-    for (int32_t s = t; s < a.n_src; s += PV_TPB) {
-      const int32_t x = a.src[3 * (int64_t)s], y = a.src[3 * (int64_t)s + 1], z = a.src[3 * (int64_t)s + 2];
-      if (x < 0 || y < 0 || z < 0 || x >= a.nx || y >= a.ny || z >= a.nz) continue;
-      const int32_t ox = x - tx * PV_TX, oy = y - ty * PV_TY, oz = z - tz * PV_TZ;      // the offset in this tile: -1 and the extent are its halo
-      if (ox < -1 || oy < -1 || oz < -1 || ox > PV_TX || oy > PV_TY || oz > PV_TZ) continue;
-      const int64_t g = pv_at(a, x, y, z);
-      if (nvbx_plan_class(a.vol[g], &a.o) < 0) continue;
-      found = 1;
-      if (ox < 0 || oy < 0 || oz < 0 || ox == PV_TX || oy == PV_TY || oz == PV_TZ) continue;      // the neighbour that owns it seeds and counts it
-      a.cost[g] = 0;
-      atomicAdd(&a.head[1], 1u);
-    }
-    const int any = __syncthreads_or(found);
-    if (t == 0) { a.active[tile] = (uint8_t)(any != 0); a.active[ntiles + tile] = 0; }
+    const int32_t dim[3] = {a.nx, a.ny, a.nz}, org[3] = {tx * PV_TX, ty * PV_TY, tz * PV_TZ};
+    plan_grid_seed<PV_TPB, PV_TX, PV_TY, PV_TZ>(a.g, a.vol, dim, org, tile, ntiles);
   }
 }
 
@@ -118,8 +99,8 @@ __global__ __launch_bounds__(PV_TPB) void k_plan3d_relax(Plan3Args a, int32_t pa
   constexpr PvMoves M = pv_moves();
   const int t = threadIdx.x;
   const int32_t ntiles = a.ntx * a.nty * a.ntz;
-  uint8_t* cur = a.active + (size_t)parity * ntiles;
-  uint8_t* nxt = a.active + (size_t)(parity ^ 1) * ntiles;
+  uint8_t* cur = a.g.active + (size_t)parity * ntiles;
+  uint8_t* nxt = a.g.active + (size_t)(parity ^ 1) * ntiles;
   for (int32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int on = cur[tile];
     __syncthreads();                      // (every thread has read the flag; the previous tile's LDS readers are done)
@@ -132,7 +113,7 @@ __global__ __launch_bounds__(PV_TPB) void k_plan3d_relax(Plan3Args a, int32_t pa
       int32_t h = -1;                     // not traversable, or outside the volume
       if (x >= 0 && y >= 0 && z >= 0 && x < a.nx && y < a.ny && z < a.nz) {
         const int64_t g = pv_at(a, x, y, z);
-        const int32_t k = a.cls[g], c = a.cost[g];
+        const int32_t k = a.g.cls[g], c = a.g.cost[g];
         if (k >= 0) h = c == NVBX_COST_UNREACHED ? c : c + k;
       }
       s_h[hx * PV_PLANE + hy * PV_ROW + hz] = h;
@@ -146,7 +127,7 @@ __global__ __launch_bounds__(PV_TPB) void k_plan3d_relax(Plan3Args a, int32_t pa
       const int32_t h = s_h[li[k]];
       ok[k] = 0; kp[k] = 0; g[k] = NVBX_COST_UNREACHED;
       if (h >= 0) {                       // traversable, hence inside the volume
-        kp[k] = a.cls[pv_at(a, tx * PV_TX + lx, ty * PV_TY + ly, tz * PV_TZ + lz)];
+        kp[k] = a.g.cls[pv_at(a, tx * PV_TX + lx, ty * PV_TY + ly, tz * PV_TZ + lz)];
         g[k] = h == NVBX_COST_UNREACHED ? h : h - kp[k];
         uint32_t trav = 0;
 #pragma unroll
@@ -176,7 +157,7 @@ __global__ __launch_bounds__(PV_TPB) void k_plan3d_relax(Plan3Args a, int32_t pa
       }
       sweep++;
       more = __syncthreads_or(ch);
-    } while (more && sweep < a.sweeps);
+    } while (more && sweep < a.g.sweeps);
     int any = 0;
 #pragma unroll
     for (int k = 0; k < PV_PPT; k++) {
@@ -184,7 +165,7 @@ __global__ __launch_bounds__(PV_TPB) void k_plan3d_relax(Plan3Args a, int32_t pa
       int i = t + PV_TPB * k;
       asm volatile("" : "+v"(i));         // (opaque: the rim tests below are worked out here, not kept as lane masks across the sweeps)
       int lx, ly, lz; pv_local(i, &lx, &ly, &lz);
-      a.cost[pv_at(a, tx * PV_TX + lx, ty * PV_TY + ly, tz * PV_TZ + lz)] = g[k];
+      a.g.cost[pv_at(a, tx * PV_TX + lx, ty * PV_TY + ly, tz * PV_TZ + lz)] = g[k];
       any = 1;
       const int dx = lx == 0 ? -1 : lx == PV_TX - 1 ? 1 : 0, dy = ly == 0 ? -1 : ly == PV_TY - 1 ? 1 : 0, dz = lz == 0 ? -1 : lz == PV_TZ - 1 ? 1 : 0;
       const bool okx = dx != 0 && tx + dx >= 0 && tx + dx < a.ntx, oky = dy != 0 && ty + dy >= 0 && ty + dy < a.nty, okz = dz != 0 && tz + dz >= 0 && tz + dz < a.ntz;
@@ -195,138 +176,39 @@ __global__ __launch_bounds__(PV_TPB) void k_plan3d_relax(Plan3Args a, int32_t pa
         nxt[(qx * a.nty + qy) * a.ntz + qz] = 1;
       }
     }
-    any = __syncthreads_or(any);
-    if (t == 0 && (any || more)) {
-      if (more) nxt[tile] = 1;            // cut off by the sweep limit: goes on in the next round
-      atomicAdd(&a.head[0], 1u);
-    }
+    plan_grid_round_end(a.g, nxt, tile, any, more);
   }
 }
 
-struct Trace3Args {
-  const float* vol; int32_t nx, ny, nz;
-  nvbx_cost_options o;
-  const int32_t* cost; const int32_t* starts; int32_t n;
-  int32_t* path; int32_t capacity; int32_t* length;
+struct PvGrid {                           // the 26 moves of nvbx_plan3d_math.h, for the walk
+  static constexpr int D = 3, MOVES = 26;
+  __device__ static int move(int d, int c) { constexpr int MV[26][3] = NVBX_PLAN_MOVES_3D; return MV[d][c]; }
+  __device__ static int k(int d) { return d < NVBX_PLAN_MOVES_3D_AXIS ? 1 : d < NVBX_PLAN_MOVES_3D_FACE ? 2 : 3; }
+  __device__ static int32_t step(int k, int32_t kp, int32_t kq) { return nvbx_plan3d_step(k, kp, kq); }
 };
 
-__device__ inline bool pv_inside(const Trace3Args& a, int32_t x, int32_t y, int32_t z) { return x >= 0 && y >= 0 && z >= 0 && x < a.nx && y < a.ny && z < a.nz; }
-__device__ inline int32_t pv_class_at(const Trace3Args& a, int32_t x, int32_t y, int32_t z) {
-  if (!pv_inside(a, x, y, z)) return NVBX_PLAN_BLOCKED;
-  return nvbx_plan_class(a.vol[((int64_t)x * a.ny + y) * a.nz + z], &a.o);
-}
-
-__global__ __launch_bounds__(64) void k_plan3d_trace(Trace3Args a) {
-  const int32_t i = (int32_t)(blockIdx.x * 64 + threadIdx.x);
-  if (i >= a.n) return;
-  constexpr int MV[26][3] = NVBX_PLAN_MOVES_3D;
-  int32_t x = a.starts[3 * (int64_t)i], y = a.starts[3 * (int64_t)i + 1], z = a.starts[3 * (int64_t)i + 2];
-  int32_t len = 0;
-  if (pv_inside(a, x, y, z) && a.cost[((int64_t)x * a.ny + y) * a.nz + z] != NVBX_COST_UNREACHED) {
-    int32_t* out = a.path + (int64_t)i * a.capacity * 3;
-    const int64_t limit = (int64_t)a.nx * a.ny * a.nz;      // G falls by at least 10 per step: no path of a field is longer
-    len = -1;
-    for (int64_t step = 0; step < limit; step++) {
-      const int32_t g = a.cost[((int64_t)x * a.ny + y) * a.nz + z];
-      if (step < a.capacity) { out[3 * step] = x; out[3 * step + 1] = y; out[3 * step + 2] = z; }
-      if (g == 0) { len = (int32_t)(step + 1); break; }
-      const int32_t kp = pv_class_at(a, x, y, z);
-      if (g < 0 || kp < 0) break;
-      int d = 0;
-      for (; d < 26; d++) {
-        const int32_t qx = x + MV[d][0], qy = y + MV[d][1], qz = z + MV[d][2];
-        const int32_t kq = pv_class_at(a, qx, qy, qz);
-        if (kq < 0) continue;
-        const int k = d < NVBX_PLAN_MOVES_3D_AXIS ? 1 : d < NVBX_PLAN_MOVES_3D_FACE ? 2 : 3;
-        bool clear = true;                // no corner is cut: every voxel p + e between p and q is traversable
-        for (int e = 1; e < 7 && clear && k > 1; e++) {
-          const int32_t ex = (e & 1) ? MV[d][0] : 0, ey = (e & 2) ? MV[d][1] : 0, ez = (e & 4) ? MV[d][2] : 0;
-          if ((ex == 0 && ey == 0 && ez == 0) || (ex == MV[d][0] && ey == MV[d][1] && ez == MV[d][2])) continue;
-          clear = pv_class_at(a, x + ex, y + ey, z + ez) >= 0;
-        }
-        if (!clear) continue;
-        const int32_t gq = a.cost[((int64_t)qx * a.ny + qy) * a.nz + qz];
-        if (gq == NVBX_COST_UNREACHED || gq < 0 || gq >= g) continue;      // (the next voxel lies strictly lower: the walk cannot circle)
-        if ((int64_t)gq + nvbx_plan3d_step(k, kp, kq) == (int64_t)g) { x = qx; y = qy; z = qz; break; }
-      }
-      if (d == 26) break;
-    }
-  }
-  a.length[i] = len;
-}
+__global__ __launch_bounds__(64) void k_plan3d_trace(PlanTraceArgs<3> a) { plan_grid_trace<PvGrid>(a); }
 
 // ------------------------------------------------------------------------------------------------ C-ABI
-namespace {
-
-int plan3d_check(const char* who, const nvbx_mapper* m, const void* volume, int32_t nx, int32_t ny, int32_t nz, const nvbx_cost_options* o, const void* cost) {
-  if (!m) return refuse(who, ": the mapper is NULL");
-  if (!volume || !o || !cost) return refuse(who, ": volume_dev, options and cost_dev are required");
-  if (nx <= 0 || ny <= 0 || nz <= 0 || (int64_t)nx * ny > NVBX_PLAN3D_MAX_VOXELS || (int64_t)nx * ny * nz > NVBX_PLAN3D_MAX_VOXELS)
-    return refuse(who, ": nx, ny and nz must be > 0 and nx x ny x nz <= 2^22");
-  if (const char* why = nvbx_plan_options_problem(o)) return refuse(who, why);
-  return NVBX_OK;
-}
-
-}  // namespace
-
 extern "C" int nvbx_cost_volume(nvbx_mapper* m, const float* volume_dev, int32_t nx, int32_t ny, int32_t nz, const nvbx_cost_options* options,
                                 const int32_t* sources_xyz_dev, int32_t n_sources, int32_t* cost_dev, int32_t* accepted_dev) {
   const char* who = "nvbx_cost_volume";
-  const int rc = plan3d_check(who, m, volume_dev, nx, ny, nz, options, cost_dev);
-  if (rc) return rc;
-  if (n_sources < 0) return refuse(who, ": n_sources is negative");
-  if (n_sources > 0 && !sources_xyz_dev) return refuse(who, ": sources_xyz_dev is required with n_sources > 0");
-  NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;      // the volume only: everything held back stays held back
-  const int64_t n = (int64_t)nx * ny * nz;
+  const int32_t dim[3] = {nx, ny, nz};
+  if (const int rc = plan_grid_check_field<3>(who, PV_WORDS, m, volume_dev, dim, options, sources_xyz_dev, n_sources, cost_dev)) return rc;
   Plan3Args a{};
   a.vol = volume_dev; a.nx = nx; a.ny = ny; a.nz = nz;
   a.ntx = (nx + PV_TX - 1) / PV_TX; a.nty = (ny + PV_TY - 1) / PV_TY; a.ntz = (nz + PV_TZ - 1) / PV_TZ;
-  a.o = *options; a.cost = cost_dev; a.src = sources_xyz_dev; a.n_src = n_sources; a.sweeps = m->plan_knobs.tile_sweeps;
-  const int64_t ntiles = (int64_t)a.ntx * a.nty * a.ntz;      // at most 2^22 / 8: a line of voxels
-  if (m->plan_scratch.ensure(m->stream, PV_HEAD + (size_t)n * 4 + (size_t)ntiles * 2)) return NVBX_E_DEVICE;
-  a.head = m->plan_scratch.as<uint32_t>();
-  a.cls = reinterpret_cast<int32_t*>(m->plan_scratch.as<uint8_t>() + PV_HEAD);
-  a.active = m->plan_scratch.as<uint8_t>() + PV_HEAD + (size_t)n * 4;
+  const int64_t n = (int64_t)nx * ny * nz, ntiles = (int64_t)a.ntx * a.nty * a.ntz;      // at most 2^22 / 8 tiles: a line of voxels
+  if (const int rc = plan_grid_setup(m, &a.g, n, ntiles, options, sources_xyz_dev, n_sources, cost_dev)) return rc;
   const dim3 grid((unsigned)ntiles);
-  NVBX_HIP(hipMemsetAsync(a.head, 0, PV_HEAD, m->stream));
   NVBX_LAUNCH(m, k_plan3d_classify, grid, dim3(PV_TPB), a);
-  NVBX_HIP(hipGetLastError());
-  // Rounds in batches, one read of the changed counter per batch; a batch in which nothing changed ends the call.  After k rounds every voxel
-  // whose best path has at most k moves is final, so n rounds reach the fixed point and one more batch sees it: more can only mean a bug.
-  const int batch = m->plan_knobs.rounds_per_wait;
-  const int64_t max_rounds = n + batch;
-  int32_t parity = 0;
-  for (int64_t rounds = 0; n_sources > 0;) {
-    NVBX_HIP(hipMemsetAsync(a.head, 0, sizeof(uint32_t), m->stream));
-    for (int k = 0; k < batch; k++, parity ^= 1) NVBX_LAUNCH(m, k_plan3d_relax, grid, dim3(PV_TPB), a, parity);
-    NVBX_HIP(hipGetLastError());
-    rounds += batch;
-    uint32_t changed = 0;
-    NVBX_HIP(hipMemcpyAsync(&changed, a.head, sizeof(changed), hipMemcpyDeviceToHost, m->stream));
-    NVBX_HIP(hipStreamSynchronize(m->stream));
-    if (!changed) break;
-    if (rounds >= max_rounds) { set_error("nvbx_cost_volume: the relaxation did not reach its fixed point within nx x ny x nz rounds"); return NVBX_E_DEVICE; }
-  }
-  if (accepted_dev) NVBX_HIP(hipMemcpyAsync(accepted_dev, a.head + 1, sizeof(int32_t), hipMemcpyDeviceToDevice, m->stream));
-  return m->wait_stream();
+  return plan_grid_relax(m, who, PV_WORDS.product, a.g, n, [&](int32_t parity) { NVBX_LAUNCH(m, k_plan3d_relax, grid, dim3(PV_TPB), a, parity); }, accepted_dev);
 }
 
 extern "C" int nvbx_trace_paths_3d(nvbx_mapper* m, const float* volume_dev, int32_t nx, int32_t ny, int32_t nz, const nvbx_cost_options* options,
                                    const int32_t* cost_dev, const int32_t* starts_xyz_dev, int32_t n_starts, int32_t* path_xyz_dev, int32_t capacity,
                                    int32_t* length_dev) {
-  const char* who = "nvbx_trace_paths_3d";
-  const int rc = plan3d_check(who, m, volume_dev, nx, ny, nz, options, cost_dev);
-  if (rc) return rc;
-  if (n_starts < 0 || capacity < 0) return refuse(who, ": n_starts and capacity must be >= 0");
-  if (n_starts > 0 && (!starts_xyz_dev || !path_xyz_dev || !length_dev)) return refuse(who, ": starts_xyz_dev, path_xyz_dev and length_dev are required with n_starts > 0");
-  if (n_starts == 0) return NVBX_OK;
-  NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
-  Trace3Args a{};
-  a.vol = volume_dev; a.nx = nx; a.ny = ny; a.nz = nz; a.o = *options; a.cost = cost_dev; a.starts = starts_xyz_dev; a.n = n_starts;
-  a.path = path_xyz_dev; a.capacity = capacity; a.length = length_dev;
-  NVBX_LAUNCH(m, k_plan3d_trace, dim3((unsigned)((n_starts + 63) / 64)), dim3(64), a);
-  NVBX_HIP(hipGetLastError());
-  return NVBX_OK;
+  const int32_t dim[3] = {nx, ny, nz};
+  return plan_grid_trace_call<3>("nvbx_trace_paths_3d", PV_WORDS, m, volume_dev, dim, options, cost_dev, starts_xyz_dev, n_starts, path_xyz_dev, capacity, length_dev,
+                                 [&](const PlanTraceArgs<3>& a, dim3 grid, dim3 block) { NVBX_LAUNCH(m, k_plan3d_trace, grid, block, a); });
 }

@@ -1248,6 +1248,36 @@ class Mapper:
         unknown_value, max_penalty, unknown_penalty, allow_unknown)."""
         return _args.struct_options(_lib.CostOptions, self.lib.nvbx_default_cost_options, kw, "cost")
 
+    def _cost_to_go(self, fn, grid, coerce, sources, name, out, accepted, options):
+        """cost_field / cost_volume: fn = the library's call, grid = the image or volume, checked; coerce = the coercer of `sources`, called `name`"""
+        torch = self._torch
+        shape = tuple(int(v) for v in grid.shape)
+        o = self.cost_options(**options)
+        src = coerce(sources, self._cuda, name)
+        cost, acc = _args.outputs((out, accepted) if out is not None or accepted is not None else None,
+                                  (("cost", shape, I32, False, True), ("accepted", (1,), I32, False, False)), self._cuda)
+        if cost is None:
+            cost = torch.empty(shape, dtype=torch.int32, device=self._cuda)
+        self._around_torch_stream(lambda: fn(self._h, ptr(grid, collapse=False), *shape, C.byref(o), ptr(src), int(src.shape[0]), ptr(cost, collapse=False), ptr(acc)))
+        return cost
+
+    def _descend(self, fn, grid, word, dims, field, coerce, starts, name, capacity, out, options, slot):
+        """trace_paths / trace_paths_3d: as _cost_to_go; word and dims = what messages call the grid and its shape, slot = where _hold keeps the inputs"""
+        shape = tuple(int(v) for v in grid.shape)
+        o = self.cost_options(**options)
+        f = _args.image(field, self._cuda, self._torch.int32, "field", dims, convert=False)
+        if tuple(f.shape) != shape:
+            raise ValueError("field must have the %s's shape %s, got %s" % (word, shape, tuple(f.shape)))
+        st = coerce(starts, self._cuda, name)
+        n, cap = int(st.shape[0]), int(capacity)
+        if cap < 0:
+            raise ValueError("capacity must be >= 0")
+        paths, lengths = _args.outputs(out, (("paths", (n, cap, len(shape)), I32, True, True), ("lengths", (n,), I32, True, True)), self._cuda)
+        self._around_torch_stream(lambda: fn(self._h, ptr(grid, collapse=False), *shape, C.byref(o), ptr(f, collapse=False), ptr(st), n, ptr(paths, collapse=False), cap, ptr(lengths)),
+                                  order=n > 0)
+        self._hold(slot, [grid, f, st])      # (the kernel reads them: they, and uploaded copies, live until the next call)
+        return paths, lengths
+
     def cost_field(self, image_dev, sources_rc, out=None, accepted=None, **options):
         """The integer cost-to-go field over a distance image (esdf_slice_image_device, esdf_slice_image_combined, or any (rows, cols) float32
         image of that form) from the source pixels sources_rc ((n, 2) int32 (row, col), torch device tensor or numpy array; slice_pixels makes
@@ -1256,18 +1286,7 @@ class Mapper:
         unknown_value must be the one the image was sliced with.  The call waits for the device (between batches of relaxation rounds) and
         returns with the field complete; it reads the image only.  out: a preallocated int32 [rows, cols] tensor; accepted: an int32 [1]
         device tensor that receives the number of accepted sources."""
-        torch = self._torch
-        img = self._image(image_dev, "image")
-        rows, cols = int(img.shape[0]), int(img.shape[1])
-        o = self.cost_options(**options)
-        src = _args.pixels2(sources_rc, self._cuda, "sources_rc")
-        cost, acc = _args.outputs((out, accepted) if out is not None or accepted is not None else None,
-                                  (("cost", (rows, cols), I32, False, True), ("accepted", (1,), I32, False, False)), self._cuda)
-        if cost is None:
-            cost = torch.empty((rows, cols), dtype=torch.int32, device=self._cuda)
-        self._around_torch_stream(lambda: self.lib.nvbx_cost_field(self._h, ptr(img, collapse=False), rows, cols, C.byref(o), ptr(src), int(src.shape[0]),
-                                                                   ptr(cost, collapse=False), ptr(acc)))
-        return cost
+        return self._cost_to_go(self.lib.nvbx_cost_field, self._image(image_dev, "image"), _args.pixels2, sources_rc, "sources_rc", out, accepted, options)
 
     def trace_paths(self, image_dev, field, starts_rc, capacity, out=None, **options):
         """The paths that descend `field` (cost_field of this image and these options) from the pixels starts_rc ((n, 2) int32 (row, col)):
@@ -1275,22 +1294,8 @@ class Mapper:
         pixel of cost 0, both included; lengths[i] is its number of pixels, also beyond `capacity` (pixels from the capacity on are not
         written; rows past a path's end are left as they were), 0 for a start outside the image or unreached, -1 where the field does not
         belong to the image.  Asynchronous.  out=(paths, lengths): preallocated tensors, nothing is allocated."""
-        torch = self._torch
-        img = self._image(image_dev, "image")
-        rows, cols = int(img.shape[0]), int(img.shape[1])
-        o = self.cost_options(**options)
-        f = _args.image(field, self._cuda, torch.int32, "field", "(rows, cols)", convert=False)
-        if tuple(f.shape) != (rows, cols):
-            raise ValueError("field must have the image's shape %s, got %s" % ((rows, cols), tuple(f.shape)))
-        st = _args.pixels2(starts_rc, self._cuda, "starts_rc")
-        n, cap = int(st.shape[0]), int(capacity)
-        if cap < 0:
-            raise ValueError("capacity must be >= 0")
-        paths, lengths = _args.outputs(out, (("paths", (n, cap, 2), I32, True, True), ("lengths", (n,), I32, True, True)), self._cuda)
-        self._around_torch_stream(lambda: self.lib.nvbx_trace_paths(self._h, ptr(img, collapse=False), rows, cols, C.byref(o), ptr(f, collapse=False), ptr(st), n,
-                                                                    ptr(paths, collapse=False), cap, ptr(lengths)), order=n > 0)
-        self._hold("_keep_tp", [img, f, st])      # (the kernel reads them: they, and uploaded copies, live until the next call)
-        return paths, lengths
+        return self._descend(self.lib.nvbx_trace_paths, self._image(image_dev, "image"), "image", "(rows, cols)", field, _args.pixels2, starts_rc, "starts_rc",
+                             capacity, out, options, "_keep_tp")
 
     def slice_pixels(self, points_xy, aabb):
         """Metres -> pixels of the ESDF slice image that came with `aabb` (esdf_slice_image_device / esdf_slice_image / ..._combined):
@@ -1331,18 +1336,7 @@ class Mapper:
         on such a voxel is ignored.  options: see cost_options.  The call waits for the device (between batches of relaxation rounds) and
         returns with the field complete; it reads the volume only.  out: a preallocated int32 [nx, ny, nz] tensor; accepted: an int32 [1]
         device tensor that receives the number of accepted sources."""
-        torch = self._torch
-        vol = self._dense_volume(volume_dev)
-        shape = tuple(int(v) for v in vol.shape)
-        o = self.cost_options(**options)
-        src = _args.voxels3(sources_xyz, self._cuda, "sources_xyz")
-        cost, acc = _args.outputs((out, accepted) if out is not None or accepted is not None else None,
-                                  (("cost", shape, I32, False, True), ("accepted", (1,), I32, False, False)), self._cuda)
-        if cost is None:
-            cost = torch.empty(shape, dtype=torch.int32, device=self._cuda)
-        self._around_torch_stream(lambda: self.lib.nvbx_cost_volume(self._h, ptr(vol, collapse=False), shape[0], shape[1], shape[2], C.byref(o), ptr(src),
-                                                                    int(src.shape[0]), ptr(cost, collapse=False), ptr(acc)))
-        return cost
+        return self._cost_to_go(self.lib.nvbx_cost_volume, self._dense_volume(volume_dev), _args.voxels3, sources_xyz, "sources_xyz", out, accepted, options)
 
     def trace_paths_3d(self, volume_dev, field, starts_xyz, capacity, out=None, **options):
         """The paths that descend `field` (cost_volume of this volume and these options) from the voxels starts_xyz ((n, 3) int32 (x, y, z)):
@@ -1350,23 +1344,8 @@ class Mapper:
         voxel of cost 0, both included; lengths[i] is its number of voxels, also beyond `capacity` (voxels from the capacity on are not
         written; rows past a path's end are left as they were), 0 for a start outside the box or unreached, -1 where the field does not
         belong to the volume.  Asynchronous.  out=(paths, lengths): preallocated tensors, nothing is allocated."""
-        torch = self._torch
-        vol = self._dense_volume(volume_dev)
-        shape = tuple(int(v) for v in vol.shape)
-        o = self.cost_options(**options)
-        f = _args.image(field, self._cuda, torch.int32, "field", "(nx, ny, nz)", convert=False)
-        if tuple(f.shape) != shape:
-            raise ValueError("field must have the volume's shape %s, got %s" % (shape, tuple(f.shape)))
-        st = _args.voxels3(starts_xyz, self._cuda, "starts_xyz")
-        n, cap = int(st.shape[0]), int(capacity)
-        if cap < 0:
-            raise ValueError("capacity must be >= 0")
-        paths, lengths = _args.outputs(out, (("paths", (n, cap, 3), I32, True, True), ("lengths", (n,), I32, True, True)), self._cuda)
-        self._around_torch_stream(lambda: self.lib.nvbx_trace_paths_3d(self._h, ptr(vol, collapse=False), shape[0], shape[1], shape[2], C.byref(o),
-                                                                       ptr(f, collapse=False), ptr(st), n, ptr(paths, collapse=False), cap, ptr(lengths)),
-                                  order=n > 0)
-        self._hold("_keep_tp3", [vol, f, st])      # (the kernel reads them: they, and uploaded copies, live until the next call)
-        return paths, lengths
+        return self._descend(self.lib.nvbx_trace_paths_3d, self._dense_volume(volume_dev), "volume", "(nx, ny, nz)", field, _args.voxels3, starts_xyz, "starts_xyz",
+                             capacity, out, options, "_keep_tp3")
 
     def volume_voxels(self, points_xyz, min_vox):
         """Metres -> voxels of the box that starts at min_vox (esdf_dense_grid_device's): points_xyz (n, 3) -> int32 numpy [n, 3] of (x, y, z)

@@ -110,6 +110,28 @@ def test_random_images_fields_and_paths(mp, cases, k):
     assert (lengths[:16] >= 1).all() and (lengths[16:] == 0).all()
 
 
+SOURCE_ON_THE_RIM = (      # (shape, blocked pixels, source, reached pixels, {pixel: cost}): figures from PI.field on the CPU
+    ((33, 33), (), (32, 32), 1089, {(0, 0): 448, (31, 31): 14}),                          # the source is alone in its 1 x 1 tile
+    ((65, 33), (), (32, 32), 2145, {}),                                                   # ... in a 1 x 32 tile: the control
+    ((64, 64), ((30, 30), (30, 31), (31, 30)), (31, 31), 4093, {(32, 32): 14}),           # ... in a full tile that it can leave only across the rim
+)
+
+
+@pytest.mark.parametrize("shape,blocked,source,reached,values", SOURCE_ON_THE_RIM)
+def test_a_source_wakes_the_tiles_that_hold_it_in_their_halo(mp, shape, blocked, source, reached, values):
+    """A source's 0 is a value no relaxation stores: the classify launch has to wake the neighbouring tiles itself."""
+    img = np.full(shape, F32(5.0))
+    for p in blocked:
+        img[p] = PI.BLOCKED
+    what = "%s, source %s" % (shape, source)
+    G = _check_field(mp, img, [source], what)
+    assert int((G != PI.UNREACHED).sum()) == reached, what
+    for p, v in values.items():
+        assert G[p] == v, (what, p, int(G[p]), v)
+    assert G[0, 0] == G[G != PI.UNREACHED].max(), what                                   # the far corner; its path crosses every tile boundary
+    assert _check_paths(mp, img, G, [(0, 0)], shape[0] + shape[1], what)[0] >= 33
+
+
 # ---- 2. many rounds, and the two knobs
 def test_serpentine_under_every_knob_setting(mp):
     img, sources = PI.serpentine(96)

@@ -842,7 +842,8 @@ void nvbx_default_align_options(nvbx_align_options* options);
  * options NULL: the defaults.  result_dev: 8-byte aligned device memory, written by the launches.  Asynchronous on the mapper's stream.
  * n == 0: NVBX_ALIGN_TOO_FEW, the accumulate launch is skipped.  NVBX_E_INVALID (nvbx_last_error set, nothing launched, the mapper stays
  * usable): an occupancy mapper; a NULL mapper, pose, result or (n > 0) point / depth pointer; n < 0; a misaligned result_dev; a pose that is
- * not finite or out of range; a camera that does not match the image; max_iterations outside 1 .. 64; subsampling < 1; min_valid < 1;
+ * not finite or out of range; image sides outside 1 .. 32768; a camera that does not match the image; max_iterations outside 1 .. 64;
+ * subsampling < 1; min_valid < 1;
  * damping / min_pivot_ratio / a stop threshold negative or not finite; min_weight, huber_delta_m or max_depth_m not a number. */
 int nvbx_align_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float T_L_S_guess[16], const nvbx_align_options* options,
                       nvbx_align_result* result_dev);

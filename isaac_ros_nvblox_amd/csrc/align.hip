@@ -14,10 +14,10 @@
 // All max_iterations pairs are enqueued up front; the pose of iteration 0 and the options travel as kernel arguments, the pose of the later
 // ones is the state the previous solve left.  Once the status is final the remaining launches read it and return at once.
 // nvbx_relocalize_* (relocalize.hip) enqueues the same launches behind its selection, which leaves iteration 0's pose -- and a status that may
-// already be final -- in the state (AlignArgs::from_state, align_from_state).
+// already be final -- in the state (AlignArgs::from_state; nvbx_align.h).
 #include <algorithm>
 #include <cmath>
-#include "nvbx_mapper.h"
+#include "nvbx_align.h"
 #include "nvbx_query_point.h"
 #include "nvbx_align_math.h"
 
@@ -28,22 +28,9 @@ constexpr int ALIGN_MAX_WG = 256, ALIGN_TPB = 256;
 enum { ALIGN_RUNNING = 0 };
 enum { MODE_ALIGN = 0, MODE_LINEARIZE = 1 };
 
-// (AlignState { double R[9], t[3]; int32_t status, iterations; }: nvbx_mapper.h -- 104 bytes, at the front of nvbx_mapper::align_buf)
+// (AlignState, AlignArgs: nvbx_align.h -- the state's 104 bytes at the front of nvbx_mapper::align_buf)
 constexpr size_t ALIGN_PARTIAL_OFFSET = 128;
 constexpr size_t ALIGN_BUF_BYTES = ALIGN_PARTIAL_OFFSET + (size_t)ALIGN_MAX_WG * ALIGN_TERMS * sizeof(double);
-
-struct AlignArgs {
-  const float* pts;                                             // [n][3], or ...
-  const float* depth; int32_t cols, cs, s; float fu, fv, cu, cv, max_d;      // ... the pixels (r s, c s): n = rs x cs of them
-  int64_t n;
-  float R0[9], t0[3];                                           // the pose of iteration 0 ...
-  int32_t from_state;                                           // ... unless set: then an earlier launch left it in *st (relocalize.hip), with the status to start from
-  int32_t iter, max_iter, mode, min_valid, nblocks;
-  float vs, min_weight;
-  double huber, damping, min_pivot, stop_t, stop_r;
-  AlignState* st; double* partial; nvbx_align_result* res;
-  float* out_p; float* out_r; float* out_g; uint8_t* out_v;     // per-point outputs of nvbx_linearize_points (each may be null)
-};
 
 template <bool DEPTH>
 __global__ __launch_bounds__(ALIGN_TPB) void k_align_accumulate(DMap m, AlignArgs a) {
@@ -61,16 +48,9 @@ __global__ __launch_bounds__(ALIGN_TPB) void k_align_accumulate(DMap m, AlignArg
   double acc[ALIGN_TERMS];
 #pragma unroll
   for (int k = 0; k < ALIGN_TERMS; k++) acc[k] = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
-    float x[3];
-    if (DEPTH) {
-      const int32_t r = (int32_t)(i / a.cs) * a.s, c = (int32_t)(i % a.cs) * a.s;
-      const float d = a.depth[(int64_t)r * a.cols + c];
-      if (!backproject_takes(d, a.max_d)) continue;
-      backproject_pixel(r, c, d, a.fu, a.fv, a.cu, a.cv, x);
-    } else {
-      x[0] = a.pts[3 * i]; x[1] = a.pts[3 * i + 1]; x[2] = a.pts[3 * i + 2];
-    }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.src.n; i += (int64_t)gridDim.x * blockDim.x) {
+    float x[3] = {0.0f, 0.0f, 0.0f};
+    if (!point_source_fetch<DEPTH>(a.src, i, x)) continue;
     float p[3], g[3], d;
     apply_rt(R, t, x[0], x[1], x[2], p);
     const bool valid = q_point<Q_TSDF, false>(m, pool, p, a.vs, a.min_weight, 0.0f, 0, &d, g);
@@ -199,39 +179,25 @@ static int align_check(const char* who, nvbx_mapper* m, const float* pts, int64_
     return refuse(who, ": min_weight / huber_delta_m / max_depth_m is not a number");
   if (!from_state && !nvbx_pose_in_range(T, m->p.voxel_size * 8.0f, 0.0f)) return refuse(who, ": the pose is not finite or out of range");
   a = AlignArgs{};
-  if (depth || cam) {
-    if (!depth || rows <= 0 || cols <= 0 || !nvbx_camera_matches(cam, rows, cols)) return refuse(who, ": the depth image and a camera of its size are required");
-    if (o.subsampling < 1) return refuse(who, ": subsampling must be >= 1");
-    const int32_t rs = (rows + o.subsampling - 1) / o.subsampling, cs = (cols + o.subsampling - 1) / o.subsampling;
-    a.depth = depth; a.cols = cols; a.cs = cs; a.s = o.subsampling;
-    a.fu = cam->fu; a.fv = cam->fv; a.cu = cam->cu; a.cv = cam->cv; a.max_d = o.max_depth_m;
-    n = (int64_t)rs * cs;
-  } else {
-    if (n < 0 || (n > 0 && !pts)) return refuse(who, ": n points need points_xyz_dev");
-    a.pts = pts;
-  }
-  a.n = n;
+  if (point_source_check(who, pts, n, depth, rows, cols, cam, o.subsampling, o.max_depth_m, &a.src)) return NVBX_E_INVALID;
   a.from_state = from_state ? 1 : 0;
-  if (!from_state)
-    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) a.R0[3 * i + j] = T[4 * i + j]; a.t0[i] = T[4 * i + 3]; }
+  if (!from_state) nvbx_pose_unpack(T, a.R0, a.t0);
   a.max_iter = mode == MODE_LINEARIZE ? 1 : o.max_iterations; a.mode = mode; a.min_valid = o.min_valid;
-  a.nblocks = (int32_t)std::min<int64_t>((n + ALIGN_TPB - 1) / ALIGN_TPB, ALIGN_MAX_WG);
+  a.nblocks = (int32_t)std::min<int64_t>((a.src.n + ALIGN_TPB - 1) / ALIGN_TPB, ALIGN_MAX_WG);
   a.vs = m->p.voxel_size; a.min_weight = o.min_weight;
   a.huber = (double)o.huber_delta_m; a.damping = o.damping; a.min_pivot = o.min_pivot_ratio; a.stop_t = o.stop_translation_m; a.stop_r = o.stop_rotation_rad;
   a.res = res; a.out_p = out_p; a.out_r = out_r; a.out_g = out_g; a.out_v = out_v;
   return NVBX_OK;
 }
 
-// the state record and the partial sums.  (A growth waits for the stream: before the first launch of a call.)
-static int align_buffers(nvbx_mapper* m, AlignArgs& a) {
+int nvbx::align_buffers(nvbx_mapper* m, AlignArgs& a) {
   if (m->align_buf.ensure(m->stream, ALIGN_BUF_BYTES)) return NVBX_E_DEVICE;
   a.st = reinterpret_cast<AlignState*>(m->align_buf.as<unsigned char>());
   a.partial = reinterpret_cast<double*>(m->align_buf.as<unsigned char>() + ALIGN_PARTIAL_OFFSET);
   return NVBX_OK;
 }
 
-// every launch of a call whose arguments align_check has accepted
-static int align_launch(nvbx_mapper* m, AlignArgs& a) {
+int nvbx::align_launch(nvbx_mapper* m, AlignArgs& a) {
   NVBX_HIP(hipSetDevice(m->device));
   // reads TSDF voxels and the TSDF flags only: held-back work stays held back, as for the TSDF point query (query.hip)
   if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
@@ -239,7 +205,7 @@ static int align_launch(nvbx_mapper* m, AlignArgs& a) {
   for (int32_t it = 0; it < a.max_iter; it++) {
     a.iter = it;
     if (a.nblocks > 0) {
-      if (a.depth) NVBX_LAUNCH(m, k_align_accumulate<true>, dim3((unsigned)a.nblocks), dim3(ALIGN_TPB), m->d, a);
+      if (a.src.depth) NVBX_LAUNCH(m, k_align_accumulate<true>, dim3((unsigned)a.nblocks), dim3(ALIGN_TPB), m->d, a);
       else NVBX_LAUNCH(m, k_align_accumulate<false>, dim3((unsigned)a.nblocks), dim3(ALIGN_TPB), m->d, a);
     }
     NVBX_LAUNCH(m, k_align_solve, dim3(1), dim3(SOLVE_TPB), a);
@@ -257,18 +223,10 @@ static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t 
   return rc ? rc : align_launch(m, a);
 }
 
-// nvbx_relocalize_* (relocalize.hip): nvbx_align_points / nvbx_align_depth whose iteration 0 reads the pose -- and whether to run at all -- from the
-// state record a launch of the caller's writes.  In steps, so that a refusal comes before the caller's first launch: ALIGN_STEP_CHECK looks at the
-// arguments only, ALIGN_STEP_STATE makes sure of the record and hands it out in *state, ALIGN_STEP_LAUNCH enqueues the iterations.
-int nvbx::align_from_state(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols,
-                           const nvbx_camera* cam, const nvbx_align_options* options, nvbx_align_result* res, AlignStep step, AlignState** state) {
-  AlignArgs a;
-  const int rc = align_check(who, m, pts, n, depth, rows, cols, cam, nullptr, true, options, res, MODE_ALIGN, nullptr, nullptr, nullptr, nullptr, a);
-  if (rc || step == ALIGN_STEP_CHECK) return rc;
-  if (step == ALIGN_STEP_LAUNCH) return align_launch(m, a);
-  if (align_buffers(m, a)) return NVBX_E_DEVICE;
-  *state = a.st;
-  return NVBX_OK;
+// nvbx_relocalize_* (relocalize.hip, described in nvbx_align.h), which then calls align_buffers and align_launch itself
+int nvbx::align_check_from_state(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols,
+                                 const nvbx_camera* cam, const nvbx_align_options* options, nvbx_align_result* res, AlignArgs& a) {
+  return align_check(who, m, pts, n, depth, rows, cols, cam, nullptr, true, options, res, MODE_ALIGN, nullptr, nullptr, nullptr, nullptr, a);
 }
 
 extern "C" void nvbx_default_align_options(nvbx_align_options* o) {
@@ -285,7 +243,7 @@ extern "C" int nvbx_align_points(nvbx_mapper* m, const float* points_xyz_dev, in
 
 extern "C" int nvbx_align_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const float T_L_C_guess[16], const nvbx_camera* camera,
                                 const nvbx_align_options* options, nvbx_align_result* result_dev) {
-  if (m && (!depth_dev || !camera)) return refuse("nvbx_align_depth", ": the depth image and the camera are required");
+  if (depth_entry_refused("nvbx_align_depth", m, depth_dev, camera)) return NVBX_E_INVALID;
   return align_run("nvbx_align_depth", m, nullptr, 0, depth_dev, rows, cols, camera, T_L_C_guess, options, result_dev, MODE_ALIGN, nullptr, nullptr, nullptr, nullptr);
 }
 

@@ -66,7 +66,7 @@ extern "C" int nvbx_transform_pointcloud(nvbx_mapper* m, const float T_L_C[16], 
   if (n_points == 0) return NVBX_OK;
   NVBX_HIP(hipSetDevice(m->device));
   Rt T;
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T.R[3 * i + j] = T_L_C[4 * i + j]; T.t[i] = T_L_C[4 * i + 3]; }
+  nvbx_pose_unpack(T_L_C, T.R, T.t);
   NVBX_LAUNCH(m, k_transform_points, dim3((unsigned)std::min<int64_t>((n_points + 255) / 256, 2048)), dim3(256), T, points_in_dev, n_points, points_out_dev);
   NVBX_HIP(hipGetLastError());
   return NVBX_OK;

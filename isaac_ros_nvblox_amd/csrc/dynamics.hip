@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void k_detect_dynamics(DMap m, RtCam g, const 
 }
 static RtCam make_rtcam(const float T_L_C[16], const nvbx_camera* camera) {
   RtCam g;
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) g.R[3 * i + j] = T_L_C[4 * i + j]; g.t[i] = T_L_C[4 * i + 3]; }
+  nvbx_pose_unpack(T_L_C, g.R, g.t);
   g.fu = camera->fu; g.fv = camera->fv; g.cu = camera->cu; g.cv = camera->cv;
   return g;
 }

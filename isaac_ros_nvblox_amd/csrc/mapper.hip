@@ -131,7 +131,7 @@ float nvbx::log_odds(float p) { return logf(p / (1.0f - p)); }
 // T_L_C row-major 4x4 -> forward and inverse rigid transforms, fixed evaluation order (matches oracle rt_from_T)
 Frame nvbx_mapper::make_frame(const float T[16], const nvbx_camera* cam, int32_t rows, int32_t cols, int32_t subsample) const {
   Frame f{};
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) f.R_LC[3 * i + j] = T[4 * i + j]; f.t_LC[i] = T[4 * i + 3]; }
+  nvbx_pose_unpack(T, f.R_LC, f.t_LC);
   for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) f.R_CL[3 * i + j] = f.R_LC[3 * j + i];
   for (int i = 0; i < 3; i++) {
     float s = f.R_CL[3 * i + 0] * f.t_LC[0];

@@ -58,11 +58,6 @@ size_t ref_voxel_bytes(uint32_t layer);
 static inline bool layer_writable(uint32_t l) { return l == F_TSDF || l == F_COLOR || l == F_ESDF || l == NVBX_LAYER_OCCUPANCY; }
 static inline bool layer_readable(uint32_t l) { return layer_writable(l) || l == F_FREESPACE; }
 static inline bool layer_listable(uint32_t l) { return layer_readable(l) || l == F_MESH || l == F_FEATURE; }      // (feature blocks are read by nvbx_get_feature_blocks)
-// align.hip.  The pose state of an alignment on the device, and the alignment whose iteration 0 starts from it (for relocalize.hip; described there)
-struct AlignState { double R[9], t[3]; int32_t status, iterations; };      // 104 bytes, at the front of nvbx_mapper::align_buf; status 0 = running
-enum AlignStep { ALIGN_STEP_CHECK, ALIGN_STEP_STATE, ALIGN_STEP_LAUNCH };
-int align_from_state(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
-                     const nvbx_align_options* options, nvbx_align_result* res, AlignStep step, AlignState** state);
 
 }  // namespace nvbx
 
@@ -94,6 +89,10 @@ static inline bool nvbx_pose_in_range(const float T[16], float block_size, float
   for (int i = 0; i < 16; i++) if (!std::isfinite(T[i])) return false;
   const float lim = nvbx_pose_limit(block_size, reach);
   return std::fabs(T[3]) < lim && std::fabs(T[7]) < lim && std::fabs(T[11]) < lim;
+}
+// a row-major 4 x 4 pose -> its rotation, row-major 3 x 3, and its translation
+static inline void nvbx_pose_unpack(const float T[16], float R[9], float t[3]) {
+  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) R[3 * i + j] = T[4 * i + j]; t[i] = T[4 * i + 3]; }
 }
 __host__ __device__ static inline bool nvbx_index_in_range(int32_t x, int32_t y, int32_t z) {
   const int32_t L = 1 << 20;

@@ -22,7 +22,7 @@ __device__ inline int32_t mask_pixel(const MaskGeom& g, int32_t r, int32_t c, fl
 #endif
 inline MaskGeom make_mask_geom(const float T_CM_CD[16], const nvbx_camera* dc, const nvbx_camera* mc, int32_t rows, int32_t cols, int32_t mask_rows, int32_t mask_cols) {
   MaskGeom g;
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) g.T.R[3 * i + j] = T_CM_CD[4 * i + j]; g.T.t[i] = T_CM_CD[4 * i + 3]; }
+  nvbx_pose_unpack(T_CM_CD, g.T.R, g.T.t);
   g.dfu = dc->fu; g.dfv = dc->fv; g.dcu = dc->cu; g.dcv = dc->cv; g.mfu = mc->fu; g.mfv = mc->fv; g.mcu = mc->cu; g.mcv = mc->cv;
   g.rows = rows; g.cols = cols; g.mrows = mask_rows; g.mcols = mask_cols;
   return g;

@@ -6,9 +6,9 @@
 //   k_score_poses   one workgroup = one pose x one chunk of the points: 256 points, one per lane, up to 1 024 chunks.  Beyond that -- and
 //                   in the one-workgroup-per-pose variant, which measured slower -- a lane takes `per_lane` CONSECUTIVE points
 //                   (neighbouring pixels or scan points lie in neighbouring voxels: the lane keeps the slot of the last base block,
-//                   q_point<.., DIST_ONLY>, and probes the hash only when the base corner leaves that block).  A lane transforms its point
-//                   (apply_rt, f32), takes the TSDF
-//                   distance of k_query_points (the same inline code) and classifies it.  The three counts are ballots and pop-counts
+//                   q_point<.., DIST_ONLY>, and probes the hash only when the base corner leaves that block).  A lane fetches its point
+//                   (point_source_fetch), transforms it (apply_rt, f32), takes the TSDF distance of k_query_points (the same inline code)
+//                   and classifies it.  The three counts are ballots and pop-counts
 //                   per wavefront, kept in scalar registers; |d| in 2^-20 m is summed per lane in 64 bits, once across the wavefront
 //                   with shuffles, once across the four wavefronts through LDS.  With one chunk the workgroup stores the record; with
 //                   more it adds to a record zeroed on the stream with vector integer atomics -- integer sums, so any order gives the
@@ -16,13 +16,13 @@
 //                   neighbours in the launch are spatial neighbours of one yaw and read neighbouring voxels), or from the result record
 //                   of a relocalisation in flight.  No per-pose copy of the points exists anywhere.
 //   k_select_pose   one workgroup: arg-max of (inliers - conflicts, inliers, -h) over the lattice's records, the result record's head,
-//                   and the state record the alignment's iterations start from (align.hip, align_from_state).
+//                   and the state record the alignment's iterations start from (align.hip, nvbx_align.h).
 // nvbx_relocalize_*: tables (host, nvbx_relocalize_math.h) -> upload -> k_score_poses -> k_select_pose -> the alignment's launches ->
 // k_score_poses of the refined pose, all enqueued at once.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include "nvbx_mapper.h"
+#include "nvbx_align.h"
 #include "nvbx_knobs.h"
 #include "nvbx_query_point.h"
 #include "nvbx_relocalize_math.h"
@@ -37,9 +37,8 @@ enum { POSE_LIST = 0, POSE_LATTICE = 1, POSE_REFINED = 2 };
 struct LatticeArgs { const nvbx_lattice_tables* tab; float t0[3]; int32_t ny, nz, nyaw, nspatial; };
 
 struct ScoreArgs {
-  const float* pts;                                             // [n][3], or ...
-  const float* depth; int32_t cols, cs, s; float fu, fv, cu, cv, max_d;      // ... the pixels (r s, c s): n = rs x cs of them
-  int64_t n, per_lane;
+  PointSource src;
+  int64_t per_lane;
   int32_t source, split;
   const float* poses;                                           // POSE_LIST: [gridDim.x][16]
   LatticeArgs lat;                                              // POSE_LATTICE
@@ -95,18 +94,8 @@ __global__ __launch_bounds__(SCORE_TPB) void k_score_poses(DMap m, ScoreArgs a) 
   long long res = 0;
   for (int64_t j = 0; j < a.per_lane; j++) {                    // (a uniform trip count: every lane of the wavefront reaches the ballots)
     const int64_t i = start + j;
-    bool take = i < a.n;
     float x[3] = {0.0f, 0.0f, 0.0f};
-    if (take) {
-      if (DEPTH) {
-        const int32_t ii = (int32_t)i, r = ii / a.cs * a.s, c = ii % a.cs * a.s;
-        const float d = a.depth[(int64_t)r * a.cols + c];
-        take = backproject_takes(d, a.max_d);
-        if (take) backproject_pixel(r, c, d, a.fu, a.fv, a.cu, a.cv, x);
-      } else {
-        x[0] = a.pts[3 * i]; x[1] = a.pts[3 * i + 1]; x[2] = a.pts[3 * i + 2];
-      }
-    }
+    const bool take = i < a.src.n && point_source_fetch<DEPTH>(a.src, i, x);
     bool valid = false;
     float d = 0.0f;
     if (take) {
@@ -210,39 +199,23 @@ int score_options_check(const char* who, const nvbx_mapper* m, const nvbx_score_
   return NVBX_OK;
 }
 
-// the point source of a call: depth != null or cam != null: the depth form.  -> the part of ScoreArgs that names the points
-int score_points_check(const char* who, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
-                       const ScoreOptions& o, ScoreArgs* a) {
-  if (depth || cam) {
-    if (!depth || !image_dims_ok(rows, cols) || !nvbx_camera_matches(cam, rows, cols)) return refuse(who, ": the depth image and a camera of its size are required");
-    const int32_t rs = (rows + o.s - 1) / o.s, cs = (cols + o.s - 1) / o.s;
-    a->depth = depth; a->cols = cols; a->cs = cs; a->s = o.s;
-    a->fu = cam->fu; a->fv = cam->fv; a->cu = cam->cu; a->cv = cam->cv; a->max_d = o.max_d;
-    a->n = (int64_t)rs * cs;
-  } else {
-    if (n < 0 || (n > 0 && !pts)) return refuse(who, ": n points need points_xyz_dev");
-    a->pts = pts; a->n = n;
-  }
-  return NVBX_OK;
-}
-
 // One launch over n_poses poses; the arguments have been checked, the mapper's stream is ready.  Chunks: a workgroup per 256 points, one point per
 // lane, for every pose count -- measured faster than one workgroup per pose even where the poses alone fill the device (DESIGN.md 2.20,
 // EXPERIMENTS.md); beyond SCORE_MAX_CHUNKS x 256 points the lanes take runs of consecutive points.  (A/B, tools/relocalize_bench.py:
 // NVBX_SCORE_CHUNKS = c forces c chunks where the points allow, 1 = one workgroup per pose; nvbx_mapper_reload_knobs lets one process measure both.)
 int score_launch(nvbx_mapper* m, ScoreArgs a, const ScoreOptions& o, int64_t n_poses, bool records_are_zero) {
   const int forced = m->knobs.score_chunks;      // (0: unset, malformed or out of range)
-  const int64_t full = std::max<int64_t>((a.n + SCORE_TPB - 1) / SCORE_TPB, 1);
+  const int64_t full = std::max<int64_t>((a.src.n + SCORE_TPB - 1) / SCORE_TPB, 1);
   const int64_t chunks_wanted = forced > 0 ? forced : SCORE_MAX_CHUNKS;
   int64_t chunks = std::min(std::min(chunks_wanted, full), SCORE_MAX_CHUNKS);
-  a.per_lane = (a.n + SCORE_TPB * chunks - 1) / (SCORE_TPB * chunks);
-  if (a.per_lane > 0) chunks = (a.n + SCORE_TPB * a.per_lane - 1) / (SCORE_TPB * a.per_lane);      // (no empty chunk)
+  a.per_lane = (a.src.n + SCORE_TPB * chunks - 1) / (SCORE_TPB * chunks);
+  if (a.per_lane > 0) chunks = (a.src.n + SCORE_TPB * a.per_lane - 1) / (SCORE_TPB * a.per_lane);      // (no empty chunk)
   a.split = chunks > 1;
   a.vs = m->p.voxel_size; a.min_weight = o.min_weight; a.inlier = o.inlier; a.conflict = o.conflict;
   a.pose_lim = nvbx_pose_limit(m->p.voxel_size * 8.0f, 0.0f);
   if (a.split && !records_are_zero) NVBX_HIP(hipMemsetAsync(a.out, 0, sizeof(nvbx_pose_score) * (size_t)n_poses, m->stream));
   const dim3 grid((unsigned)n_poses, (unsigned)chunks);
-  if (a.depth) NVBX_LAUNCH(m, k_score_poses<true>, grid, dim3(SCORE_TPB), m->d, a);
+  if (a.src.depth) NVBX_LAUNCH(m, k_score_poses<true>, grid, dim3(SCORE_TPB), m->d, a);
   else NVBX_LAUNCH(m, k_score_poses<false>, grid, dim3(SCORE_TPB), m->d, a);
   return NVBX_OK;
 }
@@ -256,7 +229,7 @@ int score_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n, cons
   if ((uintptr_t)scores & 7) return refuse(who, ": scores_dev must be 8-byte aligned");
   ScoreOptions o;
   ScoreArgs a{};
-  if (score_options_check(who, m, options, &o) || score_points_check(who, pts, n, depth, rows, cols, cam, o, &a)) return NVBX_E_INVALID;
+  if (score_options_check(who, m, options, &o) || point_source_check(who, pts, n, depth, rows, cols, cam, o.s, o.max_d, &a.src)) return NVBX_E_INVALID;
   if (n_poses == 0) return NVBX_OK;
   NVBX_HIP(hipSetDevice(m->device));
   if (m->join_side_keeping_held()) return NVBX_E_DEVICE;      // TSDF voxels and flags only: held-back colour and ESDF work stays held back (query.hip)
@@ -277,8 +250,9 @@ int relocalize_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n,
   if (!nvbx_pose_in_range(T0, m->p.voxel_size * 8.0f, 0.0f)) return refuse(who, ": T0 is not finite or out of range");
   ScoreOptions o;
   ScoreArgs a{};
-  if (score_options_check(who, m, score_options, &o) || score_points_check(who, pts, n, depth, rows, cols, cam, o, &a)) return NVBX_E_INVALID;
-  int rc = align_from_state(who, m, pts, n, depth, rows, cols, cam, align_options, &res->align, ALIGN_STEP_CHECK, nullptr);
+  if (score_options_check(who, m, score_options, &o) || point_source_check(who, pts, n, depth, rows, cols, cam, o.s, o.max_d, &a.src)) return NVBX_E_INVALID;
+  AlignArgs al;
+  const int rc = align_check_from_state(who, m, pts, n, depth, rows, cols, cam, align_options, &res->align, al);
   if (rc) return rc;
   NVBX_HIP(hipSetDevice(m->device));
   if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
@@ -286,9 +260,7 @@ int relocalize_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n,
   const int64_t K = nvbx_lattice_count(lattice);
   constexpr size_t TAB_BYTES = (sizeof(nvbx_lattice_tables) + 255) / 256 * 256;
   if (m->reloc_buf.ensure(m->stream, TAB_BYTES + (scores ? 0 : sizeof(nvbx_pose_score) * (size_t)K))) return NVBX_E_DEVICE;
-  AlignState* st = nullptr;
-  rc = align_from_state(who, m, pts, n, depth, rows, cols, cam, align_options, &res->align, ALIGN_STEP_STATE, &st);
-  if (rc) return rc;
+  if (align_buffers(m, al)) return NVBX_E_DEVICE;
   // the tables: made here, uploaded from memory that outlives the call
   m->reloc_host.resize(sizeof(nvbx_lattice_tables) / sizeof(float));
   nvbx_lattice_tables* tab_host = reinterpret_cast<nvbx_lattice_tables*>(m->reloc_host.data());
@@ -306,11 +278,10 @@ int relocalize_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n,
   if (score_launch(m, sa, o, K, false)) return NVBX_E_DEVICE;
   // 2: the selection; it zeroes the result record and leaves the state the iterations start from
   SelectArgs se{};
-  se.scores = rec; se.n_poses = (int32_t)K; se.min_inliers = min_inliers > 0 ? min_inliers : 50; se.lat = lat; se.res = res; se.st = st;
+  se.scores = rec; se.n_poses = (int32_t)K; se.min_inliers = min_inliers > 0 ? min_inliers : 50; se.lat = lat; se.res = res; se.st = al.st;
   NVBX_LAUNCH(m, k_select_pose, dim3(1), dim3(SELECT_TPB), se);
   // 3: the alignment's iterations
-  rc = align_from_state(who, m, pts, n, depth, rows, cols, cam, align_options, &res->align, ALIGN_STEP_LAUNCH, nullptr);
-  if (rc) return rc;
+  if (align_launch(m, al)) return NVBX_E_DEVICE;
   // 4: the refined pose's record (zeroed by the selection)
   ScoreArgs sr = a;
   sr.source = POSE_REFINED; sr.from = res; sr.out = &res->refined;
@@ -333,7 +304,7 @@ extern "C" int nvbx_score_poses_points(nvbx_mapper* m, const float* points_xyz_d
 
 extern "C" int nvbx_score_poses_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const nvbx_camera* camera, const float* T_L_C_dev,
                                       int32_t n_poses, const nvbx_score_options* options, nvbx_pose_score* scores_dev) {
-  if (m && (!depth_dev || !camera)) return refuse("nvbx_score_poses_depth", ": the depth image and the camera are required");
+  if (depth_entry_refused("nvbx_score_poses_depth", m, depth_dev, camera)) return NVBX_E_INVALID;
   return score_run("nvbx_score_poses_depth", m, nullptr, 0, depth_dev, rows, cols, camera, T_L_C_dev, n_poses, options, scores_dev);
 }
 
@@ -359,7 +330,7 @@ extern "C" int nvbx_relocalize_points(nvbx_mapper* m, const float* points_xyz_de
 extern "C" int nvbx_relocalize_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32_t cols, const nvbx_camera* camera, const float T0[16],
                                      const nvbx_search_lattice* lattice, const nvbx_score_options* score_options, int32_t min_inliers,
                                      const nvbx_align_options* align_options, nvbx_pose_score* scores_dev, nvbx_relocalize_result* result_dev) {
-  if (m && (!depth_dev || !camera)) return refuse("nvbx_relocalize_depth", ": the depth image and the camera are required");
+  if (depth_entry_refused("nvbx_relocalize_depth", m, depth_dev, camera)) return NVBX_E_INVALID;
   return relocalize_run("nvbx_relocalize_depth", m, nullptr, 0, depth_dev, rows, cols, camera, T0, lattice, score_options, min_inliers, align_options,
                         scores_dev, result_dev);
 }

@@ -248,7 +248,7 @@ extern "C" int nvbx_render_view_with(nvbx_mapper* m, const nvbx_render_options* 
     set_error("nvbx_render_view: T_L_C is not finite or lies outside the addressable block range (+-2^20 blocks)"); return NVBX_E_INVALID; }
   RenderArgs a;
   { const int rc = render_begin(m, options, max_ray_length_m, color_rgb_dev != nullptr, "nvbx_render_view", &a); if (rc) return rc; }
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) a.R_LC[3 * i + j] = T_L_C[4 * i + j]; a.t_LC[i] = T_L_C[4 * i + 3]; }
+  nvbx_pose_unpack(T_L_C, a.R_LC, a.t_LC);
   a.fu = camera->fu; a.fv = camera->fv; a.cu = camera->cu; a.cv = camera->cv;
   a.subsample = ss.s; a.srows = ss.rows; a.scols = ss.cols;
   a.depth = depth_dev; a.color = color_rgb_dev; a.normal = normal_xyz_dev;

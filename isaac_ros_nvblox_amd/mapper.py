@@ -816,10 +816,8 @@ class Mapper:
     def align_depth(self, depth, T_L_C_guess, cam, out=None, **options):
         """Refine a camera pose from a float32 depth image (metres; torch tensor or numpy array): the pixels (r s, c s) with
         0 < depth <= max_depth_m are back-projected inside the launch, no point buffer is written.  -> AlignResult; out as for align_points."""
-        d = self._dev(depth, self._torch.float32)
-        if d.dim() != 2:
-            raise ValueError("depth must be a (rows, cols) image")
-        T = self._T(T_L_C_guess); o = self.align_options(**options); k = self._cam(cam)
+        d, k = self._point_source(depth, cam)
+        T = self._T(T_L_C_guess); o = self.align_options(**options)
         buf = _args.result_buffer(out, ALIGN_RESULT_BYTES, self._cuda)
         # (a non-collapsing pointer: nvbx_align_depth refuses a NULL image before it looks at its size)
         self._around_torch_stream(lambda: self.lib.nvbx_align_depth(self._h, C.c_void_p(d.data_ptr()), d.shape[0], d.shape[1], _np_ptr(T), C.byref(k),
@@ -849,8 +847,9 @@ class Mapper:
         max_depth_m, subsampling).  A threshold <= 0 selects its default: one voxel size, half the truncation distance, 1e-4."""
         return _args.struct_options(_lib.ScoreOptions, self.lib.nvbx_default_score_options, kw, "score")
 
-    def _score_source(self, points_or_depth, cam):
-        """-> (device tensor, Camera | None): cam None: an (n, 3) cloud for the _points entries; else a (rows, cols) depth image for the _depth ones"""
+    def _point_source(self, points_or_depth, cam):
+        """The points of an alignment, scoring or relocalisation call -> (device tensor, Camera | None): cam None: an (n, 3) cloud for the _points
+        entries; else a (rows, cols) depth image for the _depth ones"""
         if cam is None:
             p = _args.points3(points_or_depth, self._cuda)
             return p, None
@@ -865,7 +864,7 @@ class Mapper:
         -> (counts int32 [K, 4]: points, valid, inliers, conflicts; abs_residual_q20 int64 [K]: sum of |d| in 2^-20 m over the valid points) on the
         mapper's device, two views of one int64 [K, 3] tensor of 24-byte records.  A pose that is not finite or out of range has points = -1 and
         zeros.  options: see score_options.  out: that preallocated int64 [K, 3] tensor, nothing is allocated."""
-        src, k = self._score_source(points_or_depth, cam)
+        src, k = self._point_source(points_or_depth, cam)
         T = _args.poses16(poses, self._cuda); n = int(T.shape[0])
         o = self.score_options(**options)
         rec, counts, residual = _args.score_records(out, n, self._cuda)
@@ -926,13 +925,13 @@ class Mapper:
         status is NO_CANDIDATE and no refinement runs.  score / align: dicts of score_options / align_options fields.  scores: True, or a
         preallocated int64 [K, 3] tensor: the lattice's records are kept (result.scores).  out: a preallocated result buffer (uint8 tensor of
         RELOC_RESULT_BYTES bytes)."""
-        src, _ = self._score_source(points, None)
+        src, _ = self._point_source(points, None)
         return self._relocalize(src, None, T0, half_extent_m, half_yaw_rad, steps, min_inliers, score, align, scores, out)
 
     def relocalize_depth(self, depth, T0, cam, half_extent_m, half_yaw_rad, steps, min_inliers=None, score=None, align=None, scores=None, out=None):
         """relocalize_points for a float32 depth image: scoring takes the pixels (r s, c s) of the score options' subsampling and max_depth_m, the
         refinement those of the align options', both back-projected inside the launches."""
-        src, k = self._score_source(depth, cam)
+        src, k = self._point_source(depth, cam)
         return self._relocalize(src, k, T0, half_extent_m, half_yaw_rad, steps, min_inliers, score, align, scores, out)
 
     # -- map merging (nvbx_merge_map; SEMANTICS.md "Map merging")

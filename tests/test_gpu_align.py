@@ -175,7 +175,7 @@ def test_end_to_end_refinement_reaches_the_models_fixed_point(room, frames, fixe
             assert dt <= 1e-4 and dr <= 1e-4, (f, dt, dr)
 
 
-@pytest.mark.parametrize("s", [1, 4])
+@pytest.mark.parametrize("s", [1, 3, 4])
 def test_depth_is_points(room, frames, s):
     import torch
     d_img, _, _, st = frames[22]
@@ -201,6 +201,43 @@ def test_depth_is_points(room, frames, s):
     # exactly those pixels: without the limit, and without the hole, more points are valid
     assert room.align_depth(depth, st[1], A.SMALL_CAM, subsampling=s, max_iterations=1).n_valid_first > rd.n_valid_first
     assert room.align_depth(d_img, st[1], A.SMALL_CAM, subsampling=s, max_depth_m=max_d, max_iterations=1).n_valid_first > rd.n_valid_first
+
+
+@pytest.mark.parametrize("s", [3, 7])
+def test_depth_form_is_the_point_form_lane_for_lane(room, frames, s):
+    """The depth form's pixel i = r cs + c sits in the lane and the workgroup of point i of an (rs cs, 3) cloud, and a non-finite point is never
+    valid: with a NaN row where the pixel is not taken, the cloud leaves the depth form's result record byte for byte, and its score records but for
+    `points`, which counts the NaN rows too.  (s = 3: 40 x 54 pixels, the columns leave a remainder; s = 7: 18 x 23, both sides do.)"""
+    import torch
+    from isaac_ros_nvblox_amd import mapper as M
+    d_img, T_true, _, st = frames[22]
+    depth = d_img.copy()
+    depth[40:60, 50:90] = 0.0
+    max_d = 2.5
+    fu, fv, cu, cv = (np.float32(v) for v in A.SMALL_CAM[:4])
+    d = depth[::s, ::s]
+    rs, cs = d.shape
+    assert (rs, cs) == {3: (40, 54), 7: (18, 23)}[s] and (rs - 1) * s < 120 and (cs - 1) * s < 160
+    r = (np.arange(rs) * s).astype(np.float32); c = (np.arange(cs) * s).astype(np.float32)
+    rx = ((c + np.float32(0.5)) - cu) / fu; ry = ((r + np.float32(0.5)) - cv) / fv                     # (align_independent.backproject's arithmetic)
+    pts = np.stack([d * rx[None, :], d * ry[:, None], d], -1).astype(np.float32).reshape(-1, 3)
+    take = ((d > 0) & (d <= np.float32(max_d))).reshape(-1)
+    assert np.array_equal(_bits(pts[take]), _bits(A.backproject(depth, A.SMALL_CAM, s, max_d)))
+    pts[~take] = np.nan
+    n_taken = int(take.sum())
+    assert n_taken == {3: 1912, 7: 370}[s] and (d == 0).sum() > 0 and (d > np.float32(max_d)).sum() > 0
+    dt = torch.from_numpy(depth).cuda()
+    rd = room.align_depth(dt, st[1], A.SMALL_CAM, subsampling=s, max_depth_m=max_d)
+    rp = room.align_points(pts, st[1])
+    bd, bp = _np(rd.buffer).tobytes(), _np(rp.buffer).tobytes()
+    assert len(bd) == M.ALIGN_RESULT_BYTES == 712 and bd == bp
+    assert rd.n_valid_first > 100 and rd.iterations > 1                          # (a real refinement, not a record both forms left untouched)
+    poses = np.stack([np.asarray(T, np.float32) for T in [T_true] + list(st)])
+    cd, qd = room.score_poses(dt, poses, cam=A.SMALL_CAM, subsampling=s, max_depth_m=max_d)
+    cp, qp = room.score_poses(pts, poses)
+    cd, qd, cp, qp = _np(cd), _np(qd), _np(cp), _np(qp)
+    assert np.array_equal(cd[:, 1:], cp[:, 1:]) and np.array_equal(qd, qp) and cd[0, 1] > 100
+    assert (cd[:, 0] == n_taken).all() and (cp[:, 0] == rs * cs).all()
 
 
 def test_early_stop_and_failures(room, frames):

@@ -187,7 +187,7 @@ def test_options_replace_the_thresholds(room, frames):
     assert [tuple(v) for v in _np(c)] == [(-1, 0, 0, 0) if k == "bad" else (0, 0, 0, 0) for k in kinds] and not _np(r).any()
 
 
-@pytest.mark.parametrize("s", [1, 4])
+@pytest.mark.parametrize("s", [1, 3, 4])
 def test_depth_is_points(room, frames, s):
     import torch
     d_img, T_true, _, _ = frames[22]

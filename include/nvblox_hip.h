@@ -439,6 +439,16 @@ int nvbx_esdf_dense_grid(nvbx_mapper* m, const int32_t min_vox[3], const int32_t
  * nvbx_dev_interpolate_esdf in nvblox_hip_device.h, bit-identical. */
 int nvbx_query_points(nvbx_mapper* m, uint32_t layer, const float* points_xyz_dev, int64_t n, float min_weight, float unknown_value,
                       float* distance_dev, float* gradient_xyz_dev, uint8_t* valid_dev);
+/* [U] The colour layer at n arbitrary points (SEMANTICS.md "Colour alignment and colour queries"): the lattice and the trilinear interpolant of
+ * the TSDF query above, over the colour voxels.  A corner counts when its block carries the colour layer and its voxel's weight is
+ * >= min_color_weight; the point is valid when all eight corners count.  Corner luminance Yc = (77 r + 150 g + 29 b) / 256 (levels, exact in
+ * f32); luminance_dev[n] = Y(p), gradient_xyz_dev[n][3] = dY/dp per metre, rgb_dev[n][3] = the same interpolant per channel of the raw u8
+ * values; all 0 at an invalid point.  rgb_dev, luminance_dev, gradient_xyz_dev: NULL = not written; valid_dev[n] is required when n > 0.
+ * One launch, asynchronous on the mapper's stream; n == 0 launches nothing.  Held-back colour work is carried out first (the call reads the
+ * colour layer).  NVBX_E_INVALID: a NULL mapper, points or valid pointer (n > 0); n < 0; an occupancy mapper; a min_color_weight that is not a
+ * number. */
+int nvbx_query_colors(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, float min_color_weight, float* rgb_dev, float* luminance_dev,
+                      float* gradient_xyz_dev, uint8_t* valid_dev);
 
 /* ---- rendering and ray casts ([U] SphereTracer::renderImageOnGPU / renderRgbdImageOnGPU / castOnGPU, nvblox/rays/sphere_tracer.h) -----
  * The map seen along rays (SEMANTICS.md "Rendering and ray casts"): the sphere tracing of integrateColor's occlusion image -- nearest voxel,
@@ -851,6 +861,44 @@ int nvbx_align_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, int32
                      const nvbx_align_options* options, nvbx_align_result* result_dev);
 int nvbx_linearize_points(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, const float T_L_S[16], const nvbx_align_options* options,
                           nvbx_align_result* result_dev, float* points_L_dev, float* residual_dev, float* gradient_dev, uint8_t* valid_dev);
+
+/* ---- pose alignment with a colour term ([U]; SEMANTICS.md "Colour alignment and colour queries") ----------------------------------------
+ * The calls above with a photometric term beside the geometric one, for frames whose geometry lets the pose slide (a wall, a floor).  Every
+ * point carries an rgb8 colour: colors_rgb_dev[n][3] beside a cloud, color_rgb_dev[rows][cols][3] (the depth's pixels) beside a depth image;
+ * Ys = its luminance (77 r + 150 g + 29 b) / 256.  For a point whose geometric term is valid and whose colour query
+ * (Y, gY, valid) = nvbx_query_colors(min_color_weight) at the same p is valid, in f64: e = Y - Ys (levels), kappa = voxel_size / 255,
+ * r_c = kappa e, J_c = kappa [gY, q x gY], w_c = 1 if color_huber_levels <= 0 or |e| <= color_huber_levels else color_huber_levels / |e|;
+ * H += (color_weight w_c J_c) J_c^T, b += (color_weight w_c J_c) r_c -- added to the same H and b after the point's geometric products --
+ * color_cost += (w_c e) e, n_color += 1.  A full-range intensity step across one voxel has |kappa gY| = 1, the TSDF gradient's magnitude:
+ * color_weight 1 weighs such an edge like a surface.  cost and n_valid of nvbx_align_sums stay the geometric ones; the solve, its statuses and
+ * the 712-byte result record are the plain calls', over the joint system.  With color_weight 0 the result record is the plain call's bit for
+ * bit.  The calls read the colour layer: held-back colour work is carried out first.
+ * Refused: what the plain calls refuse, in their order; then a NULL colour pointer (n > 0, or an image); a NULL or misaligned
+ * color_result_dev; a color_weight that is negative or not finite; a min_color_weight / color_huber_levels that is not a number. */
+typedef struct {
+  float   color_weight;         /* lambda >= 0 */
+  float   min_color_weight;     /* a colour corner counts with weight >= this */
+  float   color_huber_levels;   /* <= 0: plain least squares */
+  int32_t pad;
+} nvbx_align_color_options;     /* 16 bytes; offsets 0 4 8 12 */
+typedef struct {
+  double  color_cost_first, color_cost_last;      /* sum w_c e^2 (levels^2) of the first and of the last linearization */
+  int32_t n_color_first, n_color_last;            /* points with a colour term */
+} nvbx_align_color_result;      /* 24 bytes, 8-byte aligned DEVICE memory; offsets 0 8 16 20 */
+/* defaults: color_weight 1, min_color_weight 1e-4, no Huber weighting */
+void nvbx_default_align_color_options(nvbx_align_color_options* options);
+int nvbx_align_points_color(nvbx_mapper* m, const float* points_xyz_dev, const uint8_t* colors_rgb_dev, int64_t n, const float T_L_S_guess[16],
+                            const nvbx_align_options* options, const nvbx_align_color_options* color_options, nvbx_align_result* result_dev,
+                            nvbx_align_color_result* color_result_dev);
+int nvbx_align_depth_color(nvbx_mapper* m, const float* depth_dev, const uint8_t* color_rgb_dev, int32_t rows, int32_t cols, const float T_L_C_guess[16],
+                           const nvbx_camera* camera, const nvbx_align_options* options, const nvbx_align_color_options* color_options,
+                           nvbx_align_result* result_dev, nvbx_align_color_result* color_result_dev);
+/* the per-point outputs (each NULL: not written) of nvbx_linearize_points, and luminance_dev[n], color_gradient_dev[n][3], color_valid_dev[n]:
+ * bit for bit nvbx_query_colors at points_L_dev */
+int nvbx_linearize_points_color(nvbx_mapper* m, const float* points_xyz_dev, const uint8_t* colors_rgb_dev, int64_t n, const float T_L_S[16],
+                                const nvbx_align_options* options, const nvbx_align_color_options* color_options, nvbx_align_result* result_dev,
+                                nvbx_align_color_result* color_result_dev, float* points_L_dev, float* residual_dev, float* gradient_dev,
+                                uint8_t* valid_dev, float* luminance_dev, float* color_gradient_dev, uint8_t* color_valid_dev);
 
 /* ---- relocalisation ([U] scoring pose hypotheses against the TSDF; SEMANTICS.md "Relocalisation") ----------------------------------------
  * Where nvbx_align_* refine a guess within the truncation band, these calls find such a guess: they score many sensor poses against the

@@ -84,6 +84,11 @@ def points3(a, dev, what="points"):
     return _rows(a, dev, 3, torch.float32, "", what)
 
 
+def colors3(a, dev, what="colors"):
+    """-> a contiguous (n, 3) uint8 tensor of (r, g, b) on `dev`; moved, converted and reshaped as _rows says."""
+    return _rows(a, dev, 3, torch.uint8, " of (r, g, b)", what)
+
+
 def pixels2(a, dev, what="pixels"):
     """-> a contiguous (n, 2) int32 tensor of (row, col) on `dev`; moved, converted and reshaped as _rows says."""
     return _rows(a, dev, 2, torch.int32, " of (row, col)", what)

@@ -137,6 +137,16 @@ class AlignResult(C.Structure):
                 ("iterations", C.c_int32), ("status", C.c_int32)]
 
 
+class AlignColorOptions(C.Structure):
+    """nvbx_align_color_options (16 bytes); nvbx_default_align_color_options fills it"""
+    _fields_ = [("color_weight", C.c_float), ("min_color_weight", C.c_float), ("color_huber_levels", C.c_float), ("pad", C.c_int32)]
+
+
+class AlignColorResult(C.Structure):
+    """nvbx_align_color_result: the colour sums an alignment with a colour term leaves in DEVICE memory (24 bytes)"""
+    _fields_ = [("color_cost_first", C.c_double), ("color_cost_last", C.c_double), ("n_color_first", C.c_int32), ("n_color_last", C.c_int32)]
+
+
 class PoseScore(C.Structure):
     """nvbx_pose_score: one pose's record of nvbx_score_poses_* (24 bytes)"""
     _fields_ = [("points", C.c_int32), ("valid", C.c_int32), ("inliers", C.c_int32), ("conflicts", C.c_int32), ("abs_residual_q20", C.c_int64)]
@@ -269,6 +279,12 @@ SIGNATURES = {
     "nvbx_align_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp]),
     "nvbx_align_depth": (C.c_int, [_vp, _vp, _i32, _i32, _vp, C.POINTER(Camera), C.POINTER(AlignOptions), _vp]),
     "nvbx_linearize_points": (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(AlignOptions), _vp, _vp, _vp, _vp, _vp]),
+    "nvbx_query_colors": (C.c_int, [_vp, _vp, _i64, _f, _vp, _vp, _vp, _vp]),
+    "nvbx_default_align_color_options": (None, [C.POINTER(AlignColorOptions)]),
+    "nvbx_align_points_color": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.POINTER(AlignOptions), C.POINTER(AlignColorOptions), _vp, _vp]),
+    "nvbx_align_depth_color": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, C.POINTER(Camera), C.POINTER(AlignOptions), C.POINTER(AlignColorOptions), _vp, _vp]),
+    "nvbx_linearize_points_color": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.POINTER(AlignOptions), C.POINTER(AlignColorOptions), _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nvbx_default_score_options": (None, [C.POINTER(ScoreOptions)]),
     "nvbx_score_poses_points": (C.c_int, [_vp, _vp, _i64, _vp, _i32, C.POINTER(ScoreOptions), _vp]),
     "nvbx_score_poses_depth": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(Camera), _vp, _i32, C.POINTER(ScoreOptions), _vp]),

@@ -16,6 +16,12 @@ struct AlignArgs {
   double huber, damping, min_pivot, stop_t, stop_r;
   AlignState* st; double* partial; nvbx_align_result* res;
   float* out_p; float* out_r; float* out_g; uint8_t* out_v;     // per-point outputs of nvbx_linearize_points (each may be null)
+  // the colour term (nvbx_*_color).  terms = the doubles of a partial slot: 29, or 31 in a colour call (+ colour cost, colour count)
+  int32_t color, terms;
+  float min_color_weight, pad;
+  double color_w, color_huber;                                  // lambda; the Huber threshold in levels (<= 0: none)
+  nvbx_align_color_result* cres;
+  float* out_cy; float* out_cg; uint8_t* out_cv;                // per-point outputs of nvbx_linearize_points_color (each may be null)
 };
 
 // The steps of a call.  nvbx_relocalize_* takes them one by one: its alignment is nvbx_align_points / nvbx_align_depth whose iteration 0 reads the pose

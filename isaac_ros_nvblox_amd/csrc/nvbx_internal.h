@@ -293,6 +293,9 @@ __device__ inline uint4 ld_pair(const uint2* p) {
   const u4a8 v = *reinterpret_cast<const u4a8*>(p);
   return make_uint4(v.x, v.y, v.z, v.w);
 }
+// luminance in levels of an rgb8 triple, (77 r + 150 g + 29 b) / 256: exact in f32 (the integer is <= 65 280, the factor a power of two) -- the colour
+// interpolant's corner value (nvbx_query_point.h) and a sensor point's (nvbx_point_source.h)
+__device__ inline float luma_levels(uint32_t r, uint32_t g, uint32_t b) { return (float)(77u * r + 150u * g + 29u * b) * (1.0f / 256.0f); }
 // finish a lookup whose first probe `e` at `h` is already loaded: slot of any block with `key`, or SLOT_NONE
 __device__ inline uint32_t resolve_any(const DMap& m, u64 key, uint32_t h, uint4 e) {
   for (uint32_t probe = 0; probe <= m.mask; ++probe) {

@@ -10,6 +10,7 @@ struct PointSource {
   const float* pts;                                             // [n][3], or ...
   const float* depth; int32_t cols, cs, s; float fu, fv, cu, cv, max_d;      // ... the pixels (r s, c s): n = rs x cs of them
   int64_t n;
+  const uint8_t* rgb;                                           // null, or the points' colours: [n][3] beside a cloud, [rows][cols][3] rgb8 beside a depth image
 };
 
 // The refusals of a point source, in their order; *out is filled where there is none.  depth != null or cam != null: the depth form (pts and n are not
@@ -45,6 +46,16 @@ __device__ inline bool point_source_fetch(const PointSource& s, int64_t i, float
   } else {
     x[0] = s.pts[3 * i]; x[1] = s.pts[3 * i + 1]; x[2] = s.pts[3 * i + 2];
   }
+  return true;
+}
+// the same with the point's colour (s.rgb must not be null): *ys = the luminance in levels of the point's rgb8 triple -- the depth's pixel in the depth form
+template <bool DEPTH>
+__device__ inline bool point_source_fetch(const PointSource& s, int64_t i, float x[3], float* ys) {
+  if (!point_source_fetch<DEPTH>(s, i, x)) return false;
+  int64_t at = i;
+  if (DEPTH) { const int32_t ii = (int32_t)i; at = (int64_t)(ii / s.cs * s.s) * s.cols + ii % s.cs * s.s; }
+  const uint8_t* c = s.rgb + 3 * at;
+  *ys = luma_levels(c[0], c[1], c[2]);
   return true;
 }
 

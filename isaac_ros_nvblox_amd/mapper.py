@@ -193,6 +193,40 @@ class AlignResult:
         return "AlignResult(%s, iterations=%d, n_valid=%d, rmse %.4g -> %.4g)" % (self.status_name, self.iterations, self.n_valid, self.rmse_first, self.rmse_last)
 
 
+ALIGN_COLOR_RESULT_BYTES = ALIGN_RESULT_BYTES + C.sizeof(_lib.AlignColorResult)
+
+
+class AlignColorResult(AlignResult):
+    """What an alignment with a colour term left behind: `buffer` holds the nvbx_align_result record (the AlignResult view: `buffer[:712]` is
+    byte for byte what the plain call writes) and the nvbx_align_color_result record behind it; ALIGN_COLOR_RESULT_BYTES bytes."""
+
+    def _c(self):
+        self._r()
+        return self._color
+
+    def _r(self):
+        if self._host is None:
+            raw = self.buffer.cpu().numpy().tobytes()
+            self._host = _lib.AlignResult.from_buffer_copy(raw[:ALIGN_RESULT_BYTES])
+            self._color = _lib.AlignColorResult.from_buffer_copy(raw[ALIGN_RESULT_BYTES:])
+        return self._host
+
+    @staticmethod
+    def _crmse(cost, n):
+        return float(np.sqrt(cost / n)) if n > 0 else 0.0
+
+    n_color = property(lambda self: int(self._c().n_color_last), doc="points with a colour term in the last linearization")
+    n_color_first = property(lambda self: int(self._c().n_color_first))
+    color_cost_first = property(lambda self: float(self._c().color_cost_first))
+    color_cost_last = property(lambda self: float(self._c().color_cost_last))
+    color_rmse_first = property(lambda self: self._crmse(self._c().color_cost_first, self._c().n_color_first), doc="sqrt(color_cost / n_color) at the guess, in levels")
+    color_rmse_last = property(lambda self: self._crmse(self._c().color_cost_last, self._c().n_color_last), doc="... at the last linearization")
+
+    def __repr__(self):
+        return "AlignColorResult(%s, iterations=%d, n_valid=%d, n_color=%d, rmse %.4g -> %.4g m, colour %.4g -> %.4g levels)" % (
+            self.status_name, self.iterations, self.n_valid, self.n_color, self.rmse_first, self.rmse_last, self.color_rmse_first, self.color_rmse_last)
+
+
 class RelocalizeResult:
     """What relocalize_points / relocalize_depth left behind: `buffer` is the nvbx_relocalize_result record on the device (a uint8 tensor, written
     by the launches); the first field that is read copies it to the host once.  `align` is an AlignResult over the record's alignment part,
@@ -840,6 +874,76 @@ class Mapper:
         self._around_torch_stream(lambda: self.lib.nvbx_linearize_points(self._h, ptr(p), n, _np_ptr(T), C.byref(o), ptr(buf), ptr(pl), ptr(r), ptr(g), ptr(v)))
         self._hold("_keep_a", [p])
         return AlignResult(buf), pl, r, g, v
+
+    # -- colour point queries and pose alignment with a colour term (nvbx_query_colors / nvbx_*_color; SEMANTICS.md "Colour alignment and colour queries")
+    def query_color(self, points, min_color_weight=1e-4, rgb=True, out=None):
+        """The colour layer at `points` ((n, 3) float32, metres), trilinear over the TSDF query's lattice: -> (rgb [n, 3] f32 | None, luminance [n]
+        f32 in levels, its gradient [n, 3] f32 per metre, valid [n] bool) on the mapper's device; zeros at an invalid point.  A corner counts
+        with colour weight >= min_color_weight.  rgb=False: no rgb output.  out=(rgb | None, luminance | None, gradient | None, valid):
+        preallocated tensors, nothing is allocated and `rgb` is not looked at."""
+        dev = self._cuda
+        p = _args.points3(points, dev); n = p.shape[0]
+        c, y, g, v = _args.outputs(out, (("rgb", (n, 3), F32, False, rgb), ("luminance", (n,), F32, False, True), ("gradient", (n, 3), F32, False, True),
+                                         ("valid", (n,), FLAG, True, True)), dev)
+        self._around_torch_stream(lambda: self.lib.nvbx_query_colors(self._h, ptr(p), n, float(min_color_weight), ptr(c), ptr(y), ptr(g), ptr(v)), order=n > 0)
+        self._hold("_keep_q", [p])
+        return c, y, g, v
+
+    def align_color_options(self, **kw):
+        """nvbx_align_color_options: the library's defaults with the given fields replaced (color_weight, min_color_weight, color_huber_levels)."""
+        return _args.struct_options(_lib.AlignColorOptions, self.lib.nvbx_default_align_color_options, kw, "colour alignment")
+
+    def _align_color_setup(self, T, out, options):
+        """-> (pose, align options, colour options, result buffer, pointer to its colour record); `options` mixes the fields of both structs"""
+        names = [f for f, _ in _lib.AlignColorOptions._fields_]
+        co = self.align_color_options(**{k: v for k, v in options.items() if k in names})
+        o = self.align_options(**{k: v for k, v in options.items() if k not in names})
+        buf = _args.result_buffer(out, ALIGN_COLOR_RESULT_BYTES, self._cuda)
+        return self._T(T), o, co, buf, C.c_void_p(buf.data_ptr() + ALIGN_RESULT_BYTES)
+
+    def align_points_color(self, points, colors, T_L_S_guess, out=None, **options):
+        """align_points with a colour term: `colors` = (n, 3) uint8 rgb, one per point.  -> AlignColorResult.  options: the fields of
+        align_options and align_color_options.  out: a preallocated uint8 tensor of ALIGN_COLOR_RESULT_BYTES bytes."""
+        p = _args.points3(points, self._cuda); c = _args.colors3(colors, self._cuda)
+        if c.shape[0] != p.shape[0]:
+            raise ValueError("colors must hold one (r, g, b) per point: %d points, %d colours" % (p.shape[0], c.shape[0]))
+        T, o, co, buf, cbuf = self._align_color_setup(T_L_S_guess, out, options)
+        self._around_torch_stream(lambda: self.lib.nvbx_align_points_color(self._h, ptr(p), ptr(c), p.shape[0], _np_ptr(T), C.byref(o), C.byref(co), ptr(buf), cbuf))
+        self._hold("_keep_a", [p, c])
+        return AlignColorResult(buf)
+
+    def align_depth_color(self, depth, rgb, T_L_C_guess, cam, out=None, **options):
+        """align_depth with a colour term: `rgb` = the (rows, cols, 3) uint8 image registered with the depth image; the colour of a point is its
+        depth pixel's.  -> AlignColorResult; options and out as for align_points_color."""
+        d, k = self._point_source(depth, cam)
+        c = _args.image(rgb, self._cuda, self._torch.uint8, "rgb", "(rows, cols, 3)", (3,))
+        if tuple(c.shape[:2]) != tuple(d.shape):
+            raise ValueError("rgb must have the depth image's size %s, got %s" % (tuple(d.shape), tuple(c.shape[:2])))
+        T, o, co, buf, cbuf = self._align_color_setup(T_L_C_guess, out, options)
+        self._around_torch_stream(lambda: self.lib.nvbx_align_depth_color(self._h, C.c_void_p(d.data_ptr()), C.c_void_p(c.data_ptr()), d.shape[0], d.shape[1],
+                                                                          _np_ptr(T), C.byref(k), C.byref(o), C.byref(co), ptr(buf), cbuf))
+        self._hold("_keep_a", [d, c])
+        return AlignColorResult(buf)
+
+    def linearize_points_color(self, points, colors, T_L_S, per_point=True, out=None, **options):
+        """linearize_points with a colour term: -> (AlignColorResult, points_L, residual, gradient, valid, luminance [n] f32, color_gradient [n, 3] f32,
+        color_valid [n] bool); the last three are bit for bit query_color at points_L.  per_point and out (the buffer and the seven per-point
+        tensors, each may be None) as for linearize_points."""
+        dev = self._cuda
+        p = _args.points3(points, dev); n = p.shape[0]
+        c = _args.colors3(colors, dev)
+        if c.shape[0] != n:
+            raise ValueError("colors must hold one (r, g, b) per point: %d points, %d colours" % (n, c.shape[0]))
+        buf_out, rest = (None, None) if out is None else (out[0], out[1:])
+        T, o, co, buf, cbuf = self._align_color_setup(T_L_S, buf_out, options)
+        pl, r, g, v, cy, cg, cv = _args.outputs(rest, (("points_L", (n, 3), F32, False, per_point), ("residual", (n,), F32, False, per_point),
+                                                       ("gradient", (n, 3), F32, False, per_point), ("valid", (n,), FLAG, False, per_point),
+                                                       ("luminance", (n,), F32, False, per_point), ("color_gradient", (n, 3), F32, False, per_point),
+                                                       ("color_valid", (n,), FLAG, False, per_point)), dev)
+        self._around_torch_stream(lambda: self.lib.nvbx_linearize_points_color(self._h, ptr(p), ptr(c), n, _np_ptr(T), C.byref(o), C.byref(co), ptr(buf), cbuf,
+                                                                               ptr(pl), ptr(r), ptr(g), ptr(v), ptr(cy), ptr(cg), ptr(cv)))
+        self._hold("_keep_a", [p, c])
+        return AlignColorResult(buf), pl, r, g, v, cy, cg, cv
 
     # -- relocalisation (nvbx_score_poses_* / nvbx_relocalize_*; SEMANTICS.md "Relocalisation")
     def score_options(self, **kw):

@@ -997,6 +997,64 @@ void nvbx_default_merge_options(nvbx_merge_options* options);
 /* T_D_S: row-major 4 x 4, host memory.  options NULL: the defaults.  result_dev: written by the last launch, not waited for. */
 int nvbx_merge_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S[16], const nvbx_merge_options* options, nvbx_merge_result* result_dev);
 
+/* ---- change detection ([U] what differs between two maps; SEMANTICS.md "Change detection") --------------------------------------------
+ * Compares mapper `m` ("now") with a reference mapper `ref` ("before") under p_M = T_M_R p_R.  A voxel of a TSDF block of m with stored
+ * {d, w}, inside box_min_max_vox (inclusive, global voxel coordinates of m as in nvbx_find_frontiers; NULL: unbounded), is OBSERVED iff
+ * w >= min_weight, FREE iff observed and d > free_distance_m, OCCUPIED iff observed and d <= occupied_distance_m, NEAR otherwise (a NaN d
+ * is neither free nor occupied).  Its sample of ref lies at p_R = R_RM p_M + t_RM, p_M = ((float)(8 b + v) + 0.5f) voxel_size per axis and
+ * {R_RM, t_RM} the inverse pair of nvbx_merge_map.  sampling 0 (trilinear): the rule of the merge and of the TSDF point query -- all eight
+ * corners in TSDF blocks of ref with weight >= ref_min_weight, d_ref = the trilinear interpolant.  sampling 1 (nearest): the voxel
+ * floor(p_R / voxel_size) per axis in f32, valid iff its block carries the TSDF layer and its weight >= ref_min_weight, d_ref = its
+ * distance.  A valid sample is FREE / OCCUPIED / NEAR by the same two thresholds; an invalid one, or one outside the addressable block
+ * range, is UNKNOWN.  label 0 (APPEARED): m OCCUPIED and ref FREE; label 1 (REMOVED): m FREE and ref OCCUPIED; -1 otherwise;
+ * score = fabsf(d - d_ref) on a labelled voxel, 0 elsewhere.
+ * nvbx_find_changes writes the sparse volume of nvbx_find_frontiers: one entry per TSDF block of m with at least one labelled voxel, entry
+ *   order unspecified; label_dev[e][512], score_dev[e][512] (NULL: not written), t = vx 64 + vy 8 + vz; *count_dev = the number of such
+ *   blocks, also beyond capacity_blocks; entries from the capacity on are written nowhere; capacity_blocks 0 with NULL arrays only counts.
+ *   Apart from the entry order the result is bit-specified.  result_dev (may be NULL): written by the last launch, not waited for.
+ * nvbx_change_clusters: the same, then nvbx_label_components over min(*block_count_dev, capacity_blocks) entries (read on the device), with
+ *   the argument tail of nvbx_frontier_clusters; its refusals are checked before anything is launched.  A component of label 0 is an
+ *   object that appeared, one of label 1 an object that is gone, peak_score the largest distance change.
+ * Launches run on m's stream, behind everything enqueued on ref's stream so far; work enqueued on ref afterwards is ordered behind the
+ * reads (as nvbx_merge_map).  No host wait, no allocation; held-back colour / ESDF work of both mappers stays held back; neither map is
+ * written.  NVBX_E_INVALID (nvbx_last_error set, nothing launched): ref == m; different devices or voxel sizes; an occupancy mapper on
+ * either side; a pose that is not finite, out of range or no rotation; a NaN weight or distance option; occupied_distance_m >
+ * free_distance_m; sampling outside 0 / 1; the capacity, pointer and box refusals of nvbx_find_frontiers; a misaligned result_dev. */
+#define NVBX_CHANGE_OK              0
+#define NVBX_CHANGE_EMPTY_MAP       1   /* m has no TSDF block */
+#define NVBX_CHANGE_EMPTY_REFERENCE 2   /* ref has no TSDF block */
+#define NVBX_CHANGE_NO_OVERLAP      3   /* voxels_compared == 0 */
+#define NVBX_CHANGE_TRILINEAR 0
+#define NVBX_CHANGE_NEAREST   1
+typedef struct {
+  float   min_weight;           /* a voxel of m is observed with weight >= this */
+  float   ref_min_weight;       /* a voxel of ref counts with weight >= this */
+  float   free_distance_m;      /* FREE: distance > this; 0 = one voxel size */
+  float   occupied_distance_m;  /* OCCUPIED: distance <= this */
+  int32_t sampling;             /* NVBX_CHANGE_TRILINEAR / NVBX_CHANGE_NEAREST */
+  int32_t pad;
+} nvbx_change_options;          /* 24 bytes; offsets 0 4 8 12 16 20 */
+typedef struct {
+  int64_t blocks_scanned;       /* TSDF blocks of m */
+  int64_t voxels_compared;      /* in the box, observed in m, with a valid sample of ref */
+  int64_t voxels_appeared;      /* label 0 */
+  int64_t voxels_removed;       /* label 1 */
+  int64_t blocks_changed;       /* blocks with a labelled voxel (*count_dev) */
+  int32_t status;               /* NVBX_CHANGE_*, checked in the order EMPTY_MAP, EMPTY_REFERENCE, NO_OVERLAP */
+  int32_t pad[5];
+} nvbx_change_result;           /* 64 bytes, 8-byte aligned DEVICE memory; offsets 0 8 16 24 32 40 44 */
+/* defaults: min_weight 1e-4, ref_min_weight 1e-4, free_distance_m 0 (one voxel size), occupied_distance_m 0, sampling 0 */
+void nvbx_default_change_options(nvbx_change_options* options);
+/* T_M_R: row-major 4 x 4, host memory.  options NULL: the defaults. */
+int nvbx_find_changes(nvbx_mapper* m, nvbx_mapper* ref, const float T_M_R[16], const nvbx_change_options* options,
+                      const int32_t box_min_max_vox[6], nvbx_index3d* block_idx_dev, int32_t* label_dev, float* score_dev,
+                      int64_t capacity_blocks, int64_t* count_dev, nvbx_change_result* result_dev);
+int nvbx_change_clusters(nvbx_mapper* m, nvbx_mapper* ref, const float T_M_R[16], const nvbx_change_options* options,
+                         const int32_t box_min_max_vox[6], int32_t connectivity, int32_t min_voxels, nvbx_index3d* block_idx_dev,
+                         int32_t* label_dev, float* score_dev, int32_t* component_id_dev, int64_t capacity_blocks,
+                         int64_t* block_count_dev, nvbx_component* components_dev, int64_t capacity_components,
+                         int64_t* component_count_dev, nvbx_change_result* result_dev);
+
 /* ---- mask splitting (human / people-segmentation mapping) ------------------------------------------------------------
  * [U] ImageMasker::splitImageOnGPU as used by MultiMapper::integrateDepth(depth, mask, T_L_CD, T_CM_CD, depth_cam, mask_cam) --
  * nvblox_node.cpp:1018-1060: every valid depth pixel is lifted to 3-D, moved into the mask camera (T_CM_CD = T_L_CM^-1 T_L_CD)

@@ -180,6 +180,18 @@ class MergeResult(C.Structure):
                 ("color_voxels_fused", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32 * 5)]
 
 
+class ChangeOptions(C.Structure):
+    """nvbx_change_options (24 bytes); nvbx_default_change_options fills it"""
+    _fields_ = [("min_weight", C.c_float), ("ref_min_weight", C.c_float), ("free_distance_m", C.c_float), ("occupied_distance_m", C.c_float),
+                ("sampling", C.c_int32), ("pad", C.c_int32)]
+
+
+class ChangeResult(C.Structure):
+    """nvbx_change_result: what nvbx_find_changes' last launch leaves in DEVICE memory (64 bytes)"""
+    _fields_ = [("blocks_scanned", C.c_int64), ("voxels_compared", C.c_int64), ("voxels_appeared", C.c_int64), ("voxels_removed", C.c_int64),
+                ("blocks_changed", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32 * 5)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("table", C.c_void_p), ("table_mask", C.c_uint32), ("table_shift", C.c_uint32), ("slot_flags", C.c_void_p),
                 ("slot_index", C.c_void_p), ("tsdf", C.c_void_p), ("color", C.c_void_p), ("esdf", C.c_void_p),
@@ -294,6 +306,9 @@ SIGNATURES = {
                                         C.POINTER(AlignOptions), _vp, _vp]),
     "nvbx_default_merge_options": (None, [C.POINTER(MergeOptions)]),
     "nvbx_merge_map": (C.c_int, [_vp, _vp, _vp, C.POINTER(MergeOptions), _vp]),
+    "nvbx_default_change_options": (None, [C.POINTER(ChangeOptions)]),
+    "nvbx_find_changes": (C.c_int, [_vp, _vp, _vp, C.POINTER(ChangeOptions), _pi32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "nvbx_change_clusters": (C.c_int, [_vp, _vp, _vp, C.POINTER(ChangeOptions), _pi32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),
     "nvbx_block_indices": (_i64, [_vp, C.c_uint32, _vp, _i64]),
     "nvbx_get_block": (C.c_int, [_vp, C.c_uint32, Index3D, _vp]),

@@ -20,7 +20,6 @@
 using namespace nvbx;
 
 constexpr int FR_TPB = 512;
-constexpr int64_t FR_MAX_BLOCKS = 1ll << 22;      // nvbx_label_components' limit: 2^22 x 512 voxel ids fill int32
 
 struct FrontierArgs {
   float min_weight, free_dist;
@@ -198,11 +197,7 @@ int frontier_check(const nvbx_mapper* m, const char* who, float min_weight, floa
   if (tsdf_reader_refused(m, who)) return NVBX_E_INVALID;
   if (min_unknown < 1 || min_unknown > 6) return refuse(who, ": min_unknown_neighbours must be 1 .. 6");
   if (std::isnan(min_weight) || std::isnan(free_distance_m)) return refuse(who, ": min_weight / free_distance_m is not a number");
-  if (capacity < 0 || capacity > FR_MAX_BLOCKS) return refuse(who, ": capacity_blocks must be 0 .. 2^22");
-  if (!count) return refuse(who, ": the block count pointer is required");
-  if (capacity > 0 && (!block_idx || !label)) return refuse(who, ": block_idx_dev and label_dev are required with capacity_blocks > 0");
-  if (box && (box[0] > box[3] || box[1] > box[4] || box[2] > box[5])) return refuse(who, ": box_min_max_vox has min > max on an axis");
-  return NVBX_OK;
+  return sparse_volume_refused(who, box, block_idx, label, capacity, count);
 }
 
 // the launches of nvbx_find_frontiers; the arguments have been checked

@@ -83,6 +83,7 @@ static int alloc_all(nvbx_mapper* m) {
   //  not ordered with a non-blocking stream and landed after k_init_map once in a while -- a map with no free slot, tests/cpp rccl_fusion)
   NVBX_HIP(hipMemsetAsync(d.counters, 0, C_NUM * 4, m->stream));
   if (m->staging.ensure(m->stream, 8 << 20)) return NVBX_E_DEVICE;
+  if (m->change_buf.ensure(m->stream, 64)) return NVBX_E_DEVICE;      // (change.hip's counters: there from the start, the call itself allocates nothing)
   NVBX_HIP(hipHostMalloc(&m->h_counters, C_NUM * 4));
   NVBX_HIP(hipHostMalloc(&m->h_shc, S_NUM * NSH * SH_STRIDE * 4));
   NVBX_HIP(hipHostMalloc(&m->h_mirror, 64, hipHostMallocMapped));
@@ -209,7 +210,7 @@ static const char* params_problem(const nvbx_mapper_params* p) {
 
 // ------------------------------------------------------------------------------------------------ C-ABI: lifetime
 // THE read of the mapper's NVBX_* environment variables, all through nvbx_knobs.h (the frame pool's own is process-wide: frames.hip)
-static void read_knobs(nvbx_mapper* m) { const auto env = [](const char* name) -> const char* { return getenv(name); }; nvbx_knobs_read(&m->knobs, env); nvbx_plan_knobs_read(&m->plan_knobs, env); }
+static void read_knobs(nvbx_mapper* m) { const auto env = [](const char* name) -> const char* { return getenv(name); }; nvbx_knobs_read(&m->knobs, env); nvbx_plan_knobs_read(&m->plan_knobs, env); nvbx_change_knobs_read(&m->change_knobs, env); }
 extern "C" int nvbx_mapper_reload_knobs(nvbx_mapper* m) {
   if (!m) return NVBX_E_INVALID;
   NVBX_HIP(hipSetDevice(m->device));

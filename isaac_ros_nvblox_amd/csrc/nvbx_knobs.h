@@ -3,7 +3,7 @@
  * unset) and returns what the library uses.  A missing, malformed or out-of-range value gives the default, so no setting can size a launch at zero
  * or drop work; rider counts are rounded up to a multiple of 8.  No knob changes a result, only which workgroup does what.
  * struct nvbx_knobs holds one mapper's settings; nvbx_knobs_read fills it, and names every variable there and nowhere else.  The cost field's two
- * knobs have a struct and a read of their own in front of it (nvbx_plan_knobs). */
+ * knobs have a struct and a read of their own in front of it (nvbx_plan_knobs), and so has change detection's one (nvbx_change_knobs). */
 #ifndef NVBX_KNOBS_H_
 #define NVBX_KNOBS_H_
 #include <errno.h>
@@ -94,6 +94,14 @@ struct nvbx_plan_knobs { int rounds_per_wait, tile_sweeps; };
 static inline void nvbx_plan_knobs_read(struct nvbx_plan_knobs* k, const char* (*lookup)(const char* name)) {
   k->rounds_per_wait = nvbx_knob_plan_rounds_per_wait(lookup("NVBX_PLAN_ROUNDS_PER_WAIT"));
   k->tile_sweeps = nvbx_knob_plan_tile_sweeps(lookup("NVBX_PLAN_TILE_SWEEPS"));
+}
+
+/* Change detection's knob (change.hip), in a struct and a read of its own like the cost field's: NVBX_CHANGE_GRID caps
+ * k_find_changes' workgroups, as NVBX_DECAY_GRID caps k_decay's.  No result depends on it. */
+static inline int nvbx_knob_change_grid(const char* s) { return nvbx_knob_int(s, 1024, 1, NVBX_KNOB_GRID_MAX); }      /* (256 CUs x 4 resident workgroups) */
+struct nvbx_change_knobs { int grid; };
+static inline void nvbx_change_knobs_read(struct nvbx_change_knobs* k, const char* (*lookup)(const char* name)) {
+  k->grid = nvbx_knob_change_grid(lookup("NVBX_CHANGE_GRID"));
 }
 
 /* One mapper's knobs: filled at nvbx_mapper_create and again by nvbx_mapper_reload_knobs.  Four of them shape the mapper at creation and are

@@ -113,6 +113,7 @@ struct nvbx_mapper {
   // decision of this mapper reads them here.  max_capacity, use_side, color_deferral / color_staging and defer_edt take their value at creation only.
   nvbx_knobs knobs{};
   nvbx_plan_knobs plan_knobs{}; // ... and the cost field's two (plan.hip), read with them
+  nvbx_change_knobs change_knobs{}; // ... and change detection's one (change.hip)
   bool use_side = false;        // knobs.side_stream at creation (NVBX_SIDE_STREAM=1 enables)
   bool side_pending = false;    // ESDF work enqueued on `side` that `stream` has not waited for yet
   bool main_dirty = true;       // non-colour work enqueued on `stream` since ev_main was recorded
@@ -160,6 +161,8 @@ struct nvbx_mapper {
   nvbx::DevBuf reloc_buf; std::vector<float> reloc_host;
   // map merging (merge.hip), as the destination: a 64-byte head of counters and the key set that counts the distinct candidate blocks
   nvbx::DevBuf merge_buf;
+  // change detection (change.hip), as the map that is scanned: 64 bytes of counters, allocated with the map
+  nvbx::DevBuf change_buf;
   // frontier scan (frontier.hip), -DNVBX_FRONTIER_TWO_PASS variant only: 128 bytes of voxel classes per slot; the product's single pass needs none
   nvbx::DevBuf frontier_scratch;
   // cost field (plan.hip) and cost volume (plan3d.hip), sized and carved up by nvbx_plan_grid.h's plan_grid_setup alone: a 64-byte head of counters, the class word of every cell and the two sets of active-tile flags of the largest input so far
@@ -300,6 +303,17 @@ struct nvbx_mapper {
 // every call that reads the TSDF layer refuses an occupancy mapper: -> 0, or NVBX_E_INVALID with the error set
 static inline int tsdf_reader_refused(const nvbx_mapper* m, const char* who) {
   return m->p.projective_layer_type == 1 ? nvbx::refuse(who, ": an occupancy mapper has no TSDF layer") : 0;
+}
+
+// THE refusals of a call that writes a sparse voxel volume of its own scan (nvbx_find_frontiers, nvbx_find_changes), in their order: its
+// capacity, its count and block arrays, its box -> 0, or NVBX_E_INVALID with the error set
+constexpr int64_t NVBX_VOLUME_MAX_BLOCKS = 1ll << 22;      // nvbx_label_components' limit: 2^22 x 512 voxel ids fill int32
+static inline int sparse_volume_refused(const char* who, const int32_t* box, const void* block_idx, const void* label, int64_t capacity, const void* count) {
+  if (capacity < 0 || capacity > NVBX_VOLUME_MAX_BLOCKS) return nvbx::refuse(who, ": capacity_blocks must be 0 .. 2^22");
+  if (!count) return nvbx::refuse(who, ": the block count pointer is required");
+  if (capacity > 0 && (!block_idx || !label)) return nvbx::refuse(who, ": block_idx_dev and label_dev are required with capacity_blocks > 0");
+  if (box && (box[0] > box[3] || box[1] > box[4] || box[2] > box[5])) return nvbx::refuse(who, ": box_min_max_vox has min > max on an axis");
+  return 0;
 }
 
 // every kernel launch of the library goes through this macro (name = the kernel's name in rocprof output)

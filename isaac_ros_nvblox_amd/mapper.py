@@ -36,7 +36,13 @@ PoseScore = collections.namedtuple("PoseScore", "points valid inliers conflicts 
 MERGE_OK, MERGE_EMPTY_SOURCE, MERGE_NO_OVERLAP = 0, 1, 2
 MERGE_STATUS_NAMES = {0: "OK", 1: "EMPTY_SOURCE", 2: "NO_OVERLAP"}
 MERGE_RESULT_BYTES = C.sizeof(_lib.MergeResult)
-COST_UNREACHED = 0x7fffffff      # NVBX_COST_UNREACHED: cost_field's value where no move sequence leads
+# nvbx_change_result.status (find_changes / change_clusters); the labels of their volume; nvbx_change_options.sampling
+CHANGE_OK, CHANGE_EMPTY_MAP, CHANGE_EMPTY_REFERENCE, CHANGE_NO_OVERLAP = 0, 1, 2, 3
+CHANGE_STATUS_NAMES = {0: "OK", 1: "EMPTY_MAP", 2: "EMPTY_REFERENCE", 3: "NO_OVERLAP"}
+CHANGE_RESULT_BYTES = C.sizeof(_lib.ChangeResult)
+CHANGE_APPEARED, CHANGE_REMOVED = 0, 1
+CHANGE_SAMPLING = {"trilinear": 0, "nearest": 1}
+COST_UNREACHED = 0x7fffffff     # NVBX_COST_UNREACHED: cost_field's value where no move sequence leads
 ELEV_UNKNOWN, ELEV_SURFACE, ELEV_BLOCKED, ELEV_VOID = 0, 1, 2, 3      # NVBX_ELEV_*: elevation_map's status
 TERRAIN_UNKNOWN, TERRAIN_OK, TERRAIN_HAZARD = 0, 1, 2                 # NVBX_TERRAIN_*: traversability's class
 
@@ -284,6 +290,32 @@ class MergeResult:
     def __repr__(self):
         return "MergeResult(%s, %d source blocks -> %d candidates (%d new), %d voxels, %d colour voxels)" % (
             self.status_name, self.source_blocks, self.candidate_blocks, self.blocks_allocated, self.voxels_fused, self.color_voxels_fused)
+
+
+class ChangeResult:
+    """What find_changes / change_clusters left behind: `buffer` is the nvbx_change_result record on the device (a uint8 tensor, written by the
+    scan's last launch); the first field that is read copies it to the host once."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        self._host = None
+
+    def _r(self):
+        if self._host is None:
+            self._host = _lib.ChangeResult.from_buffer_copy(self.buffer.cpu().numpy().tobytes())
+        return self._host
+
+    blocks_scanned = property(lambda self: int(self._r().blocks_scanned), doc="TSDF blocks of this map")
+    voxels_compared = property(lambda self: int(self._r().voxels_compared), doc="in the box, observed here, with a valid sample of the reference")
+    voxels_appeared = property(lambda self: int(self._r().voxels_appeared))
+    voxels_removed = property(lambda self: int(self._r().voxels_removed))
+    blocks_changed = property(lambda self: int(self._r().blocks_changed), doc="blocks with a labelled voxel")
+    status = property(lambda self: int(self._r().status))
+    status_name = property(lambda self: CHANGE_STATUS_NAMES.get(int(self._r().status), "?"))
+
+    def __repr__(self):
+        return "ChangeResult(%s, %d blocks scanned, %d voxels compared: %d appeared, %d removed in %d blocks)" % (
+            self.status_name, self.blocks_scanned, self.voxels_compared, self.voxels_appeared, self.voxels_removed, self.blocks_changed)
 
 
 class Mapper:
@@ -1344,6 +1376,80 @@ class Mapper:
             self._h, ptr(p), n, C.byref(k), s, float(max_range_m) if max_range_m is not None else 0.0, mw, fd, ptr(g)), order=n > 0)
         self._hold("_keep_vg", [p])      # (the kernel reads the poses: they, and an uploaded copy, live until the next call)
         return g
+
+    # -- change detection (nvbx_find_changes / nvbx_change_clusters; SEMANTICS.md "Change detection")
+    def _change_options(self, ref, T_M_R, min_weight, ref_min_weight, free_distance_m, occupied_distance_m, sampling, box_m):
+        """-> (pose array, nvbx_change_options, box | None); free_distance_m None: 0, the library's "one voxel size"; box_m as find_frontiers takes it"""
+        if not isinstance(ref, Mapper):
+            raise TypeError("the reference must be a Mapper")
+        if sampling not in CHANGE_SAMPLING:
+            raise ValueError("sampling must be 'trilinear' or 'nearest', got %r" % (sampling,))
+        o = _args.struct_options(_lib.ChangeOptions, self.lib.nvbx_default_change_options, dict(
+            min_weight=float(min_weight), ref_min_weight=float(ref_min_weight), free_distance_m=0.0 if free_distance_m is None else float(free_distance_m),
+            occupied_distance_m=float(occupied_distance_m), sampling=CHANGE_SAMPLING[sampling]), "change")
+        _, _, _, box = self._frontier_options(min_weight, None, 1, box_m)
+        return self._T(T_M_R), o, box
+
+    def _change_count(self, ref, T, o, box):
+        """the number of blocks that hold a labelled voxel: a counting scan (capacity 0, no result record), waited for"""
+        cnt = self._torch.empty(1, dtype=self._torch.int64, device=self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_find_changes(self._h, ref._h, _np_ptr(T), C.byref(o), self._box_ptr(box), None, None, None, 0, ptr(cnt), None))
+        return int(cnt.item())
+
+    @staticmethod
+    def _change_out(out, n):
+        """out=(the n tensors of the volume ..., result buffer | None) -> (the volume's tensors, the result buffer)"""
+        if out is None:
+            return None, None
+        out = tuple(out)
+        if len(out) != n + 1:
+            raise ValueError("out must hold %d entries (the volume's %d tensors and a result buffer or None), got %d" % (n + 1, n, len(out)))
+        return out[:n], out[n]
+
+    def find_changes(self, ref, T_M_R, min_weight=1e-4, ref_min_weight=1e-4, free_distance_m=None, occupied_distance_m=0.0, sampling="trilinear",
+                     box_m=None, out=None):
+        """What differs between this map ("now") and `ref` ("before") under p_M = T_M_R p_R (row-major 4 x 4).  A voxel here is observed with
+        weight >= min_weight, free with distance > free_distance_m (None: one voxel size), occupied with distance <= occupied_distance_m; its
+        sample of `ref` ("trilinear": the point query's rule over eight corners of weight >= ref_min_weight; "nearest": the voxel that holds the
+        position) is classified by the same thresholds.  Label 0 (CHANGE_APPEARED): occupied here, free there; label 1 (CHANGE_REMOVED): free
+        here, occupied there; inside box_m (as find_frontiers takes it; None: everywhere).
+        -> (indices [n, 3] i32, labels [n, 512] i32: 0 / 1 / -1, scores [n, 512] f32: |d - d_ref| on a labelled voxel, count: one int64,
+        ChangeResult) on the mapper's device, one entry per block with a labelled voxel in no particular order -- the shape label_components
+        takes.  Buffers are sized by a counting scan first (the call scans twice and waits once for the count).  Neither map is written; the
+        launches run on this mapper's stream behind everything enqueued on `ref`'s.
+        out=(indices, labels, scores | None, count, result | None): preallocated tensors of any capacity n_cap (result: a uint8 tensor of
+        CHANGE_RESULT_BYTES bytes), nothing is allocated and nothing waited for: -> the same tensors untrimmed and the ChangeResult (None
+        without a buffer); count may exceed n_cap, entries from n_cap on are not written."""
+        T, o, box = self._change_options(ref, T_M_R, min_weight, ref_min_weight, free_distance_m, occupied_distance_m, sampling, box_m)
+        vout, rbuf = self._change_out(out, 4)
+        vol, cap, counts = _args.sparse_volume(vout, self._cuda, lambda: self._change_count(ref, T, o, box), scores_required=False)
+        idx, lab, sc, cnt = vol
+        buf = _args.result_buffer(rbuf, CHANGE_RESULT_BYTES, self._cuda) if out is None or rbuf is not None else None
+        self._around_torch_stream(lambda: self.lib.nvbx_find_changes(
+            self._h, ref._h, _np_ptr(T), C.byref(o), self._box_ptr(box), ptr(idx), ptr(lab), ptr(sc), cap, ptr(cnt), ptr(buf)))
+        res = ChangeResult(buf) if buf is not None else None
+        return vol + (res,) if out is not None else self._trim(counts, cap, (idx, lab, sc)) + (cnt, res)
+
+    def change_clusters(self, ref, T_M_R, min_weight=1e-4, ref_min_weight=1e-4, free_distance_m=None, occupied_distance_m=0.0, sampling="trilinear",
+                        box_m=None, connectivity=26, min_voxels=8, out=None):
+        """From two maps to the objects that appeared and the objects that are gone in one call: find_changes, then label_components over the
+        result.  -> (indices [n, 3] i32, labels [n, 512] i32, scores [n, 512] f32, ids [n, 512] i32, Components, ChangeResult) on the mapper's
+        device, trimmed, as frontier_clusters returns: a component of label 0 is an object that appeared, one of label 1 an object that is
+        gone, peak_score its largest distance change.  Buffers are sized by a counting scan first and for the worst-case component count.
+        out=(indices, labels, scores | None, ids, block_count, records | None, component_count, result | None): preallocated tensors of any
+        capacities, nothing is allocated and nothing waited for: -> the same tensors untrimmed and the ChangeResult (None without a buffer)."""
+        conn, mv = self._segment_options(connectivity, min_voxels)
+        T, o, box = self._change_options(ref, T_M_R, min_weight, ref_min_weight, free_distance_m, occupied_distance_m, sampling, box_m)
+        vout, rbuf = self._change_out(out, 7)
+        vol, cap, counts = _args.sparse_volume(vout, self._cuda, lambda: self._change_count(ref, T, o, box), scores_required=False,
+                                               record_words=COMPONENT_WORDS, min_voxels=mv)
+        idx, lab, sc, ids, bcnt, rec, ccnt = vol
+        buf = _args.result_buffer(rbuf, CHANGE_RESULT_BYTES, self._cuda) if out is None or rbuf is not None else None
+        self._around_torch_stream(lambda: self.lib.nvbx_change_clusters(
+            self._h, ref._h, _np_ptr(T), C.byref(o), self._box_ptr(box), conn, mv, ptr(idx), ptr(lab), ptr(sc), ptr(ids), cap, ptr(bcnt), ptr(rec),
+            int(rec.shape[0]) if rec is not None else 0, ptr(ccnt), ptr(buf)))
+        res = ChangeResult(buf) if buf is not None else None
+        return vol + (res,) if out is not None else self._trim(counts, cap, (idx, lab, sc, ids), rec) + (res,)
 
     # -- cost field and paths (nvbx_cost_field / nvbx_trace_paths; SEMANTICS.md "Cost field and paths")
     def cost_options(self, **kw):

@@ -235,9 +235,9 @@ int nvbx_flush(nvbx_mapper* m);
 int nvbx_mapper_set_color_deferral(nvbx_mapper* m, int32_t enable);
 /* The NVBX_* environment variables of the library (launch geometry and A/B switches; none changes a result) are read when a mapper is
  * created and kept per mapper.  nvbx_mapper_reload_knobs reads them again for this mapper: held-back work is carried out first, under the old
- * settings; the calls that follow use the new ones.  Four variables shape a mapper at creation and are NOT re-applied to a live one: NVBX_MAX_BLOCKS
- * (nvbx_mapper_set_max_capacity keeps what it last set), NVBX_COLOR_DEFERRAL (likewise nvbx_mapper_set_color_deferral), NVBX_SIDE_STREAM (streams and
- * events) and NVBX_DEFER_EDT.  NVBX_FRAME_POOL_MAX belongs to the process-wide frame pool, not to a mapper, and is read whenever the pool would grow. */
+ * settings; the calls that follow use the new ones.  Three variables shape a mapper at creation and are NOT re-applied to a live one: NVBX_MAX_BLOCKS
+ * (nvbx_mapper_set_max_capacity keeps what it last set), NVBX_COLOR_DEFERRAL (likewise nvbx_mapper_set_color_deferral)
+ * and NVBX_DEFER_EDT.  NVBX_FRAME_POOL_MAX belongs to the process-wide frame pool, not to a mapper, and is read whenever the pool would grow. */
 int nvbx_mapper_reload_knobs(nvbx_mapper* m);
 /* ---- Library-owned device frames: OWNERSHIP TRANSFER of input images (csrc/frames.hip).
  * Replaces the node-owned, re-used device image buffers of the reference (nvblox_node.hpp:484-488: color_image_, filled by the conversion on the

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(ALIGN_TPB) void k_align_accumulate(DMap m, AlignArg
     float p[3], g[3], d;
     uint32_t sl[8];
     apply_rt(R, t, x[0], x[1], x[2], p);
-    const bool valid = q_point<Q_TSDF, false>(m, pool, p, a.vs, a.min_weight, 0.0f, 0, &d, g, nullptr, COLOR ? sl : nullptr);
+    const bool valid = q_point<Q_TSDF>(m, pool, p, a.vs, a.min_weight, 0.0f, 0, &d, g, nullptr, COLOR ? sl : nullptr);
     float yc = 0.0f, gc[3] = {0.0f, 0.0f, 0.0f};
     bool cvalid = false;
     if (COLOR) {
@@ -270,7 +270,7 @@ int nvbx::align_launch(nvbx_mapper* m, AlignArgs& a) {
   NVBX_HIP(hipSetDevice(m->device));
   // reads TSDF voxels and the TSDF flags only: held-back work stays held back, as for the TSDF point query (query.hip).  A colour call reads the
   // colour layer, which a held-back integrateColor writes: that work is carried out first (as for nvbx_query_colors).
-  if (a.color ? m->join_side() : m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (a.color ? m->begin_call() : m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   if (align_buffers(m, a)) return NVBX_E_DEVICE;
   for (int32_t it = 0; it < a.max_iter; it++) {
     a.iter = it;

@@ -234,7 +234,7 @@ int change_launch(nvbx_mapper* m, nvbx_mapper* ref, const float* T, const nvbx_c
                   int32_t* label_dev, float* score_dev, int64_t capacity, int64_t* count_dev, nvbx_change_result* result_dev) {
   NVBX_HIP(hipSetDevice(m->device));
   // TSDF voxels and flags only: held-back colour and ESDF work of both mappers stays held back (frontier.hip)
-  if (ref->join_side_keeping_held() || m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (ref->begin_call_keeping_held() || m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   { const int rc = nvbx_mapper_wait_for(m, ref); if (rc) return rc; }
   ChangeArgs a{};
   float R_MR[9], t_MR[3];

@@ -279,7 +279,7 @@ static int replay_pair_t(nvbx_mapper* m, const nvbx_mapper::ColorPending& c) {
 }
 bool nvbx_mapper::replay_pair_applies() const {
   // (knobs.replay_pair -- A/B: 0 = three classic launches)
-  return knobs.replay_pair && held.color_pending.on && held.esdf_update_pending && p.projective_layer_type != 1 && p.esdf_mode == 0 && p.esdf_propagation == 0 && !use_side && defer_edt && !held.import_pending;
+  return knobs.replay_pair && held.color_pending.on && held.esdf_update_pending && p.projective_layer_type != 1 && p.esdf_mode == 0 && p.esdf_propagation == 0 && defer_edt && !held.import_pending;
 }
 int nvbx_mapper::replay_pair() {
   const ColorPending c = take_pending(); held.esdf_update_pending = false;
@@ -337,7 +337,7 @@ extern "C" int nvbx_integrate_color_batch(nvbx_mapper* m, int32_t n, const uint8
 
 extern "C" int nvbx_get_synthetic_depth(nvbx_mapper* m, float* out_host, int64_t capacity, int32_t* rows, int32_t* cols) {
   if (!m || !rows || !cols) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;          // (a held-back colour frame is carried out first)
+  if (m->begin_call()) return NVBX_E_DEVICE;          // (a held-back colour frame is carried out first)
   *rows = m->synth_rows; *cols = m->synth_cols;
   const int64_t n = (int64_t)m->synth_rows * m->synth_cols;
   if (!out_host || n == 0) return NVBX_OK;

@@ -38,7 +38,7 @@ extern "C" int nvbx_query_colors(nvbx_mapper* m, const float* points_xyz_dev, in
   if (n == 0) return NVBX_OK;
   NVBX_HIP(hipSetDevice(m->device));
   // reads the colour layer, which a held-back integrateColor writes: that work is carried out first (as nvbx_render_view does with a colour output)
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), block(256);
   if (rgb_dev) NVBX_LAUNCH(m, k_query_colors<true>, grid, block, m->d, points_xyz_dev, n, m->p.voxel_size, min_color_weight, rgb_dev, luminance_dev, gradient_xyz_dev, valid_dev);
   else NVBX_LAUNCH(m, k_query_colors<false>, grid, block, m->d, points_xyz_dev, n, m->p.voxel_size, min_color_weight, rgb_dev, luminance_dev, gradient_xyz_dev, valid_dev);

@@ -41,7 +41,7 @@ extern "C" int nvbx_backproject_depth(nvbx_mapper* m, const float* depth_dev, in
   if (!m || !depth_dev || !camera || !points_xyz_dev || !n_points || rows <= 0 || cols <= 0 || capacity_points < 0) {
     set_error("nvbx_backproject_depth: invalid argument"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   NVBX_HIP(hipMemsetAsync(m->export_count, 0, 4, m->stream));
   const int64_t n = (int64_t)rows * cols;
   NVBX_LAUNCH(m, k_backproject, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), depth_dev, rows, cols, camera->fu, camera->fv,
@@ -238,7 +238,7 @@ extern "C" int nvbx_split_color_by_mask(nvbx_mapper* m, const uint8_t* rgb_dev, 
 // ------------------------------------------------------------------------------------------------ device view
 extern "C" int nvbx_get_device_view(nvbx_mapper* m, nvbx_device_view* out) {
   if (!m || !out) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;           // a kernel launched with the view sees the completed ESDF update
+  if (m->begin_call()) return NVBX_E_DEVICE;           // a kernel launched with the view sees the completed ESDF update
   out->table = m->d.table; out->table_mask = m->d.mask; out->table_shift = m->d.shift;
   out->slot_flags = m->d.slot_flags; out->slot_index = m->d.slot_index;
   out->tsdf = m->d.tsdf; out->color = m->d.color; out->esdf = m->d.esdf;

@@ -131,7 +131,7 @@ extern "C" int nvbx_detect_dynamics(nvbx_mapper* m, const float* depth_dev, int3
                                     float max_distance_m, uint8_t* mask_dev) {
   if (!m || !depth_dev || !T_L_C || !camera || !mask_dev || rows <= 0 || cols <= 0) { set_error("nvbx_detect_dynamics: invalid argument"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;      // (reads TSDF voxels and the freespace layer only)
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;      // (reads TSDF voxels and the freespace layer only)
   const int64_t n = (int64_t)rows * cols;
   if (!m->d.freespace) { NVBX_HIP(hipMemsetAsync(mask_dev, 0, (size_t)n, m->stream)); return NVBX_OK; }    // no freespace layer yet: nothing is dynamic
   const RtCam g = make_rtcam(T_L_C, camera);
@@ -359,7 +359,7 @@ extern "C" int nvbx_dynamic_depth_split(nvbx_mapper* m, const float* depth_dev, 
   if (!m || !depth_dev || !T_L_C || !camera || !mask_dev || !depth_unmasked_dev || !depth_masked_dev || !image_dims_ok(rows, cols)) {
     set_error("nvbx_dynamic_depth_split: invalid argument (image sides 1 .. 32768)"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;      // (reads TSDF voxels and the freespace layer only: held-back work stays held back, as for nvbx_detect_dynamics)
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;      // (reads TSDF voxels and the freespace layer only: held-back work stays held back, as for nvbx_detect_dynamics)
   const int64_t n = (int64_t)rows * cols;
   bool grew = false;
   if (m->dyn_scratch.ensure(m->stream, (size_t)(6 * n + 16) * 4, &grew)) return NVBX_E_DEVICE;

@@ -191,7 +191,7 @@ extern "C" int nvbx_elevation_map(nvbx_mapper* m, int32_t x0, int32_t y0, int32_
     return refuse(who, ": the box leaves the addressable voxels [-2^23, 2^23)");
   if (std::isnan(min_weight) || std::isnan(unknown_value)) return refuse(who, ": min_weight / unknown_value is not a number");
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;      // TSDF voxels and flags only: everything held back stays held back
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;      // TSDF voxels and flags only: everything held back stays held back
   ElevArgs a{};
   a.x0 = x0; a.y0 = y0; a.rows = rows; a.cols = cols; a.z_lo = z_lo; a.z_hi = z_hi;
   a.min_weight = min_weight; a.unknown_value = unknown_value; a.vs = m->p.voxel_size; a.height = height_dev; a.status = status_dev;
@@ -211,7 +211,7 @@ extern "C" int nvbx_traversability(nvbx_mapper* m, const float* height_dev, cons
   if (image_size_refused(who, rows, cols)) return NVBX_E_INVALID;
   if (const char* why = nvbx_terrain_options_problem(options)) return refuse(who, why);
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;      // the two images only: everything held back stays held back
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;      // the two images only: everything held back stays held back
   TerrainArgs a{};
   a.h = height_dev; a.st = status_dev; a.rows = rows; a.cols = cols; a.words = (cols + 63) / 64;
   a.o = *options; a.vs = m->p.voxel_size; a.cls = class_dev; a.step = step_dev; a.slope2 = slope2_dev; a.dist = distance_dev;

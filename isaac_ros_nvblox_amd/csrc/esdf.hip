@@ -159,7 +159,7 @@ extern "C" int nvbx_update_esdf(nvbx_mapper* m) {
   NVBX_HIP(hipSetDevice(m->device));
   if (m->p.esdf_mode == 1) {                       // EsdfMode::k3D: esdf3d.hip
     if (m->p.esdf_max_distance_m / m->p.voxel_size >= 64.0f) { set_error("esdf_max_distance_m / voxel_size must be < 64 voxels"); return NVBX_E_INVALID; }
-    if (m->join_side()) return NVBX_E_DEVICE;
+    if (m->begin_call()) return NVBX_E_DEVICE;
     return m->update_esdf_3d();
   }
   // (parameters are validated before any state of this update changes)
@@ -168,11 +168,11 @@ extern "C" int nvbx_update_esdf(nvbx_mapper* m) {
     if (chk.bz_hi - chk.bz_lo + 1 > 63 || chk.bz_hi < chk.bz_lo) { set_error("esdf slice z band must span 1..63 blocks"); return NVBX_E_INVALID; } }
   // colour deferral (nvbx_mapper_set_color_deferral): while a colour frame is held back this update is held back behind it -- its
   // marking pass rides in that colour launch; both are carried out by the next integrateDepth (pipelined) or by whatever entry point
-  // comes first (join_side -> replay_deferred, in call order)
+  // comes first (begin_call -> replay_deferred, in call order)
   // (... or, with the switch on and no colour frame around, behind nothing: the next camera depth frame carries it alone -- depth-only hosts,
   //  occupancy mappers; nvbx_mapper::esdf_only_carry)
   const int esdf_only = m->knobs.esdf_only_carry;      // (NVBX_ESDF_ONLY_CARRY -- A/B: 0 = an updateEsdf is held back behind a colour frame only)
-  if ((m->held.color_pending.on || (esdf_only && m->color_deferral && !m->pipelined_order && !m->held.import_pending)) && !m->replaying && m->p.esdf_propagation == 0 && !m->use_side && m->defer_edt) {
+  if ((m->held.color_pending.on || (esdf_only && m->color_deferral && !m->pipelined_order && !m->held.import_pending)) && !m->replaying && m->p.esdf_propagation == 0 && m->defer_edt) {
     // (an update already held back is carried out first: two updates in a row stay two updates -- epochs and the "last update" counters as in
     //  the undeferred sequence)
     if (m->held.esdf_update_pending && m->replay_deferred()) return NVBX_E_DEVICE;
@@ -187,34 +187,26 @@ extern "C" int nvbx_update_esdf(nvbx_mapper* m) {
   if (!m->pipelined_order && m->flush_import()) return NVBX_E_DEVICE;
   if (m->dirty_since_mark) m->mark_pass++;
   const EsdfArgs a = m->make_esdf_args();
-  hipStream_t s = m->stream;
   if (m->p.esdf_propagation == 1) {                // [U] open choice: iterative propagation instead of the exact transform (above)
-    if (m->join_side()) return NVBX_E_DEVICE;
+    if (m->begin_call()) return NVBX_E_DEVICE;
     if (m->dirty_since_mark) NVBX_LAUNCH(m, k_esdf_mark, dim3((unsigned)std::min<int64_t>(m->capacity, 1024)), dim3(64), m->d, a);
     m->dirty_since_mark = false; m->premark_consumed = false; m->unresolved_marks = false; m->pass_at_last_edt = m->mark_pass;
     const int rc = run_esdf_propagation(m, a);
     m->esdf_epoch++;
     return rc;
   }
-  if (m->use_side) {
-    // run behind the last non-colour operation, beside any colour integration enqueued after it
-    if (m->main_dirty) { if (m->mark_main()) return NVBX_E_DEVICE; }
-    NVBX_HIP(hipStreamWaitEvent(m->side, m->ev_main, 0));
-    s = m->side;
-  }
   // marking pass only if something was dirtied since the last pass (integrateColor runs one fused into its own launch)
-  if (m->dirty_since_mark) NVBX_LAUNCH_ON(m, s, k_esdf_mark, dim3((unsigned)std::min<int64_t>(m->capacity, 1024)), dim3(64), m->d, a);
+  if (m->dirty_since_mark) NVBX_LAUNCH(m, k_esdf_mark, dim3((unsigned)std::min<int64_t>(m->capacity, 1024)), dim3(64), m->d, a);
   m->dirty_since_mark = false; m->premark_consumed = false;          // k_esdf_edt resets the dirty list
   m->unresolved_marks = false; m->pass_at_last_edt = m->mark_pass;    // the EDT enqueued below resolves every marking pass so far
-  if (m->defer_edt && !m->use_side) {
+  if (m->defer_edt) {
     // The EDT is held back until the next entry point: the next camera depth frame runs it inside its first launch (beside
     // the view marking, which it does not interact with); every other entry point launches it first (flush_edt).
     m->held.edt_pending = true; m->held.edt_args = a;
   } else {
-    NVBX_LAUNCH_ON(m, s, k_esdf_edt, dim3(1024), dim3(256), m->d, a);
+    NVBX_LAUNCH(m, k_esdf_edt, dim3(1024), dim3(256), m->d, a);
   }
   NVBX_HIP(hipGetLastError());
-  if (m->use_side) { NVBX_HIP(hipEventRecord(m->ev_side, m->side)); m->side_pending = true; }
   m->esdf_epoch++;
   return NVBX_OK;
 }
@@ -259,11 +251,10 @@ extern "C" int nvbx_esdf_slice_to_image(nvbx_mapper* m, float unknown_value, flo
   // (called right behind nvbx_esdf_slice_size -- the facade's EsdfSlicer sizes its image first -- nothing has been enqueued since: the counters
   //  on the host are still the device's, no second round trip)
   int rc = NVBX_OK;
-  if (m->slice_size_seq != 0 && m->slice_size_seq == m->enqueue_seq && !m->held.any() && !m->side_pending) {
-    // (the parts of join_side() that still apply: this mapper's device is the current one -- the call may come from another thread, or behind a call
-    //  into a mapper on another GPU -- and the launch below counts as work on the main stream; nothing is held back and the side stream is joined)
+  if (m->slice_size_seq != 0 && m->slice_size_seq == m->enqueue_seq && !m->held.any()) {
+    // (the part of begin_call() that still applies: this mapper's device is the current one -- the call may come from another thread, or behind a call
+    //  into a mapper on another GPU; nothing is held back)
     { int cur = -1; if (hipGetDevice(&cur) != hipSuccess || cur != m->device) NVBX_HIP(hipSetDevice(m->device)); }
-    m->main_dirty = true;
     const int32_t* c0 = m->h_counters + C_ESDF_AABB;
     if (c0[0] > c0[2]) { *rows = 0; *cols = 0; } else { *cols = (c0[2] - c0[0] + 1) * 8; *rows = (c0[3] - c0[1] + 1) * 8; }
     if (aabb && *rows) {
@@ -330,7 +321,7 @@ extern "C" int nvbx_esdf_slice_to_host(nvbx_mapper* m, float unknown_value, floa
                                        int32_t* cols, float aabb[6]) {
   if (!m || !rows || !cols) return NVBX_E_INVALID;
   *rows = 0; *cols = 0;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   // (the pinned image is at least as large as the caller's, and never smaller than 256 x 256: a caller that passes no buffer learns the size)
   int rc = ensure_slice_pinned(m, std::max<int64_t>(image_host ? capacity_elems : 0, 65536)); if (rc) return rc;
   const EsdfArgs a = m->make_esdf_args();
@@ -367,7 +358,7 @@ __global__ void k_occupancy(const float* img, int64_t n, float unknown, int8_t* 
 extern "C" int nvbx_occupancy_grid_from_slice(nvbx_mapper* m, const float* image_dev, int32_t rows, int32_t cols, float unknown_value,
                                               int8_t* grid_dev) {
   if (!m || !image_dev || !grid_dev || rows <= 0 || cols <= 0) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   const int64_t n = (int64_t)rows * cols;
   NVBX_LAUNCH(m, k_occupancy, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), image_dev, n, unknown_value, grid_dev);
   NVBX_HIP(hipGetLastError());
@@ -400,7 +391,7 @@ __global__ void k_zero_tmp2(DMap m) { m.counters[C_TMP] = 0; }
 extern "C" int nvbx_pointcloud_from_slice(nvbx_mapper* m, const float* image_dev, int32_t rows, int32_t cols, const float aabb[6],
                                           float slice_height, float unknown_value, float* points_xyzi_dev, int32_t* n_points) {
   if (!m || !image_dev || !aabb || !points_xyzi_dev || !n_points || rows <= 0 || cols <= 0) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   NVBX_LAUNCH(m, k_zero_tmp2, dim3(1), dim3(1), m->d);
   const int tiles = ((rows + 7) / 8) * ((cols + 7) / 8);
   NVBX_LAUNCH(m, k_slice_pointcloud, dim3(std::min(tiles, 4096)), dim3(64), m->d, image_dev, rows, cols, aabb[0], aabb[1],
@@ -427,7 +418,7 @@ __global__ void k_esdf_dense(DMap m, int32_t mx, int32_t my, int32_t mz, int32_t
 }
 extern "C" int nvbx_esdf_dense_grid(nvbx_mapper* m, const int32_t min_vox[3], const int32_t size_vox[3], float default_value, float* grid_dev) {
   if (!m || !min_vox || !size_vox || !grid_dev || size_vox[0] <= 0 || size_vox[1] <= 0 || size_vox[2] <= 0) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   const int64_t n = (int64_t)size_vox[0] * size_vox[1] * size_vox[2];
   NVBX_LAUNCH(m, k_esdf_dense, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), m->d, min_vox[0], min_vox[1],
                      min_vox[2], size_vox[0], size_vox[1], size_vox[2], m->p.voxel_size, default_value, grid_dev);
@@ -447,7 +438,7 @@ __global__ void k_export_dirty(DMap m, int32_t* out_idx, int32_t* out_count, int
 }
 extern "C" int nvbx_esdf_dirty_list(nvbx_mapper* m, int32_t* indices_dev_out, int32_t* count_dev_out, int64_t capacity) {
   if (!m || !indices_dev_out || !count_dev_out || capacity <= 0) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   // (a list already consumed by a marking pass still names the blocks dirtied since the last updateEsdf: export it as is)
   NVBX_LAUNCH(m, k_export_dirty, dim3(64), dim3(256), m->d, indices_dev_out, count_dev_out, (int32_t)std::min<int64_t>(capacity, m->capacity));
   NVBX_HIP(hipGetLastError());
@@ -472,11 +463,11 @@ __global__ void k_import_dirty(DMap m, const int32_t* idx, const int32_t* count,
 }
 extern "C" int nvbx_mark_esdf_dirty(nvbx_mapper* m, const int32_t* indices_dev, const int32_t* count_dev, int64_t max_count) {
   if (!m || !indices_dev || !count_dev || max_count < 0) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   if (m->begin_dirtying()) return NVBX_E_DEVICE;
   NVBX_LAUNCH(m, k_import_dirty, dim3(64), dim3(256), m->d, indices_dev, count_dev, max_count);
   NVBX_HIP(hipGetLastError());
-  return m->mark_main();
+  return NVBX_OK;
 }
 
 // all peers' lists in one launch (blockIdx.y = rank)
@@ -511,7 +502,7 @@ __global__ __launch_bounds__(64) void k_import_mark_gathered(DMap m, EsdfArgs a,
 }
 extern "C" int nvbx_mark_esdf_dirty_gathered(nvbx_mapper* m, const int32_t* gathered_dev, int32_t world, int32_t self_rank, int64_t max_count) {
   if (!m || !gathered_dev || world < 1 || max_count < 0) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   if (!(world > 1 || self_rank < 0)) return NVBX_OK;
   const EsdfArgs probe = m->make_esdf_args();
   if (m->p.esdf_mode == 0 && probe.bz_hi >= probe.bz_lo && probe.bz_hi - probe.bz_lo + 1 <= 63) {
@@ -524,7 +515,7 @@ extern "C" int nvbx_mark_esdf_dirty_gathered(nvbx_mapper* m, const int32_t* gath
     NVBX_LAUNCH(m, k_import_dirty_gathered, dim3(16, (unsigned)world), dim3(256), m->d, gathered_dev, self_rank, max_count);
   }
   NVBX_HIP(hipGetLastError());
-  return m->mark_main();
+  return NVBX_OK;
 }
 
 // Take back the marking passes that no distance transform has followed yet (nvbx_mapper.h: unresolved_marks).  A marking pass

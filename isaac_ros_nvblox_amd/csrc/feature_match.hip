@@ -263,7 +263,7 @@ extern "C" int nvbx_match_features(nvbx_mapper* m, const void* queries_dev, int3
   if (rc) return rc;
   if (capacity_blocks < 0 || !count_dev || (capacity_blocks > 0 && (!block_idx_dev || !label_dev || !score_dev))) {
     set_error("nvbx_match_features: count_dev and, with capacity_blocks > 0, block_idx_dev / label_dev / score_dev are required"); return NVBX_E_INVALID; }
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   sa.a.min_weight = min_weight;
   sa.a.vec4 = (all_scores_dev && !(n_queries & 3) && !((uintptr_t)all_scores_dev & 15)) ? 1 : 0;
   sa.block_idx = reinterpret_cast<int32_t*>(block_idx_dev); sa.label = label_dev; sa.score = score_dev; sa.all = all_scores_dev;
@@ -284,7 +284,7 @@ extern "C" int nvbx_match_points(nvbx_mapper* m, const float* points_xyz_dev, in
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!points_xyz_dev || !scores_dev || !weight_dev))) { set_error("nvbx_match_points: n >= 0; points, scores_dev and weight_dev are required"); return NVBX_E_INVALID; }
   if (n == 0) return NVBX_OK;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   a.vec4 = (!(n_queries & 3) && !((uintptr_t)scores_dev & 15)) ? 1 : 0;
   const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
   const float vs = m->p.voxel_size;

@@ -187,7 +187,7 @@ extern "C" int nvbx_enable_features(nvbx_mapper* m, int32_t channels) {
     if (m->feat_channels == channels) return NVBX_OK;
     set_error("nvbx_enable_features: the layer is already on with another channel count"); return NVBX_E_INVALID;
   }
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   const size_t vb = (size_t)m->capacity * 1024 * (size_t)channels, wb = (size_t)m->capacity * 2048;
   size_t free_b = 0, total_b = 0; NVBX_HIP(hipMemGetInfo(&free_b, &total_b));
   if (free_b < vb + wb + (64u << 20)) { set_error("nvbx_enable_features: the pools do not fit in free device memory"); return NVBX_E_DEVICE; }
@@ -212,7 +212,7 @@ extern "C" int nvbx_integrate_features(nvbx_mapper* m, const void* feat_dev, int
     set_error("nvbx_integrate_features: T_L_C is not finite or lies outside the addressable block range (+-2^20 blocks)"); return NVBX_E_INVALID; }
   const SubsampledSize ss = subsampled_size(m, 0, camera->height, camera->width);
   if (!ss.ok()) { set_error("nvbx_integrate_features: camera too small for the sphere-tracing subsampling"); return NVBX_E_INVALID; }
-  if (m->join_side()) return NVBX_E_DEVICE;            // held-back work is carried out first: classic order from here on
+  if (m->begin_call()) return NVBX_E_DEVICE;            // held-back work is carried out first: classic order from here on
   if (m->feat_synth.ensure(m->stream, (size_t)ss.rows * ss.cols * 4)) return NVBX_E_DEVICE;
   const Frame fr = m->make_frame(T_L_C, camera, camera->height, camera->width, m->p.sphere_tracing_subsampling);
   FeatTraceArgs ta{}; ta.f = fr; ta.synth = m->feat_synth.as<float>(); ta.srows = ss.rows; ta.scols = ss.cols; ta.max_steps = m->p.sphere_tracing_max_steps;
@@ -231,7 +231,7 @@ extern "C" int nvbx_query_features(nvbx_mapper* m, const float* points_xyz_dev, 
     set_error("nvbx_query_features: invalid argument (the feature output is 16-byte aligned)"); return NVBX_E_INVALID; }
   if (!m->feat_channels) { set_error("nvbx_query_features: call nvbx_enable_features first"); return NVBX_E_INVALID; }
   if (n == 0) return NVBX_OK;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   const int32_t nch = m->feat_channels / 8;
   NVBX_LAUNCH(m, k_query_features, dim3((unsigned)std::min<int64_t>((n * nch + 255) / 256, 8192)), dim3(256), m->d, static_cast<const half8*>(m->feat_val),
               (const float*)m->feat_w, nch, points_xyz_dev, n, m->p.voxel_size, static_cast<half8*>(feat_out_dev), weight_out_dev);
@@ -242,7 +242,7 @@ extern "C" int nvbx_query_features(nvbx_mapper* m, const float* points_xyz_dev, 
 extern "C" int nvbx_get_feature_blocks(nvbx_mapper* m, const nvbx_index3d* idx, int64_t n, void* feat_out, float* weight_out, int32_t* found_out) {
   if (!m || n < 0 || (n > 0 && (!idx || !feat_out || !weight_out))) { set_error("nvbx_get_feature_blocks: invalid argument"); return NVBX_E_INVALID; }
   if (!m->feat_channels) { set_error("nvbx_get_feature_blocks: call nvbx_enable_features first"); return NVBX_E_INVALID; }
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   const int32_t nch = m->feat_channels / 8;
   const size_t fb = (size_t)512 * 16 * nch, wb = 2048;
   const int64_t chunk = std::max<int64_t>(1, (int64_t)((m->staging.bytes - 65536) / (fb + wb + 16)));

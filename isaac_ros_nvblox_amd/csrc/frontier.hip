@@ -8,8 +8,6 @@
 // free voxel, or none inside the box, ends there.  Otherwise six lanes resolve the face neighbours (find_slot), wavefront f < 6 classifies
 // the facing 8 x 8 face of neighbour f into one more word (a missing neighbour: all unknown), and every thread counts its six neighbours
 // from LDS with shifts.  A block with a frontier voxel claims its entry with one atomic add on the output count.
-//   -DNVBX_FRONTIER_TWO_PASS (tools/build_variant.sh; the A/B of EXPERIMENTS.md): k_frontier_classes first writes the 16 words of every TSDF
-//   slot (128 bytes) into the mapper's scratch, the scan then reads its own words and the six neighbours' instead of voxels.
 // k_view_gain: a lane per ray, workgroups grouped by view; the lane keeps the last resolved {block, slot} and probes the hash only when a
 // sample leaves that block; four wave-level sums, four atomics per wavefront into the view's record.
 #include <algorithm>
@@ -27,7 +25,6 @@ struct FrontierArgs {
   int32_t box[6];                                  // inclusive, global voxel coordinates: min x y z, max x y z
   int32_t* block_idx; int32_t* label; float* score;
   int64_t capacity; unsigned long long* count;
-  u64* classes;                                    // two-pass variant: [capacity][16] words, free then unknown
 };
 
 // the voxel classes of SEMANTICS.md: observed = weight >= min_weight (in a block that carries the TSDF layer), free = observed and
@@ -36,18 +33,6 @@ __device__ inline bool fr_observed(float2 v, float min_weight) { return v.y >= m
 __device__ inline bool fr_free(float2 v, float min_weight, float free_dist) { return fr_observed(v, min_weight) && v.x > free_dist; }
 __device__ inline int fr_bit(u64 w, int b) { return (int)((w >> b) & 1ull); }
 
-#ifdef NVBX_FRONTIER_TWO_PASS
-__global__ __launch_bounds__(FR_TPB) void k_frontier_classes(DMap m, FrontierArgs a) {
-  const int t = threadIdx.x, w = t >> 6;
-  const int32_t hw = min(m.counters[C_HIGH_WATER], (int32_t)m.capacity);
-  for (int32_t slot = blockIdx.x; slot < hw; slot += gridDim.x) {
-    if (!(m.slot_flags[slot] & F_TSDF)) continue;      // uniform
-    const float2 v = m.tsdf[(size_t)slot * 512 + t];
-    const u64 fw = __ballot(fr_free(v, a.min_weight, a.free_dist)), uw = __ballot(!fr_observed(v, a.min_weight));
-    if ((t & 63) == 0) { a.classes[(size_t)slot * 16 + w] = fw; a.classes[(size_t)slot * 16 + 8 + w] = uw; }
-  }
-}
-#endif
 
 __global__ __launch_bounds__(FR_TPB) void k_find_frontiers(DMap m, FrontierArgs a) {
   __shared__ u64 s_free[8], s_unk[8], s_face[6];      // own slabs (bit 8y + z); faces -x +x (bit 8y + z), -y +y (8x + z), -z +z (8x + y)
@@ -62,18 +47,11 @@ __global__ __launch_bounds__(FR_TPB) void k_find_frontiers(DMap m, FrontierArgs 
     const int32_t gx = (int32_t)(8u * (uint32_t)bx) + vx, gy = (int32_t)(8u * (uint32_t)by) + vy, gz = (int32_t)(8u * (uint32_t)bz) + vz;
     const bool inbox = gx >= a.box[0] && gx <= a.box[3] && gy >= a.box[1] && gy <= a.box[4] && gz >= a.box[2] && gz <= a.box[5];
     __syncthreads();                                   // (the previous block's readers are done)
-#ifdef NVBX_FRONTIER_TWO_PASS
-    if (t < 16) (t < 8 ? s_free : s_unk)[t & 7] = a.classes[(size_t)slot * 16 + t];
-    __syncthreads();
-    const bool is_free = fr_bit(s_free[vx], 8 * vy + vz) != 0;
-    if (!__syncthreads_or(is_free && inbox)) continue;
-#else
     const float2 v = m.tsdf[(size_t)slot * 512 + t];
     const bool is_free = fr_free(v, a.min_weight, a.free_dist);
     const u64 fw = __ballot(is_free), uw = __ballot(!fr_observed(v, a.min_weight));
     if (lane == 0) { s_free[w] = fw; s_unk[w] = uw; }
     if (!__syncthreads_or(is_free && inbox)) continue;      // no free voxel (inside the box): no neighbour is touched
-#endif
     if (t < 6) {      // face neighbour t: axis t >> 1, direction -1 / +1
       const int d = (t & 1) ? 1 : -1;
       const int32_t nx = bx + ((t >> 1) == 0 ? d : 0), ny = by + ((t >> 1) == 1 ? d : 0), nz = bz + ((t >> 1) == 2 ? d : 0);
@@ -86,13 +64,8 @@ __global__ __launch_bounds__(FR_TPB) void k_find_frontiers(DMap m, FrontierArgs 
       const int axis = w >> 1, c0 = (w & 1) ? 0 : 7, p = lane >> 3, q = lane & 7;
       bool unk = true;
       if (slot_ok(ns)) {
-#ifdef NVBX_FRONTIER_TWO_PASS
-        const u64* nc = a.classes + (size_t)ns * 16 + 8;
-        unk = axis == 0 ? fr_bit(nc[c0], lane) : axis == 1 ? fr_bit(nc[p], 8 * c0 + q) : fr_bit(nc[p], 8 * q + c0);
-#else
         const int nt = axis == 0 ? 64 * c0 + lane : axis == 1 ? 64 * p + 8 * c0 + q : 64 * p + 8 * q + c0;
         unk = !fr_observed(m.tsdf[(size_t)ns * 512 + nt], a.min_weight);
-#endif
       }
       const u64 fb = __ballot(unk);
       if (lane == 0) s_face[w] = fb;
@@ -204,21 +177,14 @@ int frontier_check(const nvbx_mapper* m, const char* who, float min_weight, floa
 int frontier_launch(nvbx_mapper* m, float min_weight, float free_distance_m, int32_t min_unknown, const int32_t* box, nvbx_index3d* block_idx_dev,
                     int32_t* label_dev, float* score_dev, int64_t capacity, int64_t* count_dev) {
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;      // TSDF voxels and flags only: held-back colour and ESDF work stays held back (query.hip)
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;      // TSDF voxels and flags only: held-back colour and ESDF work stays held back (query.hip)
   FrontierArgs a{};
   a.min_weight = min_weight; a.free_dist = free_distance_m; a.min_unknown = min_unknown;
   for (int k = 0; k < 3; k++) { a.box[k] = box ? box[k] : INT32_MIN; a.box[3 + k] = box ? box[3 + k] : INT32_MAX; }
   a.block_idx = reinterpret_cast<int32_t*>(block_idx_dev); a.label = label_dev; a.score = score_dev;
   a.capacity = capacity; a.count = reinterpret_cast<unsigned long long*>(count_dev);
   const dim3 grid((unsigned)std::min<int64_t>(m->capacity, 8192));
-#ifdef NVBX_FRONTIER_TWO_PASS
-  if (m->frontier_scratch.ensure(m->stream, (size_t)m->capacity * 128)) return NVBX_E_DEVICE;
-  a.classes = m->frontier_scratch.as<u64>();
-#endif
   NVBX_HIP(hipMemsetAsync(count_dev, 0, sizeof(int64_t), m->stream));
-#ifdef NVBX_FRONTIER_TWO_PASS
-  NVBX_LAUNCH(m, k_frontier_classes, grid, dim3(FR_TPB), m->d, a);
-#endif
   NVBX_LAUNCH(m, k_find_frontiers, grid, dim3(FR_TPB), m->d, a);
   NVBX_HIP(hipGetLastError());
   return NVBX_OK;
@@ -268,7 +234,7 @@ extern "C" int nvbx_view_gain(nvbx_mapper* m, const float* T_L_C_dev, int32_t n_
   if (std::isnan(min_weight) || std::isnan(free_distance_m)) return refuse(who, ": min_weight / free_distance_m is not a number");
   if (n_views == 0) return NVBX_OK;
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   GainArgs a{};
   a.poses = T_L_C_dev; a.n_views = n_views;
   a.fu = camera->fu; a.fv = camera->fv; a.cu = camera->cu; a.cv = camera->cv; a.subsample = ss.s; a.srows = ss.rows; a.scols = ss.cols;

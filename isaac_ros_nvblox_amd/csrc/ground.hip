@@ -53,9 +53,9 @@ extern "C" int64_t nvbx_tsdf_zero_crossings(nvbx_mapper* m, float min_z_m, float
   if (!m || capacity < 0 || (capacity > 0 && !points_xyz_host) || !(max_z_m >= min_z_m)) { set_error("nvbx_tsdf_zero_crossings: invalid argument"); return NVBX_E_INVALID; }
   if (m->p.projective_layer_type == 1) return 0;                          // an occupancy mapper has no TSDF
   // The usual caller asks twice -- for the count, then with room for it (GroundPlaneEstimator::update, the Python mirror): the sorted result of
-  // the first call is kept and serves the second, as long as no other entry point has come between (join_side drops it) and the band is the same.
+  // the first call is kept and serves the second, as long as no other entry point has come between (begin_call drops it) and the band is the same.
   if (!(m->zc_valid && m->zc_min == min_z_m && m->zc_max == max_z_m)) {
-    if (m->join_side()) return NVBX_E_DEVICE;
+    if (m->begin_call()) return NVBX_E_DEVICE;
     m->zc_valid = false; m->zc_points.clear();
     int64_t cap = std::min<int64_t>(m->capacity * 64, (int64_t)1 << 24);       // one crossing per column and block in practice; a column can hold up to four
     for (int attempt = 0; attempt < 2; attempt++) {

@@ -10,9 +10,9 @@
 // WHO carries it out: the next camera integrateDepth, in PIPELINED order (tsdf.hip depth_step_*) -- view marking of the new depth frame || sphere tracing
 //   of the held-back colour frame, colour integration + ESDF marking, TSDF update of the new frame: three launches per frame instead of four, two in the
 //   fused form (a depth batch carries a colour batch, one frame one frame; what a call cannot carry it replays first).
-// EVERYONE ELSE passes join_side() as the first thing it does, which carries everything out as the calls would have run at call time, IN THIS ORDER:
+// EVERYONE ELSE passes begin_call() as the first thing it does, which carries everything out as the calls would have run at call time, IN THIS ORDER:
 //   replay_deferred (integrateColor, then updateEsdf -- which may arm a new EDT), flush_edt, flush_import (esdf.hip) -- so the API observes call order.
-//   join_side_keeping_held() skips exactly that, for the entry point that touches nothing the held-back work does: nvbx_detect_dynamics (TSDF + freespace
+//   begin_call_keeping_held() skips exactly that, for the entry point that touches nothing the held-back work does: nvbx_detect_dynamics (TSDF + freespace
 //   reads only; the dynamic-mapping frame starts with it) and the camera integrateDepth that carries the work out itself (tsdf.hip cameras_prepare).
 // Two modes switch parts of this off while they last (nvbx_mapper::ModeScope): `replaying` (the replayed calls must not be held back again, nor replay)
 //   and `pipelined_order` (the carried-out calls run inside integrateDepth: no replay, and the marking pass empties its list itself -- EsdfArgs).
@@ -25,7 +25,7 @@ int nvbx_mapper::reset_consumed_list() {
   if (premark_consumed) { NVBX_LAUNCH(this, k_reset_esdf_dirty_list, dim3(1), dim3(64), d); premark_consumed = false; }
   return NVBX_OK;
 }
-int nvbx_mapper::join_side(bool carry_out_held) {
+int nvbx_mapper::begin_call(bool carry_out_held) {
   enqueue_seq++;                     // (an entry point runs: host copies of device counters are stale from here on, esdf.hip nvbx_esdf_slice_to_image)
   zc_valid = false;                  // (whatever follows may change the TSDF: the kept zero-crossing list is dropped)
   // every entry point passes here before its first HIP call: make this mapper's device current (hosts with one mapper per GPU in
@@ -35,8 +35,6 @@ int nvbx_mapper::join_side(bool carry_out_held) {
     if (!replaying && !pipelined_order && replay_deferred()) return NVBX_E_DEVICE;      // held-back integrateColor / updateEsdf: carried out first, in call order
     if (flush_edt() || flush_import()) return NVBX_E_DEVICE;
   }
-  main_dirty = true;
-  if (side_pending) { NVBX_HIP(hipStreamWaitEvent(stream, ev_side, 0)); side_pending = false; }
   return NVBX_OK;
 }
 // the held-back calls of colour deferral, carried out as they would have been at call time: the entry point of each kind of colour call (with_color_types)
@@ -60,17 +58,13 @@ int nvbx_mapper::replay_deferred() {
 }
 extern "C" int nvbx_mapper_set_color_deferral(nvbx_mapper* m, int32_t enable) {
   if (!m) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;          // (anything held back under the old setting is carried out)
+  if (m->begin_call()) return NVBX_E_DEVICE;          // (anything held back under the old setting is carried out)
   if (enable < 0 || enable > 2) { set_error("nvbx_mapper_set_color_deferral: 0 = off, 1 = on (the caller keeps the image valid), 2 = on with a staged copy"); return NVBX_E_INVALID; }
   m->color_deferral = enable != 0; m->color_staging = enable == 2;
-  return NVBX_OK;
-}
-int nvbx_mapper::mark_main() {
-  if (use_side) { NVBX_HIP(hipEventRecord(ev_main, stream)); main_dirty = false; }
   return NVBX_OK;
 }
 extern "C" int nvbx_flush(nvbx_mapper* m) {
   if (!m) return NVBX_E_INVALID;
   NVBX_HIP(hipSetDevice(m->device));
-  return m->join_side();
+  return m->begin_call();
 }

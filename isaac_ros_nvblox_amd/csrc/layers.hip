@@ -159,7 +159,7 @@ extern "C" int64_t nvbx_block_indices(nvbx_mapper* m, uint32_t layer, nvbx_index
   if (!m || !layer_listable(layer)) return NVBX_E_INVALID;
   layer = internal_layer(m, layer);
   if (!layer) return 0;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   NVBX_LAUNCH(m, k_zero_tmp, dim3(1), dim3(1), m->d);
   NVBX_LAUNCH(m, k_collect_indices, dim3(256), dim3(256), m->d, layer, m->export_idx, (int32_t)m->capacity);
   if (m->fetch_counters()) return NVBX_E_DEVICE;
@@ -172,7 +172,7 @@ extern "C" int64_t nvbx_num_blocks(nvbx_mapper* m, uint32_t layer) { return nvbx
 extern "C" int64_t nvbx_last_depth_view(nvbx_mapper* m, nvbx_index3d* out, int64_t capacity) {
   if (!m) return NVBX_E_INVALID;
   if (m->last_view_frame == 0) return 0;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   const uint32_t cam_mask = m->last_view_batch > 1 ? (1u << (m->last_view_batch - 1)) : 0u;
   NVBX_LAUNCH(m, k_viewlist_to_indices, dim3(64), dim3(256), m->d, (const int4*)m->view_list, C_VIEW_COUNT + (int)(m->last_view_frame & 3), cam_mask, m->export_idx, (int32_t)m->capacity);
   if (m->fetch_counters()) return NVBX_E_DEVICE;
@@ -181,7 +181,7 @@ extern "C" int64_t nvbx_last_depth_view(nvbx_mapper* m, nvbx_index3d* out, int64
 }
 extern "C" int64_t nvbx_last_color_view(nvbx_mapper* m, nvbx_index3d* out, int64_t capacity) {
   if (!m) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   NVBX_LAUNCH(m, k_shardlist_to_indices, dim3(64), dim3(256), m->d, (int)S_LIST_COLOR, m->export_idx, (int32_t)m->capacity, m->export_count);
   int32_t n32 = 0;
   NVBX_HIP(hipMemcpyAsync(&n32, m->export_count, 4, hipMemcpyDeviceToHost, m->stream));
@@ -193,7 +193,7 @@ size_t nvbx::ref_voxel_bytes(uint32_t layer) { return layer == F_ESDF ? sizeof(n
 
 extern "C" int nvbx_get_blocks(nvbx_mapper* m, uint32_t layer, const nvbx_index3d* idx, int64_t n, void* voxels_out, int32_t* found_out) {
   if (!m || !idx || !voxels_out || n < 0 || !layer_readable(layer)) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   const size_t bb = 512 * ref_voxel_bytes(layer);
   const uint32_t ilayer = internal_layer(m, layer);
   if (!ilayer) { if (found_out) memset(found_out, 0, (size_t)n * 4); return NVBX_OK; }
@@ -221,7 +221,7 @@ extern "C" int nvbx_set_blocks(nvbx_mapper* m, uint32_t layer, const nvbx_index3
   const uint32_t ilayer = internal_layer(m, layer);
   if (!ilayer) { set_error("nvbx_set_blocks: this mapper's projective layer type does not hold that layer"); return NVBX_E_INVALID; }
   for (int64_t i = 0; i < n; i++) if (!nvbx_index_in_range(idx[i].x, idx[i].y, idx[i].z)) { set_error("nvbx_set_blocks: block index outside +-2^20"); return NVBX_E_INVALID; }
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   if (m->capacity < m->max_capacity) {          // explicit allocation (allocateBlockAtIndex, loadMap): room for all of it, plus the usual head-room
     if (m->fetch_counters()) return NVBX_E_DEVICE;
     m->h_mirror[0] = m->h_counters[C_FREE_TOP];

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(512) void k_clear_shapes(DMap m, ShapeArgs sh, floa
 extern "C" int nvbx_clear_tsdf_inside_shapes(nvbx_mapper* m, const nvbx_bounding_shape* shapes_host, int32_t n_shapes) {
   if (!m || n_shapes < 0 || (n_shapes > 0 && !shapes_host)) return NVBX_E_INVALID;
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   if (m->begin_dirtying()) return NVBX_E_DEVICE;
   const int grid = (int)std::min<int64_t>(m->capacity, 1024);
   for (int32_t o = 0; o < n_shapes; o += 16) {
@@ -315,7 +315,7 @@ extern "C" int nvbx_clear_tsdf_inside_shapes(nvbx_mapper* m, const nvbx_bounding
                 m->p.truncation_distance_vox * m->p.voxel_size, (int32_t)(m->p.projective_layer_type == 1));
   }
   NVBX_HIP(hipGetLastError());
-  return m->mark_main();
+  return NVBX_OK;
 }
 
 // rebuild: (1) remember each live slot's view stamp, (2) memset table, (3) re-insert live slots, recompute ESDF AABB
@@ -352,9 +352,6 @@ __global__ void k_reinsert(DMap m, const uint32_t* tmp, int32_t bz_out) {
   }
 }
 
-#ifndef NVBX_DECAY_INLINE_REBUILD
-#define NVBX_DECAY_INLINE_REBUILD 1       // (A/B: 0 = the three-launch rebuild behind every decay call, as up to round 5)
-#endif
 // Three hash tables of one size rotate through a mapper that decays: LIVE (DMap::table), NEXT (all-empty: k_decay enters the surviving slots) and DIRTY (the table
 // that was live before the previous call: emptied by riders of this call's k_decay, the next call's NEXT).  Allocated at the first two decay calls, again after a
 // growth.  *clear_out = nullptr: nothing to empty in this launch (first call).
@@ -396,29 +393,28 @@ extern "C" int nvbx_decay_occupancy(nvbx_mapper* m) {
   if (!m) return NVBX_E_INVALID;
   if (m->p.projective_layer_type != 1) { set_error("nvbx_decay_occupancy: not an occupancy mapper"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   if (m->undo_marks()) return NVBX_E_DEVICE;
   if (m->begin_dirtying()) return NVBX_E_DEVICE;
   EsdfArgs ea = m->make_esdf_args();
   if (m->p.esdf_mode == 1) { ea.bz_lo = INT32_MIN + 1; ea.bz_hi = INT32_MAX; ea.bz_out = INT32_MIN; }      // 3-D ESDF: every block is its own column
   else if (ea.plane_on) { ea.bz_lo = INT32_MIN + 1; ea.bz_hi = INT32_MAX; }      // ground-plane mode: the band's blocks vary with (x, y) -- a deallocated block of ANY height has its column re-marked
   const int64_t hw_seen = std::max<int64_t>(1, __atomic_load_n(&m->h_mirror[1], __ATOMIC_RELAXED));       // (a hint: the kernel grid-strides)
-  const bool inline_rebuild = NVBX_DECAY_INLINE_REBUILD != 0;
   Entry* next_table = nullptr; Entry* clear_table = nullptr;
-  if (inline_rebuild && prepare_tables(m, &next_table, &clear_table)) return NVBX_E_DEVICE;
+  if (prepare_tables(m, &next_table, &clear_table)) return NVBX_E_DEVICE;
   const int32_t n_clear_wg = clear_table ? 64 : 0;
   NVBX_LAUNCH(m, k_decay<true>, dim3((unsigned)std::min<int64_t>(std::min<int64_t>(m->capacity, 4096), std::max<int64_t>(512, (hw_seen + 7) / 8)) + (unsigned)n_clear_wg), dim3(512), m->d,
               log_odds(m->p.free_region_decay_probability), log_odds(m->p.occupied_region_decay_probability), 0u, 0u, (int32_t)m->mesh_list_live(),
               ea.bz_lo, ea.bz_hi, ea.bz_out, 0.0f, m->cleared_idx, (int32_t)(m->p.decay_deallocate_decayed_blocks ? 0 : 1), (int32_t)(m->p.occupancy_decay_to_free ? 1 : 0), 0.0f,
               next_table, clear_table, n_clear_wg);
-  return inline_rebuild ? rotate_tables(m) : rebuild_table(m);
+  return rotate_tables(m);
 }
 
 extern "C" int nvbx_decay_tsdf(nvbx_mapper* m, int32_t exclude_last_view) {
   if (!m) return NVBX_E_INVALID;
   if (m->p.projective_layer_type == 1) { set_error("nvbx_decay_tsdf: occupancy mapper (use nvbx_decay_occupancy)"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   if (m->undo_marks()) return NVBX_E_DEVICE;          // decay deallocates: unresolved marking passes are taken back first
   if (m->begin_dirtying()) return NVBX_E_DEVICE;
   const int decay_grid = m->knobs.decay_grid;      // (NVBX_DECAY_GRID: tools/decay_grid_sweep.sh)
@@ -428,22 +424,21 @@ extern "C" int nvbx_decay_tsdf(nvbx_mapper* m, int32_t exclude_last_view) {
   EsdfArgs ea = m->make_esdf_args();
   if (m->p.esdf_mode == 1) { ea.bz_lo = INT32_MIN + 1; ea.bz_hi = INT32_MAX; ea.bz_out = INT32_MIN; }      // 3-D ESDF: every block is its own column
   else if (ea.plane_on) { ea.bz_lo = INT32_MIN + 1; ea.bz_hi = INT32_MAX; }      // ground-plane mode: the band's blocks vary with (x, y) -- a deallocated block of ANY height has its column re-marked
-  const bool inline_rebuild = NVBX_DECAY_INLINE_REBUILD != 0;
   Entry* next_table = nullptr; Entry* clear_table = nullptr;
-  if (inline_rebuild && prepare_tables(m, &next_table, &clear_table)) return NVBX_E_DEVICE;
+  if (prepare_tables(m, &next_table, &clear_table)) return NVBX_E_DEVICE;
   const int32_t n_clear_wg = clear_table ? 64 : 0;
   NVBX_LAUNCH(m, k_decay<false>, dim3((unsigned)(grid + n_clear_wg)), dim3(512), m->d, m->p.tsdf_decay_factor, m->p.tsdf_decayed_weight_threshold,
                      exclude_last_view ? m->last_camera_view_frame : 0u, m->last_camera_view_mask, m->mesh_list_live(), ea.bz_lo, ea.bz_hi, ea.bz_out,
                      m->p.truncation_distance_vox * m->p.voxel_size, m->cleared_idx, (int32_t)(m->p.decay_deallocate_decayed_blocks ? 0 : 1),
                      (int32_t)(m->p.tsdf_set_free_distance_on_decayed ? 1 : 0), m->p.tsdf_decayed_free_distance_vox * m->p.voxel_size,
                      next_table, clear_table, n_clear_wg);
-  return inline_rebuild ? rotate_tables(m) : rebuild_table(m);
+  return rotate_tables(m);
 }
 
 extern "C" int nvbx_clear_outside_radius(nvbx_mapper* m, const float center[3], float radius) {
   if (!m || !center) return NVBX_E_INVALID;
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   if (m->undo_marks()) return NVBX_E_DEVICE;          // deallocates: unresolved marking passes are taken back first
   if (m->begin_dirtying()) return NVBX_E_DEVICE;      // (a surviving ESDF block whose column lost a projective block joins the ESDF work list)
   const int grid = (int)std::min<int64_t>((m->capacity + 511) / 512, 2048);          // 512 slots per workgroup iteration
@@ -500,7 +495,7 @@ int nvbx_mapper::grow_map(int64_t new_cap) {
   if (new_cap <= capacity) return NVBX_OK;
   if (new_cap > (1ll << 24)) new_cap = 1ll << 24;
   const int64_t old_cap = capacity;
-  if (join_side()) return NVBX_E_DEVICE;                     // held-back launches go first: they were sized for the old arrays
+  if (begin_call()) return NVBX_E_DEVICE;                     // held-back launches go first: they were sized for the old arrays
   if (fetch_counters()) return NVBX_E_DEVICE;                // (synchronises; the mesh arena cursors are needed below)
   // enough HBM?  (voxel pools dominate: 3-4 x 4 KiB per block; old and new copies of ONE array coexist at a time)
   { size_t free_b = 0, total_b = 0; NVBX_HIP(hipMemGetInfo(&free_b, &total_b));

@@ -120,7 +120,7 @@ int nvbx_mapper::wait_stream() {
   return NVBX_OK;
 }
 int nvbx_mapper::fetch_counters() {
-  if (join_side()) return NVBX_E_DEVICE;
+  if (begin_call()) return NVBX_E_DEVICE;
   NVBX_HIP(hipMemcpyAsync(h_counters, d.counters, C_NUM * 4, hipMemcpyDeviceToHost, stream));
   NVBX_HIP(hipMemcpyAsync(h_shc, d.shc, S_NUM * NSH * SH_STRIDE * 4, hipMemcpyDeviceToHost, stream));
   return wait_stream();
@@ -214,7 +214,7 @@ static void read_knobs(nvbx_mapper* m) { const auto env = [](const char* name) -
 extern "C" int nvbx_mapper_reload_knobs(nvbx_mapper* m) {
   if (!m) return NVBX_E_INVALID;
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side()) return NVBX_E_DEVICE;          // (anything held back under the old settings is carried out)
+  if (m->begin_call()) return NVBX_E_DEVICE;          // (anything held back under the old settings is carried out)
   read_knobs(m);
   return NVBX_OK;
 }
@@ -239,17 +239,9 @@ extern "C" int nvbx_mapper_create(int device, void* hip_stream, const nvbx_mappe
   if (hip_stream) { m->stream = (hipStream_t)hip_stream; m->own_stream = false; }
   else { hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking); if (e != hipSuccess) { set_error("hipStreamCreate", e); delete m; return NVBX_E_DEVICE; } m->own_stream = true; }
   nvbx::frames_register_stream(device, m->stream); m->stream_registered = true;      // (frames let go of without a fence wait for this stream too, frames.hip)
-  // ESDF on a side stream beside colour integration: off by default, NVBX_SIDE_STREAM=1 enables (the
-  // cross-stream hand-off costs ~10 us each way on this runtime, which eats most of the overlap)
-  m->use_side = m->knobs.side_stream != 0;
   m->defer_edt = m->knobs.defer_edt != 0;
   // colour deferral of a new mapper (nvbx_mapper_set_color_deferral overrides): NVBX_COLOR_DEFERRAL = 0 / 1 / 2 in the environment
   { const int cd = m->knobs.color_deferral; if (cd >= 0) { m->color_deferral = cd != 0; m->color_staging = cd == 2; } }
-  if (m->use_side) {
-    if (hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_main, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_side, hipEventDisableTiming) != hipSuccess) { set_error("side stream / events"); nvbx_mapper_destroy(m); return NVBX_E_DEVICE; }
-  }
   int rc = alloc_all(m); if (rc) { nvbx_mapper_destroy(m); return rc; }
   rc = reset_map(m); if (rc) { nvbx_mapper_destroy(m); return rc; }
   hipError_t e = hipStreamSynchronize(m->stream);
@@ -261,14 +253,10 @@ extern "C" int nvbx_mapper_create(int device, void* hip_stream, const nvbx_mappe
 extern "C" int nvbx_mapper_destroy(nvbx_mapper* m) {
   if (!m) return NVBX_OK;
   (void)hipSetDevice(m->device);
-  if (m->side) (void)hipStreamSynchronize(m->side);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
   if (m->ev_order) (void)hipEventDestroy(m->ev_order);
-  if (m->ev_main) (void)hipEventDestroy(m->ev_main);
-  if (m->ev_side) (void)hipEventDestroy(m->ev_side);
-  if (m->side) (void)hipStreamDestroy(m->side);
   for (const PoolArr& a : m->pool_arrays(m->capacity)) if (*a.p) (void)hipFree(*a.p);      // (a half-built mapper: what was not allocated is null)
-  // (both streams are idle: whatever read a held-back colour frame has finished)
+  // (the stream is idle: whatever read a held-back colour frame has finished)
   (void)m->take_pending(); m->release_consumed_frames();
   if (m->stream_registered) nvbx::frames_forget_owner(m, m->device, m->stream);
   for (auto& s : m->spans) { if (s.a) (void)hipEventDestroy(s.a); if (s.b) (void)hipEventDestroy(s.b); }
@@ -292,7 +280,7 @@ extern "C" int nvbx_mapper_set_params(nvbx_mapper* m, const nvbx_mapper_params* 
       set_error("projective_layer_type / esdf_mode can only change while the map is empty"); return NVBX_E_INVALID;
     }
   }
-  if (m->join_side()) return NVBX_E_DEVICE;        // work enqueued under the old parameters (a held-back EDT) is launched first
+  if (m->begin_call()) return NVBX_E_DEVICE;        // work enqueued under the old parameters (a held-back EDT) is launched first
   const bool trunc_changed = params->truncation_distance_vox != m->p.truncation_distance_vox;
   m->p = *params;
   if (trunc_changed && m->p.projective_layer_type != 1) {       // F_BAND is defined by the truncation distance: recompute it for every TSDF block
@@ -328,7 +316,7 @@ extern "C" int nvbx_mapper_get_params(const nvbx_mapper* m, nvbx_mapper_params* 
 }
 extern "C" int nvbx_synchronize(nvbx_mapper* m) {
   if (!m) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   return m->wait_stream();
 }
 extern "C" void nvbx_default_params(nvbx_mapper_params* p) {
@@ -392,7 +380,7 @@ extern "C" int nvbx_mapper_wait_for(nvbx_mapper* waiter, nvbx_mapper* producer) 
 extern "C" int nvbx_mapper_clear(nvbx_mapper* m) {
   if (!m) return NVBX_E_INVALID;
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   return reset_map(m);
 }
 

@@ -111,7 +111,7 @@ extern "C" int nvbx_measure_depth(nvbx_mapper* m, const float* depth_dev, int32_
   if (m->p.projective_layer_type == 2 || (m->p.do_depth_preprocessing && m->p.depth_preprocessing_num_dilations > 0)) {
     set_error("nvbx_measure_depth: mappers with depth preprocessing (dilation) or a freespace layer integrate per frame -- use nvbx_integrate_depth"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   { const int rc = m->maybe_grow(); if (rc) return rc; }
   { const int rc = next_frame_id(m); if (rc) return rc; }
   FrameSet<DepthF32, 1> fs{}; fs.n = 1; fs.img[0] = DepthF32{depth_dev};
@@ -124,7 +124,7 @@ extern "C" int nvbx_measure_depth(nvbx_mapper* m, const float* depth_dev, int32_
               (const int4*)m->view_list, (int32_t)m->capacity, reinterpret_cast<MeasRec*>(out_dev), count_dev, (int32_t)std::min<int64_t>(capacity_blocks, INT32_MAX));
   NVBX_HIP(hipGetLastError());
   m->last_view_frame = m->frame_id; m->last_camera_view_frame = m->frame_id; m->last_camera_view_mask = 1u; m->last_view_batch = 1;
-  return m->mark_main();
+  return NVBX_OK;
 }
 
 extern "C" int nvbx_apply_measurements(nvbx_mapper* m, const nvbx_measurement_block* gathered_dev, const int32_t* counts_dev, int32_t world, int64_t stride_blocks,
@@ -133,7 +133,7 @@ extern "C" int nvbx_apply_measurements(nvbx_mapper* m, const nvbx_measurement_bl
     set_error("nvbx_apply_measurements: invalid argument (1 <= world <= 8)"); return NVBX_E_INVALID; }
   if (m->p.projective_layer_type == 2) { set_error("nvbx_apply_measurements: mappers with a freespace layer integrate per frame (time stamps)"); return NVBX_E_INVALID; }
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   { const int rc = m->maybe_grow(); if (rc) return rc; }
   bool grew = false;
   if (m->apply_postab.ensure(m->stream, (size_t)m->capacity * MAX_BATCH * 4, &grew)) return NVBX_E_DEVICE;
@@ -150,5 +150,5 @@ extern "C" int nvbx_apply_measurements(nvbx_mapper* m, const nvbx_measurement_bl
               (const int4*)m->view_list, (int32_t)m->capacity, m->mesh_list_live());
   NVBX_HIP(hipGetLastError());
   m->last_view_frame = m->frame_id; m->last_camera_view_frame = m->frame_id; m->last_camera_view_mask = 1u << (world - 1); m->last_view_batch = world;
-  return m->mark_main();
+  return NVBX_OK;
 }

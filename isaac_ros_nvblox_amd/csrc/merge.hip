@@ -90,9 +90,6 @@ __global__ __launch_bounds__(512) void k_merge_fuse(DMap dst, DMap src, MergeArg
   __shared__ uint32_t s_slot[27], s_color[27];
   __shared__ int32_t s_min[3];
   __shared__ uint32_t s_cnt[2];
-#ifdef NVBX_MERGE_STAGE_LDS            // -DNVBX_MERGE_STAGE_LDS variant (tools/build_variant.sh): the up to 27 source blocks copied into 108 KiB of dynamic LDS first
-  extern __shared__ __align__(16) uint2 s_vox[];
-#endif
   int32_t n = dst.counters[C_VIEW_COUNT + (a.frame_id & 3)];
   if (n > list_cap) n = list_cap;
   const int tid = threadIdx.x;
@@ -135,10 +132,6 @@ __global__ __launch_bounds__(512) void k_merge_fuse(DMap dst, DMap src, MergeArg
       s_slot[tid] = s; s_color[tid] = cf;
     }
     __syncthreads();
-#ifdef NVBX_MERGE_STAGE_LDS
-    for (int q = 0; q < 27; q++) { const uint32_t s = s_slot[q]; if (slot_ok(s)) s_vox[q * 512 + tid] = spool[(size_t)s * 512 + tid]; }      // (uniform branch; 4 KiB per block present)
-    __syncthreads();
-#endif
     // corners: block offsets 0 .. 2 from (B0, B1, B2) per axis (ok lanes: never more, the block's centres span 7 voxels)
     const int lx = b[0] & 7, ly = b[1] & 7, lz = b[2] & 7;
     const int ox0 = ok ? (b[0] >> 3) - B0 : 0, oy0 = ok ? (b[1] >> 3) - B1 : 0, oz0 = ok ? (b[2] >> 3) - B2 : 0;
@@ -154,11 +147,6 @@ __global__ __launch_bounds__(512) void k_merge_fuse(DMap dst, DMap src, MergeArg
       if (all) {
         const int q0 = ox + 3 * oy + 9 * oz0, q1 = ox + 3 * oy + 9 * oz1;
         const uint32_t s0 = s_slot[q0];
-#ifdef NVBX_MERGE_STAGE_LDS            // (experiment, EXPERIMENTS.md: the corners come from the staged copies)
-        const uint32_t s1 = s_slot[q1];
-        if (slot_ok(s0) && slot_ok(s1)) { e0 = s_vox[q0 * 512 + lz + 8 * yy + 64 * xx]; e1 = s_vox[q1 * 512 + ((lz + 1) & 7) + 8 * yy + 64 * xx]; }
-        else all = false;
-#else
         if (lz != 7) {
           if (slot_ok(s0)) { const uint4 w = ld_pair(spool + (size_t)s0 * 512 + lz + 8 * yy + 64 * xx); e0 = make_uint2(w.x, w.y); e1 = make_uint2(w.z, w.w); }
           else all = false;
@@ -167,7 +155,6 @@ __global__ __launch_bounds__(512) void k_merge_fuse(DMap dst, DMap src, MergeArg
           if (slot_ok(s0) && slot_ok(s1)) { e0 = spool[(size_t)s0 * 512 + 7 + 8 * yy + 64 * xx]; e1 = spool[(size_t)s1 * 512 + 8 * yy + 64 * xx]; }
           else all = false;
         }
-#endif
       }
       cd[q] = __uint_as_float(e0.x); cw[q] = __uint_as_float(e0.y); cd[q + 4] = __uint_as_float(e1.x); cw[q + 4] = __uint_as_float(e1.y);
       all = all && cw[q] >= a.min_weight && cw[q + 4] >= a.min_weight;
@@ -268,7 +255,7 @@ extern "C" int nvbx_merge_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_
   if (src->fetch_counters()) return NVBX_E_DEVICE;
   const int64_t src_hw = src->h_counters[C_HIGH_WATER];
   const int64_t src_live = std::max<int64_t>(1, (int64_t)src->capacity - (int64_t)src->h_counters[C_FREE_TOP]);
-  if (dst->join_side()) return NVBX_E_DEVICE;
+  if (dst->begin_call()) return NVBX_E_DEVICE;
   { const int rc = nvbx_mapper_wait_for(dst, src); if (rc) return rc; }
   MergeArgs a{};
   nvbx_merge_transforms(T_D_S, a.R_DS, a.t_DS, a.R_SD, a.t_SD);
@@ -318,16 +305,10 @@ extern "C" int nvbx_merge_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_
   a.frame_id = dst->frame_id; a.mesh_list = dst->mesh_list_live();
   NVBX_LAUNCH(dst, k_merge_index, dim3(enum_grid), dim3(256), dst->d, src->d, a, (int4*)dst->view_list, (int32_t)dst->capacity);
   const unsigned fuse_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(dst->capacity, (int64_t)h.src_blocks * 27), 2048));
-#ifdef NVBX_MERGE_STAGE_LDS
-  constexpr size_t kStageBytes = 27 * 512 * sizeof(uint2);
-  NVBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_fuse), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStageBytes));
-  NVBX_LAUNCH_SMEM(dst, k_merge_fuse, dim3(fuse_grid), dim3(512), kStageBytes, dst->d, src->d, a, (const int4*)dst->view_list, (int32_t)dst->capacity, sc);
-#else
   NVBX_LAUNCH(dst, k_merge_fuse, dim3(fuse_grid), dim3(512), dst->d, src->d, a, (const int4*)dst->view_list, (int32_t)dst->capacity, sc);
-#endif
   NVBX_LAUNCH(dst, k_merge_result, dim3(1), dim3(64), dst->d, a.frame_id, (const MergeScratch*)sc, (int64_t)h.src_blocks, (int64_t)h.need_tsdf, 0, result_dev);
   NVBX_HIP(hipGetLastError());
   dst->last_view_frame = dst->frame_id; dst->last_view_batch = 1;      // (the view list now holds the candidates; the last CAMERA view stays what it was)
   { const int rc = nvbx_mapper_wait_for(src, dst); if (rc) return rc; }      // later work on src runs behind the merge's reads
-  return dst->mark_main();
+  return NVBX_OK;
 }

@@ -333,7 +333,7 @@ extern "C" int nvbx_update_color_mesh(nvbx_mapper* m, int32_t update_full_layer)
   if (!m) return NVBX_E_INVALID;
   NVBX_HIP(hipSetDevice(m->device));
   if (m->p.projective_layer_type == 1) return NVBX_OK;      // "Mesh integration is not implemented for occupancy layers" (nvblox_node.cpp:186)
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   MeshArgs a{};
   a.voxel_size = m->p.voxel_size; a.block_size = m->p.voxel_size * 8.0f; a.min_weight = m->p.mesh_min_weight;
   a.full = update_full_layer ? 1 : 0;

@@ -31,8 +31,6 @@ static inline int nvbx_knob_riders(const char* s, int def) {
 }
 /* an A/B switch: 0 or 1, default on */
 static inline int nvbx_knob_switch(const char* s) { return nvbx_knob_int(s, 1, 0, 1); }
-/* ... and one that is off unless asked for: 0 or 1, default off */
-static inline int nvbx_knob_opt_in(const char* s) { return nvbx_knob_int(s, 0, 0, 1); }
 
 /* NVBX_INTEG_GRID: cap on the TSDF update's workgroups; 0 = the built-in cap (1024 for one camera, 512 for a batch) */
 static inline int nvbx_knob_integ_grid(const char* s) { return nvbx_knob_int(s, 0, 1, NVBX_KNOB_GRID_MAX); }
@@ -104,12 +102,11 @@ static inline void nvbx_change_knobs_read(struct nvbx_change_knobs* k, const cha
   k->grid = nvbx_knob_change_grid(lookup("NVBX_CHANGE_GRID"));
 }
 
-/* One mapper's knobs: filled at nvbx_mapper_create and again by nvbx_mapper_reload_knobs.  Four of them shape the mapper at creation and are
- * not applied to a live one: max_blocks, side_stream, color_deferral, defer_edt (include/nvblox_hip.h). */
+/* One mapper's knobs: filled at nvbx_mapper_create and again by nvbx_mapper_reload_knobs.  Three of them shape the mapper at creation and are
+ * not applied to a live one: max_blocks, color_deferral, defer_edt (include/nvblox_hip.h). */
 struct nvbx_knobs {
   /* A/B switches */
   int fuse_colc, depth_pair, lidar_sparse, lidar_dense_list, lidar_view_grid, defer_edt, replay_pair, esdf_only_carry;      /* default on */
-  int side_stream, query_dedup;                                                                                            /* default off */
   int color_deferral, mark_tiles_first;                                                                                    /* -1 = unset */
   /* launch geometry */
   int integ_grid, color_grid, decay_grid, lidar_sparse_grid, grid_margin_pct, grid_margin_blocks;
@@ -128,8 +125,6 @@ static inline void nvbx_knobs_read(struct nvbx_knobs* k, const char* (*lookup)(c
   k->defer_edt = nvbx_knob_switch(lookup("NVBX_DEFER_EDT"));
   k->replay_pair = nvbx_knob_switch(lookup("NVBX_REPLAY_PAIR"));
   k->esdf_only_carry = nvbx_knob_switch(lookup("NVBX_ESDF_ONLY_CARRY"));
-  k->side_stream = nvbx_knob_opt_in(lookup("NVBX_SIDE_STREAM"));
-  k->query_dedup = nvbx_knob_opt_in(lookup("NVBX_QUERY_DEDUP"));
   k->color_deferral = nvbx_knob_color_deferral(lookup("NVBX_COLOR_DEFERRAL"));
   k->mark_tiles_first = nvbx_knob_mark_tiles_first(lookup("NVBX_MARK_TILES_FIRST"));
   k->integ_grid = nvbx_knob_integ_grid(lookup("NVBX_INTEG_GRID"));

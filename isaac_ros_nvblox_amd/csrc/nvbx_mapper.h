@@ -103,22 +103,13 @@ struct nvbx_mapper {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false, stream_registered = false;
-  // Side stream: the ESDF update (k_esdf_mark + k_esdf_edt) is independent of colour integration, so it
-  // runs on its own stream behind an event recorded after the last non-colour operation and overlaps integrateColor.
-  // Every other entry point joins the side stream first, so the caller still sees single-stream ordering.
-  hipStream_t side = nullptr;
-  hipEvent_t ev_main = nullptr, ev_side = nullptr;
   hipEvent_t ev_order = nullptr;     // nvbx_mapper_wait_for: this mapper's stream as the producer
   // The NVBX_* environment knobs (nvbx_knobs.h), read at nvbx_mapper_create and again by nvbx_mapper_reload_knobs: every launch-geometry and A/B
-  // decision of this mapper reads them here.  max_capacity, use_side, color_deferral / color_staging and defer_edt take their value at creation only.
+  // decision of this mapper reads them here.  max_capacity, color_deferral / color_staging and defer_edt take their value at creation only.
   nvbx_knobs knobs{};
   nvbx_plan_knobs plan_knobs{}; // ... and the cost field's two (plan.hip), read with them
   nvbx_change_knobs change_knobs{}; // ... and change detection's one (change.hip)
-  bool use_side = false;        // knobs.side_stream at creation (NVBX_SIDE_STREAM=1 enables)
-  bool side_pending = false;    // ESDF work enqueued on `side` that `stream` has not waited for yet
-  bool main_dirty = true;       // non-colour work enqueued on `stream` since ev_main was recorded
-  int join_side(bool carry_out_held = true);      // first call of every entry point (held.hip): held-back work is carried out, `stream` waits for the side stream (no host sync)
-  int mark_main();              // record ev_main on `stream` (call right after a non-colour operation)
+  int begin_call(bool carry_out_held = true);      // first call of every entry point (held.hip): the device is made current, held-back work is carried out (no host sync)
   nvbx_mapper_params p{};
   int64_t capacity = 0;
   // Pool growth (the reference allocates blocks on demand; here the pools double before they run out): kernels mirror the number of
@@ -163,8 +154,6 @@ struct nvbx_mapper {
   nvbx::DevBuf merge_buf;
   // change detection (change.hip), as the map that is scanned: 64 bytes of counters, allocated with the map
   nvbx::DevBuf change_buf;
-  // frontier scan (frontier.hip), -DNVBX_FRONTIER_TWO_PASS variant only: 128 bytes of voxel classes per slot; the product's single pass needs none
-  nvbx::DevBuf frontier_scratch;
   // cost field (plan.hip) and cost volume (plan3d.hip), sized and carved up by nvbx_plan_grid.h's plan_grid_setup alone: a 64-byte head of counters, the class word of every cell and the two sets of active-tile flags of the largest input so far
   nvbx::DevBuf plan_scratch;
   // traversability (elevation.hip): one bit row of HAZARD flags, ceil(cols / 64) 64-bit words, per row of the largest image so far
@@ -193,7 +182,7 @@ struct nvbx_mapper {
   // mark_pass when the last distance transform was enqueued (passes above it are the unresolved ones).
   bool unresolved_marks = false; uint32_t pass_at_last_edt = 0;
   int undo_marks();
-  // nvbx_tsdf_zero_crossings: the sorted result of the last call, valid until any other entry point runs (join_side) -- serves the
+  // nvbx_tsdf_zero_crossings: the sorted result of the last call, valid until any other entry point runs (begin_call) -- serves the
   // "count, then data" pair of calls with one launch, one download and one sort
   bool zc_valid = false; float zc_min = 0.0f, zc_max = 0.0f; std::vector<float> zc_points;
   // dynamic mapping (dynamics.hip)
@@ -251,9 +240,9 @@ struct nvbx_mapper {
     void leave() { if (flag) *flag = false; flag = nullptr; }
   };
   int replay_deferred();
-  int join_side_keeping_held() { return join_side(false); }      // for an entry point that touches nothing the held-back work does: it all stays held back
+  int begin_call_keeping_held() { return begin_call(false); }      // for an entry point that touches nothing the held-back work does: it all stays held back
   // a held-back updateEsdf with NO colour frame in front of it (depth-only hosts, occupancy mappers) that the next camera launch can carry in two-launch order
-  bool esdf_only_carry() const { return held.esdf_update_pending && !held.color_pending.on && p.esdf_mode == 0 && p.esdf_propagation == 0 && !held.import_pending && !use_side && defer_edt; }
+  bool esdf_only_carry() const { return held.esdf_update_pending && !held.color_pending.on && p.esdf_mode == 0 && p.esdf_propagation == 0 && !held.import_pending && defer_edt; }
   template <int NB> int pending_color_trace_rider(nvbx::TraceRiderT<NB>* out);      // color.hip, for a depth call of NB frames (1 or MAX_BATCH; a held-back call of the other count is refused): set the held-back frame(s) up, the sphere tracing as a rider
   int launch_pending_color_after_trace();
   bool replay_pair_applies() const;  // color.hip: a held-back colour frame + updateEsdf can be replayed in two launches (replay_pair)
@@ -317,14 +306,7 @@ static inline int sparse_volume_refused(const char* who, const int32_t* box, con
 }
 
 // every kernel launch of the library goes through this macro (name = the kernel's name in rocprof output)
-#define NVBX_LAUNCH_ON(m, s, kernel, grid, block, ...)                               \
-  do {                                                                               \
-    if ((m)->profiling) (m)->span_begin(#kernel, (s));                               \
-    (m)->enqueue_seq++;                                                              \
-    hipLaunchKernelGGL(kernel, grid, block, 0, (s), __VA_ARGS__);                    \
-    if ((m)->profiling) (m)->span_end((s));                                          \
-  } while (0)
-#define NVBX_LAUNCH(m, kernel, grid, block, ...) NVBX_LAUNCH_ON(m, (m)->stream, kernel, grid, block, __VA_ARGS__)
+#define NVBX_LAUNCH(m, kernel, grid, block, ...) NVBX_LAUNCH_SMEM(m, kernel, grid, block, 0, __VA_ARGS__)
 // (... with `smem` bytes of dynamic LDS per workgroup)
 #define NVBX_LAUNCH_SMEM(m, kernel, grid, block, smem, ...)                          \
   do {                                                                               \

@@ -149,11 +149,11 @@ template <int D> inline int plan_grid_check_field(const char* who, const PlanWor
   return NVBX_OK;
 }
 
-// Behind the checks of a cost-to-go call: joins the side stream (the call reads its input only: everything held back stays held back), sizes the
+// Behind the checks of a cost-to-go call: begins the call (it reads its input only: everything held back stays held back), sizes the
 // scratch for n cells and ntiles tiles, points g into it and clears the head.
 inline int plan_grid_setup(nvbx_mapper* m, PlanGridArgs* g, int64_t n, int64_t ntiles, const nvbx_cost_options* o, const int32_t* src, int32_t n_src, int32_t* cost) {
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   if (m->plan_scratch.ensure(m->stream, PLAN_HEAD + (size_t)n * 4 + (size_t)ntiles * 2)) return NVBX_E_DEVICE;
   uint8_t* base = m->plan_scratch.as<uint8_t>();
   g->head = reinterpret_cast<uint32_t*>(base); g->cls = reinterpret_cast<int32_t*>(base + PLAN_HEAD); g->active = base + PLAN_HEAD + (size_t)n * 4;
@@ -193,7 +193,7 @@ template <int D, class Launch> inline int plan_grid_trace_call(const char* who, 
     return refuse(who, (std::string(": starts_") + w.axes + "_dev, path_" + w.axes + "_dev and length_dev are required with n_starts > 0").c_str());
   if (n_starts == 0) return NVBX_OK;
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   PlanTraceArgs<D> a{};
   a.grid = grid; a.o = *o; a.cost = cost; a.starts = starts; a.n = n_starts; a.path = path; a.capacity = capacity; a.length = length;
   for (int c = 0; c < D; c++) a.dim[c] = dim[c];

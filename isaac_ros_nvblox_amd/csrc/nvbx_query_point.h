@@ -25,27 +25,11 @@ __device__ inline uint32_t q_probe(const DMap& m, int32_t x, int32_t y, int32_t 
   return SLOT_NONE;
 }
 
-// Wave-level de-duplication of the probes (NVBX_QUERY_DEDUP=1; not the default: DESIGN.md 2.11): the lanes that still need a block take the key of the first of them
-// (readlane: the key is wave-uniform, so the probe chain runs on the scalar unit), one chain serves every lane with that key.
-// At most DEDUP_ROUNDS distinct keys per wave and corner offset; the lanes left over probe on their own.
-constexpr int DEDUP_ROUNDS = 4;
-template <bool DEDUP>
+// the probe of a lane that needs the block, SLOT_NONE for one that does not (every lane probes on its own: a wave-level de-duplication of the
+// probes was measured slower on coherent and uniform batches alike)
 __device__ inline uint32_t q_lookup(const DMap& m, bool need, int32_t x, int32_t y, int32_t z, uint32_t flag) {
   uint32_t s = SLOT_NONE;
-  if (DEDUP) {
-    bool pend = need;
-    for (int r = 0; r < DEDUP_ROUNDS; r++) {
-      const unsigned long long bal = __ballot(pend);
-      if (!bal) break;
-      const int leader = __ffsll((long long)bal) - 1;
-      const int32_t lx = __builtin_amdgcn_readlane(x, leader), ly = __builtin_amdgcn_readlane(y, leader), lz = __builtin_amdgcn_readlane(z, leader);
-      const uint32_t ls = q_probe(m, lx, ly, lz, flag);
-      if (pend && x == lx && y == ly && z == lz) { s = ls; pend = false; }
-    }
-    if (pend) s = q_probe(m, x, y, z, flag);
-  } else if (need) {
-    s = q_probe(m, x, y, z, flag);
-  }
+  if (need) s = q_probe(m, x, y, z, flag);
   return s;
 }
 
@@ -55,11 +39,10 @@ struct QBlockCache { int32_t bx = INT32_MIN, by = 0, bz = 0; uint32_t slot = SLO
 
 // The query at p: returns valid; *d = the interpolant or `unknown`, g = its gradient per metre or 0.  `pool` = the layer's voxels (TSDF: m.tsdf as
 // uint2).  Corner (i, j, k) of the lane: block offset o = (i & cx) | (j & cy) << 1 | (k & cz) << 2 from the base block.
-// (DEDUP: every lane of the wavefront must make the call.)
 // DIST_ONLY (a further instantiation; the others compile to what they were): the distance alone -- g is not touched and may be null, the gradient's
 // arithmetic is dead code, *d_out has the same bits -- and the base block's slot comes from `cache` while the base corner stays in one block.
 // slots_out (null in every caller but the colour alignment; a constant after inlining): the eight block slots sl[o] the lane resolved, for q_color.
-template <int KIND, bool DEDUP, bool DIST_ONLY = false>
+template <int KIND, bool DIST_ONLY = false>
 __device__ inline bool q_point(const DMap& m, const uint2* pool, const float p[3], float vs, float min_weight, float unknown, int32_t plane_vz,
                                float* d_out, float g[3], QBlockCache* cache = nullptr, uint32_t* slots_out = nullptr) {
   constexpr uint32_t FLAG = KIND == Q_TSDF ? F_TSDF : F_ESDF;
@@ -85,7 +68,7 @@ __device__ inline bool q_point(const DMap& m, const uint2* pool, const float p[3
       }
       continue;
     }
-    sl[o] = q_lookup<DEDUP>(m, need, bx + (o & 1), by + ((o >> 1) & 1), bz + (o >> 2), FLAG);
+    sl[o] = q_lookup(m, need, bx + (o & 1), by + ((o >> 1) & 1), bz + (o >> 2), FLAG);
   }
   if (slots_out) {
 #pragma unroll

@@ -93,9 +93,6 @@ struct LidarSensor {
 #define NVBX_LIDAR_FR 6
 #define NVBX_LIDAR_PD 4
 #endif
-#ifndef NVBX_LIDAR_SPARSE_STRIDED
-#define NVBX_LIDAR_SPARSE_STRIDED 1       // (0: eight consecutive records per pass -- 126.5 instead of 116.4 us, EXPERIMENTS.md)
-#endif
 #ifndef NVBX_LIDAR_SET
 #define NVBX_LIDAR_SET 1024
 #define NVBX_LIDAR_FLUSH 256
@@ -425,9 +422,7 @@ __device__ inline void flush_set(const DMap& m, const Frame& f, u64* lset, u64* 
           hpos[r] = hh; seen[r] = st;
           if (stamp_frame(st) != f.frame_id) { claim[r] = true; old[r] = atomicCAS(&m.table[hh].stamp, st, want); }   // the returning atomics of a pass: in flight together
           else if (!(st & f.cam_bit)) atomicOr(&m.table[hh].stamp, f.cam_bit);     // stamped by another camera of this batch: add our bit (not waited for)
-#ifndef NVBX_NO_BATCH_INSERT             // (A/B: tools/build_variant.sh nobatch "-DNVBX_NO_BATCH_INSERT")
         } else if (qe >= 0) { ins[r] = true; any_ins = true; hpos[r] = (h[r] + qe) & m.mask;        // a NEW block (as far as this pass can see)
-#endif
         }
       }
     }

@@ -16,7 +16,7 @@ void nvbx_mapper::span_begin(const char* name, hipStream_t st) {
 void nvbx_mapper::span_end(hipStream_t st) { (void)hipEventRecord(spans.back().b, st); }
 extern "C" int nvbx_set_profiling(nvbx_mapper* m, int32_t enable) {
   if (!m) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   NVBX_HIP(hipStreamSynchronize(m->stream));
   for (auto& s : m->spans) { m->event_pool.push_back(s.a); m->event_pool.push_back(s.b); }
   m->spans.clear();
@@ -27,7 +27,7 @@ extern "C" int nvbx_set_profiling(nvbx_mapper* m, int32_t enable) {
 // JSON object {"kernel": {"count": n, "total_ms": t}, ...} of every launch since nvbx_set_profiling(m, 1).
 extern "C" int nvbx_get_profile(nvbx_mapper* m, char* json_out, int64_t capacity) {
   if (!m || !json_out || capacity < 4) return NVBX_E_INVALID;
-  if (m->join_side()) return NVBX_E_DEVICE;
+  if (m->begin_call()) return NVBX_E_DEVICE;
   NVBX_HIP(hipStreamSynchronize(m->stream));
   struct Acc { const char* name; int64_t n; double ms; double max_ms; };
   std::vector<Acc> acc;

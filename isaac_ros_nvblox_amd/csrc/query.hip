@@ -15,14 +15,14 @@ using namespace nvbx;
 
 namespace {
 
-template <int KIND, bool DEDUP>
+template <int KIND>
 __global__ __launch_bounds__(256) void k_query_points(DMap m, const float* __restrict__ pts, int64_t n, float vs, float min_weight, float unknown,
                                                       int32_t plane_vz, float* __restrict__ dist, float* __restrict__ grad, uint8_t* __restrict__ valid) {
   const uint2* pool = KIND == Q_TSDF ? reinterpret_cast<const uint2*>(m.tsdf) : m.esdf;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
     float g[3], d;
-    const bool all = q_point<KIND, DEDUP>(m, pool, p, vs, min_weight, unknown, plane_vz, &d, g);
+    const bool all = q_point<KIND>(m, pool, p, vs, min_weight, unknown, plane_vz, &d, g);
     dist[i] = d;
     if (grad) { grad[3 * i] = g[0]; grad[3 * i + 1] = g[1]; grad[3 * i + 2] = g[2]; }
     if (valid) valid[i] = all ? 1 : 0;
@@ -31,10 +31,8 @@ __global__ __launch_bounds__(256) void k_query_points(DMap m, const float* __res
 
 template <int KIND>
 int launch_query(nvbx_mapper* m, const float* pts, int64_t n, float min_weight, float unknown, int32_t plane_vz, float* dist, float* grad, uint8_t* valid) {
-  // (NVBX_QUERY_DEDUP -- A/B, tools/query_bench.py: 1 = the wave-level de-duplication; measured slower on coherent and uniform batches alike)
   const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), block(256);
-  if (m->knobs.query_dedup) NVBX_LAUNCH(m, (k_query_points<KIND, true>), grid, block, m->d, pts, n, m->p.voxel_size, min_weight, unknown, plane_vz, dist, grad, valid);
-  else NVBX_LAUNCH(m, (k_query_points<KIND, false>), grid, block, m->d, pts, n, m->p.voxel_size, min_weight, unknown, plane_vz, dist, grad, valid);
+  NVBX_LAUNCH(m, k_query_points<KIND>, grid, block, m->d, pts, n, m->p.voxel_size, min_weight, unknown, plane_vz, dist, grad, valid);
   NVBX_HIP(hipGetLastError());
   return NVBX_OK;
 }
@@ -49,7 +47,7 @@ extern "C" int nvbx_query_points(nvbx_mapper* m, uint32_t layer, const float* po
   if (layer == NVBX_LAYER_TSDF && tsdf_reader_refused(m, "nvbx_query_points")) return NVBX_E_INVALID;
   if (n == 0) return NVBX_OK;
   if (layer == NVBX_LAYER_ESDF) {
-    if (m->join_side()) return NVBX_E_DEVICE;                 // a held-back updateEsdf (colour deferral, held-back EDT) is carried out first
+    if (m->begin_call()) return NVBX_E_DEVICE;                 // a held-back updateEsdf (colour deferral, held-back EDT) is carried out first
     const EsdfArgs a = m->make_esdf_args();
     return m->p.esdf_mode == 1 ? launch_query<Q_ESDF3>(m, points_xyz_dev, n, min_weight, unknown_value, -1, distance_dev, gradient_xyz_dev, valid_dev)
                                : launch_query<Q_ESDF2>(m, points_xyz_dev, n, min_weight, unknown_value, a.kz_out, distance_dev, gradient_xyz_dev, valid_dev);
@@ -59,6 +57,6 @@ extern "C" int nvbx_query_points(nvbx_mapper* m, uint32_t layer, const float* po
   // exchange -- writes none of them, and every TSDF writer enqueued before this call is already on the stream.  So the held-back work stays
   // held back (as for nvbx_detect_dynamics): the query sees what classic order would show at this point, and the next integrateDepth
   // still carries the held-back frame in its two-launch pipelined order.
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   return launch_query<Q_TSDF>(m, points_xyz_dev, n, min_weight, unknown_value, 0, distance_dev, gradient_xyz_dev, valid_dev);
 }

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(SCORE_TPB) void k_score_poses(DMap m, ScoreArgs a) 
     if (take) {
       float p[3];
       apply_rt(R, t, x[0], x[1], x[2], p);
-      valid = q_point<Q_TSDF, false, true>(m, pool, p, a.vs, a.min_weight, 0.0f, 0, &d, nullptr, &cache);
+      valid = q_point<Q_TSDF, true>(m, pool, p, a.vs, a.min_weight, 0.0f, 0, &d, nullptr, &cache);
     }
     const float ad = fabsf(d);
     n_pts += __popcll(__ballot(take));
@@ -232,7 +232,7 @@ int score_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n, cons
   if (score_options_check(who, m, options, &o) || point_source_check(who, pts, n, depth, rows, cols, cam, o.s, o.max_d, &a.src)) return NVBX_E_INVALID;
   if (n_poses == 0) return NVBX_OK;
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;      // TSDF voxels and flags only: held-back colour and ESDF work stays held back (query.hip)
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;      // TSDF voxels and flags only: held-back colour and ESDF work stays held back (query.hip)
   a.source = POSE_LIST; a.poses = poses; a.out = scores;
   if (score_launch(m, a, o, n_poses, false)) return NVBX_E_DEVICE;
   NVBX_HIP(hipGetLastError());
@@ -255,7 +255,7 @@ int relocalize_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n,
   const int rc = align_check_from_state(who, m, pts, n, depth, rows, cols, cam, align_options, &res->align, al);
   if (rc) return rc;
   NVBX_HIP(hipSetDevice(m->device));
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   // buffers first: a growth waits for the stream
   const int64_t K = nvbx_lattice_count(lattice);
   constexpr size_t TAB_BYTES = (sizeof(nvbx_lattice_tables) + 255) / 256 * 256;

@@ -227,7 +227,7 @@ int render_begin(nvbx_mapper* m, const nvbx_render_options* opt, float max_ray_l
   // Without a colour output the launch reads TSDF voxels only, which nothing that is held back writes: the held-back work stays held back and
   // the next integrateDepth is still a two-launch pipelined frame (as for the TSDF point query, query.hip).  A colour output reads the colour
   // layer, which a held-back integrateColor writes: that work is carried out first, so the call shows what classic order would show.
-  if (with_color ? m->join_side() : m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (with_color ? m->begin_call() : m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   return NVBX_OK;
 }
 

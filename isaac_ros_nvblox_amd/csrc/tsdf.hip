@@ -401,7 +401,7 @@ static int depth_step_after(nvbx_mapper* m, int n_frames) {
   if (!Sensor::kLongRays) { m->last_camera_view_frame = m->frame_id; m->last_camera_view_mask = 1u << (n_frames - 1); }   // (a batch: the LAST camera's view, as separate calls would leave it)
   m->last_view_batch = n_frames;
   if (m->p.projective_layer_type == 2 && m->update_freespace()) return NVBX_E_DEVICE;     // TSDF with freespace (dynamic mapping)
-  return m->mark_main();
+  return NVBX_OK;
 }
 
 // (frames of a held-back colour image a depth call carries out: let go of on every way out, behind the launches that read them)
@@ -493,7 +493,7 @@ __global__ void k_reset_stamps(DMap m) {
 }
 int next_frame_id(nvbx_mapper* m) {
   if (m->frame_id >= STAMP_FRAME_MAX) {
-    if (m->join_side()) return NVBX_E_DEVICE;
+    if (m->begin_call()) return NVBX_E_DEVICE;
     NVBX_LAUNCH(m, k_reset_stamps, dim3(1024), dim3(256), m->d);
     NVBX_HIP(hipGetLastError());
     m->frame_id = 0; m->last_view_frame = 0; m->last_camera_view_frame = 0;
@@ -532,9 +532,9 @@ static int cameras_prepare(nvbx_mapper* m, int32_t n, const float* T_L_C /* n x 
   // held-back integrateColor / updateEsdf that this call cannot carry out in pipelined order are replayed NOW (the replayed calls launch / re-arm the EDT)
   const bool carry = !dilate_first && (m->held.color_pending.on ? m->held.color_pending.carried_by(NB) : m->esdf_only_carry());      // this call can carry the held-back calls out in pipelined order
   if (!carry && m->replay_deferred()) return NVBX_E_DEVICE;
-  // (join_side would launch a held-back EDT / union step; the EDT rides in k_mark_view instead, the union step stays held back for the next
+  // (begin_call would launch a held-back EDT / union step; the EDT rides in k_mark_view instead, the union step stays held back for the next
   //  integrateColor -- it belongs to the NEXT ESDF update and touches nothing this launch reads.  What else is still held back, this call carries out)
-  if (m->join_side_keeping_held()) return NVBX_E_DEVICE;
+  if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   { const int rc = m->maybe_grow(); if (rc) return rc; }          // (before anything of this frame is enqueued)
   return NVBX_OK;
 }
@@ -588,7 +588,7 @@ extern "C" int nvbx_integrate_depth_batch(nvbx_mapper* m, int32_t n, const float
 // unmasked part of the depth image, the foreground (occupancy) mapper the masked part, nvblox_node.cpp:1057-1062 -- in two launches instead of four.
 // See include/nvblox_hip.h; whatever the pair cannot express falls back to the two calls it is defined by.
 static bool pair_can_fuse(const nvbx_mapper* m) {
-  if (m->use_side || m->capacity > (1ll << 24)) return false;
+  if (m->capacity > (1ll << 24)) return false;
   if (m->p.do_depth_preprocessing && m->p.depth_preprocessing_num_dilations > 0) return false;          // (a dilation launch in front)
   if (m->held.color_pending.on && (m->held.color_pending.n != 1 || !fused_colour_applies(m))) return false;      // (its colour frame would be carried in three launches)
   return true;

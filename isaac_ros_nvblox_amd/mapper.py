@@ -355,7 +355,7 @@ class Mapper:
 
     def reload_knobs(self):
         """Read the library's NVBX_* environment variables again for this mapper (they are read at creation and kept per mapper).
-        Held-back work is carried out first, under the old settings.  NVBX_MAX_BLOCKS, NVBX_COLOR_DEFERRAL, NVBX_SIDE_STREAM and NVBX_DEFER_EDT
+        Held-back work is carried out first, under the old settings.  NVBX_MAX_BLOCKS, NVBX_COLOR_DEFERRAL and NVBX_DEFER_EDT
         apply at creation only."""
         self._check(self.lib.nvbx_mapper_reload_knobs(self._h))
 

@@ -4,8 +4,6 @@ import ctypes as C
 import json
 import os
 import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
@@ -280,35 +278,6 @@ def test_device_helpers_are_bit_equal_to_the_library(room2d, room3d, tmp_path, m
         assert torch.equal(g[:, col].contiguous().view(torch.int32), lg.view(torch.int32))
         assert torch.equal(ok[:, col].bool(), lv)
         assert lv.sum() > 1000
-
-
-QUERY_CHILD = textwrap.dedent('''
-    import sys, numpy as np
-    sys.path.insert(0, %(root)r); sys.path.insert(0, %(tests)r)
-    import test_gpu_query as T
-    m = T._room_mapper(1, frames=range(0, 200, 25))
-    pts = T.mixed_points(1 << 16, seed=8)
-    out = {}
-    for name, r in (("tsdf", m.query_tsdf(pts)), ("esdf", m.query_esdf(pts))):
-        for k, x in zip("dgv", r):
-            out[name + k] = x.cpu().numpy()
-    np.savez(sys.argv[1], **out)
-''')
-
-
-@pytest.mark.gpu
-def test_dedup_switch_changes_no_output_bit(hip_lib, tmp_path):
-    res = []
-    for val in ("1", "0"):
-        env = dict(os.environ, NVBX_QUERY_DEDUP=val)
-        f = str(tmp_path / ("q%s.npz" % val))
-        r = subprocess.run([sys.executable, "-c", QUERY_CHILD % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}, f], env=env,
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-        res.append(np.load(f))
-    for k in res[0].files:
-        assert res[0][k].tobytes() == res[1][k].tobytes(), k
-    assert res[0]["tsdfv"].sum() > 1000 and res[0]["esdfv"].sum() > 1000
 
 
 FACADE_SRC = r'''

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "isaac_ros_nvblox_amd", "csrc")
 
 FUNCS = ("integ_grid", "color_grid", "edt_riders", "pair_b_edt_riders", "mark_riders", "mark_tiles_first", "decay_grid", "st_lanes",
-         "fused_trace_lanes", "lidar_sparse_grid", "color_deferral", "switch", "opt_in", "score_chunks", "view_grid_reach", "view_grid_max_mb",
+         "fused_trace_lanes", "lidar_sparse_grid", "color_deferral", "switch", "score_chunks", "view_grid_reach", "view_grid_max_mb",
          "max_blocks", "frame_pool_max")
 
 # the fields of struct nvbx_knobs: (field, the variable that reaches it, what all-unset gives, a value to set, what the field then holds)
@@ -22,7 +22,6 @@ FIELDS = (
     ("fuse_colc", "NVBX_FUSE_COLC", 1, "0", 0), ("depth_pair", "NVBX_DEPTH_PAIR", 1, "0", 0), ("lidar_sparse", "NVBX_LIDAR_SPARSE", 1, "0", 0),
     ("lidar_dense_list", "NVBX_LIDAR_DENSE_LIST", 1, "0", 0), ("lidar_view_grid", "NVBX_LIDAR_VIEW_GRID", 1, "0", 0),
     ("defer_edt", "NVBX_DEFER_EDT", 1, "0", 0), ("replay_pair", "NVBX_REPLAY_PAIR", 1, "0", 0), ("esdf_only_carry", "NVBX_ESDF_ONLY_CARRY", 1, "0", 0),
-    ("side_stream", "NVBX_SIDE_STREAM", 0, "1", 1), ("query_dedup", "NVBX_QUERY_DEDUP", 0, "1", 1),
     ("color_deferral", "NVBX_COLOR_DEFERRAL", -1, "1", 1), ("mark_tiles_first", "NVBX_MARK_TILES_FIRST", -1, "0", 0),
     ("integ_grid", "NVBX_INTEG_GRID", 0, "13", 13), ("color_grid", "NVBX_COLOR_GRID", 1024, "9", 9), ("decay_grid", "NVBX_DECAY_GRID", 4096, "3", 3),
     ("lidar_sparse_grid", "NVBX_LIDAR_SPARSE_GRID", 2048, "17", 17), ("grid_margin_pct", "NVBX_GRID_MARGIN", 25, "50", 50),
@@ -92,7 +91,6 @@ CASES = {
     "grid_margin": {None: (25, 64), "0,0": (0, 0), "10": (10, 64), "50,8": (50, 8), "-5,-1": (25, 64), "50,abc": (50, 64), ",7": (25, 7),
                     "0": (0, 64), "x,0": (25, 0), "10001,0": (25, 0), "1" * 40 + ",3": (25, 3)},
     # NVBX_LIDAR_VIEW_GRID, NVBX_REPLAY_PAIR, NVBX_ESDF_ONLY_CARRY: "switch" above ("abc" was off under atoi: now the default, on)
-    "opt_in": {None: 0, "0": 0, "1": 1, "2": 0, "-1": 0, "": 0, "1x": 0, "on": 0, "11": 0},      # NVBX_QUERY_DEDUP, NVBX_SIDE_STREAM ("1x" was on)
     "score_chunks": {None: 0, "1": 1, "64": 64, "1024": 1024, "0": 0, "1025": 0, "-1": 0, "x": 0},
     "view_grid_reach": {None: 0, "1": 1, "12": 12, "1048576": 1048576, "0": 0, "-4": 0, "1048577": 0, "3 ": 0, "far": 0},
     "view_grid_max_mb": {None: 128, "1": 1, "64": 64, "1048576": 1048576, "0": 128, "-1": 128, "1048577": 128, "64MB": 128, "": 128},

@@ -2,7 +2,7 @@
 2.18) on the bench's room map, beside the composition a caller builds from the calls the library already had.
 
 The room map of the 640x480 loop (every second pose of the 200, depth only: the calls read TSDF voxels) is built once.  Reported:
-  - us per launch of the scan (k_find_frontiers; k_frontier_classes too in the -DNVBX_FRONTIER_TWO_PASS variant, selected with NVBX_LIB) by the
+  - us per launch of the scan (k_find_frontiers) by the
     library's own per-launch event spans (set_profiling), the least bytes the scan has to move -- every TSDF block read once, the six facing
     faces (3 KiB) of every block that holds a free voxel, 4 KiB + 12 B written per entry -- and that over the span as a share of the 8 TB/s HBM peak;
   - ms of find_frontiers, frontier_clusters and view_gain (64 poses, subsampling 4) by a host clock around the call + synchronize, into
@@ -147,7 +147,7 @@ def main():
     n_free_blocks = int(has_free.sum())
     least = n_tsdf * 4096 + n_free_blocks * 6 * 64 * 8 + n_entries * (4096 + 12)
     span_us = round(sum(spans.values()), 2)
-    emit({"case": "frontier_scan_room_640x480", "form": "two_pass" if any("classes" in k for k in spans) else "single_pass", "tsdf_blocks": n_tsdf,
+    emit({"case": "frontier_scan_room_640x480", "form": "single_pass", "tsdf_blocks": n_tsdf,
           "blocks_with_a_free_voxel": n_free_blocks, "frontier_blocks": n_entries, "frontier_voxels": n_voxels, "span_us": spans, "scan_span_us": span_us,
           "least_bytes": least, "share_of_hbm_peak": round(least / HBM_PEAK / (span_us * 1e-6), 4) if span_us else None,
           "call_ms_mean_min_max": call, "composition_frontier_voxels": n_found, "calls": a.calls})

@@ -1,19 +1,17 @@
 """Throughput of the interpolated point queries (nvbx_query_points).
 
 The room map of the 640x480 200-pose loop (synthetic.sequence) is built once, for a 3-D ESDF mapper and a default 2-D one, and saved;
-then child processes -- one per setting of NVBX_QUERY_DEDUP (read when the child's mappers are created), alternating, each under its own time limit --
-load the maps and time the queries with device events over >= --seconds of back-to-back calls after warm-up:
+the maps are then loaded and the queries timed with device events over >= --seconds of back-to-back calls after warm-up:
   layers: TSDF (3-D mapper), ESDF 3-D, ESDF 2-D;  distributions: coherent (4 096 clusters of points in 0.5 m boxes in the observed
   free space, cluster after cluster) and uniform (over the map's block AABB);  n = 2^20 and 2^24.
 One JSON object per case: queries/s, us per call, the algorithmic bytes (12 B in + 17 B out per point + the distinct 8-B corner voxels
 of allocated blocks + 16 B per hash probe, one probe per distinct corner block of a point) and their share of 8 TB/s, and the share of
 points whose corners lie in 1 / 2 / 4 / 8 blocks.
-Usage: python tools/query_bench.py [--n 20 24] [--reps 1] [--out FILE] [--maps DIR]
-(a kernel trace of the shipped path: rocprofv3 --kernel-trace --stats -- python tools/query_bench.py --child DIR --n 20, DIR from --maps)"""
+Usage: python tools/query_bench.py [--n 20 24] [--out FILE] [--maps DIR]
+(a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/query_bench.py --maps DIR --n 20, DIR holding the maps of an earlier run)"""
 import argparse
 import json
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -86,7 +84,8 @@ def algorithmic(p, m, plane, torch):
     return len(p) * (12 + 17) + 8 * n_vox + 16 * probes, share
 
 
-def child(d, ns, seconds):
+def measure(d, ns, seconds):
+    lines = []
     import torch
     from isaac_ros_nvblox_amd import mapper as M
     ms = {}
@@ -94,7 +93,6 @@ def child(d, ns, seconds):
         m = M.Mapper(M.default_params(esdf_mode=mode)); m.load_map(os.path.join(d, name + ".nvbx")); m.update_esdf(); m.synchronize()
         ms[name] = m
     centres = np.load(os.path.join(d, "centres.npy"))
-    dedup = os.environ.get("NVBX_QUERY_DEDUP", "0")
     plane2 = int(np.floor(np.float32(ms["2d"].params.esdf_slice_height) / np.float32(VS)))
     for logn in ns:
         n = 1 << logn
@@ -116,40 +114,26 @@ def child(d, ns, seconds):
                 e1.record(); torch.cuda.synchronize()
                 us = e0.elapsed_time(e1) * 1e3 / calls
                 nbytes, share = algorithmic(p, m, plane, torch)
-                print(json.dumps({"case": case, "dist": kind, "n": n, "dedup": int(dedup), "calls": calls, "us_per_call": round(us, 2),
-                                  "queries_per_s": round(n / us * 1e6), "valid": round(float(v_.float().mean()), 4),
-                                  "alg_bytes": nbytes, "alg_frac_8TBs": round(nbytes / (us * 1e-6) / HBM_BPS, 4),
-                                  "corner_blocks_share": share}), flush=True)
+                lines.append(json.dumps({"case": case, "dist": kind, "n": n, "calls": calls, "us_per_call": round(us, 2),
+                                         "queries_per_s": round(n / us * 1e6), "valid": round(float(v_.float().mean()), 4),
+                                         "alg_bytes": nbytes, "alg_frac_8TBs": round(nbytes / (us * 1e-6) / HBM_BPS, 4),
+                                         "corner_blocks_share": share}))
+                print(lines[-1], flush=True)
+    return lines
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[20, 24], help="log2 of the point counts")
-    ap.add_argument("--reps", type=int, default=1, help="alternations of the two paths")
     ap.add_argument("--seconds", type=float, default=1.0)
-    ap.add_argument("--timeout", type=int, default=600)
     ap.add_argument("--out", default=None)
     ap.add_argument("--maps", default=None, help="directory for the saved maps (kept; built only if missing)")
-    ap.add_argument("--child", default=None, help="(internal) time one setting on the maps in this directory")
     a = ap.parse_args()
-    if a.child:
-        child(a.child, a.n, a.seconds)
-        return
     d = a.maps or tempfile.mkdtemp(prefix="query_bench_")
     os.makedirs(d, exist_ok=True)
     if not os.path.exists(os.path.join(d, "centres.npy")):
         build_maps(d)
-    lines = []
-    for _ in range(a.reps):
-        for dedup in ("1", "0"):
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", d, "--seconds", str(a.seconds), "--n"] + [str(x) for x in a.n],
-                               env=dict(os.environ, NVBX_QUERY_DEDUP=dedup), capture_output=True, text=True, timeout=a.timeout)
-            if r.returncode != 0:
-                sys.stderr.write(r.stderr[-3000:])
-                sys.exit("query_bench: child with NVBX_QUERY_DEDUP=%s failed (%d)" % (dedup, r.returncode))
-            for line in r.stdout.splitlines():
-                if line.startswith("{"):
-                    print(line, flush=True); lines.append(line)
+    lines = measure(d, a.n, a.seconds)
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")

@@ -997,6 +997,28 @@ void nvbx_default_merge_options(nvbx_merge_options* options);
 /* T_D_S: row-major 4 x 4, host memory.  options NULL: the defaults.  result_dev: written by the last launch, not waited for. */
 int nvbx_merge_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S[16], const nvbx_merge_options* options, nvbx_merge_result* result_dev);
 
+/* ---- resampling ([U] a map brought into a mapper of a coarser voxel size; SEMANTICS.md "Resampling") ----------------------------------
+ * nvbx_merge_map with two voxel sizes: reads `src` at its voxel size vs_s and writes `dst` at vs_d, r = (double)vs_d / (double)vs_s in
+ * [1, 4], under p_D = T_D_S p_S.  Every voxel of every candidate block of dst takes n x n x n sub-samples (taps) on a lattice symmetric
+ * about its centre, offsets ((float)i + 0.5f) / n - 0.5f voxels of dst per axis, each sampled from src by the merge's rule (eight corners
+ * with weight >= min_weight).  With c valid taps the voxel fuses iff 2 c >= n^3: the sample distance is the mean over the valid taps, the
+ * sample weight the sum of their weights over n^3 (a half-seen voxel gets half the weight) times weight_scale, fused, clamped and flagged as
+ * by the merge.  With merge_color the source colour voxel nearest to the voxel's CENTRE is blended in; colour bytes are never averaged.
+ * taps: n, 1 .. 4; 0 = min(4, ceil(r)).  With vs_d == vs_s and taps 1 the map and the result record are the merge's, bit for bit.
+ * The result record is nvbx_merge_result with the merge's status values.  Ordering, the two host waits, growth and NVBX_E_CAPACITY (dst
+ * unchanged) are the merge's, and so are its refusals (NVBX_E_INVALID, dst unchanged) but the one on voxel sizes: refused are r < 1
+ * (upsampling), r > 4 and taps outside 0 .. 4.  T_D_S NULL: the identity.  Feature voxels, ESDF, occupancy and freespace are not resampled. */
+typedef struct {
+  float   min_weight;           /* a source corner counts with weight >= this */
+  float   weight_scale;         /* the sample weight is multiplied by this; finite, > 0 */
+  int32_t merge_color;          /* != 0: colour is brought over too */
+  int32_t taps;                 /* sub-samples per axis, 1 .. 4; 0 = min(4, ceil(r)) */
+} nvbx_resample_options;        /* 16 bytes; offsets 0 4 8 12 */
+/* defaults: min_weight 1e-4, weight_scale 1, merge_color 1, taps 0 */
+void nvbx_default_resample_options(nvbx_resample_options* options);
+/* T_D_S: row-major 4 x 4, host memory, or NULL.  options NULL: the defaults.  result_dev: written by the last launch, not waited for. */
+int nvbx_resample_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S[16], const nvbx_resample_options* options, nvbx_merge_result* result_dev);
+
 /* ---- change detection ([U] what differs between two maps; SEMANTICS.md "Change detection") --------------------------------------------
  * Compares mapper `m` ("now") with a reference mapper `ref` ("before") under p_M = T_M_R p_R.  A voxel of a TSDF block of m with stored
  * {d, w}, inside box_min_max_vox (inclusive, global voxel coordinates of m as in nvbx_find_frontiers; NULL: unbounded), is OBSERVED iff

@@ -180,6 +180,11 @@ class MergeResult(C.Structure):
                 ("color_voxels_fused", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32 * 5)]
 
 
+class ResampleOptions(C.Structure):
+    """nvbx_resample_options (16 bytes); nvbx_default_resample_options fills it"""
+    _fields_ = [("min_weight", C.c_float), ("weight_scale", C.c_float), ("merge_color", C.c_int32), ("taps", C.c_int32)]
+
+
 class ChangeOptions(C.Structure):
     """nvbx_change_options (24 bytes); nvbx_default_change_options fills it"""
     _fields_ = [("min_weight", C.c_float), ("ref_min_weight", C.c_float), ("free_distance_m", C.c_float), ("occupied_distance_m", C.c_float),
@@ -306,6 +311,8 @@ SIGNATURES = {
                                         C.POINTER(AlignOptions), _vp, _vp]),
     "nvbx_default_merge_options": (None, [C.POINTER(MergeOptions)]),
     "nvbx_merge_map": (C.c_int, [_vp, _vp, _vp, C.POINTER(MergeOptions), _vp]),
+    "nvbx_default_resample_options": (None, [C.POINTER(ResampleOptions)]),
+    "nvbx_resample_map": (C.c_int, [_vp, _vp, _vp, C.POINTER(ResampleOptions), _vp]),
     "nvbx_default_change_options": (None, [C.POINTER(ChangeOptions)]),
     "nvbx_find_changes": (C.c_int, [_vp, _vp, _vp, C.POINTER(ChangeOptions), _pi32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "nvbx_change_clusters": (C.c_int, [_vp, _vp, _vp, C.POINTER(ChangeOptions), _pi32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),

@@ -210,7 +210,7 @@ static const char* params_problem(const nvbx_mapper_params* p) {
 
 // ------------------------------------------------------------------------------------------------ C-ABI: lifetime
 // THE read of the mapper's NVBX_* environment variables, all through nvbx_knobs.h (the frame pool's own is process-wide: frames.hip)
-static void read_knobs(nvbx_mapper* m) { const auto env = [](const char* name) -> const char* { return getenv(name); }; nvbx_knobs_read(&m->knobs, env); nvbx_plan_knobs_read(&m->plan_knobs, env); nvbx_change_knobs_read(&m->change_knobs, env); }
+static void read_knobs(nvbx_mapper* m) { const auto env = [](const char* name) -> const char* { return getenv(name); }; nvbx_knobs_read(&m->knobs, env); nvbx_plan_knobs_read(&m->plan_knobs, env); nvbx_change_knobs_read(&m->change_knobs, env); nvbx_resample_knobs_read(&m->resample_knobs, env); }
 extern "C" int nvbx_mapper_reload_knobs(nvbx_mapper* m) {
   if (!m) return NVBX_E_INVALID;
   NVBX_HIP(hipSetDevice(m->device));

@@ -3,7 +3,8 @@
  * unset) and returns what the library uses.  A missing, malformed or out-of-range value gives the default, so no setting can size a launch at zero
  * or drop work; rider counts are rounded up to a multiple of 8.  No knob changes a result, only which workgroup does what.
  * struct nvbx_knobs holds one mapper's settings; nvbx_knobs_read fills it, and names every variable there and nowhere else.  The cost field's two
- * knobs have a struct and a read of their own in front of it (nvbx_plan_knobs), and so has change detection's one (nvbx_change_knobs). */
+ * knobs have a struct and a read of their own in front of it (nvbx_plan_knobs), and so have change detection's one (nvbx_change_knobs) and
+ * resampling's one (nvbx_resample_knobs). */
 #ifndef NVBX_KNOBS_H_
 #define NVBX_KNOBS_H_
 #include <errno.h>
@@ -100,6 +101,14 @@ static inline int nvbx_knob_change_grid(const char* s) { return nvbx_knob_int(s,
 struct nvbx_change_knobs { int grid; };
 static inline void nvbx_change_knobs_read(struct nvbx_change_knobs* k, const char* (*lookup)(const char* name)) {
   k->grid = nvbx_knob_change_grid(lookup("NVBX_CHANGE_GRID"));
+}
+
+/* Resampling's knob (resample.hip), likewise: NVBX_RESAMPLE_GRID caps k_resample_fuse's workgroups (the default is the cap
+ * k_merge_fuse has built in).  No result depends on it. */
+static inline int nvbx_knob_resample_grid(const char* s) { return nvbx_knob_int(s, 2048, 1, NVBX_KNOB_GRID_MAX); }
+struct nvbx_resample_knobs { int grid; };
+static inline void nvbx_resample_knobs_read(struct nvbx_resample_knobs* k, const char* (*lookup)(const char* name)) {
+  k->grid = nvbx_knob_resample_grid(lookup("NVBX_RESAMPLE_GRID"));
 }
 
 /* One mapper's knobs: filled at nvbx_mapper_create and again by nvbx_mapper_reload_knobs.  Three of them shape the mapper at creation and are

@@ -109,6 +109,7 @@ struct nvbx_mapper {
   nvbx_knobs knobs{};
   nvbx_plan_knobs plan_knobs{}; // ... and the cost field's two (plan.hip), read with them
   nvbx_change_knobs change_knobs{}; // ... and change detection's one (change.hip)
+  nvbx_resample_knobs resample_knobs{}; // ... and resampling's one (resample.hip)
   int begin_call(bool carry_out_held = true);      // first call of every entry point (held.hip): the device is made current, held-back work is carried out (no host sync)
   nvbx_mapper_params p{};
   int64_t capacity = 0;
@@ -150,7 +151,7 @@ struct nvbx_mapper {
   nvbx::DevBuf align_buf;
   // relocalisation (relocalize.hip): the lattice tables (4 KB) and, where the caller wants no scores, the lattice's 24-byte records; the tables' host copy
   nvbx::DevBuf reloc_buf; std::vector<float> reloc_host;
-  // map merging (merge.hip), as the destination: a 64-byte head of counters and the key set that counts the distinct candidate blocks
+  // map merging and resampling (merge.hip, resample.hip), as the destination: a 64-byte head of counters and the key set that counts the distinct candidate blocks
   nvbx::DevBuf merge_buf;
   // change detection (change.hip), as the map that is scanned: 64 bytes of counters, allocated with the map
   nvbx::DevBuf change_buf;

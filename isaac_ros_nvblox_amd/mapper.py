@@ -332,6 +332,7 @@ class Mapper:
         s = C.c_void_p(stream) if stream else None
         self._check(self.lib.nvbx_mapper_create(device, s, C.byref(self.params), block_capacity, C.byref(self._h)))
         self._capacity0 = block_capacity
+        self._stream0 = stream          # (coarsened() creates its mapper with the same stream setting)
         self._keep = []
         if max_block_capacity is not None:
             self.set_max_capacity(max_block_capacity)
@@ -1086,6 +1087,37 @@ class Mapper:
         buf = _args.result_buffer(out, MERGE_RESULT_BYTES, self._cuda)
         self._around_torch_stream(lambda: self.lib.nvbx_merge_map(self._h, other._h, _np_ptr(T), C.byref(o), ptr(buf)))
         return MergeResult(buf)
+
+    # -- resampling (nvbx_resample_map; SEMANTICS.md "Resampling")
+    def resample_options(self, **kw):
+        """nvbx_resample_options: the library's defaults with the given fields replaced (min_weight, weight_scale, merge_color, taps)."""
+        return _args.struct_options(_lib.ResampleOptions, self.lib.nvbx_default_resample_options, kw, "resample")
+
+    def resample_from(self, other, T_D_S=None, out=None, **options):
+        """Bring `other`'s TSDF and colour into this map, whose voxel size is 1 to 4 times `other`'s, under p_D = T_D_S p_S (row-major 4 x 4;
+        None: the identity): -> MergeResult.  Every voxel averages taps x taps x taps sub-samples of `other` and fuses when at least half of
+        them are valid; the rest is merge_from's.  options: see resample_options.  out: as for merge_from."""
+        if not isinstance(other, Mapper):
+            raise TypeError("resample_from needs a Mapper")
+        T = None if T_D_S is None else self._T(T_D_S)
+        o = self.resample_options(**options)
+        buf = _args.result_buffer(out, MERGE_RESULT_BYTES, self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_resample_map(self._h, other._h, None if T is None else _np_ptr(T), C.byref(o), ptr(buf)))
+        return MergeResult(buf)
+
+    def coarsened(self, factor=2.0, block_capacity=None, **options):
+        """-> (Mapper, MergeResult): a new mapper on this one's device and stream setting, with this one's params except voxel_size * factor
+        (1 <= factor <= 4), holding this map resampled under the identity.  block_capacity: the new mapper's (default: this one's initial
+        capacity; it grows on demand).  options: see resample_options."""
+        p = Params.from_buffer_copy(bytes(self.params))
+        p.voxel_size = float(np.float32(self.params.voxel_size) * np.float32(factor))
+        m = Mapper(p, device=self.device, block_capacity=self._capacity0 if block_capacity is None else int(block_capacity), stream=self._stream0)
+        try:
+            res = m.resample_from(self, None, **options)
+        except Exception:
+            m.close()
+            raise
+        return m, res
 
     # -- rendering and ray casts (nvbx_render_view / nvbx_cast_rays; SEMANTICS.md "Rendering and ray casts")
     def render(self, T_L_C, cam, subsampling=None, max_ray_length_m=None, color=True, normals=False, out=None):

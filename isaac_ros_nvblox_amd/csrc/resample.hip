@@ -1,15 +1,10 @@
 // resample.hip -- one mapper's TSDF and colour brought into a mapper of a coarser (or the same) voxel size under a rigid transform
 // (nvbx_resample_map; SEMANTICS.md "Resampling").  [U] nothing of the kind is readable in the reference tree.  The merge's
-// rule (merge.hip) with two voxel sizes and n^3 sub-samples per destination voxel; the count, index and result launches are the merge's,
-// kept here as copies -- lifted into a shared header they would have to leave merge.hip's kernels their registers (DESIGN.md 2.25 on the
-// same choice for change.hip).
+// rule (merge.hip) with two voxel sizes and n^3 sub-samples per destination voxel.
 //
-// Launches, all on dst's stream, src read-only throughout:
-//   k_resample_count   one thread per (source slot, candidate 0 .. 26): the candidate box of the slot's block (nvbx_resample_math.h) and, for
-//                      every candidate dst lacks, an insert into a scratch key set -- the distinct ones are counted.  Nothing of dst is
-//                      written: the host waits for the counts, grows dst's pools if it must, or refuses (NVBX_E_CAPACITY), dst untouched.
-//   k_resample_index   the same enumeration with mark_block on dst: missing blocks are allocated, every candidate is stamped with the call's
-//                      frame id and appended to dst's view list exactly once -- the work list of the next launch.
+// Launches, all on dst's stream, src read-only throughout.  The candidate enumeration (k_transfer_count<ResampleBox>,
+// k_transfer_index<ResampleBox>), the result record (k_transfer_result) and the host sequence around them are nvbx_map_transfer.h's, shared
+// with merge.hip; this file has the candidate box (ResampleBox: nvbx_resample_math.h), the call's own refusals and
 //   k_resample_fuse    one 512-thread workgroup per candidate block, lane = voxel z + 8y + 64x.  The taps of the block reach at most
 //                      N x N x N source blocks (N = nvbx_resample_reach <= 8, from the host): the eight corner lanes give the lowest block
 //                      index per axis (the sample position is monotone in every destination coordinate), N^3 lanes probe src's table once
@@ -17,13 +12,11 @@
 //                      z pair inside one block is one 16-B load -- sums distance and weight over the valid ones, fuses when at least half
 //                      are valid, blends the colour voxel nearest to its centre and writes its own voxel.  No lane probes the hash in
 //                      the loop, no two lanes write one voxel, the result does not depend on scheduling.
-//   k_resample_result  one thread: the caller's result record from the counters the launches left.
-#include "nvbx_view.h"
+#include "nvbx_map_transfer.h"
 #include "nvbx_query_point.h"
 #include "nvbx_resample_math.h"
 
 struct ResampleArgs {
-  float R_DS[9], t_DS[3];       // p_D = R_DS p_S + t_DS: the candidate boxes
   float R_SD[9], t_SD[3];       // p_S = R_SD p_D + t_SD: the samples
   float vs_s, vs_d, min_weight, weight_scale, trunc, max_weight;
   float off0, off1, off2, off3; // tap offsets (nvbx_resample_tap_offset), in destination voxels
@@ -31,66 +24,15 @@ struct ResampleArgs {
   int32_t merge_color, mesh_list;
   uint32_t frame_id;
 };
-// head of nvbx_mapper::merge_buf (zeroed per call); the key set follows at RESAMPLE_KEYS_OFFSET
-struct ResampleScratch { int32_t src_blocks, need_slots, need_tsdf, dst_free; unsigned long long voxels, colors; };
-constexpr size_t RESAMPLE_KEYS_OFFSET = 64;
-static_assert(sizeof(ResampleScratch) <= RESAMPLE_KEYS_OFFSET, "scratch head");
-static_assert(sizeof(nvbx_merge_result) == 64 && sizeof(nvbx_resample_options) == 16, "C-ABI layout");
+// the candidate box of source block si (nvbx_map_transfer.h)
+struct ResampleBox {
+  float R_DS[9], t_DS[3];       // p_D = R_DS p_S + t_DS
+  float vs_s, vs_d;
+  int32_t taps;
+  __device__ bool operator()(const int32_t si[3], int32_t lo[3], int32_t hi[3]) const { return nvbx_resample_candidate_box(R_DS, t_DS, si, vs_s, vs_d, taps, lo, hi); }
+};
+static_assert(sizeof(nvbx_resample_options) == 16, "C-ABI layout");
 
-// candidate c (0 .. 26) of source slot s: false if the slot holds no TSDF block or the box has no such block
-__device__ inline bool resample_candidate(const DMap& src, const ResampleArgs& a, int32_t s, int c, int32_t* x, int32_t* y, int32_t* z) {
-  if (!(src.slot_flags[s] & F_TSDF)) return false;
-  const int32_t si[3] = {src.slot_index[3 * s], src.slot_index[3 * s + 1], src.slot_index[3 * s + 2]};
-  int32_t lo[3], hi[3];
-  if (!nvbx_resample_candidate_box(a.R_DS, a.t_DS, si, a.vs_s, a.vs_d, a.taps, lo, hi)) return false;
-  *x = lo[0] + c % 3; *y = lo[1] + (c / 3) % 3; *z = lo[2] + c / 9;
-  return *x <= hi[0] && *y <= hi[1] && *z <= hi[2];
-}
-
-__global__ void k_resample_count(DMap dst, DMap src, ResampleArgs a, ResampleScratch* sc, u64* keys, uint32_t kmask) {
-  const int64_t n = (int64_t)src.counters[C_HIGH_WATER] * 27;
-  if (blockIdx.x == 0 && threadIdx.x == 0) sc->dst_free = dst.counters[C_FREE_TOP];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t s = (int32_t)(i / 27); const int c = (int)(i - (int64_t)s * 27);
-    if (c == 0 && (src.slot_flags[s] & F_TSDF)) atomicAdd(&sc->src_blocks, 1);
-    int32_t x, y, z;
-    if (!resample_candidate(src, a, s, c, &x, &y, &z)) continue;
-    // what dst has: an entry with a slot (a block of any layer shares it), and whether that slot carries a TSDF block
-    const u64 key = pack_key(x, y, z);
-    bool has_slot = false, has_tsdf = false;
-    uint32_t h = table_pos(dst, x, y, z);
-    for (uint32_t probe = 0; probe <= dst.mask; ++probe) {
-      const uint4 e = ld_entry(dst, h);
-      const u64 k = ((u64)e.y << 32) | (u64)e.x;
-      if (k == key) { has_slot = true; has_tsdf = slot_ok(e.z) && (dst.slot_flags[e.z] & F_TSDF); break; }
-      if (k == KEY_EMPTY) break;
-      h = (h + 1) & dst.mask;
-    }
-    if (has_tsdf) continue;
-    uint32_t kh = (index_hash(x, y, z) * 2654435761u) & kmask;
-    for (uint32_t probe = 0; probe <= kmask; ++probe) {
-      const u64 old = atomicCAS(&keys[kh], KEY_EMPTY, key);
-      if (old == KEY_EMPTY) { atomicAdd(&sc->need_tsdf, 1); if (!has_slot) atomicAdd(&sc->need_slots, 1); break; }
-      if (old == key) break;
-      kh = (kh + 1) & kmask;
-    }
-  }
-}
-
-__global__ void k_resample_index(DMap dst, DMap src, ResampleArgs a, int4* view_list, int32_t list_cap) {
-  int32_t* cnt = &dst.counters[C_VIEW_COUNT + (a.frame_id & 3)];
-  if (blockIdx.x == 0 && threadIdx.x == 0) dst.counters[C_VIEW_COUNT + ((a.frame_id + 1) & 3)] = 0;
-  const int64_t n = (int64_t)src.counters[C_HIGH_WATER] * 27;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t s = (int32_t)(i / 27); const int c = (int)(i - (int64_t)s * 27);
-    int32_t x, y, z;
-    if (!resample_candidate(src, a, s, c, &x, &y, &z)) continue;
-    int4 rec;
-    if (!mark_block(dst, pack_key(x, y, z), a.frame_id, 1u, &rec)) continue;      // (stamped already: another source block's candidate too)
-    const int32_t p = atomicAdd(cnt, 1);
-    if (p < list_cap) view_list[p] = rec;
-  }
-}
 
 __device__ inline float resample_tap_off(const ResampleArgs& a, int i) { return i == 0 ? a.off0 : i == 1 ? a.off1 : i == 2 ? a.off2 : a.off3; }
 
@@ -136,7 +78,7 @@ __device__ inline bool resample_tap(const uint2* spool, const uint32_t* s_slot, 
   return all;
 }
 
-__global__ __launch_bounds__(512) void k_resample_fuse(DMap dst, DMap src, ResampleArgs a, const int4* view_list, int32_t list_cap, ResampleScratch* sc) {
+__global__ __launch_bounds__(512) void k_resample_fuse(DMap dst, DMap src, ResampleArgs a, const int4* view_list, int32_t list_cap, TransferScratch* sc) {
   __shared__ uint32_t s_slot[512];
   __shared__ unsigned char s_color[512];
   __shared__ int32_t s_min[3];
@@ -255,20 +197,6 @@ __global__ __launch_bounds__(512) void k_resample_fuse(DMap dst, DMap src, Resam
   if (tid == 0) { if (s_cnt[0]) atomicAdd(&sc->voxels, (unsigned long long)s_cnt[0]); if (s_cnt[1]) atomicAdd(&sc->colors, (unsigned long long)s_cnt[1]); }
 }
 
-// empty != 0: nothing was enumerated (src has no TSDF block)
-__global__ void k_resample_result(DMap dst, uint32_t frame_id, const ResampleScratch* sc, int64_t src_blocks, int64_t allocated, int32_t empty, nvbx_merge_result* out) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  nvbx_merge_result r;
-  r.source_blocks = src_blocks;
-  r.candidate_blocks = empty ? 0 : (int64_t)dst.counters[C_VIEW_COUNT + (frame_id & 3)];
-  r.blocks_allocated = allocated;
-  r.voxels_fused = empty ? 0 : (int64_t)sc->voxels;
-  r.color_voxels_fused = empty ? 0 : (int64_t)sc->colors;
-  r.status = empty ? NVBX_MERGE_EMPTY_SOURCE : (r.voxels_fused == 0 ? NVBX_MERGE_NO_OVERLAP : NVBX_MERGE_OK);
-  for (int k = 0; k < 5; k++) r.pad[k] = 0;
-  *out = r;
-}
-
 static const char* const RESAMPLE_WHO = "nvbx_resample_map";
 static const float RESAMPLE_IDENTITY[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
@@ -278,86 +206,27 @@ extern "C" void nvbx_default_resample_options(nvbx_resample_options* o) {
 }
 
 extern "C" int nvbx_resample_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S[16], const nvbx_resample_options* options, nvbx_merge_result* result_dev) {
-  if (!dst || !src) return refuse(RESAMPLE_WHO, ": both mappers are required");
+  if (const int rc = transfer_pointers_refused(RESAMPLE_WHO, dst, src, !result_dev ? ": result_dev is required" : nullptr, result_dev)) return rc;
   nvbx_resample_options o;
   if (options) o = *options; else nvbx_default_resample_options(&o);
   if (!T_D_S) T_D_S = RESAMPLE_IDENTITY;
-  if (!result_dev) return refuse(RESAMPLE_WHO, ": result_dev is required");
-  if ((uintptr_t)result_dev & 7) return refuse(RESAMPLE_WHO, ": result_dev must be 8-byte aligned");
-  if (src == dst) return refuse(RESAMPLE_WHO, ": src and dst are the same mapper");
-  if (src->device != dst->device) return refuse(RESAMPLE_WHO, ": the mappers are on different devices");
   double r = 0.0;
   if (!nvbx_resample_ratio(dst->p.voxel_size, src->p.voxel_size, &r)) return refuse(RESAMPLE_WHO, ": dst's voxel size must be 1 to 4 times src's (upsampling and ratios above 4 are not supported)");
   const int taps = nvbx_resample_taps(r, o.taps);
   if (!taps) return refuse(RESAMPLE_WHO, ": taps must be 0 (by the ratio) or 1 .. 4");
-  if (src->p.projective_layer_type != 0 || dst->p.projective_layer_type != 0) return refuse(RESAMPLE_WHO, ": both mappers must be TSDF mappers without a freespace layer (projective_layer_type 0)");
-  if (!nvbx_pose_in_range(T_D_S, src->p.voxel_size * 8.0f, 0.0f)) return refuse(RESAMPLE_WHO, ": the pose is not finite or out of range");
-  if (!nvbx_merge_rotation_ok(T_D_S, nullptr, nullptr)) return refuse(RESAMPLE_WHO, ": the upper-left 3 x 3 of T_D_S is not a rotation (|R^T R - I| > 1e-5 or det <= 0)");
-  if (o.min_weight != o.min_weight) return refuse(RESAMPLE_WHO, ": min_weight is not a number");
-  if (!std::isfinite(o.weight_scale) || !(o.weight_scale > 0.0f)) return refuse(RESAMPLE_WHO, ": weight_scale must be finite and > 0");
-  NVBX_HIP(hipSetDevice(dst->device));
-  // src: held-back work is carried out; its block count sizes the key set (waits for src's stream)
-  if (src->fetch_counters()) return NVBX_E_DEVICE;
-  const int64_t src_hw = src->h_counters[C_HIGH_WATER];
-  const int64_t src_live = std::max<int64_t>(1, (int64_t)src->capacity - (int64_t)src->h_counters[C_FREE_TOP]);
-  if (dst->begin_call()) return NVBX_E_DEVICE;
-  { const int rc = nvbx_mapper_wait_for(dst, src); if (rc) return rc; }
+  if (const int rc = transfer_values_refused(RESAMPLE_WHO, dst, src, T_D_S, src->p.voxel_size * 8.0f, o.min_weight, o.weight_scale)) return rc;
   ResampleArgs a{};
-  nvbx_merge_transforms(T_D_S, a.R_DS, a.t_DS, a.R_SD, a.t_SD);
-  a.vs_s = src->p.voxel_size; a.vs_d = dst->p.voxel_size; a.min_weight = o.min_weight; a.weight_scale = o.weight_scale;
+  ResampleBox box{};
+  nvbx_merge_transforms(T_D_S, box.R_DS, box.t_DS, a.R_SD, a.t_SD);
+  box.vs_s = a.vs_s = src->p.voxel_size; box.vs_d = a.vs_d = dst->p.voxel_size; a.min_weight = o.min_weight; a.weight_scale = o.weight_scale;
   a.trunc = dst->p.truncation_distance_vox * dst->p.voxel_size; a.max_weight = dst->p.max_weight;
   a.merge_color = o.merge_color ? 1 : 0;
-  a.taps = taps; a.reach = nvbx_resample_reach(r, taps);
+  box.taps = a.taps = taps; a.reach = nvbx_resample_reach(r, taps);
   a.off0 = nvbx_resample_tap_offset(0, taps); a.off1 = nvbx_resample_tap_offset(taps > 1 ? 1 : 0, taps);
   a.off2 = nvbx_resample_tap_offset(taps > 2 ? 2 : 0, taps); a.off3 = nvbx_resample_tap_offset(taps > 3 ? 3 : 0, taps);
   if (a.reach < 1 || a.reach > 8) return refuse(RESAMPLE_WHO, ": the reach of a destination block exceeds 8 source blocks per axis");      // (cannot be: r <= 4)
-  // the key set: distinct candidates are at most 27 per source block; load <= 1/2
-  uint64_t entries = 64; while (entries < (uint64_t)src_live * 54) entries <<= 1;
-  if (entries > (1ull << 31)) return refuse(RESAMPLE_WHO, ": the source map is too large to enumerate");
-  if (dst->merge_buf.ensure(dst->stream, RESAMPLE_KEYS_OFFSET + (size_t)entries * 8)) return NVBX_E_DEVICE;
-  ResampleScratch* sc = dst->merge_buf.as<ResampleScratch>();
-  u64* keys = reinterpret_cast<u64*>(dst->merge_buf.as<unsigned char>() + RESAMPLE_KEYS_OFFSET);
-  NVBX_HIP(hipMemsetAsync(sc, 0, RESAMPLE_KEYS_OFFSET, dst->stream));
-  ResampleScratch h{};
-  const unsigned enum_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((src_hw * 27 + 255) / 256, 2048));
-  if (src_hw > 0) {
-    NVBX_HIP(hipMemsetAsync(keys, 0xFF, (size_t)entries * 8, dst->stream));
-    NVBX_LAUNCH(dst, k_resample_count, dim3(enum_grid), dim3(256), dst->d, src->d, a, sc, keys, (uint32_t)(entries - 1));
-    NVBX_HIP(hipGetLastError());
-    NVBX_HIP(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, dst->stream));
-    NVBX_HIP(hipStreamSynchronize(dst->stream));                    // the one wait between enumerating and allocating
-  }
-  if (h.src_blocks == 0) {
-    NVBX_LAUNCH(dst, k_resample_result, dim3(1), dim3(64), dst->d, 0u, (const ResampleScratch*)sc, (int64_t)0, (int64_t)0, 1, result_dev);
-    NVBX_HIP(hipGetLastError());
-    return nvbx_mapper_wait_for(src, dst);
-  }
-  // room for every candidate dst lacks, or nothing is touched
-  {
-    const int64_t need = h.need_slots, free_now = h.dst_free;
-    if (need > free_now + (dst->max_capacity - dst->capacity)) {
-      set_error("nvbx_resample_map: dst's max_capacity cannot hold the candidate blocks, nothing was resampled");
-      return NVBX_E_CAPACITY;
-    }
-    const int64_t cap_before = dst->capacity;
-    if (dst->capacity < dst->max_capacity) {
-      dst->h_mirror[0] = (int32_t)free_now;
-      const int rc = dst->maybe_grow(need); if (rc) return rc;
-    }
-    if (need > free_now + (dst->capacity - cap_before)) {
-      set_error("nvbx_resample_map: dst's block pools could not grow to hold the candidate blocks, nothing was resampled");
-      return NVBX_E_CAPACITY;
-    }
-  }
-  if (dst->begin_dirtying()) return NVBX_E_DEVICE;
-  { const int rc = next_frame_id(dst); if (rc) return rc; }
-  a.frame_id = dst->frame_id; a.mesh_list = dst->mesh_list_live();
-  NVBX_LAUNCH(dst, k_resample_index, dim3(enum_grid), dim3(256), dst->d, src->d, a, (int4*)dst->view_list, (int32_t)dst->capacity);
-  const unsigned fuse_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(dst->capacity, (int64_t)h.src_blocks * 27), dst->resample_knobs.grid));      // (NVBX_RESAMPLE_GRID)
-  NVBX_LAUNCH(dst, k_resample_fuse, dim3(fuse_grid), dim3(512), dst->d, src->d, a, (const int4*)dst->view_list, (int32_t)dst->capacity, sc);
-  NVBX_LAUNCH(dst, k_resample_result, dim3(1), dim3(64), dst->d, a.frame_id, (const ResampleScratch*)sc, (int64_t)h.src_blocks, (int64_t)h.need_tsdf, 0, result_dev);
-  NVBX_HIP(hipGetLastError());
-  dst->last_view_frame = dst->frame_id; dst->last_view_batch = 1;      // (the view list now holds the candidates; the last CAMERA view stays what it was)
-  { const int rc = nvbx_mapper_wait_for(src, dst); if (rc) return rc; }      // later work on src runs behind the reads
-  return NVBX_OK;
+  return transfer_call(RESAMPLE_WHO, "resampled", dst, src, box, dst->resample_knobs.grid, result_dev, [&](unsigned grid, uint32_t frame_id, int32_t mesh_list, TransferScratch* sc) {      // (NVBX_RESAMPLE_GRID)
+    a.frame_id = frame_id; a.mesh_list = mesh_list;
+    NVBX_LAUNCH(dst, k_resample_fuse, dim3(grid), dim3(512), dst->d, src->d, a, (const int4*)dst->view_list, (int32_t)dst->capacity, sc);
+  });
 }

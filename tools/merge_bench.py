@@ -4,7 +4,8 @@ library already had.
 The room map of the 640x480 loop (every second pose of the 200, depth and colour) is built once in `src`.  It is merged into an empty mapper
 and into a copy of itself (the same blocks, uploaded through set_blocks), under the identity and under a transform 3 cm and 1.5 degrees off
 about a general axis:
-  - us per launch (k_merge_count, k_merge_index, k_merge_fuse, k_merge_result) by the library's own per-launch event spans (set_profiling);
+  - us per launch (k_transfer_count<Box>, k_transfer_index<Box>, k_merge_fuse, k_transfer_result: the enumeration and the result record are
+    csrc/nvbx_map_transfer.h's) by the library's own per-launch event spans (set_profiling);
   - ms of the whole call by a host clock around merge_from + synchronize (the call waits on the host twice, so the host clock is the honest one);
     the empty destination is cleared before every call, outside the timed window;
   - the least bytes the fuse launch has to move, from the call's own counts -- every candidate block's TSDF read once, 8 bytes written per
@@ -115,7 +116,7 @@ def main():
                 dst.merge_from(src, T, out=buf); dst.synchronize()
                 p = dst.profile(); dst.set_profiling(False)
                 for k, v in p.items():
-                    if "k_merge" in k:
+                    if "k_merge" in k or "k_transfer" in k:
                         s = spans.setdefault(k, [0.0, 0]); s[0] += v["total_ms"] * 1e3; s[1] += v["count"]
             span_us = {k: round(v[0] / max(v[1], 1), 2) for k, v in spans.items()}
             fuse_us = next((v for k, v in span_us.items() if "k_merge_fuse" in k), None)

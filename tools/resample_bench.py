@@ -5,7 +5,8 @@ The room map of the 640x480 loop (every second pose of the 200, depth and colour
 empty mapper (cleared before every call, outside the timed window) at 0.10 m with 2 taps per axis, at 0.20 m with 4 taps and with 1 tap, and
 at 0.05 m with 1 tap -- next to merge_from into the same kind of mapper, in the same run -- each under the identity and under a transform
 3 cm and 1.5 degrees off about a general axis:
-  - us per launch (count, index, fuse, result) by the library's own per-launch event spans (set_profiling);
+  - us per launch (count, index, fuse, result: k_transfer_count<Box>, k_transfer_index<Box>, the call's fuse kernel, k_transfer_result) by the
+    library's own per-launch event spans (set_profiling);
   - ms of the whole call by a host clock around the call + synchronize (the call waits on the host twice, so the host clock is the honest one);
   - the least bytes the fuse launch has to move, from the call's own counts -- every candidate block's TSDF read once, 8 bytes written per
     fused voxel, 16 per blended colour voxel, every source TSDF and colour block read once -- and that over the span as a share of the
@@ -93,7 +94,7 @@ def main():
     lanes = np.arange(512); lane_xyz = np.stack([lanes >> 6, (lanes >> 3) & 7, lanes & 7], 1)
     lines = []
 
-    def measure(dst, call_fn, kernel_tag):
+    def measure(dst, call_fn, fuse_kernel):
         """-> (result record of one call, host ms, us per launch) of call_fn(out) into the cleared dst"""
         buf = torch.empty(M.MERGE_RESULT_BYTES, dtype=torch.uint8, device="cuda")
         dst.clear()
@@ -108,7 +109,7 @@ def main():
             call_fn(buf); dst.synchronize()
             p = dst.profile(); dst.set_profiling(False)
             for k, v in p.items():
-                if kernel_tag in k:
+                if fuse_kernel in k or "k_transfer" in k:      # (the enumeration and the result record: csrc/nvbx_map_transfer.h)
                     s = spans.setdefault(k, [0.0, 0]); s[0] += v["total_ms"] * 1e3; s[1] += v["count"]
         span_us = {k: round(v[0] / max(v[1], 1), 2) for k, v in spans.items()}
         return status, counts, call, span_us
@@ -117,7 +118,7 @@ def main():
         dst = M.Mapper(M.default_params(voxel_size=vd))
         trunc = float(dst.params.truncation_distance_vox * dst.params.voxel_size)
         for tname, T in transforms.items():
-            status, counts, call, span_us = measure(dst, lambda buf: dst.resample_from(src, T, out=buf, taps=taps), "k_resample")
+            status, counts, call, span_us = measure(dst, lambda buf: dst.resample_from(src, T, out=buf, taps=taps), "k_resample_fuse")
             fuse_us = next((v for k, v in span_us.items() if "k_resample_fuse" in k), None)
             least = counts["candidate_blocks"] * 4096 + counts["voxels_fused"] * 8 + counts["color_voxels_fused"] * 16 + (n_t + n_c) * 4096
             rec = {"case": "resample_room_640x480", "what": cname, "voxel_size_dst": vd, "taps": taps, "transform": tname, "status": status, **counts,
@@ -125,7 +126,7 @@ def main():
                    "fuse_least_bytes": int(least), "fuse_share_of_hbm_peak": round(least / HBM_PEAK / (fuse_us * 1e-6), 4) if fuse_us else None,
                    "grid_cap": os.environ.get("NVBX_RESAMPLE_GRID", "default"), "calls": a.calls}
             if vd == VS and taps == 1:                        # the merge in the same run, into the same kind of mapper
-                m_status, m_counts, m_call, m_span = measure(dst, lambda buf: dst.merge_from(src, T, out=buf), "k_merge")
+                m_status, m_counts, m_call, m_span = measure(dst, lambda buf: dst.merge_from(src, T, out=buf), "k_merge_fuse")
                 rec.update({"merge_call_ms": round(m_call[0], 3), "merge_call_ms_min_max": [round(m_call[1], 3), round(m_call[2], 3)], "merge_span_us": m_span,
                             "merge_counts_equal": m_counts == counts and m_status == status})
 

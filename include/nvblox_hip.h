@@ -1077,6 +1077,48 @@ int nvbx_change_clusters(nvbx_mapper* m, nvbx_mapper* ref, const float T_M_R[16]
                          int64_t* block_count_dev, nvbx_component* components_dev, int64_t capacity_components,
                          int64_t* component_count_dev, nvbx_change_result* result_dev);
 
+/* ---- surface points and map-to-map registration (SEMANTICS.md "Surface points", "Registering two maps") ----------------
+ * [U] nvbx_surface_points: the TSDF's zero crossings as a point cloud in DEVICE memory, with colour and normals, asynchronous on the mapper's
+ * stream.  A voxel {d, w} is OBSERVED iff its block is allocated with a TSDF layer, w >= min_weight and d == d.  The edge from an ORIGIN voxel
+ * g to g + e_a (a = 0, 1, 2; across block borders) holds a crossing iff both voxels are observed and (d0 <= 0) != (d1 <= 0); a neighbour in a
+ * block that is missing, has no TSDF layer or is not addressable gives none.  The point: along axis a
+ *   (((float)b_a * (8 vs) + (float)v_a * vs) + vs * 0.5f) + vs * (-d0 / (d1 - d0)),   on the other two axes the voxel centre (the first term).
+ * Filters: the origin voxel inside box_min_max_vox (inclusive, global voxel coordinates, only with use_box != 0) and g_x, g_y, g_z all
+ * multiples of stride (mathematical modulo); require_color != 0: only crossings with a colour (below).
+ * Outputs, each may be NULL: points_dev[capacity][3] f32; colors_dev[capacity][3] u8 = the stored r, g, b of the colour voxel of the edge's
+ * endpoint nearer the surface (|d0| <= |d1|: the origin) where its block carries colour and its colour weight is > 0, else 0, 0, 0;
+ * normals_dev[capacity][3] f32 = nvbx_query_points' TSDF gradient at the point (same min_weight) divided by its length, 0 where the query is
+ * invalid or the gradient zero.  *count_dev (required) = the number of crossings, also beyond capacity; rows from capacity on are not written.
+ * ORDER: ascending pool slot of the origin block, then t = vx 64 + vy 8 + vz, then axis -- a function of the mapper's state alone: two calls
+ * write identical bytes.  TSDF mappers only; reads the map only; a call without colour output leaves held-back colour / ESDF work held back,
+ * one with colors_dev or require_color carries it out first (as nvbx_query_colors).
+ * Refused: NULL mapper or count_dev, capacity < 0 or > 2^30, capacity > 0 without points_dev, stride < 1, a NaN min_weight, a used box with
+ * min > max on an axis, an occupancy mapper. */
+typedef struct {
+  float min_weight;             /* 1e-4 */
+  int32_t stride;               /* 1 */
+  int32_t use_box;              /* 0 */
+  int32_t require_color;        /* 0 */
+  int32_t box_min_max_vox[6];   /* min x y z, max x y z */
+} nvbx_surface_options;         /* 40 bytes; offsets 0 4 8 12 16 */
+void nvbx_default_surface_options(nvbx_surface_options* options);
+int nvbx_surface_points(nvbx_mapper* m, const nvbx_surface_options* options, float* points_dev, uint8_t* colors_dev, float* normals_dev,
+                        int64_t capacity, int64_t* count_dev);
+/* nvbx_align_map: the pose T_D_S (p_D = T_D_S p_S, nvbx_merge_map's argument) of map src in map dst, refined from a guess: src's surface
+ * points (surface_options; NULL: defaults) go into scratch of dst, then exactly the launches of nvbx_align_points over them against dst's TSDF
+ * -- or, with color_options != NULL, of nvbx_align_points_color with the points' colours (require_color is then forced on and
+ * color_result_dev is required).  Runs on dst's stream behind what src's stream holds; later work on src is ordered behind the reads.
+ * ONE host wait: for the 8-byte point count, which sizes the scratch and the alignment's grid; everything after it is enqueued without
+ * waiting.  No crossing: as nvbx_align_points with n = 0.  The voxel sizes may differ.  Every refusal of either half comes before the first
+ * launch; refused as well: dst == src, different devices, an occupancy mapper on either side.
+ * nvbx_relocalize_map: the same in front of nvbx_relocalize_points' launches (its lattice, options, scores_dev and result record). */
+int nvbx_align_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S_guess[16], const nvbx_surface_options* surface_options,
+                   const nvbx_align_options* align_options, const nvbx_align_color_options* color_options, nvbx_align_result* result_dev,
+                   nvbx_align_color_result* color_result_dev);
+int nvbx_relocalize_map(nvbx_mapper* dst, nvbx_mapper* src, const float T0[16], const nvbx_search_lattice* lattice,
+                        const nvbx_surface_options* surface_options, const nvbx_score_options* score_options, int32_t min_inliers,
+                        const nvbx_align_options* align_options, nvbx_pose_score* scores_dev, nvbx_relocalize_result* result_dev);
+
 /* ---- mask splitting (human / people-segmentation mapping) ------------------------------------------------------------
  * [U] ImageMasker::splitImageOnGPU as used by MultiMapper::integrateDepth(depth, mask, T_L_CD, T_CM_CD, depth_cam, mask_cam) --
  * nvblox_node.cpp:1018-1060: every valid depth pixel is lifted to 3-D, moved into the mask camera (T_CM_CD = T_L_CM^-1 T_L_CD)

@@ -197,6 +197,12 @@ class ChangeResult(C.Structure):
                 ("blocks_changed", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32 * 5)]
 
 
+class SurfaceOptions(C.Structure):
+    """nvbx_surface_options (40 bytes); nvbx_default_surface_options fills it"""
+    _fields_ = [("min_weight", C.c_float), ("stride", C.c_int32), ("use_box", C.c_int32), ("require_color", C.c_int32),
+                ("box_min_max_vox", C.c_int32 * 6)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("table", C.c_void_p), ("table_mask", C.c_uint32), ("table_shift", C.c_uint32), ("slot_flags", C.c_void_p),
                 ("slot_index", C.c_void_p), ("tsdf", C.c_void_p), ("color", C.c_void_p), ("esdf", C.c_void_p),
@@ -316,6 +322,11 @@ SIGNATURES = {
     "nvbx_default_change_options": (None, [C.POINTER(ChangeOptions)]),
     "nvbx_find_changes": (C.c_int, [_vp, _vp, _vp, C.POINTER(ChangeOptions), _pi32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "nvbx_change_clusters": (C.c_int, [_vp, _vp, _vp, C.POINTER(ChangeOptions), _pi32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "nvbx_default_surface_options": (None, [C.POINTER(SurfaceOptions)]),
+    "nvbx_surface_points": (C.c_int, [_vp, C.POINTER(SurfaceOptions), _vp, _vp, _vp, _i64, _vp]),
+    "nvbx_align_map": (C.c_int, [_vp, _vp, _vp, C.POINTER(SurfaceOptions), C.POINTER(AlignOptions), C.POINTER(AlignColorOptions), _vp, _vp]),
+    "nvbx_relocalize_map": (C.c_int, [_vp, _vp, _vp, C.POINTER(SearchLattice), C.POINTER(SurfaceOptions), C.POINTER(ScoreOptions), _i32,
+                                      C.POINTER(AlignOptions), _vp, _vp]),
     "nvbx_num_blocks": (_i64, [_vp, C.c_uint32]),
     "nvbx_block_indices": (_i64, [_vp, C.c_uint32, _vp, _i64]),
     "nvbx_get_block": (C.c_int, [_vp, C.c_uint32, Index3D, _vp]),

@@ -291,10 +291,17 @@ int nvbx::align_launch(nvbx_mapper* m, AlignArgs& a) {
 
 static int align_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
               const float T[16], const nvbx_align_options* options, nvbx_align_result* res, int mode, float* out_p, float* out_r, float* out_g,
-              uint8_t* out_v, const AlignColorIn* color = nullptr) {
+              uint8_t* out_v, const AlignColorIn* color = nullptr, bool check_only = false) {
   AlignArgs a;
   const int rc = align_check(who, m, pts, n, depth, rows, cols, cam, T, false, options, res, mode, out_p, out_r, out_g, out_v, a, color);
-  return rc ? rc : align_launch(m, a);
+  return rc || check_only ? rc : align_launch(m, a);
+}
+
+// nvbx_align_map (surface.hip, described in nvbx_align.h)
+int nvbx::align_points_call(const char* who, nvbx_mapper* m, const float* pts, const uint8_t* rgb, int64_t n, const float T[16], const nvbx_align_options* options,
+                            bool color, const nvbx_align_color_options* color_options, nvbx_align_result* res, nvbx_align_color_result* cres, bool check_only) {
+  const AlignColorIn c{rgb, color_options, cres, nullptr, nullptr, nullptr};
+  return align_run(who, m, pts, n, nullptr, 0, 0, nullptr, T, options, res, MODE_ALIGN, nullptr, nullptr, nullptr, nullptr, color ? &c : nullptr, check_only);
 }
 
 // nvbx_relocalize_* (relocalize.hip, described in nvbx_align.h), which then calls align_buffers and align_launch itself

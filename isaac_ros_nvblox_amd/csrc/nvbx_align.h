@@ -32,4 +32,15 @@ int align_check_from_state(const char* who, nvbx_mapper* m, const float* pts, in
 int align_buffers(nvbx_mapper* m, AlignArgs& a);      // 2: a.st, a.partial.  (A growth waits for the stream: before the first launch of a call.)
 int align_launch(nvbx_mapper* m, AlignArgs& a);       // 3: every launch of a checked call (it makes sure of the buffers itself)
 
+// nvbx_align_map / nvbx_relocalize_map (surface.hip) have their points only after their first launches, and every refusal has to come before
+// those: they make the point call twice.  check_only: the call's refusals for n = 0 (pts and rgb null), nothing is launched; then, with the
+// points, the call itself.  who: the name the refusals carry.
+// nvbx_align_points, or with `color` nvbx_align_points_color (rgb: the points' colours)
+int align_points_call(const char* who, nvbx_mapper* m, const float* pts, const uint8_t* rgb, int64_t n, const float T[16], const nvbx_align_options* options,
+                      bool color, const nvbx_align_color_options* color_options, nvbx_align_result* res, nvbx_align_color_result* cres, bool check_only);
+// nvbx_relocalize_points (relocalize.hip)
+int relocalize_points_call(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float T0[16], const nvbx_search_lattice* lattice,
+                           const nvbx_score_options* score_options, int32_t min_inliers, const nvbx_align_options* align_options, nvbx_pose_score* scores,
+                           nvbx_relocalize_result* res, bool check_only);
+
 }  // namespace nvbx

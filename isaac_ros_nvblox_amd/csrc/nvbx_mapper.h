@@ -155,6 +155,10 @@ struct nvbx_mapper {
   nvbx::DevBuf merge_buf;
   // change detection (change.hip), as the map that is scanned: 64 bytes of counters, allocated with the map
   nvbx::DevBuf change_buf;
+  // surface points (surface.hip), as the mapper whose stream runs the call: a 64-byte head (the count of nvbx_align_map / nvbx_relocalize_map), the
+  // crossing count and the three neighbour slots of every slot of the scanned map and the sums and offsets of the scan's tiles; and, apart from it (a growth keeps no contents),
+  // the points and colours those two calls hand to the alignment
+  nvbx::DevBuf surface_buf, surface_pts;
   // cost field (plan.hip) and cost volume (plan3d.hip), sized and carved up by nvbx_plan_grid.h's plan_grid_setup alone: a 64-byte head of counters, the class word of every cell and the two sets of active-tile flags of the largest input so far
   nvbx::DevBuf plan_scratch;
   // traversability (elevation.hip): one bit row of HAZARD flags, ceil(cols / 64) 64-bit words, per row of the largest image so far

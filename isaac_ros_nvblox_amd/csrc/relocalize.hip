@@ -241,7 +241,7 @@ int score_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n, cons
 
 int relocalize_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float* depth, int32_t rows, int32_t cols, const nvbx_camera* cam,
                    const float T0[16], const nvbx_search_lattice* lattice, const nvbx_score_options* score_options, int32_t min_inliers,
-                   const nvbx_align_options* align_options, nvbx_pose_score* scores, nvbx_relocalize_result* res) {
+                   const nvbx_align_options* align_options, nvbx_pose_score* scores, nvbx_relocalize_result* res, bool check_only = false) {
   if (!m) return NVBX_E_INVALID;
   if (tsdf_reader_refused(m, who)) return NVBX_E_INVALID;
   if (!T0 || !lattice || !res) return refuse(who, ": T0, the lattice and result_dev are required");
@@ -253,7 +253,7 @@ int relocalize_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n,
   if (score_options_check(who, m, score_options, &o) || point_source_check(who, pts, n, depth, rows, cols, cam, o.s, o.max_d, &a.src)) return NVBX_E_INVALID;
   AlignArgs al;
   const int rc = align_check_from_state(who, m, pts, n, depth, rows, cols, cam, align_options, &res->align, al);
-  if (rc) return rc;
+  if (rc || check_only) return rc;
   NVBX_HIP(hipSetDevice(m->device));
   if (m->begin_call_keeping_held()) return NVBX_E_DEVICE;
   // buffers first: a growth waits for the stream
@@ -291,6 +291,13 @@ int relocalize_run(const char* who, nvbx_mapper* m, const float* pts, int64_t n,
 }
 
 }  // namespace
+
+// nvbx_relocalize_map (surface.hip, described in nvbx_align.h)
+int nvbx::relocalize_points_call(const char* who, nvbx_mapper* m, const float* pts, int64_t n, const float T0[16], const nvbx_search_lattice* lattice,
+                                 const nvbx_score_options* score_options, int32_t min_inliers, const nvbx_align_options* align_options, nvbx_pose_score* scores,
+                                 nvbx_relocalize_result* res, bool check_only) {
+  return relocalize_run(who, m, pts, n, nullptr, 0, 0, nullptr, T0, lattice, score_options, min_inliers, align_options, scores, res, check_only);
+}
 
 extern "C" void nvbx_default_score_options(nvbx_score_options* o) {
   if (!o) return;

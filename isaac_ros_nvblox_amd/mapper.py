@@ -1119,6 +1119,88 @@ class Mapper:
             raise
         return m, res
 
+    # -- surface points and map-to-map registration (nvbx_surface_points / nvbx_align_map / nvbx_relocalize_map; SEMANTICS.md "Surface points")
+    def surface_options(self, **kw):
+        """nvbx_surface_options: the library's defaults with the given fields replaced (min_weight, stride, require_color, and
+        box_min_max_vox = (min x, y, z, max x, y, z) in global voxel coordinates, inclusive, which also sets use_box)."""
+        kw = dict(kw)
+        box = kw.pop("box_min_max_vox", None)
+        if "require_color" in kw:
+            kw["require_color"] = int(bool(kw["require_color"]))
+        o = _args.struct_options(_lib.SurfaceOptions, self.lib.nvbx_default_surface_options, kw, "surface")
+        if box is not None:
+            b = [int(v) for v in np.asarray(box).reshape(-1)]
+            if len(b) != 6:
+                raise ValueError("box_min_max_vox must hold (min x, y, z, max x, y, z)")
+            o.box_min_max_vox = (C.c_int32 * 6)(*b)
+            if "use_box" not in kw:
+                o.use_box = 1
+        return o
+
+    def surface_points(self, color=False, normals=False, capacity=None, out=None, **options):
+        """The TSDF's zero crossings as a point cloud on the mapper's device: -> (points [n, 3] f32, colors [n, 3] u8 | None, normals [n, 3] f32
+        | None, count), in the order (pool slot of the origin block, voxel, axis); two calls on an unchanged mapper give identical tensors.
+        count is the number of crossings, n = min(count, capacity).  capacity=None: a first call counts (one wait), a second one emits.
+        out=(points, colors | None, normals | None): preallocated tensors of one row count, the capacity; color and normals are then not
+        looked at.  Both forms wait once more, for the count the tensors are trimmed to.  options: see surface_options."""
+        dev = self._cuda; torch = self._torch
+        o = self.surface_options(**options)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        if out is not None:
+            if not out or out[0] is None:
+                raise ValueError("out needs a points tensor")
+            capacity = int(out[0].shape[0])
+        elif capacity is None:
+            self._around_torch_stream(lambda: self.lib.nvbx_surface_points(self._h, C.byref(o), None, None, None, 0, ptr(count)))
+            capacity = int(count.item())
+        cap = int(capacity)
+        p, c, nr = _args.outputs(out, (("points", (cap, 3), F32, True, True), ("colors", (cap, 3), U8, False, color),
+                                       ("normals", (cap, 3), F32, False, normals)), dev)
+        self._around_torch_stream(lambda: self.lib.nvbx_surface_points(self._h, C.byref(o), ptr(p), ptr(c), ptr(nr), cap, ptr(count)))
+        total = int(count.item())
+        n = min(total, cap)
+        return p[:n], (c[:n] if c is not None else None), (nr[:n] if nr is not None else None), total
+
+    def _surface_of(self, other, surface, what):
+        if not isinstance(other, Mapper):
+            raise TypeError("%s needs a Mapper" % what)
+        return other.surface_options(**(surface or {}))
+
+    def align_map(self, other, T_D_S_guess, color_weight=None, surface=None, out=None, **options):
+        """Refine the pose T_D_S of `other`'s map in this one (p_D = T_D_S p_S: merge_from's argument) from a guess inside the truncation band:
+        `other`'s surface points (surface: a dict of surface_options fields, e.g. stride) are aligned against this map's TSDF by align_points'
+        launches -> AlignResult; with color_weight (a number) by align_points_color's, over the crossings that have a colour ->
+        AlignColorResult.  Runs on this mapper's stream behind `other`'s; waits once on the host, for the point count.  options: the fields of
+        align_options and, with color_weight, of align_color_options.  out: as for align_points / align_points_color."""
+        so = self._surface_of(other, surface, "align_map")
+        if color_weight is None:
+            T = self._T(T_D_S_guess); o = self.align_options(**options)
+            buf = _args.result_buffer(out, ALIGN_RESULT_BYTES, self._cuda)
+            self._around_torch_stream(lambda: self.lib.nvbx_align_map(self._h, other._h, _np_ptr(T), C.byref(so), C.byref(o), None, ptr(buf), None))
+            return AlignResult(buf)
+        T, o, co, buf, cbuf = self._align_color_setup(T_D_S_guess, out, dict(options, color_weight=float(color_weight)))
+        self._around_torch_stream(lambda: self.lib.nvbx_align_map(self._h, other._h, _np_ptr(T), C.byref(so), C.byref(o), C.byref(co), ptr(buf), cbuf))
+        return AlignColorResult(buf)
+
+    def relocalize_map(self, other, T0, half_extent_m, half_yaw_rad, steps, min_inliers=None, surface=None, score=None, align=None, scores=None, out=None):
+        """Find the pose of `other`'s map in this one from a guess that may be far outside the truncation band: relocalize_points over `other`'s
+        surface points (surface: a dict of surface_options fields).  -> RelocalizeResult; its align.T is T_D_S.  Stream order and the one host
+        wait as for align_map; the other arguments as for relocalize_points."""
+        so = self._surface_of(other, surface, "relocalize_map")
+        lat = self._lattice(half_extent_m, half_yaw_rad, steps); T = self._T(T0)
+        sc = self.score_options(**(score or {})); ao = self.align_options(**(align or {}))
+        buf = _args.result_buffer(out, RELOC_RESULT_BYTES, self._cuda)
+        views = None
+        rec = None
+        if scores is not None and scores is not False:
+            K = int(np.prod([int(s) for s in lat.steps]))
+            rec, counts, residual = _args.score_records(None if scores is True else scores, K, self._cuda)
+            views = (counts, residual)
+        mi = int(min_inliers) if min_inliers is not None else 0
+        self._around_torch_stream(lambda: self.lib.nvbx_relocalize_map(self._h, other._h, _np_ptr(T), C.byref(lat), C.byref(so), C.byref(sc), mi,
+                                                                       C.byref(ao), ptr(rec), ptr(buf)))
+        return RelocalizeResult(buf, views)
+
     # -- rendering and ray casts (nvbx_render_view / nvbx_cast_rays; SEMANTICS.md "Rendering and ray casts")
     def render(self, T_L_C, cam, subsampling=None, max_ray_length_m=None, color=True, normals=False, out=None):
         """The map seen from camera `cam` at pose T_L_C: -> (depth [rows/s, cols/s] f32, color [.., 3] u8 | None, normals [.., 3] f32 | None) on the

@@ -512,14 +512,22 @@ int nvbx_cast_rays_with(nvbx_mapper* m, const nvbx_render_options* options, cons
  *   addressable range.  Chained behind nvbx_cast_rays / nvbx_render_view it gives a feature image of the map from any pose.
  * nvbx_get_feature_blocks: whole blocks in the public layout -- voxel t = vx 64 + vy 8 + vz, C contiguous halfs per voxel: feat_out [n][512][C]
  *   fp16, weight_out [n][512] f32, found_out [n] (NULL: not written); pointer conventions of nvbx_get_blocks (host memory, synchronous).
- * All three carry held-back work out first (as nvbx_flush) and run in classic order on the mapper's stream; integrate and query are
+ * nvbx_set_feature_blocks: its mirror -- feat_in [n][512][C] fp16 and weight_in [n][512] f32 in the same public layout; pointer conventions
+ *   of nvbx_set_blocks (host memory, synchronous).  Block i is written only if its slot carries the TSDF layer (features do not keep a block
+ *   alive: an orphan would be unreachable); any other block is skipped, written_out[i] = 0 (written_out may be NULL).  A write replaces all 512
+ *   voxels, stores the weights as given and sets NVBX_LAYER_FEATURE; it touches nothing but the two feature pools and that flag: no dirty
+ *   list, no view list, no mesh.  The indices of one call are distinct.  NVBX_E_INVALID (nothing written): a weight that is negative or not
+ *   a number; NULL pointers with n > 0.  With it a caller puts features back into a loaded map (nvbx_load_map starts without them).
+ * All of them carry held-back work out first (as nvbx_flush) and run in classic order on the mapper's stream; integrate and query are
  * asynchronous.  Before nvbx_enable_features they return NVBX_E_INVALID.  Not covered: map files, mesh vertices, multi-GPU exchange,
- * batches, LiDAR, nvbx_device_view.  Scoring the layer against query embeddings: "feature matching" below. */
+ * batches, LiDAR, nvbx_device_view.  Scoring the layer against query embeddings: "feature matching" below; bringing another mapper's
+ * layer into this one: "feature merging". */
 int nvbx_enable_features(nvbx_mapper* m, int32_t channels);
 int nvbx_integrate_features(nvbx_mapper* m, const void* feat_dev, int32_t rows_f, int32_t cols_f, int32_t stride, const float T_L_C[16],
                             const nvbx_camera* camera);
 int nvbx_query_features(nvbx_mapper* m, const float* points_xyz_dev, int64_t n, void* feat_out_dev, float* weight_out_dev);
 int nvbx_get_feature_blocks(nvbx_mapper* m, const nvbx_index3d* idx, int64_t n, void* feat_out, float* weight_out, int32_t* found_out);
+int nvbx_set_feature_blocks(nvbx_mapper* m, const nvbx_index3d* idx, int64_t n, const void* feat_in, const float* weight_in, int32_t* written_out);
 
 /* ---- feature matching (open-vocabulary search over the feature layer; SEMANTICS.md "Feature matching") -------------------------------
  * Scores feature voxels against Q query embeddings on the matrix cores, without moving the layer anywhere.
@@ -967,7 +975,7 @@ int nvbx_relocalize_depth(nvbx_mapper* m, const float* depth_dev, int32_t rows, 
  * weight_scale; a valid sample is fused as a weighted mean, clamped to +-truncation and dst's max_weight; an invalid one leaves the voxel
  * untouched.  With merge_color the nearest source colour voxel is blended into dst's.  Band flags, ESDF-dirty and mesh-dirty lists of dst
  * are kept as by any TSDF writer; src is not modified.  Both mappers: TSDF mappers (projective_layer_type 0) on one device with one
- * voxel_size.  Feature voxels, ESDF, occupancy and freespace are not merged.
+ * voxel_size.  ESDF, occupancy and freespace are not merged; feature voxels by a call of their own (nvbx_merge_features below).
  * Launches run on dst's stream, ordered behind everything enqueued on src's so far; work enqueued on src afterwards is ordered behind the
  * merge's reads.  A maintenance call: it waits on the host for src's block count and, once, between enumerating the candidates and
  * allocating them (dst's pools grow if they must).  NVBX_E_CAPACITY (dst unchanged): dst's max_capacity cannot hold the candidates.
@@ -996,6 +1004,41 @@ typedef struct {
 void nvbx_default_merge_options(nvbx_merge_options* options);
 /* T_D_S: row-major 4 x 4, host memory.  options NULL: the defaults.  result_dev: written by the last launch, not waited for. */
 int nvbx_merge_map(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S[16], const nvbx_merge_options* options, nvbx_merge_result* result_dev);
+
+/* ---- feature merging (the feature layer of one map brought into another; SEMANTICS.md "Feature merging") --------------------------------
+ * A call of its own, meant to follow nvbx_merge_map with the same pose p_D = T_D_S p_S.  For every block of src that carries features, the
+ * blocks of dst whose voxel centres can fall into it are candidates -- those dst HAS with its TSDF layer: this call allocates nothing and
+ * never grows a pool.  Every voxel of a candidate takes the source voxel that CONTAINS R_SD p_D + t_SD (floor(p / voxel_size) per axis,
+ * nvbx_query_features' rule: features are never interpolated); it contributes iff its block carries features in src and its stored weight
+ * w_s satisfies w_s > 0 and w_s >= min_weight, with w_1 = w_s weight_scale.  Blend, per channel: w_0 = dst's stored weight (0 in a block
+ * that carried no features when the call began), tw = w_0 + w_1, v = old (w_0 / tw) + f (w_1 / tw) rounded to fp16 to nearest even; weight
+ * = min(tw, dst's max_weight) -- the feature integrator's blend with w_1 in place of 1.  A candidate without features in which a voxel
+ * contributes is flagged and written whole (weight 0 and zero values where nothing contributed); one in which none does is neither.
+ * Only dst's feature pools and NVBX_LAYER_FEATURE flags change: TSDF, colour, ESDF, every other flag, the dirty lists, the view list,
+ * nvbx_last_depth_view, counters and mesh stay bit for bit; src is not modified.
+ * Launches run on dst's stream, ordered behind everything enqueued on src's so far; work enqueued on src afterwards is ordered behind the
+ * call's reads; both mappers' held-back work is carried out first.  The only host wait is the one for src's block count, which sizes the
+ * scratch: nothing waits between enumerating and fusing.
+ * NVBX_E_INVALID (nvbx_last_error names the call, dst unchanged): what nvbx_merge_map refuses of its mappers, pose, weight_scale and
+ * result_dev; different voxel sizes; the feature layer off on either side; different channel counts; min_weight negative or not a number. */
+typedef struct {
+  float   min_weight;           /* a source voxel counts with weight > 0 and >= this */
+  float   weight_scale;         /* its weight is multiplied by this; finite, > 0 */
+  int32_t reserved[6];          /* 0 */
+} nvbx_feature_merge_options;   /* 32 bytes; offsets 0 4 8 */
+typedef struct {
+  int64_t source_blocks;        /* feature blocks of src */
+  int64_t candidate_blocks;     /* distinct blocks of dst the call went over */
+  int64_t blocks_flagged;       /* ... of which it gave the feature layer */
+  int64_t voxels_fused;
+  int32_t status;               /* NVBX_MERGE_*: OK, EMPTY_SOURCE (src has no feature block), NO_OVERLAP (no voxel fused) */
+  int32_t pad[7];
+} nvbx_feature_merge_result;    /* 64 bytes, 8-byte aligned DEVICE memory; offsets 0 8 16 24 32 36 */
+/* defaults: min_weight 0, weight_scale 1 */
+void nvbx_default_feature_merge_options(nvbx_feature_merge_options* options);
+/* T_D_S: row-major 4 x 4, host memory.  options NULL: the defaults.  result_dev: written by the last launch, not waited for. */
+int nvbx_merge_features(nvbx_mapper* dst, nvbx_mapper* src, const float T_D_S[16], const nvbx_feature_merge_options* options,
+                        nvbx_feature_merge_result* result_dev);
 
 /* ---- resampling ([U] a map brought into a mapper of a coarser voxel size; SEMANTICS.md "Resampling") ----------------------------------
  * nvbx_merge_map with two voxel sizes: reads `src` at its voxel size vs_s and writes `dst` at vs_d, r = (double)vs_d / (double)vs_s in

@@ -180,6 +180,17 @@ class MergeResult(C.Structure):
                 ("color_voxels_fused", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32 * 5)]
 
 
+class FeatureMergeOptions(C.Structure):
+    """nvbx_feature_merge_options (32 bytes); nvbx_default_feature_merge_options fills it"""
+    _fields_ = [("min_weight", C.c_float), ("weight_scale", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
+class FeatureMergeResult(C.Structure):
+    """nvbx_feature_merge_result: what nvbx_merge_features' last launch leaves in DEVICE memory (64 bytes)"""
+    _fields_ = [("source_blocks", C.c_int64), ("candidate_blocks", C.c_int64), ("blocks_flagged", C.c_int64), ("voxels_fused", C.c_int64),
+                ("status", C.c_int32), ("pad", C.c_int32 * 7)]
+
+
 class ResampleOptions(C.Structure):
     """nvbx_resample_options (16 bytes); nvbx_default_resample_options fills it"""
     _fields_ = [("min_weight", C.c_float), ("weight_scale", C.c_float), ("merge_color", C.c_int32), ("taps", C.c_int32)]
@@ -283,6 +294,7 @@ SIGNATURES = {
     "nvbx_integrate_features": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, C.POINTER(Camera)]),
     "nvbx_query_features": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "nvbx_get_feature_blocks": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "nvbx_set_feature_blocks": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "nvbx_match_features": (C.c_int, [_vp, _vp, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i64, _vp]),
     "nvbx_match_points": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
     "nvbx_label_components": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
@@ -317,6 +329,8 @@ SIGNATURES = {
                                         C.POINTER(AlignOptions), _vp, _vp]),
     "nvbx_default_merge_options": (None, [C.POINTER(MergeOptions)]),
     "nvbx_merge_map": (C.c_int, [_vp, _vp, _vp, C.POINTER(MergeOptions), _vp]),
+    "nvbx_default_feature_merge_options": (None, [C.POINTER(FeatureMergeOptions)]),
+    "nvbx_merge_features": (C.c_int, [_vp, _vp, _vp, C.POINTER(FeatureMergeOptions), _vp]),
     "nvbx_default_resample_options": (None, [C.POINTER(ResampleOptions)]),
     "nvbx_resample_map": (C.c_int, [_vp, _vp, _vp, C.POINTER(ResampleOptions), _vp]),
     "nvbx_default_change_options": (None, [C.POINTER(ChangeOptions)]),

@@ -18,6 +18,8 @@
 //                        (chunked slot scan, ballot on the flags, frustum vote of 8 lanes).  Projection, synthetic-depth taps and the
 //                        occlusion verdict once per voxel; then a loop over chunks of 8 channels: four 16-B tap loads, one 16-B voxel load,
 //                        one 16-B voxel store per lane.  Registers do not scale with C.
+// Whole blocks in the public layout are read by k_gather_feature_blocks and written by k_scatter_feature_blocks (nvbx_get_feature_blocks /
+// nvbx_set_feature_blocks); another mapper's layer is merged in by feature_merge.hip.
 #include <algorithm>
 #include <cstring>
 #include "nvbx_mapper.h"
@@ -177,6 +179,20 @@ __global__ __launch_bounds__(512) void k_gather_feature_blocks(DMap m, const hal
   for (int q = 0; q < 8; q++) z[q] = (_Float16)0.0f;
   for (int k = 0; k < nch; k++) feat_out[((size_t)i * 512 + t) * nch + k] = slot_ok(s) ? val[((size_t)s * nch + k) * 512 + t] : z;
 }
+// the reverse: block i of the list, in the public layout, -> the pools.  Only a block whose slot carries the TSDF layer is written (features do not
+// keep a block alive); all 512 voxels are replaced and the slot is flagged.  Nothing else of the map is touched.
+__global__ __launch_bounds__(512) void k_scatter_feature_blocks(DMap m, half8* val, float* w, int32_t nch, const int32_t* idx, int32_t n, const half8* feat_in,
+                                                                const float* w_in, int32_t* written) {
+  const int i = blockIdx.x; if (i >= n) return;
+  const int t = threadIdx.x;
+  const int32_t x = idx[3 * i], y = idx[3 * i + 1], z = idx[3 * i + 2];
+  const uint32_t s = nvbx_index_in_range(x, y, z) ? find_slot(m, x, y, z, F_TSDF) : SLOT_NONE;
+  if (t == 0) written[i] = slot_ok(s) ? 1 : 0;
+  if (!slot_ok(s)) return;
+  w[(size_t)s * 512 + t] = w_in[(size_t)i * 512 + t];
+  for (int k = 0; k < nch; k++) val[((size_t)s * nch + k) * 512 + t] = feat_in[((size_t)i * 512 + t) * nch + k];
+  if (t == 0) atomicOr(&m.slot_flags[s], F_FEATURE);
+}
 
 // ------------------------------------------------------------------------------------------------ C-ABI
 extern "C" int nvbx_enable_features(nvbx_mapper* m, int32_t channels) {
@@ -257,6 +273,31 @@ extern "C" int nvbx_get_feature_blocks(nvbx_mapper* m, const nvbx_index3d* idx, 
     NVBX_HIP(hipMemcpyAsync((uint8_t*)feat_out + (size_t)o * fb, d_f, (size_t)c * fb, hipMemcpyDeviceToHost, m->stream));
     NVBX_HIP(hipMemcpyAsync((uint8_t*)weight_out + (size_t)o * wb, d_w, (size_t)c * wb, hipMemcpyDeviceToHost, m->stream));
     if (found_out) NVBX_HIP(hipMemcpyAsync(found_out + o, d_found, (size_t)c * 4, hipMemcpyDeviceToHost, m->stream));
+    NVBX_HIP(hipStreamSynchronize(m->stream));
+  }
+  return NVBX_OK;
+}
+
+extern "C" int nvbx_set_feature_blocks(nvbx_mapper* m, const nvbx_index3d* idx, int64_t n, const void* feat_in, const float* weight_in, int32_t* written_out) {
+  if (!m || n < 0 || (n > 0 && (!idx || !feat_in || !weight_in))) { set_error("nvbx_set_feature_blocks: invalid argument"); return NVBX_E_INVALID; }
+  if (!m->feat_channels) { set_error("nvbx_set_feature_blocks: call nvbx_enable_features first"); return NVBX_E_INVALID; }
+  for (int64_t i = 0; i < n * 512; i++)
+    if (!(weight_in[i] >= 0.0f)) { set_error("nvbx_set_feature_blocks: a weight is negative or not a number"); return NVBX_E_INVALID; }
+  if (m->begin_call()) return NVBX_E_DEVICE;            // held-back work is carried out first
+  const int32_t nch = m->feat_channels / 8;
+  const size_t fb = (size_t)512 * 16 * nch, wb = 2048;
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)((m->staging.bytes - 65536) / (fb + wb + 16)));
+  for (int64_t o = 0; o < n; o += chunk) {
+    const int64_t c = std::min(chunk, n - o);
+    int32_t* d_idx = m->staging.as<int32_t>(); int32_t* d_written = d_idx + 3 * c;
+    uint8_t* d_w = m->staging.as<uint8_t>() + (((size_t)c * 16 + 255) & ~(size_t)255);
+    uint8_t* d_f = d_w + (size_t)c * wb;                         // (256-byte aligned: wb is)
+    NVBX_HIP(hipMemcpyAsync(d_idx, idx + o, (size_t)c * 12, hipMemcpyHostToDevice, m->stream));
+    NVBX_HIP(hipMemcpyAsync(d_f, (const uint8_t*)feat_in + (size_t)o * fb, (size_t)c * fb, hipMemcpyHostToDevice, m->stream));
+    NVBX_HIP(hipMemcpyAsync(d_w, (const uint8_t*)weight_in + (size_t)o * wb, (size_t)c * wb, hipMemcpyHostToDevice, m->stream));
+    NVBX_LAUNCH(m, k_scatter_feature_blocks, dim3((unsigned)c), dim3(512), m->d, static_cast<half8*>(m->feat_val), m->feat_w, nch, (const int32_t*)d_idx, (int32_t)c,
+                reinterpret_cast<const half8*>(d_f), reinterpret_cast<const float*>(d_w), d_written);
+    if (written_out) NVBX_HIP(hipMemcpyAsync(written_out + o, d_written, (size_t)c * 4, hipMemcpyDeviceToHost, m->stream));
     NVBX_HIP(hipStreamSynchronize(m->stream));
   }
   return NVBX_OK;

@@ -36,6 +36,7 @@ PoseScore = collections.namedtuple("PoseScore", "points valid inliers conflicts 
 MERGE_OK, MERGE_EMPTY_SOURCE, MERGE_NO_OVERLAP = 0, 1, 2
 MERGE_STATUS_NAMES = {0: "OK", 1: "EMPTY_SOURCE", 2: "NO_OVERLAP"}
 MERGE_RESULT_BYTES = C.sizeof(_lib.MergeResult)
+FEATURE_MERGE_RESULT_BYTES = C.sizeof(_lib.FeatureMergeResult)      # (merge_features_from; its status values are the merge's)
 # nvbx_change_result.status (find_changes / change_clusters); the labels of their volume; nvbx_change_options.sampling
 CHANGE_OK, CHANGE_EMPTY_MAP, CHANGE_EMPTY_REFERENCE, CHANGE_NO_OVERLAP = 0, 1, 2, 3
 CHANGE_STATUS_NAMES = {0: "OK", 1: "EMPTY_MAP", 2: "EMPTY_REFERENCE", 3: "NO_OVERLAP"}
@@ -290,6 +291,31 @@ class MergeResult:
     def __repr__(self):
         return "MergeResult(%s, %d source blocks -> %d candidates (%d new), %d voxels, %d colour voxels)" % (
             self.status_name, self.source_blocks, self.candidate_blocks, self.blocks_allocated, self.voxels_fused, self.color_voxels_fused)
+
+
+class FeatureMergeResult:
+    """What merge_features_from left behind: `buffer` is the nvbx_feature_merge_result record on the device (a uint8 tensor, written by the
+    call's last launch); the first field that is read copies it to the host once."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        self._host = None
+
+    def _r(self):
+        if self._host is None:
+            self._host = _lib.FeatureMergeResult.from_buffer_copy(self.buffer.cpu().numpy().tobytes())
+        return self._host
+
+    source_blocks = property(lambda self: int(self._r().source_blocks), doc="feature blocks of the source")
+    candidate_blocks = property(lambda self: int(self._r().candidate_blocks), doc="distinct blocks of this map the call went over")
+    blocks_flagged = property(lambda self: int(self._r().blocks_flagged), doc="... of which it gave the feature layer")
+    voxels_fused = property(lambda self: int(self._r().voxels_fused))
+    status = property(lambda self: int(self._r().status))
+    status_name = property(lambda self: MERGE_STATUS_NAMES.get(int(self._r().status), "?"))
+
+    def __repr__(self):
+        return "FeatureMergeResult(%s, %d source blocks -> %d candidates (%d flagged), %d voxels)" % (
+            self.status_name, self.source_blocks, self.candidate_blocks, self.blocks_flagged, self.voxels_fused)
 
 
 class ChangeResult:
@@ -1088,6 +1114,26 @@ class Mapper:
         self._around_torch_stream(lambda: self.lib.nvbx_merge_map(self._h, other._h, _np_ptr(T), C.byref(o), ptr(buf)))
         return MergeResult(buf)
 
+    # -- feature merging (nvbx_merge_features; SEMANTICS.md "Feature merging")
+    def feature_merge_options(self, **kw):
+        """nvbx_feature_merge_options: the library's defaults with the given fields replaced (min_weight, weight_scale)."""
+        if "reserved" in kw:
+            raise TypeError("unknown feature merge option 'reserved'")
+        return _args.struct_options(_lib.FeatureMergeOptions, self.lib.nvbx_default_feature_merge_options, kw, "feature merge")
+
+    def merge_features_from(self, other, T_D_S=None, out=None, **options):
+        """Bring `other`'s feature layer into this map under p_D = T_D_S p_S (row-major 4 x 4; None: the identity): -> FeatureMergeResult.
+        Meant to follow merge_from with the same pose: only blocks this map already has are written, nothing is allocated; a voxel takes
+        the voxel of `other` that contains its centre.  `other` is not modified.  The launches run on this mapper's stream behind everything
+        enqueued on `other`'s.  options: see feature_merge_options.  out: a preallocated result buffer (uint8 tensor of
+        FEATURE_MERGE_RESULT_BYTES bytes)."""
+        if not isinstance(other, Mapper):
+            raise TypeError("merge_features_from needs a Mapper")
+        T = self._T(np.eye(4, dtype=np.float32) if T_D_S is None else T_D_S); o = self.feature_merge_options(**options)
+        buf = _args.result_buffer(out, FEATURE_MERGE_RESULT_BYTES, self._cuda)
+        self._around_torch_stream(lambda: self.lib.nvbx_merge_features(self._h, other._h, _np_ptr(T), C.byref(o), ptr(buf)))
+        return FeatureMergeResult(buf)
+
     # -- resampling (nvbx_resample_map; SEMANTICS.md "Resampling")
     def resample_options(self, **kw):
         """nvbx_resample_options: the library's defaults with the given fields replaced (min_weight, weight_scale, merge_color, taps)."""
@@ -1275,6 +1321,19 @@ class Mapper:
         found = np.zeros(idx.shape[0], np.int32)
         self._check(self.lib.nvbx_get_feature_blocks(self._h, _np_ptr(idx), idx.shape[0], _np_ptr(f), _np_ptr(w), _np_ptr(found)))
         return f, w, found.astype(bool)
+
+    def set_feature_blocks(self, indices, features, weights):
+        """Whole feature blocks, the layout of feature_blocks: features [n, 512, C] float16, weights [n, 512] float32 (numpy arrays) -> written
+        [n] bool.  A block is written -- all 512 voxels replaced -- only where this map has it with its TSDF layer; nothing else of the map
+        changes.  The indices are distinct."""
+        idx = np.ascontiguousarray(np.asarray(indices, np.int32).reshape(-1, 3)); n = idx.shape[0]
+        ch = getattr(self, "feature_channels", 0)      # (0: not enabled -- the library refuses the call)
+        f = np.ascontiguousarray(np.asarray(features, np.float16)); w = np.ascontiguousarray(np.asarray(weights, np.float32))
+        if (ch and f.shape != (n, 512, ch)) or w.shape != (n, 512):
+            raise ValueError("features must be (%d, 512, %d) and weights (%d, 512), got %s and %s" % (n, ch, n, f.shape, w.shape))
+        written = np.zeros(n, np.int32)
+        self._check(self.lib.nvbx_set_feature_blocks(self._h, _np_ptr(idx), n, _np_ptr(f), _np_ptr(w), _np_ptr(written)))
+        return written.astype(bool)
 
     # -- feature matching (nvbx_match_features / nvbx_match_points; SEMANTICS.md "Feature matching")
     _METRICS = {"dot": 0, "cosine": 1}
